@@ -2,6 +2,7 @@
 """bench.py -- throughput of the GeoT sampling/grouping hot path and of the model that calls it, on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--clouds B] [--workload model|sa|backbone_ops|ntm|fixmatch]
+                    [--full] [--dump-outputs DIR]
 
 Default workload = BASELINE.json configs[2] (the config the metric "clouds/s ... fwd+bwd" is quoted on):
 B = 8 synthetic 24 000-point tooth clouds per GPU through the configured backbone PointTransformer_seg_T
@@ -19,6 +20,10 @@ Other workloads: `sa` = configs[1] (one SetAbstraction forward, eval); `backbone
 backbone alone (dense layers replaced by nothing); `ntm` = the unlabelled half of the NTM block alone;
 `fixmatch` = configs[4], one full FixMatch+NTM iteration (teacher 2 clouds, student 6 clouds, NTM block, losses,
 both optimisers) per rank.
+
+A plain run sets up, warms up, times --steps steps and prints the headline figure; --full adds every other figure
+(roofline and per-kernel times, the other mode's leg, CPU baseline, the `also` legs, ...).  --dump-outputs DIR writes
+what the last timed step computed as .npy files, so that two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0 (DESIGN.md section 7 explains every field).
 """
@@ -91,6 +96,13 @@ def parse():
     ap.add_argument("--no-graph", action="store_true",
                     help="model / fixmatch: time the eager step only, no replay leg; N > 1 always runs eagerly "
                          "(DistributedDataParallel is host logic)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: per-kernel roofline figures and the hot-path attribution, "
+                         "the other mode's leg (eager / replay), the legs without look-ahead and in the reference's op order, "
+                         "the saturated SetAbstraction run, the CPU baseline, the `also` legs and the N > 1 comm audit")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (and, model / fixmatch, a fixed "
+                         "seeded sample of the parameters it left) to DIR/<name>.npy in float32 / float64")
     return ap.parse_args()
 
 
@@ -146,6 +158,7 @@ def also_legs(args, run=subprocess.run):
         cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-also"] + extra
         if args.no_cpu_baseline:
             cmd.append("--no-cpu-baseline")
+        cmd.append("--full")                     # (the legs run under --full only, and keep their own figures)
         t0 = time.time()
         try:
             r = run(cmd, env=env, capture_output=True, text=True, timeout=900)
@@ -173,6 +186,41 @@ def _finite(obj):
     if isinstance(obj, float) and not math.isfinite(obj):
         return None
     return obj
+
+
+DUMP_SAMPLE = 1 << 22       # elements kept of an output larger than this (float32: 16 MB); parameters: PARAM_SAMPLE
+PARAM_SAMPLE = 1 << 20
+
+
+def _sampled(flat, k, seed):
+    """`flat` (1-D tensor) whole, or -- when it holds more than k elements -- at a fixed, seeded set of at most k positions
+    (ascending), the same for every run of the same shape."""
+    import numpy as np
+    import torch
+    if flat.numel() <= k:
+        return flat
+    pos = np.unique(np.random.default_rng(seed).integers(0, flat.numel(), size=k))
+    return flat[torch.from_numpy(pos).to(flat.device)]
+
+
+def dump_outputs(out_dir, name, out, trainer=None):
+    """--dump-outputs: what the timed path returned in its last step (`name`.npy) and, for a training step, a fixed sample
+    of the parameters it left (parameters_sample.npy: the optimizers' parameters flattened in order); floating outputs as
+    float32 (float64 stays float64), integer ones as float64; 64 MB at most in all."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    o = out.detach().reshape(-1)
+    o = o.double() if (o.dtype == torch.float64 or not o.is_floating_point()) else o.float()
+    arrays = {name: _sampled(o, DUMP_SAMPLE, 1609).cpu().numpy().reshape(out.shape if o.numel() <= DUMP_SAMPLE else -1)}
+    if trainer is not None:
+        params = [p for opt in trainer.optimizers() for g in opt.param_groups for p in g["params"]]
+        flat = torch.cat([p.detach().reshape(-1).float() for p in params])
+        arrays["parameters_sample"] = _sampled(flat, PARAM_SAMPLE, 1610).cpu().numpy()
+        del flat
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 class EventTimer:
@@ -775,7 +823,8 @@ def main():
             undo.append(lambda: setattr(sa_fused_mod, "fused_group_mlp_max", orig_mlp))
         return undo
 
-    undo = [] if use_graph else install_timers()
+    full = args.full
+    undo = [] if (use_graph or not full) else install_timers()      # (the per-kernel events feed --full's roofline only)
     if args.streams > 1 and workload == "sa":
         pool = [torch.cuda.Stream(device=dev) for _ in range(args.streams)]
         dealt = [0]
@@ -792,8 +841,11 @@ def main():
     HOST_ISSUE_MAIN["ms"] = 1e3 * HOST_ISSUE["s"] / max(args.steps, 1)
     HOST_ISSUE_MAIN["cpu_ms"] = 1e3 * HOST_ISSUE["cpu_s"] / max(args.steps, 1)
     assert torch.isfinite(out).all()
-    other_leg = None
-    if can_replay:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"model": "loss", "fixmatch": "loss", "sa": "new_features"}.get(workload, "output"),
+                     out, (trainer_g if (use_graph and multi) else trainer) if workload in ("model", "fixmatch") else None)
+    other_leg = other = None
+    if can_replay and full:
         # the same iterations in the OTHER mode, in this run (same model state continuing): what the replay is worth at this
         # size.  The per-kernel HIP events are taken on eager steps -- no event can be recorded inside a replay.
         k_e = max(2, min(args.steps, 10))
@@ -831,7 +883,7 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     fps_ms = fps_timer.mean_ms()
     fps_alone_ms = None
-    if workload == "model" and fps_rounds:
+    if full and workload == "model" and fps_rounds:
         # the same launch with the chip to itself: inside the step the kernel shares its CUs with the GEMMs of the stream it
         # runs beside (the previous batch's backward under look-ahead, the encoder otherwise) and its loop waits for issue
         # slots -- the in-step duration above is what the roofline uses, this one says how much of it is contention
@@ -877,10 +929,10 @@ def main():
         "data": "synthetic" if not rehearsal else "synthetic (REHEARSAL: all ranks on one GPU over gloo -- not a measurement)",
         "config": {"workload": desc + graph_note, "clouds_per_gpu": clouds_per_step, "points": N_POINTS,
                    "parallelism": parallelism, "stand_in": workload in ("ops_only", "ntm")},
-        "roofline": fps_roofline if (fps_rounds and not args.graph) else None,
+        **({"roofline": fps_roofline if (fps_rounds and not args.graph) else None} if full else {}),
         "final_loss": float(out.float().mean()) if workload in ("model", "fixmatch") else None,   # of the last timed step (rank 0)
     }
-    if workload == "model":
+    if full and workload == "model":
         # dominant kernel of the step by rocprofv3 time (profiles/r02_bench_model_*_window.csv): the 8192-sample FPS
         # (one workgroup per cloud, on the side stream beside the encoder).  Next to it the widest library GEMM of the
         # decoder (propogation_0.mlp.layer1: 1536 -> 384 over B*24000 points), timed from module hooks.
@@ -940,13 +992,14 @@ def main():
                            "knn_all_launches_ms_per_step": k_ms,
                            "knn_Mqueries_per_s": B * (512 + 4096 * 2 + 8192 * 2) / (k_ms * 1e-3) / 1e6,
                            "note": "kNN: k=32 512x24000 + k=4 {512->4096, 4096^2, 4096->8192, 8192^2} per cloud per step"}
+    if workload == "model":
         result["dense"] = {"mode": dense_mode,
                            "gemm_selection": ("PyTorch TunableOp, recorded: " + os.path.relpath(gemm_file, ROOT)) if gemm_file
                            else "library defaults",
                            "reference_gflop_fwd_per_cloud": DENSE_GFLOP_FWD_REFERENCE,
                            "note": "factored: first 1x1 conv behind a gather evaluated before the gather (same function, "
                                    "fewer flops); reference: the reference's op order"}
-    if workload == "sa" and mlp_timer.pairs:
+    if full and workload == "sa" and mlp_timer.pairs:
         mlp_ms = mlp_timer.mean_ms()
         widths = [MLP[0] + 3] + MLP[1:]   # use_xyz: 3 relative coordinates + 3 features
         mlp_flop = 2.0 * B * NPOINT * NSAMPLE * sum(a * b for a, b in zip(widths[:-1], widths[1:]))
@@ -958,7 +1011,7 @@ def main():
             "avg_launch_ms": mlp_ms,
             "note": "fused group + [6,64,64,128] 1x1-conv stack on fp32 MFMA + max over nsample; algorithmic flop = "
                     "2*rows*sum(Cin*Cout) with the unpadded 3+3 input channels"}
-    if workload == "fixmatch":
+    if full and workload == "fixmatch":
         fps_roofline.update(kernel="fps_pruned_kernel<768,32,false,8> (the student's pointops.fps 24000 -> 8192 over its "
                                    "%d clouds: the longest kernel of the iteration; the teacher runs the same on %d)" % (fps_clouds, bu))
         att = hot_path_attribution(eager_step)
@@ -967,7 +1020,7 @@ def main():
                               "top_entry_points_ms": dict(sorted(att.items(), key=lambda kv: -kv[1])[:8]),
                               "note": "HIP-event durations around every C-ABI launch in 2 extra untimed iterations; the FPS "
                                       "launches and the teacher run on side streams, so this is GPU work, not wall time"}
-    if multi:
+    if full and multi:
         # Audit trail for a multi-GPU record: (a) an all-reduce of ones over the backend the step used -- the number of
         # ranks that really took part; (b) what the gradient all-reduce costs on the critical path: the same steps with
         # DDP's reduction switched off (no_sync: gradients stay local; SyncBatchNorm and the anchor exchange still talk)
@@ -1036,10 +1089,10 @@ def main():
         result["graph"] = {"replayed": bool(use_graph),
                            "note": ("primary mode = hipGraph replay (geot_amd/graph_step.py: training graph + the next batch's "
                                     "look-ahead graph on a side stream, bit-identical to the eager step, "
-                                    "tests/test_graph_step_gpu.py); the eager leg of the same run is `eager`") if use_graph else
+                                    "tests/test_graph_step_gpu.py); the eager leg of the same run (--full) is `eager`") if use_graph else
                                    ("primary mode = eager: N > 1 runs DistributedDataParallel, whose buckets and collectives are "
                                     "host logic" if multi else
-                                    "primary mode = eager" + ("; the hipGraph replay of the same iterations is `replay` (primary for "
+                                    "primary mode = eager" + ("; the hipGraph replay of the same iterations (--full) is `replay` (primary for "
                                                               "the FixMatch iteration and at <= 3 clouds, where the eager "
                                                               "step is host-bound)" if can_replay else
                                                              (" (the replay was refused: `replay_refused`)" if replay_refused else " (--no-graph)")))}
@@ -1060,7 +1113,7 @@ def main():
         result["config"]["lookahead"] = ("the step is handed the next batch's coordinates (two batches alternate) and queues "
                                          "their sampling / grouping / index work beside its own backward"
                                          if lookahead else "off: all of a batch's work inside its own step")
-    if workload in ("model", "fixmatch") and not multi and lookahead and not args.no_dense_reference:
+    if full and workload in ("model", "fixmatch") and not multi and lookahead and not args.no_dense_reference:
         # the same steps without the look-ahead (every batch's sampling at the head of its own step), observed in this run
         runner = graphed if use_graph else trainer      # (the replay's "plain" variant is captured by the first call)
 
@@ -1074,7 +1127,7 @@ def main():
         result["lookahead"] = {"ms_per_step_without": 1e3 * t_plain / k3, "clouds_per_s_without": clouds_per_step * k3 / t_plain,
                                "steps": k3, "note": "same model, same alternating batches, next_pos=None: every step samples "
                                                     "and groups its own batch before its encoder can start"}
-    if workload == "model" and not multi and dense_mode != "reference" and not args.no_dense_reference:
+    if full and workload == "model" and not multi and dense_mode != "reference" and not args.no_dense_reference:
         # the same step with every layer in the REFERENCE's op order (first 1x1 conv after the gather, op-by-op attention /
         # LayerNorm) on the same kernels: what the algebraic re-ordering is worth, observed in this run
         del trainer, net
@@ -1094,7 +1147,7 @@ def main():
                                               "steps": 3, "note": "--dense reference: the reference's op order, same HIP "
                                                                   "kernels and GEMM selection; 1 warm-up + 3 timed steps"}
         del ref_trainer, ref_model
-    if workload == "sa" and not multi and not args.graph and not args.no_saturated and B < 64:
+    if full and workload == "sa" and not multi and not args.graph and not args.no_saturated and B < 64:
         # one cloud occupies ONE of the 256 CUs in FPS (96 % of this step): the same module at 256 clouds per launch
         # is what the chip does when every CU has a cloud (the reference's per-cloud semantics are unchanged)
         bs = 256
@@ -1110,7 +1163,7 @@ def main():
                                "steps": 3, "note": "same SetAbstraction forward with one cloud per CU (256 clouds in one "
                                                    "call): throughput when FPS fills the chip"}
         del xs, fs
-    if rank == 0 and not multi and not args.no_cpu_baseline:
+    if full and rank == 0 and not multi and not args.no_cpu_baseline:
         if workload == "sa":
             from geot_amd.pointnet2.pointnet2_modules import PointnetSAModuleVotes
             torch.manual_seed(1609)
@@ -1121,7 +1174,7 @@ def main():
             result["cpu_baseline"] = cpu_baseline_model()
         elif workload == "fixmatch":
             result["cpu_baseline"] = cpu_baseline_fixmatch(bl, bu)
-    if (rank == 0 and not multi and workload == "model" and not args.no_also and args.clouds is None
+    if (full and rank == 0 and not multi and workload == "model" and not args.no_also and args.clouds is None
             and args.points == N_POINTS and not args.graph and not args.no_graph and args.dense is None):
         # the driver's default invocation: configs[1] and configs[4] into the same record, after the primary leg's timing
         torch.cuda.empty_cache()

@@ -1,11 +1,14 @@
-"""Regenerate tests/golden/grid_subsampling_ref.npz (run in the BUILD container only).
+"""Regenerate tests/golden/grid_subsampling_ref.npz and grid_subsampling_compiled_ref.npz (run where the
+reference checkout is present).
 
     python oracle/build_ref.py && python tests/golden/make_grid_fixture.py
 
 Inputs: seeded clouds (with duplicate points and negative coordinates).  Expected outputs: what the
 REFERENCE's own grid_subsampling() returns for them -- compiled from /root/reference by oracle/build_ref.py
-into oracle/_ref/ -- in the reference's own row order.  The fixture holds inputs and outputs only.
+into oracle/_ref/ -- in the reference's own row order.  grid_subsampling_ref.npz holds inputs and outputs only;
+grid_subsampling_compiled_ref.npz only digests and labels (compiled_cases).
 """
+import hashlib
 import os
 import sys
 
@@ -21,6 +24,9 @@ CASES = [  # name, n, dl, fdim, ldim, scale
     ("b", 2000, 0.05, 2, 1, (1.0, 1.0, 0.3)),
     ("c", 800, 0.30, 1, 2, (2.0, 0.5, 0.5)),
 ]
+# tests/test_data_cpu.py::test_grid_subsampling_restatement_matches_compiled_reference: seed, n, dl, fdim, ldim
+COMPILED_CASES = [(0, 5000, 0.1, 0, 0), (1, 20000, 0.05, 4, 1), (2, 3000, 0.3, 2, 2),
+                  (3, 1, 0.1, 1, 1), (4, 60, 10.0, 1, 1), (5, 40000, 0.013, 1, 1)]
 
 
 def main():
@@ -40,6 +46,47 @@ def main():
         if ldim:
             out[name + "_labels"], out[name + "_ref_labels"] = lab, r["labels"]
     np.savez_compressed(os.path.join(HERE, "grid_subsampling_ref.npz"), **out)
+    print("wrote", sorted(out))
+    compiled_cases()
+
+
+def compiled_case_inputs(seed, n, fdim, ldim):
+    """The seeded cloud of one COMPILED_CASES entry (the test regenerates it; the fixture keeps its digest)."""
+    rng = np.random.default_rng(seed)
+    p = (rng.standard_normal((n, 3)) * np.array([1, 0.7, 0.4])).astype(np.float32)
+    if n > 100:
+        p[rng.integers(0, n, n // 50)] = p[rng.integers(0, n, n // 50)]
+    f = rng.standard_normal((n, fdim)).astype(np.float32) if fdim else None
+    lab = rng.integers(-2, 6, (n, ldim)).astype(np.int32) if ldim else None
+    return p, f, lab
+
+
+def digest(*arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        if a is not None:
+            h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def compiled_cases():
+    """grid_subsampling_compiled_ref.npz, keyed "<seed>_<name>": the digest of the case's inputs, and of the reference's
+    rows for them sorted by np_data.row_order (points; features), the row count, and the sorted labels themselves (int8:
+    they are compared only where the vote is not tied)."""
+    out = {}
+    for seed, n, dl, fdim, ldim in COMPILED_CASES:
+        p, f, lab = compiled_case_inputs(seed, n, fdim, ldim)
+        r = np_data.grid_subsampling_reference(p, f, lab, dl)
+        order = np_data.row_order(r["points"])
+        out["%d_inputs_sha256" % seed] = np.array(digest(p, f, lab))
+        out["%d_rows" % seed] = np.int64(len(order))
+        out["%d_points_sha256" % seed] = np.array(digest(r["points"][order]))
+        if fdim:
+            out["%d_features_sha256" % seed] = np.array(digest(r["features"][order]))
+        if ldim:
+            assert r["labels"].min() >= -128 and r["labels"].max() <= 127
+            out["%d_ref_labels" % seed] = r["labels"][order].astype(np.int8)
+    np.savez_compressed(os.path.join(HERE, "grid_subsampling_compiled_ref.npz"), **out)
     print("wrote", sorted(out))
 
 

@@ -21,6 +21,7 @@ def _load_bench():
 def test_bench_imports_and_parses_without_a_gpu():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
     assert r.returncode == 0 and "--gpus" in r.stdout and "--workload" in r.stdout
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
 
 
 def test_spawn_ranks_sets_the_rendezvous_and_reports_the_worst_exit(tmp_path, monkeypatch):
@@ -94,6 +95,36 @@ def test_also_legs_schema_and_failure_handling():
         assert "--no-also" in cmd and "RANK" not in env          # a child never recurses and never inherits a rendezvous
     fm = [c for c, _ in seen if "fixmatch" in c][0]
     assert fm[fm.index("--steps") + 1] == "10" and fm[fm.index("--warmup") + 1] == "3"
+
+
+def test_dump_outputs_writes_the_last_step_and_a_fixed_sample(tmp_path):
+    """--dump-outputs: the returned array as float32 / float64 .npy, a large one and the parameters at fixed seeded
+    positions (ascending, the same in every run), 64 MB at most in all."""
+    import numpy as np
+    import torch
+    bench = _load_bench()
+
+    class Trainer:
+        def __init__(self):
+            self.opt = torch.optim.SGD([torch.nn.Parameter(torch.arange(3 << 20, dtype=torch.float32)),
+                                        torch.nn.Parameter(-torch.ones(5, 7))], lr=0.1)
+
+        def optimizers(self):
+            return [self.opt]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), "loss", torch.tensor(1.5), Trainer())
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.dtype == np.float32 and loss.shape == () and float(loss) == 1.5
+    pa, pb = np.load(tmp_path / "a" / "parameters_sample.npy"), np.load(tmp_path / "b" / "parameters_sample.npy")
+    assert pa.dtype == np.float32 and 0 < pa.size <= 1 << 20 and np.array_equal(pa, pb)
+    assert np.all(np.diff(pa[pa >= 0]) > 0)       # positions ascending (the first parameter is an arange)
+    bench.dump_outputs(str(tmp_path / "c"), "output", torch.arange(5 << 20, dtype=torch.int64))
+    o = np.load(tmp_path / "c" / "output.npy")
+    assert o.dtype == np.float64 and 0 < o.size <= 1 << 22 and np.all(np.diff(o) > 0)
+    assert sorted(os.listdir(tmp_path / "c")) == ["output.npy"] and o.nbytes <= 64 << 20
+    small = torch.randn(2, 3, 4, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "d"), "output", small)
+    assert np.array_equal(np.load(tmp_path / "d" / "output.npy"), small.numpy())
 
 
 def test_trace_window_summarises_only_the_steady_state(tmp_path):

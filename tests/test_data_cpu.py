@@ -1,14 +1,18 @@
 """Dataloader-side ops, CPU part: the numpy restatement of grid_subsampling against the
-fixture generated from the reference's own compiled code, and against that code itself when oracle/_ref was
-built in this checkout; the numpy pc_norm / class-weight restatement against fp64."""
+fixtures generated from the reference's own compiled code; the numpy pc_norm / class-weight restatement against fp64."""
 import os
+import sys
 
 import numpy as np
 import pytest
 
 from oracle import np_data
 
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+import make_grid_fixture  # noqa: E402
+
 GOLD = os.path.join(os.path.dirname(__file__), "golden", "grid_subsampling_ref.npz")
+GOLD_COMPILED = os.path.join(os.path.dirname(__file__), "golden", "grid_subsampling_compiled_ref.npz")
 
 
 def compare_with_reference_rows(got, ref_points, ref_features, ref_labels):
@@ -33,19 +37,24 @@ def test_grid_subsampling_restatement_matches_reference_fixture(case):
     assert np.all(np.diff(got["keys"].astype(np.int64)) > 0) and got["count"].sum() == len(g("points"))
 
 
-@pytest.mark.skipif(not np_data.have_reference(), reason="oracle/_ref not built (needs /root/reference)")
-@pytest.mark.parametrize("seed,n,dl,fdim,ldim", [(0, 5000, 0.1, 0, 0), (1, 20000, 0.05, 4, 1), (2, 3000, 0.3, 2, 2),
-                                                   (3, 1, 0.1, 1, 1), (4, 60, 10.0, 1, 1), (5, 40000, 0.013, 1, 1)])
+@pytest.mark.parametrize("seed,n,dl,fdim,ldim", make_grid_fixture.COMPILED_CASES)
 def test_grid_subsampling_restatement_matches_compiled_reference(seed, n, dl, fdim, ldim):
-    rng = np.random.default_rng(seed)
-    p = (rng.standard_normal((n, 3)) * np.array([1, 0.7, 0.4])).astype(np.float32)
-    if n > 100:
-        p[rng.integers(0, n, n // 50)] = p[rng.integers(0, n, n // 50)]
-    f = rng.standard_normal((n, fdim)).astype(np.float32) if fdim else None
-    lab = rng.integers(-2, 6, (n, ldim)).astype(np.int32) if ldim else None
+    """Against the rows the reference's own compiled grid_subsampling() returned for these seeded clouds, bit for bit:
+    tests/golden/grid_subsampling_compiled_ref.npz holds the digests of the inputs and of the reference's sorted rows, and
+    its sorted labels (generator tests/golden/make_grid_fixture.py)."""
+    z = np.load(GOLD_COMPILED)
+    g = lambda k: z["%d_%s" % (seed, k)] if "%d_%s" % (seed, k) in z else None
+    p, f, lab = make_grid_fixture.compiled_case_inputs(seed, n, fdim, ldim)
+    assert make_grid_fixture.digest(p, f, lab) == str(g("inputs_sha256")), "the seeded inputs are not the fixture's"
     got = np_data.grid_subsampling(p, f, lab, dl)
-    ref = np_data.grid_subsampling_reference(p, f, lab, dl)
-    compare_with_reference_rows(got, ref["points"], ref["features"], ref["labels"])
+    a = np_data.row_order(got["points"])
+    assert len(a) == int(g("rows"))
+    assert make_grid_fixture.digest(got["points"][a]) == str(g("points_sha256"))
+    if fdim:
+        assert make_grid_fixture.digest(got["features"][a]) == str(g("features_sha256"))
+    if ldim:
+        free = ~got["tied"][a]
+        assert np.array_equal(got["labels"][a][free], g("ref_labels")[free].astype(np.int32))
 
 
 def test_pc_norm_numpy_within_tolerance_of_fp64():

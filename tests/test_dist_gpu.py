@@ -38,8 +38,8 @@ def test_bench_two_rank_rehearsal_emits_an_auditable_line(workload):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--clouds", "1", "--steps", "2",
-                        "--warmup", "1", "--workload", workload, "--points", "8192"], env=env, capture_output=True, text=True,
-                       timeout=900, cwd=ROOT)
+                        "--warmup", "1", "--workload", workload, "--points", "8192", "--full"], env=env, capture_output=True,
+                       text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]            # rank 0 alone prints
@@ -369,8 +369,8 @@ def test_bench_one_gpu_line_has_both_modes_or_says_why_not(packet_capture_env):
     if packet_capture_env is not None:
         env["DEBUG_CLR_GRAPH_PACKET_CAPTURE"] = packet_capture_env
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--clouds", "2", "--steps", "3", "--warmup", "1",
-                        "--points", "8192", "--no-cpu-baseline", "--no-dense-reference", "--no-also"], env=env, capture_output=True, text=True,
-                       timeout=900, cwd=ROOT)
+                        "--points", "8192", "--no-cpu-baseline", "--no-dense-reference", "--no-also", "--full"], env=env,
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     rec = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert rec["n_gpus"] == 1 and rec["value"] > 0 and np.isfinite(rec["ms_per_step"])
@@ -384,6 +384,28 @@ def test_bench_one_gpu_line_has_both_modes_or_says_why_not(packet_capture_env):
         assert all(set(v) == {"kernel"} for v in g["nodes"].values())
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """Without --full the line holds the headline figure alone (no other leg, roofline, baseline or `also`); --dump-outputs
+    writes what the last timed step returned (the loss) and a fixed sample of the parameters it left."""
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    out = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--clouds", "2", "--steps", "3", "--warmup", "1",
+                        "--points", "8192", "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=900,
+                       cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, lines
+    rec = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in rec, k
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["value"] > 0 and np.isfinite(rec["ms_per_step"])
+    assert not set(rec) & {"roofline", "roofline_hbm", "hot_path", "cpu_baseline", "also", "eager", "replay", "lookahead", "comm"}
+    loss = np.load(out / "loss.npy")
+    params = np.load(out / "parameters_sample.npy")
+    assert loss.dtype == np.float32 and loss.shape == () and float(loss) == rec["final_loss"]
+    assert params.dtype == np.float32 and 0 < params.size <= 1 << 20 and np.isfinite(params).all()
+
+
 @pytest.mark.parametrize("workload", ["model", "fixmatch"])
 def test_bench_multi_gpu_code_paths_on_one_rank_over_rccl(workload):
     """GEOT_BENCH_SOLO_DP=1: every line the N > 1 bench will execute, on ONE rank over RCCL -- DDP + SyncBatchNorm wrapped, the
@@ -395,7 +417,7 @@ def test_bench_multi_gpu_code_paths_on_one_rank_over_rccl(workload):
                         "GEOT_GRAPH_LAUNCH")}
     env["GEOT_BENCH_SOLO_DP"] = "1"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--clouds", "2" if workload == "model" else "1",
-           "--steps", "3", "--warmup", "1", "--points", "8192", "--no-cpu-baseline", "--no-dense-reference", "--no-also"]
+           "--steps", "3", "--warmup", "1", "--points", "8192", "--no-cpu-baseline", "--no-dense-reference", "--no-also", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -15,7 +15,7 @@ for rep in 1 2 3; do
   for which in old new; do
     if [ $which = old ]; then cp "$OLD" "$CUR"; else cp "$NEW" "$CUR"; fi
     python -m geot_amd.build --force > /dev/null 2>&1 || { echo BUILD FAILED; exit 1; }
-    python bench.py --steps 20 --no-cpu-baseline --no-dense-reference 2>/dev/null | python -c "
+    python bench.py --steps 20 --full --no-cpu-baseline --no-dense-reference 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('$which', round(d['value'],2), 'clouds/s', round(d['ms_per_step'],3), 'ms;', 'edge grad', round(d['hot_path']['top_entry_points_ms'].get('geot_edgeconv_gn_max_grad_rix',0),3))"
