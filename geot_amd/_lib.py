@@ -138,6 +138,8 @@ PLAIN = {
     "geot_knnquery_heap_ws_bytes": ([_c_int, _c_int, _c_int, _c_int], ctypes.c_longlong),
     "geot_grad_ws_needs_zero": ([_c_int, _c_int, _c_int, ctypes.c_longlong, _c_int], _c_int),
     "geot_scatter_grad_ws_floats": ([_c_int, _c_int, _c_int, ctypes.c_longlong, _c_int, _c_int], ctypes.c_longlong),
+    "geot_scatter_grad_plan": ([_c_int, _c_int, _c_int, ctypes.c_longlong, _c_int, _c_int, ctypes.POINTER(ctypes.c_longlong), _c_int],
+                               _c_int),
     "geot_ntm_sig_t_mean_ws_floats": ([_c_int, _c_int], ctypes.c_longlong),
     "geot_ntm_threed_loss_ws_bytes": ([_c_int, _c_int, _c_int], ctypes.c_longlong),
     "geot_ntm_correct_ws_floats": ([_c_int, _c_int], ctypes.c_longlong),
@@ -161,7 +163,7 @@ PLAIN = {
     "geot_rowdot_small_slices": ([_c_int] * 2, _c_int),
     "geot_colsum_ws_floats": ([_c_int] * 2, ctypes.c_longlong),
 }
-ABI_VERSION = 7     # include/geot_hip.h GEOT_ABI_VERSION this binding was written against
+ABI_VERSION = 8     # include/geot_hip.h GEOT_ABI_VERSION this binding was written against
 
 _lib = None
 

@@ -1053,6 +1053,20 @@ static bool csr_preferred(int b, int c, int m, long long L, int nt)
            csr_applies(b, c, m, L, nt, rix_ws_ints(b, c, m, L, nt));
 }
 
+// The form a *_grad_ws / _grad_out / _grad_from call takes for these sizes -- the one decision behind their launches,
+// geot_grad_ws_needs_zero and the host-only query geot_scatter_grad_plan.  tp receives the tile plan of GRAD_TILES.
+enum GradForm { GRAD_NONE = 0, GRAD_TILES = 1, GRAD_CSR = 2, GRAD_CL = 3 };
+static GradForm grad_form(int b, int c, int m, long long L, int nt, bool weighted, TsPlan *tp = nullptr)
+{
+    if (b < 1 || c < 1 || m < 1 || L < 1 || nt < 1) return GRAD_NONE;
+    TsPlan p;
+    if (!csr_preferred(b, c, m, L, nt) && ts_plan(b, c, m, L, nt, weighted, p)) {
+        if (tp) *tp = p;
+        return GRAD_TILES;
+    }
+    return csr_applies(b, c, m, L, nt, geot_scatter_grad_ws_floats(b, c, m, L, nt, weighted)) ? GRAD_CSR : GRAD_CL;
+}
+
 // returns hipErrorNotSupported when this path does not apply (caller falls back)
 template <int NT, bool WEIGHTED>
 static hipError_t scatter_via_csr(int b, int c, int m, int L, size_t src_bstride, const float *grad_out,
@@ -1841,9 +1855,10 @@ GEOT_EXPORT int geot_gather_points_grad_ws(int b, int c, int n, int m, const flo
     if (b < 0 || c < 0 || n < 0 || m < 0 || !workspace) return hipErrorInvalidValue;
     if (b == 0 || c == 0 || m == 0 || n == 0) return hipSuccess;
     const long long wsf = geot_scatter_grad_ws_floats(b, c, n, m, 1, 0);
-    hipError_t e = csr_preferred(b, c, n, m, 1) ? hipErrorNotSupported
-                                                : scatter_via_tiles(b, c, n, m, 1, (size_t)c * m, grad_out, idx, nullptr, grad_points, workspace,
-                                                                    wsf, (hipStream_t)stream, false);
+    hipError_t e = grad_form(b, c, n, m, 1, false) != GRAD_TILES
+                          ? hipErrorNotSupported
+                          : scatter_via_tiles(b, c, n, m, 1, (size_t)c * m, grad_out, idx, nullptr, grad_points, workspace, wsf,
+                                              (hipStream_t)stream, false);
     if (e != hipErrorNotSupported) return e;
     if (b <= 65535) {
         e = scatter_via_csr<1, false>(b, c, n, m, (size_t)c * m, grad_out, idx, nullptr, grad_points, workspace, wsf, (hipStream_t)stream);
@@ -1952,8 +1967,21 @@ GEOT_EXPORT int geot_three_interpolate_grad(int b, int c, int n, int m, const fl
 // only uses it as scratch (reverse-index path) and any contents will do.
 GEOT_EXPORT int geot_grad_ws_needs_zero(int b, int c, int m, long long L, int nt)
 {
-    if (!csr_preferred(b, c, m, L, nt) && ts_ws_ints(b, c, m, L, nt, nt == 3) > 0) return 0;
-    return csr_applies(b, c, m, L, nt, geot_scatter_grad_ws_floats(b, c, m, L, nt, nt == 3)) ? 0 : 1;
+    const GradForm f = grad_form(b, c, m, L, nt, nt == 3);
+    return f == GRAD_TILES || f == GRAD_CSR ? 0 : 1;
+}
+
+// host-only: the form of the *_grad_ws / _grad_out / _grad_from entry points for these sizes and, for the sorted pair
+// stream, its plan (grad_form: the same decision the launches take)
+GEOT_EXPORT int geot_scatter_grad_plan(int b, int c, int m, long long L, int nt, int weighted, long long *out, int n_out)
+{
+    TsPlan p;
+    const GradForm f = grad_form(b, c, m, L, nt, weighted != 0, &p);
+    if (f == GRAD_TILES && out) {
+        const long long v[8] = {p.ch, p.tl, p.q, p.ppp, p.cap, (long long)p.lds, (long long)p.lds_build, p.ints};
+        for (int i = 0; i < n_out && i < 8; ++i) out[i] = v[i];
+    }
+    return (int)f;
 }
 
 // floats of workspace the *_grad_ws / _grad_out / _grad_from entry points take for these sizes: b*m*c (the
@@ -1977,8 +2005,8 @@ static int three_interpolate_grad_launch(int b, int c, int n, int m, const float
     if (b > 65535) return hipErrorInvalidValue;
     {
         const long long wsf = geot_scatter_grad_ws_floats(b, c, m, n, 3, 1);
-        hipError_t e = csr_preferred(b, c, m, n, 3) ? hipErrorNotSupported
-                                                    : scatter_via_tiles(b, c, m, n, 3, grad_bstride, grad_out, idx, weight, grad_points,
+        hipError_t e = grad_form(b, c, m, n, 3, true) != GRAD_TILES ? hipErrorNotSupported
+                                                                : scatter_via_tiles(b, c, m, n, 3, grad_bstride, grad_out, idx, weight, grad_points,
                                                                         workspace, wsf, s, overwrite);
         if (e != hipErrorNotSupported) return e;
         e = scatter_via_csr<3, true>(b, c, m, n, grad_bstride, grad_out, idx, weight, grad_points, workspace,
@@ -2172,8 +2200,8 @@ GEOT_EXPORT int geot_group_points_grad_ws(int b, int c, int n, int npoints, int 
     if (npns > 0x7fffffffLL || b > 65535) return hipErrorInvalidValue;
     {
         const long long wsf = geot_scatter_grad_ws_floats(b, c, n, npns, 1, 0);
-        hipError_t e = csr_preferred(b, c, n, npns, 1) ? hipErrorNotSupported
-                                                       : scatter_via_tiles(b, c, n, (int)npns, 1, (size_t)c * npns, grad_out, idx, nullptr,
+        hipError_t e = grad_form(b, c, n, npns, 1, false) != GRAD_TILES ? hipErrorNotSupported
+                                                                   : scatter_via_tiles(b, c, n, (int)npns, 1, (size_t)c * npns, grad_out, idx, nullptr,
                                                                            grad_points, workspace, wsf, (hipStream_t)stream, false);
         if (e != hipErrorNotSupported) return e;
         e = scatter_via_csr<1, false>(b, c, n, (int)npns, (size_t)c * npns, grad_out, idx, nullptr, grad_points, workspace,
@@ -2223,8 +2251,8 @@ GEOT_EXPORT int geot_graph_feature_grad(int b, int c, int nq, int nk, int k, con
     const int L = nq * k;
     {
         const long long wsf = geot_scatter_grad_ws_floats(b, c, nk, L, 1, 0);
-        hipError_t e = csr_preferred(b, c, nk, L, 1) ? hipErrorNotSupported
-                                                     : scatter_via_tiles(b, c, nk, L, 1, (size_t)2 * c * L, grad_out, idx, nullptr, grad_xk,
+        hipError_t e = grad_form(b, c, nk, L, 1, false) != GRAD_TILES ? hipErrorNotSupported
+                                                                 : scatter_via_tiles(b, c, nk, L, 1, (size_t)2 * c * L, grad_out, idx, nullptr, grad_xk,
                                                                          workspace, wsf, s, false);
         if (e != hipErrorNotSupported) return e;
         e = scatter_via_csr<1, false>(b, c, nk, L, (size_t)2 * c * L, grad_out, idx, nullptr, grad_xk,

@@ -224,19 +224,23 @@ static inline hipError_t allow_big_lds(const void *kernel, size_t lds, int max_b
     if (lds <= 64 * 1024) return hipSuccess;
     if (lds > (size_t)max_bytes) return hipErrorInvalidValue;
     static std::mutex mu;
-    static std::vector<std::pair<const void *, int>> done;
+    struct Granted {
+        const void *kernel;
+        int dev, room;
+    };
+    static std::vector<Granted> done;
     int dev = 0;
     (void)hipGetDevice(&dev);
     std::lock_guard<std::mutex> guard(mu);
-    for (const auto &d : done)
-        if (d.first == kernel && d.second == dev) return hipSuccess;
+    for (const auto &d : done)   // (an earlier grant does not cover a larger request: the room is checked every time)
+        if (d.kernel == kernel && d.dev == dev) return (long long)lds > d.room ? hipErrorInvalidValue : hipSuccess;
     hipFuncAttributes attr;
     hipError_t e = hipFuncGetAttributes(&attr, kernel);     // the kernel's static LDS counts against the same 160 KB
     if (e != hipSuccess) return e;
     const int room = max_bytes - (int)attr.sharedSizeBytes;
     if ((long long)lds > room) return hipErrorInvalidValue;
     e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, room);
-    if (e == hipSuccess) done.emplace_back(kernel, dev);
+    if (e == hipSuccess) done.push_back({kernel, dev, room});
     return e;
 }
 // (2) scratch counters are cleared by a kernel, not hipMemsetAsync: a plain kernel node replays identically in a

@@ -5,6 +5,17 @@
 
 namespace geot {
 
+// The launch plan of one call shape (ts_plan): the scatter kernel's LDS = the sums of m x ch targets, two staged tiles of
+// tl x ch floats and q 16-word wave tables; the sort's LDS = m + 1 counters and one tile's ppp pair ids
+struct TsPlan {
+    int ch, tl, q, ppp, cap;              // channels per workgroup, sources per tile, tiles, pairs per tile, entry slots per tile
+    size_t lds, lds_build;                // dynamic LDS bytes of ts_scatter_kernel / ts_build_kernel
+    long long ent_words, ints;            // 4-byte words of the entries / of the whole workspace
+};
+// false when the shape does not fit this path (or GEOT_GATHER_IMPL selects another form); a plan it returns is within
+// every limit of the two kernels, LDS included -- the one planner behind the launch and the host-only queries
+bool ts_plan(int b, int c, int m, long long L, int nt, bool weighted, TsPlan &p);
+
 // grad_table[b, ch, j] (+)= sum over the pairs (e, t) with idx[b, e, t] == j of w[b, e, t] * grad_out[b, ch, e]
 //   grad_out : (b, c, L) rows, `src_bstride` floats between batches;  idx / weight : (b, L, nt) (weight null: all 1)
 //   grad_table : (b, c, m);  overwrite: every element is stored (the buffer may arrive uninitialised), else added to

@@ -53,15 +53,9 @@ constexpr int TS_NPF = 4;                 // chunks of the next tile's entries a
 constexpr int TS_PMAX = 31;               // plain chunks per wave and tile at most (5-bit field; the rest joins the sorted run)
 constexpr uint32_t TS_NONE = 0xffffffffu; // padding entry of a sorted run's last chunk
 
-struct TsPlan {
-    int ch, tl, q, ppp, cap;              // channels per workgroup, sources per tile, tiles, pairs per tile, entry slots per tile
-    size_t lds, lds_build;
-    long long ent_words, ints;
-};
-
 static inline long long ts_acc_floats(int m, int ch) { return ((long long)m * ch + 3) & ~3LL; }
 
-static bool ts_plan(int b, int c, int m, long long L, int nt, bool weighted, TsPlan &p)
+bool ts_plan(int b, int c, int m, long long L, int nt, bool weighted, TsPlan &p)
 {
     const char *env = getenv("GEOT_GATHER_IMPL");   // plain | atomic | csr | sell: the older forms (A/B runs); unset | tiles: this one
     if (env && env[0] && env[0] != 't') return false;
@@ -86,7 +80,8 @@ static bool ts_plan(int b, int c, int m, long long L, int nt, bool weighted, TsP
         if (!fits || tl < 4) continue;
         if (tl < 256 && tl < ((L + 3) & ~3LL)) continue;   // tiles this short are all barrier: fewer channels per workgroup
         if (q > TS_MAX_Q) continue;
-        tl = ((L + q - 1) / q + 3) & ~3LL;                   // equal tiles
+        const long long tl_eq = ((L + q - 1) / q + 3) & ~3LL;   // equal tiles: the same q, no longer than the fitted ones
+        tl = tl_eq;
         // ... whose 16 shares are a few pairs short of whole chunks: a share of 64 j + (0 .. 3) pairs plus the spill of its last
         // target is j + 1 chunks with one or two entries in the last
         {
@@ -98,18 +93,24 @@ static bool ts_plan(int b, int c, int m, long long L, int nt, bool weighted, TsP
         }
         q = (L + tl - 1) / tl;
         if (q > TS_MAX_Q) continue;
+        if (accb + 2 * tl * ch * 4 + q * TS_WAVES * 4 > TS_LDS) {  // the extra tiles' wave tables overflow LDS: equal tiles
+            tl = tl_eq;                                          // (their LDS is at most the fitted tiles')
+            q = (L + tl - 1) / tl;
+        }
         const long long ppp = tl * nt;
         const long long cap = ((ppp + 64LL * TS_WAVES + 63) & ~63LL) + 64 * TS_NPF;
         if (cap > 0xffff) continue;                          // a wave's first slot is a 16-bit field of its table entry
         const long long ent = (long long)b * q * cap * (weighted ? 2 : 1);
         if (ent > 0x7ffffff0LL) continue;
+        const long long lds = accb + 2 * tl * ch * 4 + q * TS_WAVES * 4, lds_build = ((long long)m + 1) * 4 + ppp * 4;
+        if (lds > TS_LDS || lds_build > TS_LDS - 2048) continue;   // (the retune above keeps both: a plan is launchable as returned)
         p.ch = ch;
         p.tl = (int)tl;
         p.q = (int)q;
         p.ppp = (int)ppp;
         p.cap = (int)cap;
-        p.lds = (size_t)(accb + 2 * tl * ch * 4 + q * TS_WAVES * 4);
-        p.lds_build = (size_t)(((long long)m + 1) * 4 + ppp * 4);
+        p.lds = (size_t)lds;
+        p.lds_build = (size_t)lds_build;
         p.ent_words = (ent + 1) & ~1LL;
         p.ints = p.ent_words + (long long)b * q * TS_WAVES + 8;
         return true;
@@ -515,11 +516,22 @@ __global__ __launch_bounds__(TS_THREADS) void ts_scatter_kernel(int c, int m, in
     TS_STAMP_FLUSH
 }
 
+static inline bool ts_vec_ok(int L, size_t src_bstride, const float *grad_out)
+{   // rows that start on 16-byte boundaries: float4 staging loads
+    return (L & 3) == 0 && (src_bstride & 3) == 0 && (((uintptr_t)grad_out) & 15) == 0;
+}
+
+template <int CH, bool WEIGHTED>
+static const void *ts_scatter_fn(bool vec)
+{
+    return vec ? (const void *)ts_scatter_kernel<CH, WEIGHTED, true> : (const void *)ts_scatter_kernel<CH, WEIGHTED, false>;
+}
+
 template <int CH, bool WEIGHTED>
 static hipError_t ts_launch(const TsPlan &p, int b, int c, int m, int L, size_t src_bstride, const float *grad_out,
                             const uint32_t *ent, const int *wr, float *grad_table, int set, hipStream_t s)
 {
-    const bool vec_ok = (L & 3) == 0 && (src_bstride & 3) == 0 && (((uintptr_t)grad_out) & 15) == 0;
+    const bool vec_ok = ts_vec_ok(L, src_bstride, grad_out);
     const dim3 grid((c + CH - 1) / CH, b);
     hipError_t e;
     if (vec_ok) {
@@ -546,15 +558,21 @@ hipError_t scatter_via_tiles(int b, int c, int m, int L, int nt, size_t src_bstr
         return hipErrorNotSupported;
     uint32_t *ent = (uint32_t *)workspace;
     int *wr = (int *)(ent + p.ent_words);
-    hipError_t e;
+    // both kernels' LDS is granted before anything is launched: a refusal falls back whole instead of leaving a sort
+    // without its scatter
+    const bool vec_ok = ts_vec_ok(L, src_bstride, grad_out);
+    const void *scat = p.ch == 4 ? (weighted ? ts_scatter_fn<4, true>(vec_ok) : ts_scatter_fn<4, false>(vec_ok))
+                     : p.ch == 2 ? (weighted ? ts_scatter_fn<2, true>(vec_ok) : ts_scatter_fn<2, false>(vec_ok))
+                                 : (weighted ? ts_scatter_fn<1, true>(vec_ok) : ts_scatter_fn<1, false>(vec_ok));
+    hipError_t e = allow_big_lds(scat, p.lds);
+    if (e == hipSuccess)
+        e = allow_big_lds(weighted ? (const void *)ts_build_kernel<true> : (const void *)ts_build_kernel<false>, p.lds_build);
+    if (e == hipErrorInvalidValue) return hipErrorNotSupported;     // more LDS than the kernel may have
+    if (e != hipSuccess) return e;
     if (weighted) {
-        e = allow_big_lds((const void *)ts_build_kernel<true>, p.lds_build);
-        if (e != hipSuccess) return e;
         hipLaunchKernelGGL((ts_build_kernel<true>), dim3(p.q, b), dim3(TS_THREADS), p.lds_build, s, m, L, nt, p.tl, p.q, p.ppp, p.cap,
                            idx, weight, ent, wr);
     } else {
-        e = allow_big_lds((const void *)ts_build_kernel<false>, p.lds_build);
-        if (e != hipSuccess) return e;
         hipLaunchKernelGGL((ts_build_kernel<false>), dim3(p.q, b), dim3(TS_THREADS), p.lds_build, s, m, L, nt, p.tl, p.q, p.ppp, p.cap,
                            idx, weight, ent, wr);
     }

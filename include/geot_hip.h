@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 7
+#define GEOT_ABI_VERSION 8
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
 
 /* ABI version / diagnostics. */
@@ -106,6 +106,13 @@ int geot_group_points_grad_ws(int b, int c, int n, int npoints, int nsample, con
 /* 0 when the *_grad_ws entry points only use their workspace as scratch for these sizes (gradient as a
  * gather over a reverse index), 1 when they accumulate in it and it must arrive zero-filled. */
 int geot_grad_ws_needs_zero(int b, int c, int m_targets, long long n_sources, int slots_per_source);
+/* Host-only (ABI 8): the form the *_grad_ws / _grad_out / _grad_from entry points take for these sizes -- 1 = the sorted
+ * pair stream (tiles), 2 = the whole-row list walk (csr), 3 = the channels-last scatter with float atomics in the
+ * workspace, 0 = nothing to launch -- under the same GEOT_GATHER_IMPL as the launches.  For 1, out receives the first
+ * n_out of: channels per workgroup, sources per tile, tiles, pairs per tile, entry slots per tile, LDS bytes of the
+ * scatter, LDS bytes of the sort, workspace words.  out is a HOST array. */
+int geot_scatter_grad_plan(int b, int c, int m_targets, long long n_sources, int slots_per_source, int weighted,
+                           long long *out, int n_out);
 int geot_three_interpolate_grad_ws(int b, int c, int n, int m, const float *grad_out, const int *idx,
                                    const float *weight, float *grad_points, float *workspace,
                                    void *stream);

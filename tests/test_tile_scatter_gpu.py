@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from _scatter_ref import rel, scatter64
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
@@ -13,23 +15,6 @@ DEV = "cuda"
 def dev(a, dtype=None):
     t = torch.from_numpy(np.ascontiguousarray(a))
     return (t if dtype is None else t.to(dtype)).to(DEV)
-
-
-def rel(got, want64):
-    """largest error relative to the scale of the element's row (the tolerance rule of tests/test_ref_fixtures_gpu.py)"""
-    got, want64 = got.double().cpu(), want64.double().cpu()
-    scale = want64.abs().amax(dim=-1, keepdim=True).clamp_min(1e-30)
-    return float(((got - want64).abs() / scale).max())
-
-
-def scatter64(g, idx, w, m):
-    """fp64 restatement: out[b, c, idx[b, e, t]] += w[b, e, t] * g[b, c, e]"""
-    b, c, L = g.shape
-    nt = idx.shape[-1]
-    src = g.double().cpu().unsqueeze(-1) * (w.double().cpu().unsqueeze(1) if w is not None else 1.0)
-    out = torch.zeros(b, c, m, dtype=torch.float64)
-    out.scatter_add_(2, idx.long().cpu().reshape(b, 1, L * nt).expand(-1, c, -1), src.reshape(b, c, L * nt).expand(b, c, L * nt))
-    return out
 
 
 def case(b, c, n, m, seed, hubs=False, dup_slots=False):
