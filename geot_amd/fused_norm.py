@@ -10,7 +10,9 @@ only a parameter / buffer container here; tensors the kernels do not cover (CPU,
 Further down: the small autograd ops that replace runs of torch launches around the dense layers (profiles/DESIGN_r01_r03.md 4.10) --
 ``max_last``, ``add_last_broadcast``, ``thin_mm``, ``linear`` (bias gradient as column sums), ``res_ln`` (residual add +
 LayerNorm), ``qkv_split`` (attention head split) and ``softmax_last``.  Each falls back to the torch composition where its
-kernel does not apply, so callers never branch.
+kernel does not apply, so callers never branch.  The float4 kernels (segment max / sum, bn_pool, qkv_split) refuse storage
+that is not 16-byte aligned: a contiguous view can start at any element, and autograd can hand a backward such a
+gradient (a slice of a cat), so the forward wrappers check it (_aligned16) and the backwards copy (_fresh16).
 """
 import torch
 import torch.nn as nn
@@ -19,6 +21,17 @@ from torch.autograd import Function
 from . import _lib
 from .ext._common import call, ptr
 from .pointnet2 import pointnet2_utils as pt_utils
+
+
+def _aligned16(t):
+    """does t's first element sit on a 16-byte boundary (what the float4 kernels need)?"""
+    return t.data_ptr() % 16 == 0
+
+
+def _fresh16(t):
+    """t contiguous and 16-byte aligned: as it is, or a copy in fresh (caching-allocator aligned) storage"""
+    t = t.contiguous()
+    return t if _aligned16(t) else t.clone()
 
 
 def _sync_group(bn):
@@ -564,7 +577,7 @@ class _SegmentMaxFn(Function):
     @staticmethod
     def backward(ctx, dy):
         arg, = ctx.saved_tensors
-        dy = dy.contiguous()
+        dy = dy.contiguous()                            # read per row: any alignment (dx, fresh, takes the float4 stores)
         dx = torch.empty(tuple(arg.shape) + (ctx.n,), dtype=torch.float32, device=dy.device)
         call("geot_segment_max_grad", dy.device, arg.numel(), ctx.n, ptr(dy), ptr(arg), ptr(dx))
         return dx, None
@@ -574,7 +587,8 @@ def max_last(x):
     """x.max(dim=-1)[0] for a contiguous float32 GPU tensor whose last dimension is a multiple of 4 and <= 256 (the
     group / nsample axis): one streaming kernel each way instead of torch's generic reduction + index scatter."""
     n = x.shape[-1]
-    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and 4 <= n <= 256 and n % 4 == 0 and x.numel() > 0):
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and 4 <= n <= 256 and n % 4 == 0 and x.numel() > 0
+            and _aligned16(x)):
         return x.max(dim=-1)[0]
     return _SegmentMaxFn.apply(x, n)
 
@@ -587,7 +601,7 @@ class _AddLastBroadcastFn(Function):
 
     @staticmethod
     def backward(ctx, g):
-        g = g.contiguous()
+        g = _fresh16(g)
         gp = torch.empty(g.shape[:-1], dtype=torch.float32, device=g.device)
         call("geot_segment_sum", g.device, gp.numel(), ctx.n, ptr(g), ptr(gp))
         return g, gp
@@ -772,7 +786,7 @@ class _QkvSplitFn(Function):
     @staticmethod
     def backward(ctx, gq, gk, gv):
         b, n, heads, d, scale = ctx.cfg
-        gq, gk, gv = (None if g is None else g.contiguous() for g in (gq, gk, gv))
+        gq, gk, gv = (None if g is None else _fresh16(g) for g in (gq, gk, gv))
         dev = next(g for g in (gq, gk, gv) if g is not None).device
         grad = torch.empty((b, n, 3 * heads * d), dtype=torch.float32, device=dev)
         call("geot_qkv_split_grad", dev, b, n, heads, d, scale, ptr(gq), ptr(gk), ptr(gv), ptr(grad))
@@ -782,7 +796,7 @@ class _QkvSplitFn(Function):
 def qkv_split(qkv, heads, scale):
     """qkv (B, N, 3*H*d) -> (q * scale, k, v), each (B*H, N, d) contiguous (csrc/layernorm.hip); None where it does not apply."""
     if not (qkv.is_cuda and qkv.dtype == torch.float32 and qkv.dim() == 3 and qkv.is_contiguous() and qkv.numel() > 0
-            and qkv.shape[2] % (3 * heads) == 0 and (qkv.shape[2] // (3 * heads)) % 4 == 0):
+            and qkv.shape[2] % (3 * heads) == 0 and (qkv.shape[2] // (3 * heads)) % 4 == 0 and _aligned16(qkv)):
         return None
     return _QkvSplitFn.apply(qkv, heads, scale)
 
@@ -853,5 +867,7 @@ def bn_relu_max(bn, y, n):
     if not fused:
         return max_last(bn_act(bn, y, relu=True).view(b, c, l // n, n))
     y = y.contiguous()
+    if not _aligned16(y):                                                   # (bn_pool reads y as float4)
+        return max_last(bn_act(bn, y, relu=True).view(b, c, l // n, n))
     stats, count, _ = _batch_statistics(bn, y, bn.weight, bn.bias, None, None)
     return _BnPoolFn.apply(y, bn.weight, bn.bias, stats, n, count)

@@ -215,7 +215,8 @@ int geot_res_ln_grad(int rows, int c, int rows_per_sample, const float *gz, cons
 /* Attention head split (transformer.py:70-72): the (b, n, 3, h, d) qkv projection -> out (3, b*h, n, d) = (q * scale, k,
  * v) contiguous for the batched GEMMs, d a multiple of 4; _grad: three (b*h, n, d) gradients (NULL: zero) back into
  * the (b, n, 3, h, d) gradient with d q scaled -- one launch each instead of a stack, a permuted copy and an
- * element-wise pass over the (b, h, n, n) score gradient. */
+ * element-wise pass over the (b, h, n, n) score gradient.  Every pointer given (qkv, out; gq, gk, gv, grad_qkv) must be
+ * 16-byte aligned: hipErrorInvalidValue otherwise. */
 int geot_qkv_split(int b, int n, int h, int d, float scale, const float *qkv, float *out, void *stream);
 int geot_qkv_split_grad(int b, int n, int h, int d, float scale, const float *gq, const float *gk, const float *gv,
                         float *grad_qkv, void *stream);
