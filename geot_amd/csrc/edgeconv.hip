@@ -25,6 +25,9 @@ namespace geot {
 
 constexpr int EC_THREADS = 1024;
 constexpr int EC_LDS_BYTES = 150 * 1024; // of the CU's 160 KB
+constexpr int EC_REC = 4;                 // floats per forward (channel, slice) record: s1, s2, pivot, count
+constexpr int EC_MAX_SLICES = 32;         // forward and dP grids; the backward's reduce takes at most EC_MAX_RED_SLICES
+constexpr int EC_MAX_RED_SLICES = 16;
 
 __device__ __forceinline__ void ec_load_row(float *__restrict__ dst, const float *__restrict__ src, int count)
 {
@@ -55,7 +58,13 @@ __device__ __forceinline__ float ec_wave_sum(float v)
 }
 
 // ---- forward 1: gather + add, select over k, sums for the statistics ---------------------------------------
-// K4: k == 4 and the index rows are int4-aligned (the configured backbone); otherwise the generic k loop.
+// K4: k == 4 and idx 16-byte aligned (the host checks the pointer: every index row is then one int4 load); otherwise the
+// generic k loop.  The other vector accesses check their own alignment (ec_load_row; edge_out_kernel).
+// The statistics are accumulated SHIFTED, as bn_stats_kernel's: a (channel, slice) sums d = y - p and d^2 around a pivot
+// p = the y of the slice's first pair, in fp32, and hands over (s1, s2, p, count); edge_stats_kernel rebuilds sum y and
+// sum y^2 in fp64.  (Plain fp32 sums of y and y^2 lose (mean / std)^2 of the variance's digits: P and Q carry whatever
+// offset the features have.)
+// grid (slices, ceil(c / CH), b): partial[((b * c + ch) * slices + s) * EC_REC + {0..3}] = s1, s2, pivot, count
 template <bool K4, int CH>
 __global__ __launch_bounds__(EC_THREADS) void edge_fwd_kernel(
     int c, int nq, int nk, int k, const float *__restrict__ P, const float *__restrict__ Q,
@@ -69,12 +78,16 @@ __global__ __launch_bounds__(EC_THREADS) void edge_fwd_kernel(
     bool want_max[CH];
 #pragma unroll
     for (int l = 0; l < CH; ++l) want_max[l] = l < nch ? gamma[c0 + l] >= 0.f : true;
-    __syncthreads();
     const int per = (nq + gridDim.x - 1) / gridDim.x;
     const int i0 = blockIdx.x * per, i1 = min(nq, i0 + per);
-    float s[CH], ss[CH];
+    const int n0 = i0 < i1 ? idx[(size_t)bi * nq * k + (size_t)i0 * k] : 0;
+    __syncthreads();
+    float s[CH], ss[CH], piv[CH];
 #pragma unroll
-    for (int l = 0; l < CH; ++l) s[l] = ss[l] = 0.f;
+    for (int l = 0; l < CH; ++l) {
+        s[l] = ss[l] = 0.f;
+        piv[l] = l < nch && i0 < i1 ? ec_rows[l * nk + n0] + Q[((size_t)bi * c + c0 + l) * nq + i0] : 0.f;
+    }
     if (K4 && nch == CH) {
         // The configured case, written for loads in flight: the indices and the CH values of Q of the NEXT query are requested
         // (unconditionally, index clamped) before this query's 3 CH stores are issued, so the wait at the top of the loop is a
@@ -112,14 +125,14 @@ __global__ __launch_bounds__(EC_THREADS) void edge_fwd_kernel(
                     int bj = 0;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const float y = pv[l][j] + qv[l];
+                        const float y = pv[l][j] + qv[l], d = y - piv[l];
                         sum += y;
-                        ss[l] = fmaf(y, y, ss[l]);
+                        s[l] += d;
+                        ss[l] = fmaf(d, d, ss[l]);
                         const bool take = j == 0 || (want_max[l] ? y > best : y < best); // first extremum wins
                         best = take ? y : best;
                         bj = take ? j : bj;
                     }
-                    s[l] += sum;
                     const size_t o = qb + (size_t)l * nq + i;
                     ysel[o] = best;
                     ysum[o] = sum;
@@ -146,14 +159,14 @@ __global__ __launch_bounds__(EC_THREADS) void edge_fwd_kernel(
                     int bj = 0;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
-                        const float y = R[nn[j]] + q;
+                        const float y = R[nn[j]] + q, d = y - piv[l];
                         sum += y;
-                        ss[l] = fmaf(y, y, ss[l]);
+                        s[l] += d;
+                        ss[l] = fmaf(d, d, ss[l]);
                         const bool take = j == 0 || (want_max[l] ? y > best : y < best); // first extremum wins
                         best = take ? y : best;
                         bj = take ? j : bj;
                     }
-                    s[l] += sum;
                     ysel[o] = best;
                     ysum[o] = sum;
                     jsel[o] = (uint8_t)bj;
@@ -169,14 +182,14 @@ __global__ __launch_bounds__(EC_THREADS) void edge_fwd_kernel(
                     float best = 0.f, sum = 0.f;
                     int bj = 0;
                     for (int j = 0; j < k; ++j) {
-                        const float y = R[idx[row * k + j]] + q;
+                        const float y = R[idx[row * k + j]] + q, d = y - piv[l];
                         sum += y;
-                        ss[l] = fmaf(y, y, ss[l]);
+                        s[l] += d;
+                        ss[l] = fmaf(d, d, ss[l]);
                         const bool take = j == 0 || (want_max[l] ? y > best : y < best);
                         best = take ? y : best;
                         bj = take ? j : bj;
                     }
-                    s[l] += sum;
                     ysel[o] = best;
                     ysum[o] = sum;
                     jsel[o] = (uint8_t)bj;
@@ -196,20 +209,28 @@ __global__ __launch_bounds__(EC_THREADS) void edge_fwd_kernel(
         if (l < nch) {
             float t = 0.f;
             for (int v = 0; v < EC_THREADS / 64; ++v) t += red[v][l][w]; // fixed order: deterministic
-            partial[(((size_t)bi * c + c0 + l) * gridDim.x + blockIdx.x) * 2 + w] = t;
+            float *dst = partial + (((size_t)bi * c + c0 + l) * gridDim.x + blockIdx.x) * EC_REC;
+            dst[w] = t;
+            dst[2 + w] = w ? (float)(max(i1 - i0, 0) * k) : piv[l];   // count < 2^24: exact
         }
     }
 }
 
-// ---- forward 2: per (batch, group) mean and 1/sqrt(var + eps) from the per-(channel, slice) partial sums ----
+// ---- forward 2: per (batch, group) mean and 1/sqrt(var + eps) from the per-(channel, slice) shifted sums ----
+// sum y = s1 + n p and sum y^2 = s2 + 2 p s1 + n p^2, in fp64 (exact products of fp32 values but n p^2)
 __global__ __launch_bounds__(256) void edge_stats_kernel(int c, int groups, int slices, double count, float eps,
                                                          const float *__restrict__ partial, float *__restrict__ stats)
 {
     __shared__ double red[256][2];
     const int bg = blockIdx.x, bi = bg / groups, g = bg - bi * groups, cpg = c / groups;
-    const float *src = partial + ((size_t)bi * c + (size_t)g * cpg) * slices * 2;
+    const float *src = partial + ((size_t)bi * c + (size_t)g * cpg) * slices * EC_REC;
     double a = 0.0, b = 0.0;
-    for (int e = threadIdx.x; e < cpg * slices; e += 256) { a += src[2 * e]; b += src[2 * e + 1]; }
+    for (int e = threadIdx.x; e < cpg * slices; e += 256) {
+        const float *r = src + (size_t)e * EC_REC;
+        const double s1 = r[0], s2 = r[1], p = r[2], n = r[3];
+        a += s1 + n * p;
+        b += s2 + 2.0 * p * s1 + n * p * p;
+    }
     red[threadIdx.x][0] = a;
     red[threadIdx.x][1] = b;
     __syncthreads();
@@ -539,15 +560,13 @@ __global__ __launch_bounds__(EC_THREADS) void edge_bwd_p_kernel(
 // CU, 492 us per step; <= 4: 466; <= 2: 448 -- profiles/r03_edge_sweep.txt); longer rows take what the CU's LDS holds
 static int ec_fwd_ch(int nk)
 {
-    int fit = 64 * 1024 / ((int)sizeof(float) * nk);
-    if (fit < 1) fit = EC_LDS_BYTES / ((int)sizeof(float) * nk);
-    if (fit > 4) fit = 4;
-    return fit >= 8 ? 8 : (fit >= 4 ? 4 : (fit >= 2 ? 2 : (fit >= 1 ? 1 : 0)));
+    long long fit = 64 * 1024 / ((long long)sizeof(float) * nk);
+    if (fit < 1) fit = EC_LDS_BYTES / ((long long)sizeof(float) * nk);
+    return fit >= 4 ? 4 : (fit >= 2 ? 2 : (fit >= 1 ? 1 : 0));
 }
 static int ec_bwd_ch(int nq)
 {
-    int fit = EC_LDS_BYTES / (9 * nq);
-    if (fit > 4) fit = 4;
+    const long long fit = EC_LDS_BYTES / (9LL * nq);
     return fit >= 4 ? 4 : (fit >= 2 ? 2 : (fit >= 1 ? 1 : 0));
 }
 // lanes per target in the dP walk (log2): a lane's share of the mean list is about EC_E pairs
@@ -565,14 +584,42 @@ static int ec_slices(int b, int c, int ch, int n)
     const long long maxs = n / 2048;
     if (sl > maxs) sl = maxs;
     if (sl < 1) sl = 1;
-    if (sl > 32) sl = 32;
+    if (sl > EC_MAX_SLICES) sl = EC_MAX_SLICES;
     return (int)sl;
 }
-static bool ec_ok(int b, int c, int nq, int nk, int k, int groups)
+
+// Every sizing decision of the launchers, in one place: geot_edgeconv_gn_max, ec_grad, geot_edgeconv_ws_bytes and the
+// host-only query geot_edgeconv_plan all read it, so the query cannot drift from the dispatch.  The sizes are formed for
+// any positive b, c, nq, nk, k; ok says whether the kernels take the shape.
+// Workspace: [partials: b c EC_MAX_SLICES EC_REC floats | reverse index of idx (EcRix)]; the forward's records and the
+// backward's (s, dz-sums) pairs both start at the partials' base, the backward's per-group coefficients sit at their tail.
+struct EcPlan {
+    bool ok, k4;
+    int fwd_ch, fwd_slices, red_slices, bwd_ch, pslices, lg;
+    long long fwd_lds, bwd_lds, part_floats, coef_off, rix_off, ws_bytes;
+};
+static EcPlan ec_plan(int b, int c, int nq, int nk, int k, int groups)
 {
-    return b >= 1 && c >= 1 && nq >= 1 && nk >= 1 && k >= 1 && k <= 255 && groups >= 1 && c % groups == 0 &&
-           b <= 65535 && c <= 65535 * 8 && ec_fwd_ch(nk) >= 1 && ec_bwd_ch(nq) >= 1 &&
-           (long long)b * nq * k <= 0x7fffffffLL && (long long)nq * k <= 0x7fffffffLL;
+    EcPlan p = {};
+    if (b < 1 || c < 1 || nq < 1 || nk < 1 || k < 1) return p;
+    p.fwd_ch = ec_fwd_ch(nk);
+    p.bwd_ch = ec_bwd_ch(nq);
+    p.k4 = k == 4;
+    p.fwd_slices = ec_slices(b, c, p.fwd_ch > 0 ? p.fwd_ch : 1, nq);
+    p.fwd_lds = (long long)p.fwd_ch * nk * (long long)sizeof(float);
+    p.red_slices = std::min(ec_slices(b, c, 1, nq), EC_MAX_RED_SLICES);
+    p.pslices = ec_slices(b, c, p.bwd_ch > 0 ? p.bwd_ch : 1, nk);
+    p.bwd_lds = (long long)p.bwd_ch * nq * 9;               // (a, u) float2 + jsel byte per query and channel
+    p.lg = ec_lanes_log2(nq, nk, k);
+    p.part_floats = (long long)b * c * EC_MAX_SLICES * EC_REC;
+    p.coef_off = p.part_floats - 2LL * b * (groups > 0 ? groups : 1) - 8;
+    p.rix_off = p.part_floats * (long long)sizeof(float);
+    const long long t = (long long)b * nk, pairs = (long long)b * nq * k;
+    const long long rix = ((t + 1) + scan_blocks(t) + 3 * pairs + 8) * (long long)sizeof(int);   // counts, scan, rank, rev, pair ids
+    p.ws_bytes = p.rix_off + rix + 256;
+    p.ok = k <= 255 && groups >= 1 && c % groups == 0 && b <= 65535 && c <= 65535 && p.fwd_ch >= 1 && p.bwd_ch >= 1 &&
+           pairs <= 0x7ffffff0LL && t <= 0x7ffffff0LL;
+    return p;
 }
 template <typename K>
 static hipError_t ec_allow_lds(K kernel, size_t lds)
@@ -586,16 +633,24 @@ using namespace geot;
 
 GEOT_EXPORT int geot_edgeconv_eligible(int b, int c, int nq, int nk, int k, int groups)
 {
-    return ec_ok(b, c, nq, nk, k, groups) ? 1 : 0;
+    return ec_plan(b, c, nq, nk, k, groups).ok ? 1 : 0;
 }
 
-// bytes of scratch both directions need (partials; reverse index)
+// bytes of scratch both directions need (partials; reverse index); the layout does not depend on groups
 GEOT_EXPORT long long geot_edgeconv_ws_bytes(int b, int c, int nq, int nk, int k)
 {
-    const long long part = (long long)b * c * 32 * 2 * (long long)sizeof(float);
-    const long long t = (long long)b * nk, pairs = (long long)b * nq * k;
-    const long long rix = ((t + 1) + scan_blocks(t) + 3 * pairs + 8) * (long long)sizeof(int);   // counts, scan, rank, rev, pair ids
-    return part + rix + 256;
+    return ec_plan(b, c, nq, nk, k, 1).ws_bytes;
+}
+
+GEOT_EXPORT int geot_edgeconv_plan(int b, int c, int nq, int nk, int k, int groups, long long *out, int n_out)
+{
+    const EcPlan p = ec_plan(b, c, nq, nk, k, groups);
+    if (p.ok && out) {
+        const long long v[14] = {p.fwd_ch, p.fwd_slices, p.fwd_lds, p.k4, p.red_slices, p.bwd_ch, p.pslices, p.bwd_lds,
+                                 p.lg, EC_REC, p.part_floats, p.coef_off, p.rix_off, p.ws_bytes};
+        for (int i = 0; i < n_out && i < 14; ++i) out[i] = v[i];
+    }
+    return p.ok ? 1 : 0;
 }
 
 GEOT_EXPORT int geot_edgeconv_gn_max(int b, int c, int nq, int nk, int k, int groups, float eps, float slope,
@@ -603,13 +658,14 @@ GEOT_EXPORT int geot_edgeconv_gn_max(int b, int c, int nq, int nk, int k, int gr
                                      const float *beta, float *out, float *ysel, float *ysum, unsigned char *jsel,
                                      float *stats, void *workspace, long long ws_bytes, void *stream)
 {
-    if (!ec_ok(b, c, nq, nk, k, groups) || ws_bytes < geot_edgeconv_ws_bytes(b, c, nq, nk, k)) return hipErrorInvalidValue;
+    const EcPlan p = ec_plan(b, c, nq, nk, k, groups);
+    if (!p.ok || ws_bytes < p.ws_bytes) return hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
     float *partial = (float *)workspace;
-    const int ch = ec_fwd_ch(nk), slices = ec_slices(b, c, ch, nq);
-    const size_t lds = (size_t)ch * nk * sizeof(float);
+    const int ch = p.fwd_ch, slices = p.fwd_slices;
+    const size_t lds = (size_t)p.fwd_lds;
     const dim3 grid(slices, (c + ch - 1) / ch, b);
-    const bool k4 = k == 4;
+    const bool k4 = p.k4 && ((uintptr_t)idx & 15) == 0;     // int4 index rows
     hipError_t e = hipSuccess;
 #define GEOT_EC_FWD(KV, CHV)                                                                                       \
     {                                                                                                              \
@@ -619,9 +675,9 @@ GEOT_EXPORT int geot_edgeconv_gn_max(int b, int c, int nq, int nk, int k, int gr
                            gamma, ysel, ysum, jsel, partial);                                                      \
     }
     if (k4) {
-        if (ch == 8) GEOT_EC_FWD(true, 8) else if (ch == 4) GEOT_EC_FWD(true, 4) else if (ch == 2) GEOT_EC_FWD(true, 2) else GEOT_EC_FWD(true, 1)
+        if (ch == 4) GEOT_EC_FWD(true, 4) else if (ch == 2) GEOT_EC_FWD(true, 2) else GEOT_EC_FWD(true, 1)
     } else {
-        if (ch == 8) GEOT_EC_FWD(false, 8) else if (ch == 4) GEOT_EC_FWD(false, 4) else if (ch == 2) GEOT_EC_FWD(false, 2) else GEOT_EC_FWD(false, 1)
+        if (ch == 4) GEOT_EC_FWD(false, 4) else if (ch == 2) GEOT_EC_FWD(false, 2) else GEOT_EC_FWD(false, 1)
     }
 #undef GEOT_EC_FWD
     e = hipGetLastError();
@@ -692,15 +748,15 @@ static int ec_grad(int b, int c, int nq, int nk, int k, int groups, float slope,
                    const float *stats, const float *grad_out, float *grad_p, float *grad_q, float *grad_gamma, float *grad_beta,
                    void *workspace, long long ws_bytes, const int *rix, hipStream_t s)
 {
-    if (!ec_ok(b, c, nq, nk, k, groups) || ws_bytes < geot_edgeconv_ws_bytes(b, c, nq, nk, k)) return hipErrorInvalidValue;
+    const EcPlan p = ec_plan(b, c, nq, nk, k, groups);
+    if (!p.ok || ws_bytes < p.ws_bytes) return hipErrorInvalidValue;
     float *bpart = (float *)workspace;
-    float *coef = bpart + (size_t)b * c * 32 * 2 - (size_t)b * groups * 2 - 8; // tail of the partials area (slices <= 16 used)
-    int slices = ec_slices(b, c, 1, nq);
-    if (slices > 16) slices = 16;
+    float *coef = bpart + p.coef_off;      // tail of the partials area, past the reduce's b c red_slices pairs
+    const int slices = p.red_slices;
     const EcRix r = ec_rix_layout(b, nq, nk, k);
     hipError_t e;
     if (!rix) {                 // no index given: build it in the workspace, on this stream
-        int *own = (int *)((char *)workspace + (size_t)b * c * 32 * 2 * sizeof(float));
+        int *own = (int *)((char *)workspace + p.rix_off);
         e = ec_rix_build(b, nq, nk, k, idx, own, s);
         if (e != hipSuccess) return e;
         rix = own;
@@ -712,11 +768,10 @@ static int ec_grad(int b, int c, int nq, int nk, int k, int groups, float slope,
     const double count = (double)(c / groups) * nq * k;
     hipLaunchKernelGGL(edge_bwd_coef_kernel, dim3(b * groups + (c + 255) / 256), dim3(256), 0, s, b, c, groups, slices, count,
                        gamma, bpart, coef, grad_gamma, grad_beta);
-    const int ch = ec_bwd_ch(nq), pslices = ec_slices(b, c, ch, nk);
-    const size_t lds = (size_t)ch * nq * 9;
+    const int ch = p.bwd_ch, pslices = p.pslices, lg = p.lg;
+    const size_t lds = (size_t)p.bwd_lds;
     const dim3 grid(pslices, (c + ch - 1) / ch, b);
-    const bool k4 = k == 4;
-    const int lg = ec_lanes_log2(nq, nk, k);
+    const bool k4 = p.k4;
 #define GEOT_EC_BWD(KV, CHV)                                                                                       \
     {                                                                                                              \
         e = ec_allow_lds(edge_bwd_p_kernel<KV, CHV>, lds);                                                         \

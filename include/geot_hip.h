@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 8
+#define GEOT_ABI_VERSION 9
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
 
 /* ABI version / diagnostics. */
@@ -336,10 +336,18 @@ int geot_gather_rows_csr_bn_cl(int b, int c, int L, int m, int nt, int relu, con
  * (b,c,nq) the selected y, ysum (b,c,nq) = sum_j y, jsel (b,c,nq) uint8 the selected slot, stats (b,groups,2) =
  * (mean, 1/sqrt(var+eps)).  _grad writes grad_p (b,c,nk), grad_q (b,c,nq), grad_gamma (c), grad_beta (c) in full
  * (no atomics: deterministic).  workspace: geot_edgeconv_ws_bytes() bytes of scratch, contents irrelevant.
- * Needs slope >= 0, c % groups == 0, k <= 255 and rows that fit the LDS (nk <= 38400, nq <= 17066):
- * geot_edgeconv_eligible() tells; callers fall back to the composed ops otherwise. */
+ * Needs slope >= 0, c % groups == 0, k <= 255, b <= 65535, c <= 65535, b nq k and b nk <= 2^31 - 16, and rows that
+ * fit the LDS (nk <= 38400, nq <= 17066): geot_edgeconv_eligible() tells; callers fall back to the composed ops
+ * otherwise.  Any alignment of the arrays is taken (16-byte aligned idx with k = 4 takes the int4 index loads). */
 int geot_edgeconv_eligible(int b, int c, int nq, int nk, int k, int groups);
 long long geot_edgeconv_ws_bytes(int b, int c, int nq, int nk, int k);
+/* Host-only (ABI 9): the launch plan of geot_edgeconv_gn_max[_grad[_rix]] for these sizes, from the function the
+ * launches use.  Returns 1 and fills the first n_out of: forward channels per workgroup, forward slices, forward LDS
+ * bytes, k == 4 instances (1/0), backward-reduce slices, dP channels per workgroup, dP slices, dP LDS bytes, dP lanes
+ * per target (log2), floats per forward partial record, floats of the partials area, float offset of the backward's
+ * per-group coefficients, byte offset of the reverse index, workspace bytes -- when the shape is eligible; returns 0
+ * and leaves out alone otherwise.  out is a HOST array. */
+int geot_edgeconv_plan(int b, int c, int nq, int nk, int k, int groups, long long *out, int n_out);
 int geot_edgeconv_gn_max(int b, int c, int nq, int nk, int k, int groups, float eps, float slope, const float *P,
                          const float *Q, const int *idx, const float *gamma, const float *beta, float *out,
                          float *ysel, float *ysum, unsigned char *jsel, float *stats, void *workspace,

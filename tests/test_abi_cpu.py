@@ -126,6 +126,18 @@ def test_host_only_planning_entry_points(monkeypatch):
     assert lib.geot_grad_ws_needs_zero(1, 16, 8192, 24000, 3) == 1           # workspace too small for their index
     monkeypatch.delenv("GEOT_GATHER_IMPL")
     assert lib.geot_sa_param_floats(3, 3, (__import__("ctypes").c_int * 3)(64, 64, 128)) == 6 * 64 + 64 + 64 * 64 + 64 + 64 * 128 + 128
+    # fused EdgeConv tail (ABI 9): the plan of an eligible shape, nothing for one that is not; workspace = its query
+    import ctypes
+    out = (ctypes.c_longlong * 14)(*([-7] * 14))
+    assert lib.geot_edgeconv_plan(8, 384, 8192, 8192, 4, 4, out, 14) == 1
+    assert list(out)[:10] == [2, 1, 65536, 1, 1, 2, 1, 147456, 0, 4]
+    assert out[13] == lib.geot_edgeconv_ws_bytes(8, 384, 8192, 8192, 4) and lib.geot_edgeconv_eligible(8, 384, 8192, 8192, 4, 4) == 1
+    short = (ctypes.c_longlong * 14)(*([-7] * 14))
+    assert lib.geot_edgeconv_plan(8, 384, 8192, 8192, 4, 4, short, 2) == 1 and list(short) == [2, 1] + [-7] * 12
+    for args in ((8, 384, 8192, 8192, 4, 5), (1, 8, 100, 100, 256, 1), (1, 8, 100, 38401, 4, 1), (1, 8, 17067, 100, 4, 1)):
+        untouched = (ctypes.c_longlong * 14)(*([-7] * 14))
+        assert lib.geot_edgeconv_plan(*args, untouched, 14) == 0 and list(untouched) == [-7] * 14
+        assert lib.geot_edgeconv_eligible(*args) == 0
 
 
 def test_header_is_plain_c_and_links(tmp_path):
