@@ -150,6 +150,8 @@ PLAIN = {
     "geot_ball_grid_eligible": ([_c_int, _c_int, _c_int, _c_float, _c_int], _c_int),
     "geot_edgeconv_eligible": ([_c_int] * 6, _c_int),
     "geot_edgeconv_plan": ([_c_int] * 6 + [ctypes.POINTER(ctypes.c_longlong), _c_int], _c_int),
+    "geot_sa_plan": ([_c_int] * 5 + [ctypes.POINTER(_c_int), _c_int, _c_int, ctypes.POINTER(ctypes.c_longlong), _c_int],
+                     _c_int),
     "geot_bn_slices": ([_c_int] * 3, _c_int),
     "geot_fp_front_slices": ([_c_int] * 4, _c_int),
     "geot_cl_tiles": ([_c_int, ctypes.c_longlong, _c_int], _c_int),
@@ -164,7 +166,7 @@ PLAIN = {
     "geot_rowdot_small_slices": ([_c_int] * 2, _c_int),
     "geot_colsum_ws_floats": ([_c_int] * 2, ctypes.c_longlong),
 }
-ABI_VERSION = 9     # include/geot_hip.h GEOT_ABI_VERSION this binding was written against
+ABI_VERSION = 10    # include/geot_hip.h GEOT_ABI_VERSION this binding was written against
 
 _lib = None
 

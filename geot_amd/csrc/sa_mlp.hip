@@ -18,6 +18,7 @@
 // A-fragment read, lane -> (row = lane&31, k = lane>>5), is bank-conflict free), weights
 // for all layers sit in LDS as W^T [K][C] (B-fragment read is lane-contiguous).  No
 // cross-wave synchronisation after the initial weight load.
+#include <algorithm>
 #include <cstdint>
 #include <cstdlib>
 #include <type_traits>
@@ -38,10 +39,15 @@ struct SaDesc {
     int cp[SA_MAX_LAYERS];   // padded output width of layer l (32, 64, 128 or 256)
     int woff[SA_MAX_LAYERS]; // float offset of W^T [kp][cp] in the parameter block
     int boff[SA_MAX_LAYERS]; // float offset of bias [cp]
+    int w[SA_MAX_LAYERS];    // unpadded output width of layer l (the columns past it are stored as 0)
     int relu_mask;           // bit l = ReLU after layer l
     int total;               // floats in the parameter block
     int act_stride;          // floats per activation row (widest STORED activation + 1, odd; the last layer is pooled from registers)
 };
+
+// max that propagates NaN like torch.relu / torch.max (fmaxf returns the other operand): llvm.maximum, one
+// v_maximum3_f32 on gfx950.  It also orders -0 below +0, so any order of the same maxima gives the same bits.
+__device__ __forceinline__ float sa_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
 
 template <int NCT>
 __device__ __forceinline__ void sa_layer(const float *__restrict__ W, const float *__restrict__ bias,
@@ -69,22 +75,27 @@ __device__ __forceinline__ void sa_layer(const float *__restrict__ W, const floa
 #pragma unroll
         for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) acc[ct][e] = fmaxf(acc[ct][e], 0.f);
+            for (int e = 0; e < 16; ++e) acc[ct][e] = sa_max(acc[ct][e], 0.f);
     }
 }
 
 // D layout of the 32x32 tile: col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5).
+// Columns at or past the layer's width w are stored as 0: their weights and bias are 0, but 0 * inf is NaN, and the
+// next layer's (zero) weights would carry that NaN into every real column where the composed module has none.
 template <int NCT>
-__device__ __forceinline__ void sa_store_act(const f32x16 (&acc)[NCT], float *__restrict__ act, int act_stride)
+__device__ __forceinline__ void sa_store_act(const f32x16 (&acc)[NCT], float *__restrict__ act, int act_stride, int w)
 {
     const int lane = lane_id(), c = lane & 31, h = lane >> 5;
+    const bool padded = w < NCT * 32;   // uniform over the wave
 #pragma unroll
-    for (int ct = 0; ct < NCT; ++ct)
+    for (int ct = 0; ct < NCT; ++ct) {
+        const bool live = ct * 32 + c < w;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             int row = (e & 3) + 8 * (e >> 2) + 4 * h;
-            act[row * act_stride + ct * 32 + c] = acc[ct][e];
+            act[row * act_stride + ct * 32 + c] = (!padded || live) ? acc[ct][e] : 0.f;
         }
+    }
 }
 
 // Max over the rows of each group inside the tile, merged into pool[g_local][col].
@@ -98,19 +109,19 @@ __device__ __forceinline__ void sa_pool(const f32x16 (&acc)[NCT], float *__restr
         float m[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float v = fmaxf(fmaxf(acc[ct][4 * j], acc[ct][4 * j + 1]), fmaxf(acc[ct][4 * j + 2], acc[ct][4 * j + 3]));
-            m[j] = fmaxf(v, __shfl_xor(v, 32));
+            float v = sa_max(sa_max(acc[ct][4 * j], acc[ct][4 * j + 1]), sa_max(acc[ct][4 * j + 2], acc[ct][4 * j + 3]));
+            m[j] = sa_max(v, __shfl_xor(v, 32));
         }
         if (lane < 32) {
             if (gpt == 1) {
-                float v = fmaxf(fmaxf(m[0], m[1]), fmaxf(m[2], m[3]));
-                pool[ct * 32 + c] = fmaxf(pool[ct * 32 + c], v);
+                float v = sa_max(sa_max(m[0], m[1]), sa_max(m[2], m[3]));
+                pool[ct * 32 + c] = sa_max(pool[ct * 32 + c], v);
             } else if (gpt == 2) {
-                pool[ct * 32 + c] = fmaxf(pool[ct * 32 + c], fmaxf(m[0], m[1]));
-                pool[cp + ct * 32 + c] = fmaxf(pool[cp + ct * 32 + c], fmaxf(m[2], m[3]));
+                pool[ct * 32 + c] = sa_max(pool[ct * 32 + c], sa_max(m[0], m[1]));
+                pool[cp + ct * 32 + c] = sa_max(pool[cp + ct * 32 + c], sa_max(m[2], m[3]));
             } else {
 #pragma unroll
-                for (int j = 0; j < 4; ++j) pool[j * cp + ct * 32 + c] = fmaxf(pool[j * cp + ct * 32 + c], m[j]);
+                for (int j = 0; j < 4; ++j) pool[j * cp + ct * 32 + c] = sa_max(pool[j * cp + ct * 32 + c], m[j]);
             }
         }
     }
@@ -128,8 +139,8 @@ __device__ __forceinline__ void sa_pool_direct(const f32x16 (&acc)[NCT], float (
     for (int ct = 0; ct < NCT; ++ct) {
         float v = acc[ct][0];
 #pragma unroll
-        for (int e = 1; e < 16; ++e) v = fmaxf(v, acc[ct][e]);
-        val[ct] = fmaxf(v, __shfl_xor(v, 32));
+        for (int e = 1; e < 16; ++e) v = sa_max(v, acc[ct][e]);
+        val[ct] = sa_max(v, __shfl_xor(v, 32));
     }
 #pragma unroll
     for (int p2 = 0; p2 < 4; ++p2) {
@@ -165,7 +176,7 @@ __device__ __forceinline__ void sa_run_layer(const SaDesc &d, int l, const float
 {
     f32x16 acc[NCT];
     sa_layer<NCT>(P + d.woff[l], P + d.boff[l], d.kp[l], d.cp[l], (d.relu_mask >> l) & 1, act, d.act_stride, acc);
-    if (l + 1 < d.nlayers) sa_store_act<NCT>(acc, act, d.act_stride);
+    if (l + 1 < d.nlayers) sa_store_act<NCT>(acc, act, d.act_stride, d.w[l]);
     else if (direct) sa_pool_direct<NCT>(acc, o);
     else sa_pool<NCT>(acc, pool, d.cp[l], gpt);
 }
@@ -357,6 +368,69 @@ __global__ __launch_bounds__(MAXW >= 8 ? 512 : SA_WAVES * 64) void sa_group_mlp_
 
 static inline int pad_cols(int c) { return c <= 32 ? 32 : c <= 64 ? 64 : c <= 128 ? 128 : 256; }
 
+// Every launch decision of geot_sa_group_mlp_max, in one place: the launcher and the host-only query geot_sa_plan
+// both read it, so the query cannot drift from the dispatch.  cus = the device's CU count (the persistent grid's cap);
+// out_aligned16 = the output starts on a 16-byte boundary (the run-of-8 stores are dwordx4).  The GEOT_SA_FAST /
+// GEOT_SA_RUN overrides are the launcher's, not the plan's.  ok says whether the kernel takes the shape.
+struct SaPlan {
+    bool ok, wide;
+    int waves, gpt, tpg, fast_np, run_len;
+    long long lds, blocks, nunits;
+    SaDesc d;
+};
+static SaPlan sa_plan(int b, int npoint, int nsample, int c_feat, int nlayers, const int *widths, int cus,
+                      bool out_aligned16)
+{
+    SaPlan p = {};
+    if (b < 0 || npoint < 0 || c_feat < 0 || nlayers < 1 || nlayers > SA_MAX_LAYERS || !widths || cus < 1) return p;
+    if (!(nsample == 8 || nsample == 16 || (nsample >= 32 && nsample % 32 == 0))) return p;
+    for (int l = 0; l < nlayers; ++l)
+        if (widths[l] < 1 || widths[l] > 256) return p;
+    // the descriptor; sizes in 64 bits until the LDS bound has capped them
+    SaDesc &d = p.d;
+    long long kp = (3LL + c_feat + 1) & ~1LL, off = 0, maxw = kp;
+    long long kps[SA_MAX_LAYERS], offs[2 * SA_MAX_LAYERS];
+    for (int l = 0; l < nlayers; ++l) {
+        const int cp = pad_cols(widths[l]);
+        kps[l] = kp; offs[2 * l] = off; off += kp * cp; offs[2 * l + 1] = off; off += cp;
+        if (l + 1 < nlayers && cp > maxw) maxw = cp; // the last layer's output never goes to the activation tile
+        kp = cp;
+    }
+    p.gpt = nsample >= 32 ? 1 : 32 / nsample;          // groups per 32-row tile
+    p.tpg = nsample >= 32 ? nsample / 32 : 1;          // tiles per group
+    for (int l = 0; l < nlayers; ++l) p.wide = p.wide || pad_cols(widths[l]) > 128;
+    // As many waves per workgroup (= per CU: the weights + activation tiles fill its LDS) as fit next to the
+    // weights, up to 3 per SIMD: one wave's gather, LDS round trips and accumulator hand-offs between layers
+    // then overlap with the others' MFMA chains.
+    const long long per_wave = 32 * (maxw + 1) + (long long)p.gpt * pad_cols(widths[nlayers - 1]);
+    p.waves = p.wide ? 8 : SA_WAVES;
+    while (p.waves > 4 && (off + p.waves * per_wave) * (long long)sizeof(float) > 160 * 1024) p.waves -= 4;
+    p.lds = (off + p.waves * per_wave) * (long long)sizeof(float);
+    if (p.lds > 160 * 1024) return p;
+    d.nlayers = nlayers;
+    for (int l = 0; l < nlayers; ++l) {
+        d.kp[l] = (int)kps[l]; d.cp[l] = pad_cols(widths[l]); d.w[l] = widths[l];
+        d.woff[l] = (int)offs[2 * l]; d.boff[l] = (int)offs[2 * l + 1];
+    }
+    d.total = (int)off;
+    d.act_stride = (int)maxw + 1;
+    p.nunits = ((long long)b * npoint + p.gpt - 1) / p.gpt;
+    // persistent workgroups: one per CU (the weights + activation tiles fill its LDS), each looping over its
+    // share of the tiles, so the 52 KB of weights are staged once per CU and not once per 8 tiles
+    p.blocks = std::min((p.nunits + p.waves - 1) / p.waves, (long long)cus);
+    // register-pooled, software-pipelined path (see the kernel): one 32-row tile per group, few feature channels,
+    // no padded output columns
+    const int c_last = widths[nlayers - 1];
+    const long long ngroups = (long long)b * npoint;
+    if (nsample == 32 && c_feat <= 8 && c_last == d.cp[nlayers - 1] && c_last >= 64 && ngroups < 0x7fffffffLL &&
+        ngroups * 32 < 0x7fffffffLL * 4)
+        p.fast_np = c_last / 64;
+    // runs of 8 consecutive groups per wave (sector-sized output stores) once every wave still gets >= 2 runs
+    p.run_len = (p.fast_np && npoint % 8 == 0 && out_aligned16 && p.nunits >= 16 * p.blocks * p.waves) ? 8 : 1;
+    p.ok = true;
+    return p;
+}
+
 } // namespace geot
 
 using namespace geot;
@@ -364,15 +438,33 @@ using namespace geot;
 GEOT_EXPORT int geot_sa_param_floats(int c_feat, int nlayers, const int *widths)
 {
     if (nlayers < 1 || nlayers > SA_MAX_LAYERS || c_feat < 0) return -1;
-    long long total = 0;
-    int kp = (3 + c_feat + 1) & ~1;
+    long long total = 0, kp = (3LL + c_feat + 1) & ~1LL;
     for (int l = 0; l < nlayers; ++l) {
         if (widths[l] < 1 || widths[l] > 256) return -1;
         int cp = pad_cols(widths[l]);
-        total += (long long)kp * cp + cp;
+        total += kp * cp + cp;
         kp = cp;
     }
-    return (int)total;
+    return total > 0x7fffffffLL ? -1 : (int)total;
+}
+
+GEOT_EXPORT int geot_sa_plan(int b, int npoint, int nsample, int c_feat, int nlayers, const int *widths, int cus,
+                             int out_aligned16, long long *out, int n_out)
+{
+    const SaPlan p = sa_plan(b, npoint, nsample, c_feat, nlayers, widths, cus, out_aligned16 != 0);
+    if (p.ok && out) {
+        const SaDesc &d = p.d;
+        long long v[11 + 4 * SA_MAX_LAYERS] = {p.wide, p.waves, p.lds, p.blocks, p.gpt, p.tpg, p.fast_np, p.run_len,
+                                               p.nunits, d.total, d.act_stride};
+        for (int l = 0; l < d.nlayers; ++l) {
+            v[11 + l] = d.kp[l];
+            v[11 + SA_MAX_LAYERS + l] = d.cp[l];
+            v[11 + 2 * SA_MAX_LAYERS + l] = d.woff[l];
+            v[11 + 3 * SA_MAX_LAYERS + l] = d.boff[l];
+        }
+        for (int i = 0; i < n_out && i < 11 + 4 * SA_MAX_LAYERS; ++i) out[i] = v[i];
+    }
+    return p.ok ? 1 : 0;
 }
 
 GEOT_EXPORT int geot_sa_group_mlp_max(int b, int n, int npoint, int nsample, int c_feat,
@@ -383,61 +475,27 @@ GEOT_EXPORT int geot_sa_group_mlp_max(int b, int n, int npoint, int nsample, int
     if (b < 0 || n < 0 || npoint < 0 || nlayers < 1 || nlayers > SA_MAX_LAYERS || c_feat < 0)
         return hipErrorInvalidValue;
     if (!(nsample == 8 || nsample == 16 || (nsample >= 32 && nsample % 32 == 0))) return hipErrorInvalidValue;
+    if (b == 0 || npoint == 0) return hipSuccess;      // nothing to read: the arrays may be NULL
     if (c_feat > 0 && !features) return hipErrorInvalidValue;
-    if (b == 0 || npoint == 0) return hipSuccess;
-    SaDesc d{};
-    d.nlayers = nlayers;
-    d.relu_mask = relu_mask;
-    int kp = (3 + c_feat + 1) & ~1, off = 0, maxw = kp;
-    for (int l = 0; l < nlayers; ++l) {
-        if (widths[l] < 1 || widths[l] > 256) return hipErrorInvalidValue;
-        int cp = pad_cols(widths[l]);
-        d.kp[l] = kp; d.cp[l] = cp; d.woff[l] = off; off += kp * cp; d.boff[l] = off; off += cp;
-        if (l + 1 < nlayers && cp > maxw) maxw = cp; // the last layer's output never goes to the activation tile
-        kp = cp;
-    }
-    d.total = off;
-    d.act_stride = maxw + 1;
-    // As many waves per workgroup (= per CU: the weights + activation tiles fill its LDS) as fit next to the
-    // weights, up to 3 per SIMD: one wave's gather, LDS round trips and accumulator hand-offs between layers
-    // then overlap with the others' MFMA chains.
-    int gpt = nsample >= 32 ? 1 : 32 / nsample;
-    bool wide = false;
-    for (int l = 0; l < nlayers; ++l) wide = wide || d.cp[l] > 128;
-    const size_t per_wave = 32 * (size_t)d.act_stride + (size_t)gpt * d.cp[nlayers - 1];
-    int waves = wide ? 8 : SA_WAVES;
-    while (waves > 4 && ((size_t)d.total + waves * per_wave) * sizeof(float) > 160 * 1024) waves -= 4;
-    const size_t lds = ((size_t)d.total + waves * per_wave) * sizeof(float);
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    SaPlan p = sa_plan(b, npoint, nsample, c_feat, nlayers, widths, device_cus(), ((uintptr_t)out & 15) == 0);
+    if (!p.ok) return hipErrorInvalidValue;
+    p.d.relu_mask = relu_mask;
     {   // > 64 KB of dynamic LDS is opt-in, per device and per kernel: raised once (geot_common.h allow_big_lds)
-        hipError_t e = wide ? allow_big_lds((const void *)sa_group_mlp_max_kernel<8>, lds)
-                            : allow_big_lds((const void *)sa_group_mlp_max_kernel<4>, lds);
+        hipError_t e = p.wide ? allow_big_lds((const void *)sa_group_mlp_max_kernel<8>, p.lds)
+                              : allow_big_lds((const void *)sa_group_mlp_max_kernel<4>, p.lds);
         if (e != hipSuccess) return e;
     }
-    long long nunits = ((long long)b * npoint + gpt - 1) / gpt;
-    long long blocks = (nunits + waves - 1) / waves;
-    // persistent workgroups: one per CU (the weights + activation tiles fill its LDS), each looping over its
-    // share of the tiles, so the 52 KB of weights are staged once per CU and not once per 8 tiles
-    const int n_cus = device_cus();
-    if (blocks > n_cus) blocks = n_cus;
-    // register-pooled, software-pipelined path (see the kernel): one 32-row tile per group, few feature channels,
-    // no padded output columns
-    const int c_last = widths[nlayers - 1];
-    int fast_np = 0;
-    if (nsample == 32 && c_feat <= 8 && c_last == d.cp[nlayers - 1] && c_last >= 64 && (long long)b * npoint < 0x7fffffffLL &&
-        (long long)b * npoint * 32 < 0x7fffffffLL * 4)
-        fast_np = c_last / 64;
+    int fast_np = p.fast_np, run_len = p.run_len;
     if (const char *fe = getenv("GEOT_SA_FAST")) fast_np = atoi(fe) ? fast_np : 0;
-    // runs of 8 consecutive groups per wave (sector-sized output stores) once every wave still gets >= 2 runs
-    int run_len = (fast_np && npoint % 8 == 0 && ((uintptr_t)out & 15) == 0 && nunits >= 16 * blocks * waves) ? 8 : 1;
+    if (!fast_np) run_len = 1;
     if (const char *re = getenv("GEOT_SA_RUN")) run_len = (atoi(re) == 8 && npoint % 8 == 0 && ((uintptr_t)out & 15) == 0) ? 8 : 1;
-    if (wide)
-        hipLaunchKernelGGL(sa_group_mlp_max_kernel<8>, dim3((unsigned)blocks), dim3(waves * 64), lds, (hipStream_t)stream,
-                           d, b, n, npoint, nsample, c_feat, widths[nlayers - 1], xyz, new_xyz, features, idx, xyz_scale,
+    if (p.wide)
+        hipLaunchKernelGGL(sa_group_mlp_max_kernel<8>, dim3((unsigned)p.blocks), dim3(p.waves * 64), p.lds, (hipStream_t)stream,
+                           p.d, b, n, npoint, nsample, c_feat, widths[nlayers - 1], xyz, new_xyz, features, idx, xyz_scale,
                            params, out, fast_np, run_len);
     else
-        hipLaunchKernelGGL(sa_group_mlp_max_kernel<4>, dim3((unsigned)blocks), dim3(waves * 64), lds, (hipStream_t)stream,
-                           d, b, n, npoint, nsample, c_feat, widths[nlayers - 1], xyz, new_xyz, features, idx, xyz_scale,
+        hipLaunchKernelGGL(sa_group_mlp_max_kernel<4>, dim3((unsigned)p.blocks), dim3(p.waves * 64), p.lds, (hipStream_t)stream,
+                           p.d, b, n, npoint, nsample, c_feat, widths[nlayers - 1], xyz, new_xyz, features, idx, xyz_scale,
                            params, out, fast_np, run_len);
     return hipGetLastError();
 }

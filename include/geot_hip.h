@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 9
+#define GEOT_ABI_VERSION 10
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
 
 /* ABI version / diagnostics. */
@@ -453,8 +453,26 @@ int geot_aggregation_cl_grad(int n, int nsample, int c, int w_c, const float *in
  * W^T zero-padded to [kp][cp] then bias [cp], with kp_0 = 3+c_feat rounded up to even,
  * kp_l = cp_{l-1}, cp = width rounded up to 32/64/128/256;
  * geot_sa_param_floats returns its length (or -1 for unsupported shapes).
- * nsample must be 8, 16 or a multiple of 32. */
+ * nsample must be 8, 16 or a multiple of 32.  ReLU and the max propagate NaN (as torch.relu and torch.max do), and
+ * the padding columns of an activation are 0 even where a real column is +-inf.  b == 0 or npoint == 0 launches
+ * nothing.  Refused (hipErrorInvalidValue): b, n, npoint or c_feat < 0, nlayers outside 1..4, a width outside
+ * 1..256, another nsample, c_feat > 0 with NULL features, or weights + activation tiles over 160 KiB of LDS at the
+ * smallest launch (geot_sa_plan returns 0 for these). */
 int geot_sa_param_floats(int c_feat, int nlayers, const int *widths);
+/* Host-only (ABI 10): the launch plan of geot_sa_group_mlp_max for these sizes, from the function the launcher
+ * uses; cus = the device's CU count, out_aligned16 = 1 when out is 16-byte aligned.  Returns 1 and fills the first
+ * n_out (up to 27) of: wide variant (1: some padded width is 256, 8 waves at most; 0: 12 at most), waves per
+ * workgroup (12, 8 or 4: the most that fit), LDS bytes, workgroups (min(units / waves rounded up, cus): persistent,
+ * each takes a contiguous share; 0 when b * npoint == 0), groups per 32-row tile (gpt: 4, 2, 1 for nsample 8, 16,
+ * >= 32), tiles per group (nsample / 32, or 1), fast_np (the register-pooled path with padded last width / 64
+ * stores per group, 0 = the LDS-pooled path; needs nsample 32, c_feat <= 8, an unpadded last width >= 64 and
+ * b * npoint < 2^31), run_len (8: the fast path stores runs of 8 groups, needs npoint % 8 == 0, out_aligned16 and
+ * >= 16 units per wave of the grid; else 1), units (b * npoint / gpt rounded up), parameter floats, activation row
+ * stride, then per layer 0..3 the padded input width kp, the padded output width cp, the float offsets of W^T and
+ * of the bias (0 past nlayers) -- when the kernel takes the shape; returns 0 and leaves out alone otherwise.
+ * The launcher's GEOT_SA_FAST / GEOT_SA_RUN overrides are not part of the plan.  out is a HOST array. */
+int geot_sa_plan(int b, int npoint, int nsample, int c_feat, int nlayers, const int *widths, int cus, int out_aligned16,
+                 long long *out, int n_out);
 int geot_sa_group_mlp_max(int b, int n, int npoint, int nsample, int c_feat, const float *xyz,
                           const float *new_xyz, const float *features, const int *idx,
                           float xyz_scale, int nlayers, const int *widths, int relu_mask,

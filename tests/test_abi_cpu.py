@@ -138,6 +138,19 @@ def test_host_only_planning_entry_points(monkeypatch):
         untouched = (ctypes.c_longlong * 14)(*([-7] * 14))
         assert lib.geot_edgeconv_plan(*args, untouched, 14) == 0 and list(untouched) == [-7] * 14
         assert lib.geot_edgeconv_eligible(*args) == 0
+    # fused SetAbstraction (ABI 10): configs[1]'s plan on 256 CUs, a prefix on request, nothing for a refused shape
+    w3 = (ctypes.c_int * 3)(64, 64, 128)
+    sa = (ctypes.c_longlong * 27)(*([-7] * 27))
+    assert lib.geot_sa_plan(1, 6000, 32, 3, 3, w3, 256, 1, sa, 27) == 1
+    assert list(sa)[:11] == [0, 12, 157696, 256, 1, 1, 2, 1, 6000, 6 * 64 + 64 + 64 * 64 + 64 + 64 * 128 + 128, 65]
+    assert list(sa)[11:] == [6, 64, 64, 0, 64, 64, 128, 0, 0, 448, 4608, 0, 384, 4544, 12800, 0]
+    assert sa[9] == lib.geot_sa_param_floats(3, 3, w3)
+    short = (ctypes.c_longlong * 27)(*([-7] * 27))
+    assert lib.geot_sa_plan(1, 6000, 32, 3, 3, w3, 256, 1, short, 2) == 1 and list(short) == [0, 12] + [-7] * 25
+    for args in ((1, 6000, 24, 3, 3, w3), (1, 6000, 32, 3, 3, (ctypes.c_int * 3)(128, 128, 128)),
+                 (1, 6000, 32, 3, 3, (ctypes.c_int * 3)(64, 257, 128)), (-1, 6000, 32, 3, 3, w3)):
+        untouched = (ctypes.c_longlong * 27)(*([-7] * 27))
+        assert lib.geot_sa_plan(*args, 256, 1, untouched, 27) == 0 and list(untouched) == [-7] * 27
 
 
 def test_header_is_plain_c_and_links(tmp_path):
