@@ -664,7 +664,7 @@ GEOT_EXPORT int geot_knn_grid_eligible(int b, int nq, int nr, int k)
 GEOT_EXPORT int geot_knn_sorted_ws(int b, int nq, int nr, int k, const float *query, const float *ref, int *idx,
                                    float *dist2, void *workspace, long long ws_bytes, void *stream)
 {
-    if (b < 0 || nq < 0 || nr < 0 || k < 0 || k > 256) return hipErrorInvalidValue;
+    if (b < 0 || nq < 0 || nr < 0 || k < 0 || k > GEOT_KNN_KMAX_SORTED) return hipErrorInvalidValue;
     if (b == 0 || nq == 0 || k == 0) return hipSuccess;
     if (b > 65535) return hipErrorInvalidValue;
     if (!workspace || !geot_knn_grid_eligible(b, nq, nr, k) || ws_bytes < geot_knn_grid_ws_bytes(b, nr))

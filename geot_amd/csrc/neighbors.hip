@@ -152,17 +152,20 @@ __global__ __launch_bounds__(NN_THREADS) void three_nn_kernel(
 // ---------------------------------------------------------------------------
 constexpr int KNN_THREADS = 64;
 
+// LANES lists interleaved [slot][lane]: a workgroup of LANES lanes holds nsample * LANES * 8 bytes of LDS
+template <int LANES = KNN_THREADS>
 struct LdsList {
     float *d;
     int *i;
-    __device__ __forceinline__ float &D(int s) { return d[s * KNN_THREADS]; }
-    __device__ __forceinline__ int &I(int s) { return i[s * KNN_THREADS]; }
+    __device__ __forceinline__ float &D(int s) { return d[s * LANES]; }
+    __device__ __forceinline__ int &I(int s) { return i[s * LANES]; }
 };
 
 // Max-heap sift-down with the reference's exact comparison structure
 // (knnquery_cuda_kernel.cu:21-36): take the right child only if strictly
 // larger; stop only if root strictly larger than that child.
-__device__ __forceinline__ void heap_sift(LdsList h, int k)
+template <int LANES>
+__device__ __forceinline__ void heap_sift(LdsList<LANES> h, int k)
 {
     int root = 0, child = 1;
     while (child < k) {
@@ -176,15 +179,18 @@ __device__ __forceinline__ void heap_sift(LdsList h, int k)
     }
 }
 
-// qlist / qcount (nullable): process only the listed queries (the ones the fast path could not certify)
-__global__ __launch_bounds__(KNN_THREADS) void knnquery_heap_kernel(
+// qlist / qcount (nullable): process only the listed queries (the ones the fast path could not certify).
+// LANES queries per workgroup: 64 up to nsample 128 (64 KB of lists), fewer for the longer lists (the 1024-slot
+// lists of 16 lanes take 128 KB), so that nsample up to KMAX_HEAP fits one CU's LDS.
+template <int LANES>
+__global__ __launch_bounds__(LANES) void knnquery_heap_kernel(
     int b, int m, int nsample, const float *__restrict__ xyz, const float *__restrict__ new_xyz,
     const int *__restrict__ offset, const int *__restrict__ new_offset, const int *__restrict__ qlist,
     const int *__restrict__ qcount, int *__restrict__ idx, float *__restrict__ dist2)
 {
     extern __shared__ float knn_lds[];
-    LdsList h{knn_lds + threadIdx.x, (int *)(knn_lds + nsample * KNN_THREADS) + threadIdx.x};
-    const int t = blockIdx.x * KNN_THREADS + threadIdx.x;
+    LdsList<LANES> h{knn_lds + threadIdx.x, (int *)(knn_lds + nsample * LANES) + threadIdx.x};
+    const int t = blockIdx.x * LANES + threadIdx.x;
     if (t >= (qcount ? min(*qcount, m) : m)) return;
     const int p = qlist ? qlist[t] : t;
     int bt = segment_of(p, new_offset, b);
@@ -218,7 +224,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_sorted_kernel(
     int *__restrict__ idx, float *__restrict__ dist2)
 {
     extern __shared__ float knn_lds[];
-    LdsList h{knn_lds + threadIdx.x, (int *)(knn_lds + k * KNN_THREADS) + threadIdx.x};
+    LdsList<> h{knn_lds + threadIdx.x, (int *)(knn_lds + k * KNN_THREADS) + threadIdx.x};
     const int bi = blockIdx.y;
     const int j = blockIdx.x * KNN_THREADS + threadIdx.x;
     if (j >= nq) return;
@@ -389,6 +395,237 @@ __global__ __launch_bounds__(KW_WAVES * 64) void knn_wave_nd_kernel(
     }
 }
 
+// ---------------------------------------------------------------------------
+// Sorted kNN for long lists (65 <= k <= KMAX_SORTED): one workgroup per query.
+//   1. every squared distance, as its IEEE bits (a non-negative float orders like its bits), kept in LDS when the
+//      cloud fits (`cache`), recomputed from the L2-resident coordinates on every pass otherwise; min / max of the keys;
+//   2. radix select of the k-th smallest key T over the key range [min, max]: each pass histograms the keys still in
+//      the candidate range by their next 11 bits (int LDS atomics), one wave finds the bin that holds rank k and the
+//      range shrinks to it -- at most three passes for 32-bit keys;
+//   3. one pass in index order collects every key < T (unordered) and the first k - #(< T) keys == T by ascending
+//      index (a block-wide prefix count), so the selected set is the k smallest by (d2, index);
+//   4. a bitonic sort of the (d2 bits << 32 | index) words in LDS gives the (d2, index) order.
+// Slots beyond nr are (inf, 0).  `cert_ns` > 0 is pointops.knn's fast path (k = cert_ns + 1): a query whose k sorted
+// distances are strictly increasing and below the heap's 1e10 sentinel has the literal heap's answer, which is written
+// (cert_ns slots, global indices bi * nr + r); the others are appended to qlist for the literal heap.
+// ---------------------------------------------------------------------------
+constexpr int KS_BITS = 11;
+constexpr int KS_BINS = 1 << KS_BITS;
+constexpr int KS_RED = 128;       // LDS words: [0,16) min, [16,32) max, [32,34) select, [36] count, [37] flag, [64,80) waves
+constexpr int KS_CACHE_THREADS = 1024;
+
+__host__ __device__ constexpr int ks_pow2(int k)
+{
+    int n = 2;
+    while (n < k) n <<= 1;
+    return n;
+}
+
+__global__ __launch_bounds__(KS_CACHE_THREADS) void knn_select_kernel(
+    int nq, int nr, int k, int cache, const float *__restrict__ query, const float *__restrict__ ref,
+    int *__restrict__ idx, float *__restrict__ dist2, int cert_ns, int *__restrict__ qlist, int *__restrict__ qcount)
+{
+    extern __shared__ unsigned long long ks_lds[];
+    const int n2 = ks_pow2(k);
+    unsigned long long *cand = ks_lds;
+    uint32_t *hist = (uint32_t *)(cand + n2);
+    uint32_t *red = hist + KS_BINS;
+    uint32_t *ck = red + KS_RED;                       // the key cache (nr words) when `cache`
+    const int tid = threadIdx.x, T = blockDim.x, lane = lane_id(), wave = tid >> 6, W = T >> 6;
+    const int bi = blockIdx.y, j = blockIdx.x;
+    const float *Q = query + ((size_t)bi * nq + j) * 3;
+    const float *R = ref + (size_t)bi * nr * 3;
+    const float qx = Q[0], qy = Q[1], qz = Q[2];
+    auto key_of = [&](int r) -> uint32_t {
+        return cache ? ck[r] : __float_as_uint(sqdist3(qx, qy, qz, R[r * 3], R[r * 3 + 1], R[r * 3 + 2]));
+    };
+
+    // 1. keys, their min and max
+    uint32_t kmin = 0xffffffffu, kmax = 0u;
+    for (int r = tid; r < nr; r += T) {
+        const uint32_t key = __float_as_uint(sqdist3(qx, qy, qz, R[r * 3], R[r * 3 + 1], R[r * 3 + 2]));
+        if (cache) ck[r] = key;
+        kmin = min(kmin, key);
+        kmax = max(kmax, key);
+    }
+    kmin = wave_min_u32(kmin);
+    kmax = wave_max_u32(kmax);
+    if (lane == 0) { red[wave] = kmin; red[16 + wave] = kmax; }
+    __syncthreads();
+    for (int w = 0; w < W; ++w) { kmin = min(kmin, red[w]); kmax = max(kmax, red[16 + w]); }
+
+    // 2. radix select: the keys < lo number `below`, the wanted key has rank `want` (1-based) within [lo, hi]
+    const bool all = nr <= k;                          // every point is a neighbour
+    uint32_t lo = kmin, hi = kmax;
+    int below = 0, want = k;
+    while (!all && hi != lo) {
+        const uint32_t range = hi - lo;
+        const int width = 32 - __clz(range);
+        const int shift = width > KS_BITS ? width - KS_BITS : 0;
+        const int nb = (int)(range >> shift) + 1;
+        for (int i = tid; i < nb; i += T) hist[i] = 0u;
+        __syncthreads();
+        for (int r = tid; r < nr; r += T) {
+            const uint32_t key = key_of(r);
+            if (key >= lo && key <= hi) atomicAdd(&hist[(key - lo) >> shift], 1u);
+        }
+        __syncthreads();
+        if (wave == 0) {                               // 32 bins per lane, scan over the lanes
+            constexpr int PER = KS_BINS / 64;
+            int sum = 0;
+            for (int e = 0; e < PER; ++e) sum += lane * PER + e < nb ? (int)hist[lane * PER + e] : 0;
+            int inc = sum;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int o = __shfl_up(inc, d);
+                if (lane >= d) inc += o;
+            }
+            int run = inc - sum;
+            if (run < want && want <= inc) {
+                for (int e = 0; e < PER; ++e) {
+                    const int c = lane * PER + e < nb ? (int)hist[lane * PER + e] : 0;
+                    if (run + c >= want) { red[32] = (uint32_t)(lane * PER + e); red[33] = (uint32_t)run; break; }
+                    run += c;
+                }
+            }
+        }
+        __syncthreads();
+        const uint32_t bin = red[32];
+        const int before = (int)red[33];
+        below += before;
+        want -= before;
+        lo += bin << shift;
+        const unsigned long long top = (unsigned long long)lo + ((1ull << shift) - 1ull);
+        hi = top < (unsigned long long)hi ? (uint32_t)top : hi;
+        if (shift == 0) break;                         // (red[32..33] are rewritten only after the next two barriers)
+    }
+    const uint32_t thr = lo;                           // the k-th smallest key; `want` keys == thr are taken
+
+    // 3. collect: keys < thr anywhere in [0, below), keys == thr in index order into [below, k)
+    if (tid == 0) { red[36] = 0u; red[37] = 0u; }
+    __syncthreads();
+    int eq_seen = 0;
+    for (int c0 = 0; c0 < nr; c0 += T) {
+        const int r = c0 + tid;
+        const uint32_t key = r < nr ? key_of(r) : 0xffffffffu;
+        const bool lt = r < nr && (all || key < thr);
+        const unsigned long long mlt = __ballot(lt);
+        if (mlt) {
+            int base = 0;
+            if (lane == 0) base = (int)atomicAdd(&red[36], (uint32_t)__popcll(mlt));
+            base = __shfl(base, 0);
+            if (lt) cand[base + __popcll(mlt & ((1ull << lane) - 1ull))] = ((unsigned long long)key << 32) | (uint32_t)r;
+        }
+        if (!all && eq_seen < want) {                  // block-uniform
+            const bool eq = r < nr && key == thr;
+            const unsigned long long meq = __ballot(eq);
+            if (lane == 0) red[64 + wave] = (uint32_t)__popcll(meq);
+            __syncthreads();
+            int off = eq_seen, tot = 0;
+            for (int w = 0; w < W; ++w) {
+                const int c = (int)red[64 + w];
+                off += w < wave ? c : 0;
+                tot += c;
+            }
+            const int rank = off + __popcll(meq & ((1ull << lane) - 1ull));
+            if (eq && rank < want) cand[below + rank] = ((unsigned long long)key << 32) | (uint32_t)r;
+            eq_seen += tot;
+            __syncthreads();
+        }
+    }
+    const int n = all ? nr : k;
+    for (int s = n + tid; s < n2; s += T) cand[s] = ~0ull;
+    __syncthreads();
+
+    // 4. bitonic sort of the n2 words
+    for (int size = 2; size <= n2; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int i = tid; i < (n2 >> 1); i += T) {
+                const int a = 2 * i - (i & (stride - 1)), c = a + stride;
+                const unsigned long long x = cand[a], y = cand[c];
+                if ((x > y) == ((a & size) == 0)) { cand[a] = y; cand[c] = x; }
+            }
+            __syncthreads();
+        }
+    }
+
+    const size_t p = (size_t)bi * nq + j;
+    if (cert_ns == 0) {
+        for (int s = tid; s < k; s += T) {
+            const unsigned long long v = cand[s];
+            idx[p * k + s] = s < n ? (int)(uint32_t)v : 0;
+            dist2[p * k + s] = s < n ? __uint_as_float((uint32_t)(v >> 32)) : INFINITY;
+        }
+        return;
+    }
+    bool strict = !all || nr > cert_ns;                // k = cert_ns + 1 real candidates are needed
+    for (int s = tid; s < cert_ns && strict; s += T)
+        strict = __uint_as_float((uint32_t)(cand[s] >> 32)) < __uint_as_float((uint32_t)(cand[s + 1] >> 32));
+    if (tid == 0) strict = strict && __uint_as_float((uint32_t)(cand[cert_ns] >> 32)) < 1e10f;
+    if (!strict) red[37] = 1u;                         // (same value from every writer)
+    __syncthreads();
+    if (red[37] == 0u) {
+        for (int s = tid; s < cert_ns; s += T) {
+            const unsigned long long v = cand[s];
+            idx[p * cert_ns + s] = bi * nr + (int)(uint32_t)v;
+            dist2[p * cert_ns + s] = __uint_as_float((uint32_t)(v >> 32));
+        }
+    } else if (tid == 0) {
+        qlist[atomicAdd(qcount, 1)] = (int)p;
+    }
+}
+
+// LDS of knn_select_kernel: the sort words, the histogram, the reduction words and (cache) one key per point
+static size_t ks_lds_bytes(int k, int nr, bool cache)
+{
+    return (size_t)ks_pow2(k) * 8 + (size_t)(KS_BINS + KS_RED) * 4 + (cache ? (size_t)nr * 4 : 0);
+}
+
+static hipError_t launch_knn_select(int b, int nq, int nr, int k, const float *query, const float *ref, int *idx,
+                                    float *dist2, int cert_ns, int *qlist, int *qcount, hipStream_t s)
+{
+    const bool cache = ks_lds_bytes(k, nr, true) <= (size_t)160 * 1024;
+    const size_t lds = ks_lds_bytes(k, nr, cache);
+    hipError_t e = allow_big_lds((const void *)knn_select_kernel, lds);
+    if (e != hipSuccess) return e;
+    const int threads = nr >= 4096 ? KS_CACHE_THREADS : 256;
+    hipLaunchKernelGGL(knn_select_kernel, dim3(nq, b), dim3(threads), lds, s, nq, nr, k, cache ? 1 : 0, query, ref, idx,
+                       dist2, cert_ns, qlist, qcount);
+    return hipGetLastError();
+}
+
+static bool nn_impl_basic()
+{
+    const char *e = getenv("GEOT_NN_IMPL"); // "basic" = the one-lane-per-query kernels (A/B testing)
+    return e && e[0] == 'b';
+}
+
+template <int LANES>
+static hipError_t launch_heap(int b, int m, int nsample, const float *xyz, const float *new_xyz, const int *offset,
+                              const int *new_offset, const int *qlist, const int *qcount, int *idx, float *dist2,
+                              hipStream_t s)
+{
+    const size_t lds = (size_t)nsample * LANES * 8;
+    hipError_t e = allow_big_lds((const void *)knnquery_heap_kernel<LANES>, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(knnquery_heap_kernel<LANES>, dim3((int)(((long long)m + LANES - 1) / LANES)), dim3(LANES), lds, s,
+                       b, m, nsample, xyz, new_xyz, offset, new_offset, qlist, qcount, idx, dist2);
+    return hipGetLastError();
+}
+
+// the literal heap: 64 lanes per workgroup up to nsample 128 (GEOT_NN_IMPL=basic: up to 256, 128 KB), 32 lanes up to
+// 256 and 16 lanes up to KMAX_HEAP (64 / 128 KB), so that the lists always fit
+static hipError_t launch_heap_any(int b, int m, int nsample, const float *xyz, const float *new_xyz, const int *offset,
+                                  const int *new_offset, const int *qlist, const int *qcount, int *idx, float *dist2,
+                                  hipStream_t s)
+{
+    if (nsample <= 128 || (nsample <= 256 && nn_impl_basic()))
+        return launch_heap<64>(b, m, nsample, xyz, new_xyz, offset, new_offset, qlist, qcount, idx, dist2, s);
+    if (nsample <= 256)
+        return launch_heap<32>(b, m, nsample, xyz, new_xyz, offset, new_offset, qlist, qcount, idx, dist2, s);
+    return launch_heap<16>(b, m, nsample, xyz, new_xyz, offset, new_offset, qlist, qcount, idx, dist2, s);
+}
+
 static inline int grid_cap(long long want, int cap) { return (int)(want < cap ? (want < 1 ? 1 : want) : cap); }
 
 } // namespace geot
@@ -445,13 +682,10 @@ GEOT_EXPORT int geot_knnquery_heap(int b, int m, int nsample, const float *xyz, 
                                    const int *offset, const int *new_offset, int *idx, float *dist2,
                                    void *stream)
 {
-    if (b < 0 || m < 0 || nsample < 0 || nsample > 256) return hipErrorInvalidValue;
+    if (b < 0 || m < 0 || nsample < 0 || nsample > GEOT_KNN_KMAX_HEAP) return hipErrorInvalidValue;
     if (b == 0 || m == 0 || nsample == 0) return hipSuccess;
-    size_t lds = (size_t)nsample * KNN_THREADS * 8;
-    hipLaunchKernelGGL(knnquery_heap_kernel, dim3((m + KNN_THREADS - 1) / KNN_THREADS),
-                       dim3(KNN_THREADS), lds, (hipStream_t)stream, b, m, nsample, xyz, new_xyz, offset,
-                       new_offset, nullptr, nullptr, idx, dist2);
-    return hipGetLastError();
+    return launch_heap_any(b, m, nsample, xyz, new_xyz, offset, new_offset, nullptr, nullptr, idx, dist2,
+                           (hipStream_t)stream);
 }
 
 // ---- pointops kNN, fast path for uniform batches ------------------------------------------------
@@ -459,7 +693,8 @@ GEOT_EXPORT int geot_knnquery_heap(int b, int m, int nsample, const float *xyz, 
 // order; only the order among EQUAL distances depends on the heap mechanics.  So: sorted (k+1)-NN from the
 // exact grid search; a query whose first k+1 distances are strictly increasing has a unique answer, which
 // is copied; the others (duplicates, lattice ties, fewer than k+1 candidates) are listed and go through the
-// literal heap kernel.  Identical output to geot_knnquery_heap.
+// literal heap kernel.  Identical output to geot_knnquery_heap.  From nsample 64 on, the sorted (k+1)-NN comes from
+// knn_select_kernel, which certifies in its epilogue (same rule), so the workspace is only the query list.
 __global__ __launch_bounds__(256) void knn_heap_certify_kernel(int m_total, int m_per, int n_per, int k,
                                                                const int *__restrict__ tidx, const float *__restrict__ td2,
                                                                int *__restrict__ idx, float *__restrict__ dist2,
@@ -486,10 +721,19 @@ extern "C" int geot_knn_grid_eligible(int b, int nq, int nr, int k);
 extern "C" int geot_knn_sorted_ws(int b, int nq, int nr, int k, const float *query, const float *ref, int *idx,
                                   float *dist2, void *workspace, long long ws_bytes, void *stream);
 
+constexpr int KNN_CERT_MIN = 64;   // nsample from which pointops.knn's fast path is knn_select_kernel's certification
+
+// 1 if geot_knnquery_heap_ws certifies through knn_select_kernel (its workspace: the query list and its count)
+static bool knn_heap_select_eligible(int b, int nsample)
+{
+    return nsample >= KNN_CERT_MIN && nsample <= GEOT_KNN_KMAX_HEAP && b <= 65535 && !nn_impl_basic();
+}
+
 GEOT_EXPORT long long geot_knnquery_heap_ws_bytes(int b, int n_per, int m_per, int nsample)
 {
     if (b < 0 || n_per < 0 || m_per < 0 || nsample < 0) return -1;
     const long long mt = (long long)b * m_per;
+    if (nsample >= KNN_CERT_MIN) return (4 * (mt + 4) + 15) & ~15LL;
     long long bytes = geot_knn_grid_ws_bytes(b, n_per);
     bytes += 4 * (2 * mt * (nsample + 1) + mt + 4);
     return (bytes + 15) & ~15LL;
@@ -499,14 +743,24 @@ GEOT_EXPORT int geot_knnquery_heap_ws(int b, int n_per, int m_per, int nsample, 
                                       const float *new_xyz, const int *offset, const int *new_offset, int *idx,
                                       float *dist2, void *workspace, long long ws_bytes, void *stream)
 {
-    if (b < 0 || n_per < 0 || m_per < 0 || nsample < 0 || nsample > 256) return hipErrorInvalidValue;
+    if (b < 0 || n_per < 0 || m_per < 0 || nsample < 0 || nsample > GEOT_KNN_KMAX_HEAP) return hipErrorInvalidValue;
     const long long mt = (long long)b * m_per;
     if (b == 0 || mt == 0 || nsample == 0) return hipSuccess;
     if (mt > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (!workspace || nsample > 63 || !geot_knn_grid_eligible(b, m_per, n_per, nsample + 1) ||
-        ws_bytes < geot_knnquery_heap_ws_bytes(b, n_per, m_per, nsample) || ((uintptr_t)workspace & 15) != 0)
-        return geot_knnquery_heap(b, (int)mt, nsample, xyz, new_xyz, offset, new_offset, idx, dist2, stream);
+    const bool usable = workspace && ws_bytes >= geot_knnquery_heap_ws_bytes(b, n_per, m_per, nsample) &&
+                        ((uintptr_t)workspace & 15) == 0;
     hipStream_t s = (hipStream_t)stream;
+    if (usable && knn_heap_select_eligible(b, nsample)) {
+        int *qlist = (int *)workspace;
+        int *qcount = qlist + mt;
+        hipError_t e = zero_words(qcount, 1, s);
+        if (e != hipSuccess) return e;
+        e = launch_knn_select(b, m_per, n_per, nsample + 1, new_xyz, xyz, idx, dist2, nsample, qlist, qcount, s);
+        if (e != hipSuccess) return e;
+        return launch_heap_any(b, (int)mt, nsample, xyz, new_xyz, offset, new_offset, qlist, qcount, idx, dist2, s);
+    }
+    if (!usable || nsample >= KNN_CERT_MIN || !geot_knn_grid_eligible(b, m_per, n_per, nsample + 1))
+        return geot_knnquery_heap(b, (int)mt, nsample, xyz, new_xyz, offset, new_offset, idx, dist2, stream);
     const long long gbytes = geot_knn_grid_ws_bytes(b, n_per);
     int *tidx = (int *)((char *)workspace + gbytes);
     float *td2 = (float *)(tidx + mt * (nsample + 1));
@@ -518,26 +772,28 @@ GEOT_EXPORT int geot_knnquery_heap_ws(int b, int n_per, int m_per, int nsample, 
     if (rc != 0) return rc;
     hipLaunchKernelGGL(knn_heap_certify_kernel, dim3((int)((mt + 255) / 256)), dim3(256), 0, s, (int)mt, m_per, n_per,
                        nsample, tidx, td2, idx, dist2, qlist, qcount);
-    size_t lds = (size_t)nsample * KNN_THREADS * 8;
-    hipLaunchKernelGGL(knnquery_heap_kernel, dim3((int)((mt + KNN_THREADS - 1) / KNN_THREADS)), dim3(KNN_THREADS), lds, s, b,
-                       (int)mt, nsample, xyz, new_xyz, offset, new_offset, qlist, qcount, idx, dist2);
-    return hipGetLastError();
+    return launch_heap_any(b, (int)mt, nsample, xyz, new_xyz, offset, new_offset, qlist, qcount, idx, dist2, s);
 }
 
 GEOT_EXPORT int geot_knn_sorted(int b, int nq, int nr, int k, const float *query, const float *ref,
                                 int *idx, float *dist2, void *stream)
 {
-    if (b < 0 || nq < 0 || nr < 0 || k < 0 || k > 256) return hipErrorInvalidValue;
+    if (b < 0 || nq < 0 || nr < 0 || k < 0 || k > GEOT_KNN_KMAX_SORTED) return hipErrorInvalidValue;
     if (b == 0 || nq == 0 || k == 0) return hipSuccess;
     if (b > 65535) return hipErrorInvalidValue;
-    const char *e = getenv("GEOT_NN_IMPL");
-    if (k <= 64 && !(e && e[0] == 'b')) {
+    const bool basic = nn_impl_basic();
+    if (k <= 64 && !basic) {
         int per_block = KW_WAVES * KW_QW;
         hipLaunchKernelGGL(knn_wave_kernel, dim3((nq + per_block - 1) / per_block, b), dim3(KW_WAVES * 64), 0,
                            (hipStream_t)stream, nq, nr, k, query, ref, idx, dist2);
         return hipGetLastError();
     }
+    if (k > 256 || (k > 64 && !basic))
+        return launch_knn_select(b, nq, nr, k, query, ref, idx, dist2, 0, nullptr, nullptr, (hipStream_t)stream);
+    // GEOT_NN_IMPL=basic, k <= 256: the one-lane-per-query insertion kernel (A/B runs)
     size_t lds = (size_t)k * KNN_THREADS * 8;
+    hipError_t e = allow_big_lds((const void *)knn_sorted_kernel, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(knn_sorted_kernel, dim3((nq + KNN_THREADS - 1) / KNN_THREADS, b),
                        dim3(KNN_THREADS), lds, (hipStream_t)stream, nq, nr, k, query, ref, idx, dist2);
     return hipGetLastError();

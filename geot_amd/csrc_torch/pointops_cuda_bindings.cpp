@@ -17,6 +17,8 @@ void knnquery_cuda(int m, int nsample, at::Tensor xyz, at::Tensor new_xyz, at::T
     check_f32(xyz, "xyz", 2); check_f32(new_xyz, "new_xyz", 2); check_i32(offset, "offset", 1); check_i32(new_offset, "new_offset", 1);
     check_i32(idx, "idx"); check_f32(dist2, "dist2");
     same_device({&xyz, &new_xyz, &offset, &new_offset, &idx, &dist2});
+    TORCH_CHECK(nsample >= 0 && nsample <= GEOT_KNN_KMAX_HEAP, "knnquery: nsample = ", nsample, " is outside [0, ",
+                GEOT_KNN_KMAX_HEAP, "] (GEOT_KNN_KMAX_HEAP)");
     const int b = offset.size(0);
     TORCH_CHECK(new_offset.size(0) == b, "offset/new_offset length mismatch");
     TORCH_CHECK(new_xyz.size(0) >= m && idx.numel() == (int64_t)m * nsample && dist2.numel() == (int64_t)m * nsample,
@@ -33,6 +35,8 @@ void knnquery_uniform(int b, int n_per, int m_per, int nsample, at::Tensor xyz, 
     check_f32(xyz, "xyz", 2); check_f32(new_xyz, "new_xyz", 2); check_i32(offset, "offset", 1); check_i32(new_offset, "new_offset", 1);
     check_i32(idx, "idx"); check_f32(dist2, "dist2");
     same_device({&xyz, &new_xyz, &offset, &new_offset, &idx, &dist2});
+    TORCH_CHECK(nsample >= 0 && nsample <= GEOT_KNN_KMAX_HEAP, "knnquery: nsample = ", nsample, " is outside [0, ",
+                GEOT_KNN_KMAX_HEAP, "] (GEOT_KNN_KMAX_HEAP)");
     TORCH_CHECK(xyz.size(0) == (int64_t)b * n_per && new_xyz.size(0) == (int64_t)b * m_per &&
                     idx.numel() == (int64_t)b * m_per * nsample && dist2.numel() == (int64_t)b * m_per * nsample &&
                     offset.size(0) == b && new_offset.size(0) == b,

@@ -10,10 +10,16 @@ reference passes it (pointops.py:69-71).
 import torch
 
 from ._common import f32, i32, same_device, need, call, ptr
+from .._lib import KNN_KMAX_HEAP
 
 
 def _as_int(v):
     return int(v.item()) if isinstance(v, torch.Tensor) else int(v)
+
+
+def _check_nsample(nsample):
+    need(0 <= nsample <= KNN_KMAX_HEAP, "knnquery: nsample = %d is outside [0, %d] (GEOT_KNN_KMAX_HEAP)"
+         % (nsample, KNN_KMAX_HEAP))
 
 
 def knnquery_cuda(m, nsample, xyz, new_xyz, offset, new_offset, idx, dist2):
@@ -21,6 +27,7 @@ def knnquery_cuda(m, nsample, xyz, new_xyz, offset, new_offset, idx, dist2):
     i32(idx, "idx"); f32(dist2, "dist2")
     dev = same_device(xyz, new_xyz, offset, new_offset, idx, dist2)
     m, nsample = _as_int(m), _as_int(nsample)
+    _check_nsample(nsample)
     b = offset.shape[0]
     need(new_offset.shape[0] == b, "offset/new_offset length mismatch")
     need(new_xyz.shape[0] >= m and idx.numel() == m * nsample and dist2.numel() == m * nsample,
@@ -31,10 +38,11 @@ def knnquery_cuda(m, nsample, xyz, new_xyz, offset, new_offset, idx, dist2):
 
 def knnquery_uniform(b, n_per, m_per, nsample, xyz, new_xyz, offset, new_offset, idx, dist2):
     """knnquery_cuda for batches of equal segments (b x n_per support, b x m_per queries): same output through
-    the grid search + tie certification (not part of the reference module; used by pointops.knn)."""
+    a sorted search + tie certification (not part of the reference module; used by pointops.knn)."""
     f32(xyz, "xyz", 2); f32(new_xyz, "new_xyz", 2); i32(offset, "offset", 1); i32(new_offset, "new_offset", 1)
     i32(idx, "idx"); f32(dist2, "dist2")
     dev = same_device(xyz, new_xyz, offset, new_offset, idx, dist2)
+    _check_nsample(int(nsample))
     need(xyz.shape[0] == b * n_per and new_xyz.shape[0] == b * m_per and idx.numel() == b * m_per * nsample
          and dist2.numel() == b * m_per * nsample and offset.shape[0] == b and new_offset.shape[0] == b,
          "knnquery_uniform size mismatch")

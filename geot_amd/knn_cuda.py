@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from .ext._common import f32, same_device, need, call, ptr, knn_workspace
+from ._lib import KNN_KMAX_SORTED
 
 
 def knn_sorted(query, ref, k):
@@ -22,6 +23,7 @@ def knn_sorted(query, ref, k):
     b, nq, d = query.shape
     need(d == 3 and ref.shape[2] == 3 and ref.shape[0] == b, "knn expects (B, N, 3) coordinates")
     nr = ref.shape[1]
+    need(int(k) <= KNN_KMAX_SORTED, "knn: k = %d exceeds %d (GEOT_KNN_KMAX_SORTED)" % (int(k), KNN_KMAX_SORTED))
     idx = torch.empty((b, nq, k), dtype=torch.int32, device=dev)
     dist2 = torch.empty((b, nq, k), dtype=torch.float32, device=dev)
     wp, wb, _keep = knn_workspace(dev, b, nq, nr, int(k))   # grid search when the problem is big enough

@@ -25,7 +25,9 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 10
+#define GEOT_ABI_VERSION 11
+#define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
+#define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
 
 /* ABI version / diagnostics. */
@@ -393,7 +395,9 @@ int geot_three_interpolate_grad(int b, int c, int n, int m, const float *grad_ou
 /* ---- kNN --------------------------------------------------------------------
  * Heap-ordered, offset-batched: pointops/src/knnquery/knnquery_cuda_kernel.cu:111-116
  * knnquery_cuda_launcher (extern "C" in knnquery_cuda_kernel.h:9-17).
- * idx (m,nsample) global indices, dist2 (m,nsample) squared.  nsample <= 256. */
+ * idx (m,nsample) global indices, dist2 (m,nsample) squared.  0 <= nsample <= GEOT_KNN_KMAX_HEAP (1024; the reference
+ * allows 1000), anything else is hipErrorInvalidValue before any launch.  The reference's literal max-heap, one list per
+ * lane in LDS: 64 lanes per workgroup up to nsample 128, 32 up to 256, 16 up to 1024 (128 KB). */
 int geot_knnquery_heap(int b, int m, int nsample, const float *xyz, const float *new_xyz,
                        const int *offset, const int *new_offset, int *idx, float *dist2,
                        void *stream);
@@ -403,9 +407,13 @@ int geot_knnquery_heap(int b, int m, int nsample, const float *xyz, const float 
 int geot_knn_sorted_nd(int b, int nq, int nr, int d, int k, const float *query, const float *ref, int *idx,
                        float *dist2, void *stream);
 /* geot_knnquery_heap for uniform batches (every segment n_per support points, m_per queries, as
- * pointops.knn builds them): sorted (nsample+1)-NN from the grid search; queries whose first nsample+1
- * distances are strictly increasing have a unique answer and are copied, the rest (ties, too few
- * candidates) go through the literal heap.  Identical output.  workspace: geot_knnquery_heap_ws_bytes. */
+ * pointops.knn builds them): sorted (nsample+1)-NN -- from the grid search for nsample <= 63, from the
+ * long-list selection kernel of geot_knn_sorted for 64 <= nsample <= GEOT_KNN_KMAX_HEAP, which certifies
+ * in its epilogue; queries whose first nsample+1 distances are strictly increasing (and below the heap's
+ * 1e10 sentinel) have a unique answer and are written, the rest (ties, too few candidates) go through the
+ * literal heap.  Identical output.  workspace: geot_knnquery_heap_ws_bytes, 16-byte aligned; (ABI 11) from nsample
+ * 64 on it is 4 * (b * m_per + 4) bytes rounded up to 16, independent of nsample.  Without a (large
+ * enough) workspace, or under GEOT_NN_IMPL=basic, the literal heap serves every query. */
 long long geot_knnquery_heap_ws_bytes(int b, int n_per, int m_per, int nsample);
 int geot_knnquery_heap_ws(int b, int n_per, int m_per, int nsample, const float *xyz, const float *new_xyz,
                           const int *offset, const int *new_offset, int *idx, float *dist2, void *workspace,
@@ -414,7 +422,11 @@ int geot_knnquery_heap_ws(int b, int n_per, int m_per, int nsample, const float 
  * (openpoints/models/backbone/transformer.py:280,293,313,353) and of
  * knn_point = cdist + topk (openpoints/models/layers/knn.py:7-20).
  * query (b,nq,3), ref (b,nr,3) -> idx (b,nq,k) int32, dist2 (b,nq,k) squared,
- * ascending by (dist2, index); missing neighbours are (inf, 0).  k <= 256. */
+ * ascending by (dist2, index); missing neighbours are (inf, 0).  0 <= k <= GEOT_KNN_KMAX_SORTED (4096),
+ * anything else is hipErrorInvalidValue before any launch.  k <= 64: one wave per 4 queries (or the grid
+ * search of geot_knn_sorted_ws); 65 <= k <= 4096: one workgroup per query, radix select of the k-th
+ * (d2, index) over the distance bits + an LDS bitonic sort, no workspace (GEOT_NN_IMPL=basic keeps the
+ * one-lane insertion kernel for k <= 256, for A/B runs). */
 int geot_knn_sorted(int b, int nq, int nr, int k, const float *query, const float *ref, int *idx,
                     float *dist2, void *stream);
 
