@@ -131,6 +131,8 @@ PROTOTYPES.update({
     "geot_edgeconv_rix_build": [_c_int] * 4 + [_P, _P, ctypes.c_longlong, _c_void_p],
 })
 PROTOTYPES["geot_rowsum_f64"] = [ctypes.c_longlong, _c_int, _P, _P, _c_void_p]
+PROTOTYPES["geot_fixmatch_meters_count"] = [_c_int, _c_int, _c_int, _c_float] + [_P] * 5 + [_c_void_p]
+PROTOTYPES["geot_fixmatch_meters_finalize"] = [_c_int] * 5 + [_P] * 10 + [_c_void_p]
 # entry points that do not follow the "(..., stream) -> hipError_t" shape
 PLAIN = {
     "geot_sa_param_floats": ([_c_int, _c_int, ctypes.POINTER(_c_int)], _c_int),
@@ -166,7 +168,7 @@ PLAIN = {
     "geot_rowdot_small_slices": ([_c_int] * 2, _c_int),
     "geot_colsum_ws_floats": ([_c_int] * 2, ctypes.c_longlong),
 }
-ABI_VERSION = 11    # include/geot_hip.h GEOT_ABI_VERSION this binding was written against
+ABI_VERSION = 12    # include/geot_hip.h GEOT_ABI_VERSION this binding was written against
 KNN_KMAX_HEAP = 1024      # GEOT_KNN_KMAX_HEAP: largest nsample of the heap-ordered kNN (knnquery_cuda, pointops.knn)
 KNN_KMAX_SORTED = 4096    # GEOT_KNN_KMAX_SORTED: largest k of the sorted kNN (knn_cuda.KNN, knn_point in 3-D)
 

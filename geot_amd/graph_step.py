@@ -11,7 +11,10 @@ An iteration is two SINGLE-STREAM graphs (geot_amd/streams.py: on ROCm 7.0 a gra
 
 * **P** -- the step's `lookahead_work()`: everything that depends on a batch and on frozen state alone.  Supervised step:
   the batch's geometry (Group, the 8192-sample FPS, the index plan).  FixMatch+NTM: the student's and the teacher's
-  geometry, the frozen teacher's forward -> pseudo labels, the kNN graph and Morton order of the 3-D loss.
+  geometry, the frozen teacher's forward -> pseudo labels, the kNN graph and Morton order of the 3-D loss; after the
+  step's switch_ep (FixMatchNTMStep.set_epoch) the student's geometry and the kNN graph / order only -- each phase has a
+  P and an M of its own ("P" / "M" and "P@2" / "M@2"), captured on first use, and a look-ahead made under one phase is
+  never handed to the other's M (P then runs in line, same results).
 * **M** -- the training iteration proper over P's product: forward, losses, backward, AdamW (capturable=True; under
   fused=True the step counters live on the device either way: the same kernel), the EMA transition matrix updated in
   its buffer.
@@ -132,12 +135,14 @@ class _Graphed:
         self.warmup = int(warmup)
         self.calls = 0
         self.device = None
-        self.graphs = {}          # "P" / "M" -> (CUDAGraph, static outputs)
-        self.node_types = {}      # "P" / "M" -> {"kernel": n, ...} of the captured graph
+        self.graphs = {}          # "P" / "M" (/ "M1" / "M2"; + "@2" for FixMatch's second phase) -> (CUDAGraph, static outputs)
+        self.node_types = {}      # same keys -> {"kernel": n, ...} of the captured graph
         self._eager_runs = {"P": 0, "M": 0}
         self.side = None          # the stream P replays on beside M
-        self.pre = None           # P's product in M's input buffers
+        self.pre = None           # P's product in M's input buffers (of the phase that runs now)
+        self._pres = {}           # phase tag -> its M's input buffers
         self._pre_next = None     # P's product as P left it (for the batch `_announced` describes)
+        self._pre_tag = None      # the phase tag P ran under for _pre_next
         self._announced = None
         self._pending = False     # a P is in flight on the side stream
         for opt in step.optimizers():
@@ -202,7 +207,9 @@ class _Graphed:
 
     @property
     def captured(self):
-        return ("M" in self.graphs or "M2" in self.graphs) and "P" in self.graphs
+        """A P and an M (or M2) of the same phase are captured."""
+        tags = {k[k.index("@"):] if "@" in k else "" for k in self.graphs}
+        return any(("M" + t in self.graphs or "M2" + t in self.graphs) and "P" + t in self.graphs for t in tags)
 
     def _join_pending(self):
         """The current stream waits for the P of the previous call (its product, and its reads of P's static inputs)."""
@@ -210,44 +217,50 @@ class _Graphed:
             torch.cuda.current_stream(self.device).wait_stream(self.side)
             self._pending = False
 
-    def _iterate(self, announced_now, next_src, load_next, lookahead, train):
+    def _iterate(self, announced_now, next_src, load_next, lookahead, train, tag=""):
         """announced_now: does the pending look-ahead describe the batch that was just copied in?  next_src: the tensors
         of the announced next batch (None: no look-ahead); load_next(current: bool): fill P's static inputs from the
-        current batch / the announced one; lookahead() / train(): the bodies of P / M.  (_join_pending() has run.)"""
+        current batch / the announced one; lookahead() / train(): the bodies of P / M; tag: the phase, appended to the
+        graph names (each phase its own P and M, and its own M input buffers).  (_join_pending() has run.)"""
         dev = self.device
         main = torch.cuda.current_stream(dev)
         if self.side is None:
             self.side = torch.cuda.Stream(device=dev)
-        if not (announced_now and self._pre_next is not None):
-            # nobody looked ahead for this batch (first call, an unannounced batch, no look-ahead): P now, in line
+        if not (announced_now and self._pre_next is not None and self._pre_tag == tag):
+            # nobody looked ahead for this batch (first call, an unannounced batch, no look-ahead, a look-ahead made under
+            # the other phase): P now, in line
             load_next(True)
-            self._pre_next = self._run("P", lookahead)
+            self._pre_next = self._run("P" + tag, lookahead)
         with torch.no_grad():
-            if self.pre is None:
-                self.pre = tree_clone(self._pre_next)
+            pre = self._pres.get(tag)
+            if pre is None:
+                self._pres[tag] = pre = tree_clone(self._pre_next)
             else:
-                tree_copy_(self.pre, self._pre_next)
-        self._pre_next = None
+                tree_copy_(pre, self._pre_next)
+            self.pre = pre
+        self._pre_next = self._pre_tag = None
         self._announced = None
         mid = None
         if isinstance(train, tuple):                 # (forward, backward): P starts between the two, beside the backward
-            mid = self._run("M1", train[0])
+            mid = self._run("M1" + tag, train[0])
         if next_src is not None:
             load_next(False)
             self.side.wait_stream(main)              # behind the copies above (and behind M's previous replay)
             with torch.cuda.stream(self.side):
-                self._pre_next = self._run("P", lookahead)
+                self._pre_next = self._run("P" + tag, lookahead)
+            self._pre_tag = tag
             self._pending = True
             self._announced = tuple((t, t._version) for t in next_src)
-        fresh = isinstance(train, tuple) and "M2" not in self.graphs
-        out = self._run("M2", lambda: train[1](mid), pool_of="M1") if isinstance(train, tuple) else self._run("M", train)
-        if fresh and "M2" in self.graphs:
+        m1, m2 = "M1" + tag, "M2" + tag
+        fresh = isinstance(train, tuple) and m2 not in self.graphs
+        out = self._run(m2, lambda: train[1](mid), pool_of=m1) if isinstance(train, tuple) else self._run("M" + tag, train)
+        if fresh and m2 in self.graphs:
             # M1's stored product (the cut: tensors with the capture-time iteration's autograd graph behind them) has done its
             # job -- M2 is captured and a replay never runs the python backward again.  Kept as it was, it would hold that
             # graph, every parameter's AccumulateGrad node with it (created on the capture stream), for the life of the
             # wrapper, and an eager step afterwards (bench.py's other leg) would find them on the wrong stream.
-            g1, o1 = self.graphs["M1"]
-            self.graphs["M1"] = (g1, tree_detach(o1))
+            g1, o1 = self.graphs[m1]
+            self.graphs[m1] = (g1, tree_detach(o1))
         self.calls += 1
         return out
 
@@ -313,10 +326,14 @@ class GraphedSupervisedStep(_Graphed):
 
 
 _P_KEYS = (("pos",), ("pos_s", "pos_w", "x_w", "cls_w", "raw_pos"))      # what FixMatchNTMStep.lookahead_work reads
+_P_KEYS_2 = (("pos",), ("pos_s", "pos_w", "raw_pos"))                     # ... after switch_ep (no teacher forward)
 
 
 class GraphedFixMatchStep(_Graphed):
-    """FixMatchNTMStep.__call__ from hipGraphs.  The returned losses are static tensors the next call overwrites."""
+    """FixMatchNTMStep.__call__ from hipGraphs.  The returned losses are static tensors the next call overwrites.  The phase
+    follows the wrapped step's epoch (step.set_epoch, or set_epoch here): a P and an M per phase, each captured on first use.
+    With the step's meters on, data_u["y"] is copied into the static buffers like every other key, and the meters' two
+    kernels are nodes of M."""
 
     def __init__(self, step, warmup=2, split=None, agree=None):
         """split: as GraphedSupervisedStep -- M1 ends where the backward reaches the student's transformer blocks, P starts
@@ -329,6 +346,7 @@ class GraphedFixMatchStep(_Graphed):
 
     def __call__(self, data, data_u, next_batches=None):
         step = self.step
+        step.check_meter_batch(data_u)
         if self.data is None:
             self.device = data["pos"].device
             self.data = {k: v.detach().clone().contiguous() for k, v in data.items() if torch.is_tensor(v)}
@@ -338,7 +356,9 @@ class GraphedFixMatchStep(_Graphed):
             for k, v in dst.items():
                 _fits(v, src[k], "%s[%r]" % (what, k))
         self._check_lr()
-        announced_now = self._is_announced([b[k] for b, keys in zip((data, data_u), _P_KEYS) for k in keys])
+        self_labelling = step.self_labelling
+        tag, p_keys = ("@2", _P_KEYS_2) if self_labelling else ("", _P_KEYS)
+        announced_now = self._is_announced([b[k] for b, keys in zip((data, data_u), p_keys) for k in keys])
         self._join_pending()
         for dst, src in ((self.data, data), (self.data_u, data_u)):
             for k, v in dst.items():
@@ -346,13 +366,13 @@ class GraphedFixMatchStep(_Graphed):
 
         def load_next(current):
             srcs = (self.data, self.data_u) if current else next_batches
-            for dst, src, keys in zip(self.next, srcs, _P_KEYS):
+            for dst, src, keys in zip(self.next, srcs, p_keys):
                 for k in keys:
                     _fits(dst[k], src[k], "next[%r]" % k)
                     dst[k].copy_(src[k])
 
         def lookahead():
-            return step.lookahead_work(self.next[0], self.next[1])
+            return step.lookahead_work(self.next[0], self.next[1], self_labelling=self_labelling)
 
         def train():
             pre = self.pre
@@ -368,5 +388,9 @@ class GraphedFixMatchStep(_Graphed):
                 rest()
                 return self._losses
             train = (head, rest_update)
-        next_src = None if next_batches is None else [b[k] for b, keys in zip(next_batches, _P_KEYS) for k in keys]
-        return self._iterate(announced_now, next_src, load_next, lookahead, train)
+        next_src = None if next_batches is None else [b[k] for b, keys in zip(next_batches, p_keys) for k in keys]
+        return self._iterate(announced_now, next_src, load_next, lookahead, train, tag)
+
+    def set_epoch(self, epoch):
+        """The wrapped step's set_epoch."""
+        self.step.set_epoch(epoch)

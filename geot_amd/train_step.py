@@ -1,13 +1,15 @@
 """The training steps the BASELINE configs time, composed from the mirrored modules -- the part of
 examples/segmentation/train.py that drives the hot path, and nothing else of the driver (no loaders,
-meters, logging, checkpoints):
+logging, checkpoints; the epoch meters only on request, computed on the device):
 
 * ``SupervisedStep``  -- configs[2]/[3]: forward of the segmentor on a batch of clouds, Poly1FocalLoss,
   backward, (DDP gradient all-reduce when wrapped,) clip + AdamW step (train.py:436-452, 646-657).
-* ``FixMatchNTMStep`` -- configs[4]: one semi-supervised iteration (train.py:455-602, 646-660): frozen
-  teacher on the weak view -> pseudo labels; student on labelled + strong + weak (WholePartSeg, 6 clouds
-  at B_l = B_u = 2); class-level transition (anchors, Gaussian prior, EMA); per-point transition matrices
-  (T_predictor); corrected strong logits; 3-D smoothness loss; Poly1Focal losses; backward; both optimisers.
+* ``FixMatchNTMStep`` -- configs[4]: one semi-supervised iteration (train.py:455-602, 646-699): frozen
+  teacher on the weak view -> pseudo labels (after cfg switch_ep: the student's own weak view, set_epoch());
+  student on labelled + strong + weak (WholePartSeg, 6 clouds at B_l = B_u = 2); class-level transition (anchors,
+  Gaussian prior, EMA); per-point transition matrices (T_predictor); corrected strong logits; 3-D smoothness loss;
+  Poly1Focal losses; backward; both optimisers.  Optionally the epoch meters (train.py:599-644, 672-699) on the
+  device: geot_amd/meters.py.
 
 Both are plain callables over device tensors; `ddp()` wraps student and T_predictor the way train.py:159-166
 does (SyncBatchNorm + DistributedDataParallel) -- and also wraps T_predictor, which the reference leaves
@@ -26,7 +28,7 @@ from .openpoints.models.segmentation import WholePartSeg
 
 NTM_CFG = dict(threshold=0.0, unsupervised_loss_weight=1.0, ema_t_decay=0.999, lambma=0.9, geo_lambma=0.999,
                threed_loss_weight=0.1, threed_k=32, threed_sigma=1.0, filter_outlier=False, lr=1e-3,
-               weight_decay=1e-4, grad_norm_clip=None, batch_size_l=2, batch_size_u=2, num_classes=17)
+               weight_decay=1e-4, grad_norm_clip=None, batch_size_l=2, batch_size_u=2, num_classes=17, switch_ep=50)
 # cfgs/tooth_semi/transformer_finetune_fixmatch_ntm.yaml:45-96 (+ default.yaml)
 
 
@@ -290,9 +292,14 @@ class SupervisedStep:
 
 
 class FixMatchNTMStep:
-    """State of train_one_epoch that survives an iteration: ema_t (C,C), cm (C,C), both optimisers."""
+    """State of train_one_epoch that survives an iteration: ema_t (C,C), cm (C,C), both optimisers (and the epoch meters,
+    when asked for).  The epoch set by set_epoch() picks the pseudo labels' source, as train.py:469-498 does: the frozen
+    teacher up to cfg switch_ep (and when no epoch was ever set), the student's own weak view after it."""
 
-    def __init__(self, student, teacher, t_predictor, cm=None, cfg=None, group=None):
+    def __init__(self, student, teacher, t_predictor, cm=None, cfg=None, group=None, meters=None):
+        """meters: None / False (off: nothing runs), True (a geot_amd.meters.FixMatchMeters from cfg) or such an object --
+        updated by every iteration on the device, read with its read(), emptied with its reset().  The unlabelled batch
+        must then carry the ground truth data_u["y"] (B_u, N) or (B_u, N, 1)."""
         self.cfg = dict(NTM_CFG, **(cfg or {}))
         c = self.cfg["num_classes"]
         self.model, self.model_t, self.T_predictor = student, teacher, t_predictor
@@ -314,12 +321,41 @@ class FixMatchNTMStep:
         self.overlap_teacher = os.environ.get("GEOT_TEACHER_STREAM", "1") != "0"
         self.share_weak_geometry = os.environ.get("GEOT_SHARE_WEAK_GEOMETRY", "1") != "0"
         self.grad_sync = None          # a GradSync: see SupervisedStep
+        self.epoch = None              # set_epoch(); None: never set (the teacher's phase)
+        if meters is True:
+            from .meters import FixMatchMeters
+            meters = FixMatchMeters(c, dev, self.cfg["batch_size_l"], self.cfg["batch_size_u"], self.cfg["threshold"], self.ema_t)
+        self.meters = meters or None
+        if self.meters is not None and self.meters.ema_t is None:
+            self.meters.ema_t = self.ema_t           # read() reports the step's transition buffer
 
     def optimizers(self):
         return [self.optimizer, self.T_optimizer]
 
     def sync_modules(self):
         return [self.model, self.T_predictor]
+
+    def set_epoch(self, epoch):
+        """The epoch of the iterations that follow (train.py's loop variable): above cfg switch_ep the pseudo labels come
+        from the student's own weak view and the teacher no longer runs (train.py:469-475, 494-498)."""
+        self.epoch = None if epoch is None else int(epoch)
+
+    @property
+    def self_labelling(self):
+        """True after switch_ep: the phase in which the student labels its own weak view."""
+        return self.epoch is not None and self.epoch > self.cfg["switch_ep"]
+
+    def check_meter_batch(self, data_u):
+        """With the meters on, the unlabelled batch must carry its ground truth data_u["y"] on the meters' GPU: checked
+        before anything of the iteration is queued (the meters' kernels read it through a raw device pointer)."""
+        if self.meters is None:
+            return
+        y = data_u.get("y")
+        if not torch.is_tensor(y):
+            raise RuntimeError("FixMatchNTMStep(meters=...): the unlabelled batch carries no ground truth data_u['y']")
+        if y.device != self.meters.counts.device:
+            raise RuntimeError("FixMatchNTMStep(meters=...): data_u['y'] is on %s, the meters on %s -- move it to the GPU"
+                               % (y.device, self.meters.counts.device))
 
     def __call__(self, data, data_u, next_batches=None):
         """data: labelled batch {pos (B_l,N,3), x (B_l,3,N), cls (B_l,1), y (B_l,N)}; data_u: unlabelled batch
@@ -328,6 +364,7 @@ class FixMatchNTMStep:
         the next student and teacher batches is queued behind this iteration's student forward (SupervisedStep's look-ahead;
         the caller must then pass exactly those dicts next time -- the positions are matched by identity and version
         counter, not trusted)."""
+        self.check_meter_batch(data_u)
         geoms = self._geometry
         self._geometry = (None, None)
         if geoms[0] is not None and not _same_positions_impl(self._geometry_src, data, data_u):
@@ -355,29 +392,34 @@ class FixMatchNTMStep:
             g = inner.weak_view_geometry(geom_s, data, data_u)
         return g if g is not None else self.model_t.prefetch_geometry(data_u, if_teacher=True, inline=inline)
 
-    def lookahead_work(self, data, data_u):
+    def lookahead_work(self, data, data_u, self_labelling=None):
         """Everything of an iteration that depends on its batches and on FROZEN state alone, on the CURRENT stream: the
         student's and the teacher's geometry, the teacher's forward -> pseudo labels (the teacher is never updated:
         train.py:218-222 loads and freezes it; it is in eval mode and draws no random numbers), the kNN graph and Morton
         order of the 3-D loss.  -> the `pre` dict student_iteration() takes.  graph_step.py replays this as a graph of its own
         on a second stream beside the PREVIOUS iteration's training graph; the eager iteration() below spreads the same work
-        over side streams inside the iteration instead."""
+        over side streams inside the iteration instead.  After switch_ep (self_labelling; default: the step's epoch) the
+        teacher does not run: the student's geometry and the 3-D loss's graph only, "pseudo" is None."""
+        if self_labelling is None:
+            self_labelling = self.self_labelling
         _mode(self.model, True)
         inner = self.model.module if hasattr(self.model, "module") else self.model
         with torch.no_grad():
             geom_s = inner.prefetch_geometry(data, data_u, fixmatch=True, inline=True)
-            _mode(self.model_t, False)
-            geom_t = self._teacher_geometry(inner, geom_s, data, data_u, inline=True)
+            if not self_labelling:
+                _mode(self.model_t, False)
+                geom_t = self._teacher_geometry(inner, geom_s, data, data_u, inline=True)
             raw = data_u["raw_pos"].contiguous()
             nbr = self.threed_loss.neighbours(raw)
             order = ntm_mod.spatial_order(raw)
-        pred_u, logits_u_aug, label_u_aug = self._pseudo_labels(data_u, geom_t)
-        return {"geom_s": geom_s, "pseudo": (pred_u, logits_u_aug, label_u_aug), "knn": (nbr, order)}
+        pseudo = None if self_labelling else self._pseudo_labels(data_u, geom_t)
+        return {"geom_s": geom_s, "pseudo": pseudo, "knn": (nbr, order)}
 
     def iteration(self, data, data_u, geoms=(None, None), next_batches=None):
         """One iteration, eagerly, its batch-only work spread over side streams -> (dict of detached losses, (student,
-        teacher) geometries queued for next_batches)."""
+        teacher) geometries queued for next_batches; no teacher geometry after switch_ep)."""
         geom_s, geom_t = geoms
+        self_labelling = self.self_labelling
         # the kNN graph of the 3-D loss needs raw_pos only: build it beside the teacher / student forwards
         dev = data["pos"].device
         nbr = order = None
@@ -395,14 +437,16 @@ class FixMatchNTMStep:
         #    depends on it, so it is queued on a stream of its own and the student's kernels fill the gap (the eval-mode
         #    teacher draws no random numbers: identical results).  Its outputs are first used at step 3, after the join;
         #    next iteration's entry wait keeps the stream's allocations ordered behind this iteration's readers.
-        t_stream = None
-        if dev.type == "cuda" and self.overlap_teacher:
+        #    After switch_ep there is no teacher: student_iteration takes the pseudo labels from the student's weak view.
+        t_stream = pseudo = None
+        if dev.type == "cuda" and self.overlap_teacher and not self_labelling:
             if self._teacher_stream is None:
                 self._teacher_stream = torch.cuda.Stream(device=dev)
             t_stream = self._teacher_stream
             t_stream.wait_stream(torch.cuda.current_stream(dev))
-        with (torch.cuda.stream(t_stream) if t_stream is not None else contextlib.nullcontext()):
-            pseudo = self._pseudo_labels(data_u, geom_t)
+        if not self_labelling:
+            with (torch.cuda.stream(t_stream) if t_stream is not None else contextlib.nullcontext()):
+                pseudo = self._pseudo_labels(data_u, geom_t)
         inner = self.model.module if hasattr(self.model, "module") else self.model
         queued = [(None, None)]
         queue = None
@@ -410,9 +454,10 @@ class FixMatchNTMStep:
             nd, nu = next_batches
 
             def queue():
-                _mode(self.model_t, False)
+                if not self_labelling:
+                    _mode(self.model_t, False)
                 g_s = inner.prefetch_geometry(nd, nu, fixmatch=True)
-                queued[0] = (g_s, self._teacher_geometry(inner, g_s, nd, nu))
+                queued[0] = (g_s, None if self_labelling else self._teacher_geometry(inner, g_s, nd, nu))
         at_blocks = _lookahead_at_blocks(inner.segmentor, "forward")
         if queue is not None and at_blocks:
             inner.segmentor.at_blocks_backward = queue      # runs when the student's backward reaches the transformer blocks
@@ -440,13 +485,16 @@ class FixMatchNTMStep:
     def student_iteration(self, data, data_u, geom_s, pseudo, knn_graph, after_forward=None, ema_in_place=False,
                           defer_rest=False):
         """Steps 2-5 of the iteration (train.py:478-602, 646-660): the student on labelled + strong + weak views, the class
-        transition, the per-point matrices, the corrected logits, the losses, backward, both optimisers.
-        pseudo = (pred_u, logits_u_aug, label_u_aug) of the teacher; knn_graph = (nbr, order) of raw_pos or a callable that
-        returns them (called where they are first needed); after_forward(): called behind the student's forward (the eager
-        iteration joins its teacher stream and queues its look-ahead there); ema_in_place: update ema_t IN its buffer
-        (a captured graph holds the buffer, not the attribute); defer_rest: stop where the backward reaches the student's
-        transformer blocks (the segmentor cuts its autograd graph there) and return (losses, rest) -- rest() runs the backward
-        of the blocks and the patch encoder, the EMA update and both optimisers (graph_step's split capture)."""
+        transition, the per-point matrices, the corrected logits, the losses, backward, both optimisers (and the meters).
+        pseudo = (pred_u, logits_u_aug, label_u_aug) of the teacher, or None after switch_ep: then they are the soft-max of
+        the student's weak-view slice and its maximum (train.py:494-498) -- from the DETACHED slice: the reference only
+        ever uses detached copies of that pred_u (:498, :507), so autograd stays out of it; knn_graph = (nbr, order) of
+        raw_pos or a callable that returns them (called where they are first needed); after_forward(): called behind the
+        student's forward (the eager iteration joins its teacher stream and queues its look-ahead there); ema_in_place:
+        update ema_t IN its buffer (a captured graph holds the buffer, not the attribute); defer_rest: stop where the
+        backward reaches the student's transformer blocks (the segmentor cuts its autograd graph there) and return
+        (losses, rest) -- rest() runs the backward of the blocks and the patch encoder, the EMA update and both optimisers
+        (graph_step's split capture)."""
         cfg = self.cfg
         seg = getattr(self.model.module if hasattr(self.model, "module") else self.model, "segmentor", None)
         can_cut = defer_rest and hasattr(seg, "take_cut")
@@ -466,7 +514,12 @@ class FixMatchNTMStep:
         cut = seg.take_cut() if can_cut else None
         # (split, not two slices: its backward is one concatenation kernel; a slice's backward copies the gradient into a zero
         # tensor with a device-to-device memcpy -- a memcpy node when the iteration is captured)
-        pred_l, pred_u_strong = torch.split(pred_all, [bl, bu, pred_all.shape[0] - bl - bu])[:2]
+        pred_l, pred_u_strong, pred_u_weak = torch.split(pred_all, [bl, bu, pred_all.shape[0] - bl - bu])
+        if pseudo is None:
+            with torch.no_grad():
+                pred_u = F.softmax(pred_u_weak.detach(), dim=1)
+                logits_u_aug, label_u_aug = torch.max(pred_u, dim=1)
+            pseudo = (pred_u, logits_u_aug, label_u_aug)
         if after_forward is not None:
             after_forward()
         pred_u, logits_u_aug, label_u_aug = pseudo
@@ -475,7 +528,8 @@ class FixMatchNTMStep:
             pred_u, sigma, self.ema_t, cfg["geo_lambma"], cfg["ema_t_decay"], group=self.group,
             filter_outlier=cfg["filter_outlier"])
         # 4. per-point matrices + corrected strong logits (train.py:547-552)
-        ins_t = _inner(self.T_predictor, self.grad_sync is not None)(F.softmax(pred_u_strong, dim=1).detach(), self.cm)
+        prob_s = F.softmax(pred_u_strong, dim=1).detach()
+        ins_t = _inner(self.T_predictor, self.grad_sync is not None)(prob_s, self.cm)
         pred_u_strong_corr = ntm_mod.correct_logits(pred_u_strong, ins_t, ema_t_corr, cfg["lambma"])
         if not ema_in_place:
             with torch.no_grad():      # in its buffer, never rebound: a captured replay (graph_step) holds this very tensor
@@ -489,6 +543,10 @@ class FixMatchNTMStep:
         thresh_mask = logits_u_aug.ge(cfg["threshold"])
         unsup_loss = unsup_loss * (cfg["unsupervised_loss_weight"] * (bu * n) / thresh_mask.sum())
         loss = sup_loss + unsup_loss + loss_3d
+        if self.meters is not None:
+            if "y" not in data_u:
+                raise RuntimeError("FixMatchNTMStep(meters=...): the unlabelled batch carries no ground truth data_u['y']")
+            self.meters.update(label_u_aug, logits_u_aug, data_u["y"], prob_s, loss, sup_loss, unsup_loss, loss_3d, ema_t_corr)
         loss.backward()
         rest_in = None if cut is None else (cut[0], [d.grad for d in cut[1]])
 
@@ -518,10 +576,11 @@ def _same_positions_impl(src, data, data_u):
         and all(t._version == v for t, v in zip(src, src[3]))
 
 
-def build_fixmatch(device, seg_cfg=None, cfg=None, use_ddp=True, group=None, graph_sync=False, min_world=2):
+def build_fixmatch(device, seg_cfg=None, cfg=None, use_ddp=True, group=None, graph_sync=False, min_world=2, meters=None):
     """Student, frozen teacher and T_predictor as train.py:154-226 builds them (random init: the pretrained
     checkpoints are the authors' local files).  graph_sync: the data-parallel form for a replay from hipGraphs -- bare
-    SyncBatchNorm-converted modules + one flat gradient all-reduce (sync_only / GradSync) instead of DDP wrappers."""
+    SyncBatchNorm-converted modules + one flat gradient all-reduce (sync_only / GradSync) instead of DDP wrappers.
+    meters: see FixMatchNTMStep."""
     from .openpoints.models.backbone.transformer import TOOTH_SEG_CFG
     seg = dict(NAME="PointTransformer_seg_T", **(seg_cfg or TOOTH_SEG_CFG))
     student = WholePartSeg(segmentor_args=seg).to(device)
@@ -531,11 +590,11 @@ def build_fixmatch(device, seg_cfg=None, cfg=None, use_ddp=True, group=None, gra
     if graph_sync:
         import torch.distributed as dist
         student = sync_only(student, min_world=min_world)
-        step = FixMatchNTMStep(student, teacher, t_pred, cfg=cfg, group=group)
+        step = FixMatchNTMStep(student, teacher, t_pred, cfg=cfg, group=group, meters=meters)
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() >= min_world:
             step.grad_sync = GradSync([student, t_pred], group)
         return step
     if use_ddp:
         student = ddp(student, device, unused=UNUSED_FIXMATCH, min_world=min_world)
         t_pred = ddp(t_pred, device, sync_bn=False, min_world=min_world)
-    return FixMatchNTMStep(student, teacher, t_pred, cfg=cfg, group=group)
+    return FixMatchNTMStep(student, teacher, t_pred, cfg=cfg, group=group, meters=meters)

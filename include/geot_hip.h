@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 11
+#define GEOT_ABI_VERSION 12
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -626,6 +626,29 @@ int geot_pc_norm_stats(int n, const float *points, float *stats, void *ws, long 
 int geot_cloud_sample(int n, int m, int num_classes, const float *points, const int *labels,
                       const long long *selected, const float *stats, float *out_points, long long *out_labels,
                       float *class_weights, int *hist_ws, void *stream);
+
+/* ---- FixMatch epoch meters (ABI 12) ----------------------------------------------------------------------------------
+ * The per-iteration statistics of examples/segmentation/train.py:599-644 and their AverageMeters (:672-699), on the device
+ * (geot_amd/csrc/meters.hip): no host synchronisation, capturable.  b * n < 2^24 unlabelled points, 1 <= c <= GEOT_NTM_MAX_C.
+ * geot_fixmatch_meters_count adds into counts (8 + 4 c ints, zero on entry -- the finalize leaves them so):
+ *   pseudo t (b,n) int64, conf (b,n) fp32 -> mask m = conf >= threshold; gt g (b,n) int64; prob (b,c,n) fp32, the student's
+ *   strong-view soft-max -> s = its first maximum over c (a NaN counts as the maximum, as torch.max picks it).
+ *   [0] sum m  [1] sum [t=g]  [2] sum [s=g]  [3] sum m[t=g]  [4] sum [t>0]  [5] sum m[t>0]  [6] sum m[t>0][t=g]
+ *   [7] labels t or g outside [0, c)  [8 + k c + cls], k = 0..3: sum m[t=cls], sum m[t=cls][g=cls], sum [t=cls], sum [g=cls]
+ * geot_fixmatch_meters_finalize (one workgroup) forms the iteration's values from counts with the reference's arithmetic,
+ * updates the meters with n = n_u (n_l + n_u for the total loss, n_l for the supervised loss) and zeroes counts.
+ *   meters_f32 (18): value[6], sum[6], avg[6] of th_percentage, mean_pseudo_label_acc, teacher_acc, student_acc,
+ *                    over_th_wobg, over_acc_wobg (fp32 tensors in the reference)
+ *   meters_f64 (18 + 9 c): value[6], sum[6], avg[6] of the loss meters loss, loss_l, loss_u, feat (0), identity (0), 3d;
+ *                    then value[3c], sum[3c], avg[3c] of the per-class lists pseudo_label_acc, th_meter_u, th_meter_u_recall
+ *   meters_i64 (5):  count of n_l + n_u, of n_l, of n_u; labels outside [0, c) so far; iterations
+ *   loss / sup / unsup / threed: device fp32 scalars; ema_corr (c,c) is copied to ema_corr_out (both may be NULL). */
+int geot_fixmatch_meters_count(int b, int n, int c, float threshold, const long long *pseudo, const float *conf,
+                               const long long *gt, const float *prob, int *counts, void *stream);
+int geot_fixmatch_meters_finalize(int b, int n, int c, int n_l, int n_u, const float *loss, const float *sup,
+                                  const float *unsup, const float *threed, const float *ema_corr, int *counts,
+                                  float *meters_f32, double *meters_f64, long long *meters_i64, float *ema_corr_out,
+                                  void *stream);
 
 #ifdef __cplusplus
 }
