@@ -133,6 +133,8 @@ PROTOTYPES.update({
 PROTOTYPES["geot_rowsum_f64"] = [ctypes.c_longlong, _c_int, _P, _P, _c_void_p]
 PROTOTYPES["geot_fixmatch_meters_count"] = [_c_int, _c_int, _c_int, _c_float] + [_P] * 5 + [_c_void_p]
 PROTOTYPES["geot_fixmatch_meters_finalize"] = [_c_int] * 5 + [_P] * 10 + [_c_void_p]
+PROTOTYPES["geot_seg_confusion"] = [_c_int, _c_int] + [_P] * 4 + [_c_void_p]
+PROTOTYPES["geot_seg_confusion_interp"] = [_c_int] * 3 + [_P] * 6 + [_c_void_p]
 # entry points that do not follow the "(..., stream) -> hipError_t" shape
 PLAIN = {
     "geot_sa_param_floats": ([_c_int, _c_int, ctypes.POINTER(_c_int)], _c_int),
@@ -168,7 +170,7 @@ PLAIN = {
     "geot_rowdot_small_slices": ([_c_int] * 2, _c_int),
     "geot_colsum_ws_floats": ([_c_int] * 2, ctypes.c_longlong),
 }
-ABI_VERSION = 12    # include/geot_hip.h GEOT_ABI_VERSION this binding was written against
+ABI_VERSION = 13    # include/geot_hip.h GEOT_ABI_VERSION this binding was written against
 KNN_KMAX_HEAP = 1024      # GEOT_KNN_KMAX_HEAP: largest nsample of the heap-ordered kNN (knnquery_cuda, pointops.knn)
 KNN_KMAX_SORTED = 4096    # GEOT_KNN_KMAX_SORTED: largest k of the sorted kNN (knn_cuda.KNN, knn_point in 3-D)
 

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 12
+#define GEOT_ABI_VERSION 13
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -649,6 +649,28 @@ int geot_fixmatch_meters_finalize(int b, int n, int c, int n_l, int n_u, const f
                                   const float *unsup, const float *threed, const float *ema_corr, int *counts,
                                   float *meters_f32, double *meters_f64, long long *meters_i64, float *ema_corr_out,
                                   void *stream);
+
+/* ---- validation metrics (ABI 13) ---------------------------------------------------------------------------------------
+ * The counts behind examples/segmentation/train.py:802-832 get_seg_metrics (per-scan accuracy, IoU and DSC of the classes
+ * present) and :757-763 (jaw and whole means), on the device (geot_amd/csrc/seg_metrics.hip): no host synchronisation.
+ * b >= 0 scans in one launch (b == 0: nothing to do, success), 1 <= c <= GEOT_NTM_MAX_C; anything else is
+ * hipErrorInvalidValue before any launch.  offsets (b + 1) int64 on the device: scan s owns vertices
+ * [offsets[s], offsets[s + 1]) of the concatenated per-vertex arrays, at most 2^31 - 1 of them.
+ * counts: b slots of c (c + 1) + 1 int64 each; the caller zeroes them, the launch ADDS into them (batches accumulate):
+ *   [label * (c + 1) + pred]  vertices with that label and prediction, both in [0, c)
+ *   [label * (c + 1) + c]     vertices with that label in [0, c) and a prediction outside [0, c)
+ *   [c (c + 1)]               vertices whose label is outside [0, c)
+ * Integer atomics only: the counts do not depend on the schedule.
+ * geot_seg_confusion: pred / label int64 per vertex.
+ * geot_seg_confusion_interp: the prediction is get_pred_whole's (train.py:781-800), made per vertex in registers:
+ *   prob (b, c, n) fp32 = the soft-max of the n sampled points; idx (M, 3) int32 / dist2 (M, 3) fp32 = three_nn of every
+ *   vertex among its scan's sampled points (squared distances); weights 1.0 / (sqrt(d2) + 1e-8) over their torch.sum
+ *   ((r0 + r2) + r1), the interpolation p0 w0 + p1 w1 + p2 w2 un-contracted, torch.argmax's rule (first maximum, a NaN
+ *   wins).  n >= 1. */
+int geot_seg_confusion(int b, int c, const long long *offsets, const long long *pred, const long long *label,
+                       long long *counts, void *stream);
+int geot_seg_confusion_interp(int b, int c, int n, const long long *offsets, const float *prob, const int *idx,
+                              const float *dist2, const long long *label, long long *counts, void *stream);
 
 #ifdef __cplusplus
 }
