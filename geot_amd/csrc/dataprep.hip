@@ -5,6 +5,7 @@
 //                     (voxel barycentres of points and features, majority label per voxel)
 //   pc_norm + random-choice gather + class weights
 //                     openpoints/dataset/tooth_semi/tooth_dataset.py:108-147
+//                     (per scan, and for a whole batch of scans in five launches: geot_cloud_sample_batch)
 //
 // grid_subsampling is HBM/latency-bound integer + fp32 work.  The reference builds a hash map and adds each
 // point into its voxel in input order; the sums are fp32, so the order is part of the result.  Here:
@@ -321,6 +322,164 @@ __global__ void pn_weights_kernel(int num_classes, const int *__restrict__ hist,
     }
 }
 
+// ---- the same for S scans of a concatenated set in one launch each (geot_cloud_sample_batch) ----------------------------------
+// blockIdx.y = batch slot.  Every per-scan statement above is kept as it is -- the fp64 tree of pn_sum_kernel with its
+// PN_BLOCKS x PN_THREADS layout, the centroid's serial sum over the blocks, the fp32 norm, the divide -- so a slot's results
+// carry the bits of the single-scan calls.  The sizes live on the device (offsets), so no grid depends on them.
+struct PnScan {
+    long long base;      // first vertex of the slot's scan in the concatenated arrays
+    int n;               // its vertex count; 0: the slot's table entries are unusable
+};
+__device__ __forceinline__ PnScan pnb_scan(int slot, int n_scans, long long total, const long long *__restrict__ offsets,
+                                           const long long *__restrict__ scan_ids)
+{
+    PnScan r = {0, 0};
+    const long long id = scan_ids ? scan_ids[slot] : (long long)slot;
+    if (id < 0 || id >= n_scans) return r;
+    const long long a = offsets[id], b = offsets[id + 1];
+    if (a < 0 || b > total || b <= a || b - a > 0x7fffffffLL) return r;
+    r.base = a;
+    r.n = (int)(b - a);
+    return r;
+}
+
+__global__ __launch_bounds__(PN_THREADS) void pnb_sum_kernel(int n_scans, long long total, const float *__restrict__ points,
+                                                             const long long *__restrict__ offsets,
+                                                             const long long *__restrict__ scan_ids, double *__restrict__ partial)
+{
+    __shared__ double red[3][PN_THREADS];
+    const PnScan sc = pnb_scan(blockIdx.y, n_scans, total, offsets, scan_ids);
+    const float *pts = points + 3 * (size_t)sc.base;
+    double s[3] = {0, 0, 0};
+    for (int i = blockIdx.x * PN_THREADS + threadIdx.x; i < sc.n; i += PN_BLOCKS * PN_THREADS) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) s[a] += (double)pts[3 * (size_t)i + a];
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) red[a][threadIdx.x] = s[a];
+    __syncthreads();
+    for (int w = PN_THREADS / 2; w >= 1; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) red[a][threadIdx.x] += red[a][threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) partial[((size_t)blockIdx.y * PN_BLOCKS + blockIdx.x) * 3 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// one workgroup per slot: centroid, scale := 0, and the slot's histogram and flag cleared (2 = unusable table entry)
+__global__ __launch_bounds__(64) void pnb_centroid_kernel(int num_classes, int n_scans, long long total,
+                                                          const long long *__restrict__ offsets,
+                                                          const long long *__restrict__ scan_ids,
+                                                          const double *__restrict__ partial, float *__restrict__ stats,
+                                                          int *__restrict__ hist, int *__restrict__ bad)
+{
+    const int slot = blockIdx.x, a = threadIdx.x;
+    const PnScan sc = pnb_scan(slot, n_scans, total, offsets, scan_ids);
+    if (a < 3) {
+        double s = 0;
+        for (int b = 0; b < PN_BLOCKS; ++b) s += partial[((size_t)slot * PN_BLOCKS + b) * 3 + a];
+        stats[slot * 4 + a] = sc.n ? (float)(s / (double)sc.n) : 0.f;
+    } else if (a == 3) {
+        stats[slot * 4 + 3] = 0.f;
+        bad[slot] = sc.n ? 0 : 2;
+    }
+    for (int c = a; c < num_classes; c += blockDim.x) hist[(size_t)slot * num_classes + c] = 0;
+}
+
+__global__ __launch_bounds__(256) void pnb_max_kernel(int n_scans, long long total, const float *__restrict__ points,
+                                                      const long long *__restrict__ offsets,
+                                                      const long long *__restrict__ scan_ids, float *__restrict__ stats)
+{
+    const PnScan sc = pnb_scan(blockIdx.y, n_scans, total, offsets, scan_ids);
+    const float *pts = points + 3 * (size_t)sc.base;
+    float *st = stats + blockIdx.y * 4;
+    const float cx = st[0], cy = st[1], cz = st[2];
+    float m = 0.f;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < sc.n; i += gridDim.x * blockDim.x) {
+        const float x = pts[3 * (size_t)i] - cx, y = pts[3 * (size_t)i + 1] - cy, z = pts[3 * (size_t)i + 2] - cz;
+        const float r = sqrtf((x * x + y * y) + z * z);
+        m = r > m ? r : m;
+    }
+    m = wave_max_f32(m);
+    if (lane_id() == 0 && sc.n) atomicMax((uint32_t *)&st[3], __float_as_uint(m));
+}
+
+__global__ __launch_bounds__(256) void pnb_sample_kernel(int m, int num_classes, int n_scans, long long total,
+                                                         const float *__restrict__ points, const int *__restrict__ labels,
+                                                         const long long *__restrict__ offsets,
+                                                         const long long *__restrict__ scan_ids,
+                                                         const long long *__restrict__ sel_all, const float *__restrict__ stats,
+                                                         float *__restrict__ raw, long long *__restrict__ y,
+                                                         int *__restrict__ hist, int *__restrict__ bad)
+{
+    extern __shared__ int lh[];
+    const int slot = blockIdx.y;
+    for (int c = threadIdx.x; c < num_classes; c += blockDim.x) lh[c] = 0;
+    __syncthreads();
+    const PnScan sc = pnb_scan(slot, n_scans, total, offsets, scan_ids);
+    const float *pts = points + 3 * (size_t)sc.base;
+    const int *lab = labels + sc.base;
+    const long long *sel = sel_all + (size_t)slot * m;
+    float *out_pts = raw + (size_t)slot * m * 3;
+    long long *out_labels = y + (size_t)slot * m;
+    const float cx = stats[slot * 4], cy = stats[slot * 4 + 1], cz = stats[slot * 4 + 2], scl = stats[slot * 4 + 3];
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) {
+        if (!sc.n) {                     // unusable slot (flag 2): nothing is read
+            out_pts[3 * (size_t)i] = out_pts[3 * (size_t)i + 1] = out_pts[3 * (size_t)i + 2] = 0.f;
+            out_labels[i] = 0;
+            continue;
+        }
+        long long s = sel[i];
+        if (s < 0 || s >= sc.n) {
+            atomicOr(&bad[slot], 1);
+            s = 0;
+        }
+        out_pts[3 * (size_t)i] = (pts[3 * (size_t)s] - cx) / scl;
+        out_pts[3 * (size_t)i + 1] = (pts[3 * (size_t)s + 1] - cy) / scl;
+        out_pts[3 * (size_t)i + 2] = (pts[3 * (size_t)s + 2] - cz) / scl;
+        const int l = lab[s];
+        out_labels[i] = (long long)l;
+        if (l >= 0 && l < num_classes) atomicAdd(&lh[l], 1);
+    }
+    __syncthreads();
+    for (int c = threadIdx.x; c < num_classes; c += blockDim.x)
+        if (lh[c]) atomicAdd(&hist[(size_t)slot * num_classes + c], lh[c]);
+}
+
+__global__ __launch_bounds__(64) void pnb_weights_kernel(int num_classes, const int *__restrict__ hist_all,
+                                                         const float *__restrict__ stats, float *__restrict__ w_all,
+                                                         float *__restrict__ center, float *__restrict__ scale)
+{
+    const int slot = blockIdx.x;
+    const int *hist = hist_all + (size_t)slot * num_classes;
+    float *w = w_all + (size_t)slot * num_classes;
+    float total = 0.f;
+    for (int c = 0; c < num_classes; ++c) total += (float)hist[c];
+    for (int c = threadIdx.x; c < num_classes; c += blockDim.x) {
+        const float v = (float)hist[c] / total;
+        w[c] = isinf(v) ? 0.f : v;
+    }
+    if (threadIdx.x < 3) center[slot * 3 + threadIdx.x] = stats[slot * 4 + threadIdx.x];
+    else if (threadIdx.x == 3) scale[slot] = stats[slot * 4 + 3];
+}
+
+struct PnbLayout {
+    size_t partial, stats, hist, total;
+};
+static PnbLayout pnb_layout(int s, int num_classes)
+{
+    PnbLayout L;
+    size_t o = 0;
+    auto take = [&](size_t bytes) { size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+    L.partial = take((size_t)s * PN_BLOCKS * 3 * sizeof(double));
+    L.stats = take((size_t)s * 4 * sizeof(float));
+    L.hist = take((size_t)s * num_classes * sizeof(int));
+    L.total = o;
+    return L;
+}
+
 } // namespace geot
 
 using namespace geot;
@@ -402,5 +561,39 @@ GEOT_EXPORT int geot_cloud_sample(int n, int m, int num_classes, const float *po
     hipLaunchKernelGGL(pn_sample_kernel, dim3(nb < 1024 ? nb : 1024), dim3(256), (size_t)(nc + 1) * sizeof(int), s, n, m, nc,
                        points, labels, selected, stats, out_points, out_labels, hist_ws, hist_ws + nc);
     if (labels) hipLaunchKernelGGL(pn_weights_kernel, dim3(1), dim3(64), 0, s, nc, hist_ws, class_weights);
+    return hipGetLastError();
+}
+
+GEOT_EXPORT long long geot_cloud_sample_batch_ws_bytes(int s, int num_classes)
+{
+    if (s < 1 || num_classes < 1 || num_classes > 4096) return 0;
+    return (long long)pnb_layout(s, num_classes).total;
+}
+
+GEOT_EXPORT int geot_cloud_sample_batch(int s, int m, int num_classes, int n_scans, long long total, const float *points,
+                                        const int *labels, const long long *offsets, const long long *scan_ids,
+                                        const long long *sel, float *raw, long long *y, float *class_weights, float *center,
+                                        float *scale, int *bad, void *ws, long long ws_bytes, void *stream)
+{
+    if (s < 1 || s > 65535 || m < 1 || num_classes < 1 || num_classes > 4096 || n_scans < 1 || total < 1) return hipErrorInvalidValue;
+    if (!scan_ids && n_scans < s) return hipErrorInvalidValue;
+    if (!points || !labels || !offsets || !sel || !raw || !y || !class_weights || !center || !scale || !bad || !ws)
+        return hipErrorInvalidValue;
+    const PnbLayout L = pnb_layout(s, num_classes);
+    if (ws_bytes < (long long)L.total) return hipErrorInvalidValue;
+    hipStream_t st = (hipStream_t)stream;
+    char *base = (char *)ws;
+    double *partial = (double *)(base + L.partial);
+    float *stats = (float *)(base + L.stats);
+    int *hist = (int *)(base + L.hist);
+    hipLaunchKernelGGL(pnb_sum_kernel, dim3(PN_BLOCKS, s), dim3(PN_THREADS), 0, st, n_scans, total, points, offsets, scan_ids,
+                       partial);
+    hipLaunchKernelGGL(pnb_centroid_kernel, dim3(s), dim3(64), 0, st, num_classes, n_scans, total, offsets, scan_ids, partial,
+                       stats, hist, bad);
+    hipLaunchKernelGGL(pnb_max_kernel, dim3(256, s), dim3(256), 0, st, n_scans, total, points, offsets, scan_ids, stats);
+    const int nb = (m + 255) / 256;
+    hipLaunchKernelGGL(pnb_sample_kernel, dim3(nb < 1024 ? nb : 1024, s), dim3(256), (size_t)num_classes * sizeof(int), st, m,
+                       num_classes, n_scans, total, points, labels, offsets, scan_ids, sel, stats, raw, y, hist, bad);
+    hipLaunchKernelGGL(pnb_weights_kernel, dim3(s), dim3(64), 0, st, num_classes, hist, stats, class_weights, center, scale);
     return hipGetLastError();
 }

@@ -1,0 +1,345 @@
+"""FixMatch training batches built on the GPU from scans that already live there -- what the reference's two training
+loaders do per item on CPU workers (openpoints/dataset/tooth_semi/tooth_dataset.py:116-206, 308-415, the transform lists of
+cfgs/tooth_semi/transformer_finetune_fixmatch_ntm.yaml in openpoints/transforms/point_transformer_gpu.py, default collation
+in openpoints/dataset/build.py:128-189) plus the `.cuda()` / `transpose` lines of train.py:442-445, 465-467, 482-486:
+
+    labelled   PointCloudScaling, PointCloudCenterAndNormalize                                            "train"
+    weak       PointCloudCenterAndNormalize                                                               "train_w"
+    strong     PointCloudScaling_s, PointCloudCenterAndNormalize, PointCloudRotation_s, PointCloudTranslation_s   "train_s"
+
+A batch costs a constant number of launches (geot_cloud_sample_batch: 5, geot_fixmatch_views: 1, one gather of the jaw flags,
+three small pinned host-to-device copies) and never synchronises with the host.  The random numbers stay on the host and are
+drawn with the reference's statements in the reference's order (draw_view_params), so a caller who seeds numpy and torch as
+the reference's worker did gets the reference's views.
+
+Three things of the reference a user may not expect, all kept:
+
+1. PointCloudRotation_s reads the keyword `angle_s`; the yaml only gives `angle`.  The configured rotation bound is therefore
+   [0, 0, 0] and the strong view's R is exactly the identity -- but the three np.random.uniform draws and the
+   np.random.shuffle still consume numpy's stream.  Pass kwargs with an `angle_s` entry for real rotations.
+2. The dataset sets data['x'] = data['pos'] (the same tensor), PointCloudScaling* scales it in place and
+   PointCloudCenterAndNormalize rebinds data['pos']: x / x_s are the SCALED, un-centred clouds, x_w is the sampled cloud.
+3. The unlabelled dataset deep-copies the sample before transforming: the un-suffixed pos / x / y / cls / class_weights of
+   the unlabelled batch are the untransformed sample; every key of the transformed copies reappears with _w / _s.
+"""
+import numpy as np
+import torch
+
+from ... import _lib
+from ...ext._common import call, f32, need, ptr
+
+# cfgs/tooth_semi/transformer_finetune_fixmatch_ntm.yaml datatransforms.kwargs, the entries the three lists read.
+# `angle` is what the file says (its second entry; a yaml loader keeps the last duplicate) and NOTHING reads it:
+# PointCloudRotation_s takes `angle_s`, which is absent -> its default [0, 0, 0] (quirk 1 above).
+TOOTH_VIEW_KWARGS = {
+    "scale": [0.9, 1.1],
+    "gravity_dim": 1,
+    "scale_s": [0.8, 1.2],
+    "shift_s": [0.2, 0.2, 0.2],
+    "angle": [1, 1, 1],
+}
+KINDS = ("train", "train_w", "train_s")
+_DEFAULTS = {"scale": [2. / 3, 3. / 2], "scale_s": [2. / 3, 3. / 2], "shift_s": [0.2, 0.2, 0.], "angle_s": [0, 0, 0],
+             "gravity_dim": 2}         # the transform classes' own defaults for absent keywords
+
+
+def _kw(kwargs, key):
+    return kwargs[key] if key in kwargs else _DEFAULTS[key]
+
+
+def _draw_scale(bounds):
+    lo, hi = np.array(bounds).astype(np.float32)
+    return (torch.rand(3, dtype=torch.float32) * (hi - lo) + lo).numpy()
+
+
+def _axis_rotation(axis, theta):
+    if theta == 0:
+        return np.eye(3)                 # expm(0) exactly; the configured case needs no scipy
+    from scipy.linalg import expm, norm  # the reference's own routine: its Pade approximant is part of R's bits
+    return expm(np.cross(np.eye(3), axis / norm(axis) * theta))
+
+
+def draw_view_params(kind, kwargs=TOOTH_VIEW_KWARGS):
+    """The random parameters of one view, drawn on the host from the GLOBAL torch-CPU and numpy generators with the
+    reference's statements in the reference's order -> dict(kind, s (3,), R (3,3), t (3,) float32, rotate, translate).
+
+      "train"    s = torch.rand(3) * (hi - lo) + lo over kwargs["scale"]
+      "train_w"  nothing is drawn
+      "train_s"  s over kwargs["scale_s"]; three np.random.uniform(-b, b) with b = kwargs["angle_s"] * pi (absent: 0, see the
+                 module text), one np.random.shuffle of the three axis rotations, R = float32 of their product;
+                 t = torch.rand(3) * kwargs["shift_s"]
+    """
+    need(kind in KINDS, "draw_view_params: kind must be one of %s, got %r" % (KINDS, kind))
+    out = {"kind": kind, "s": np.ones(3, np.float32), "R": np.eye(3, dtype=np.float32), "t": np.zeros(3, np.float32),
+           "rotate": False, "translate": False}
+    if kind == "train":
+        out["s"] = _draw_scale(_kw(kwargs, "scale"))
+    elif kind == "train_s":
+        out["s"] = _draw_scale(_kw(kwargs, "scale_s"))
+        mats = []
+        for ax, bound in enumerate(np.array(_kw(kwargs, "angle_s")) * np.pi):
+            axis = np.zeros(3)
+            axis[ax] = 1
+            mats.append(_axis_rotation(axis, np.random.uniform(-bound, bound)))
+        np.random.shuffle(mats)
+        out["R"] = torch.tensor(mats[0] @ mats[1] @ mats[2], dtype=torch.float32).numpy()
+        shift = torch.from_numpy(np.array(_kw(kwargs, "shift_s"))).to(torch.float32)
+        out["t"] = (torch.rand(3, dtype=torch.float32) * shift).numpy()
+        out["rotate"] = out["translate"] = True
+    return out
+
+
+def _check_params(p):
+    need(isinstance(p, dict) and all(k in p for k in ("s", "R", "t")), "view parameters: a dict with s, R, t "
+         "(draw_view_params)")
+    s, r, t = (np.asarray(p[k], dtype=np.float32) for k in ("s", "R", "t"))
+    need(s.shape == (3,) and r.shape == (3, 3) and t.shape == (3,), "view parameters: s (3,), R (3,3), t (3,)")
+    return s, r, t, bool(p.get("rotate", True)), bool(p.get("translate", True))
+
+
+def pack_view_jobs(jobs, n_rows, n_out):
+    """jobs: sequence of (source row of raw, output row, params) -> (J, VIEW_JOB_WORDS) int32 host array in the record
+    layout of include/geot_hip.h geot_fixmatch_views.  Everything is checked here, on the host."""
+    need(len(jobs) >= 1, "fixmatch_views: at least one job")
+    table = np.zeros((len(jobs), _lib.VIEW_JOB_WORDS), dtype=np.int32)
+    as_f = table.view(np.float32)
+    seen = set()
+    for j, job in enumerate(jobs):
+        need(len(job) == 3, "fixmatch_views: a job is (source row, output row, params)")
+        src, dst = int(job[0]), int(job[1])
+        need(0 <= src < n_rows, "fixmatch_views: job %d reads row %d of %d" % (j, src, n_rows))
+        need(0 <= dst < n_out and dst not in seen, "fixmatch_views: job %d writes row %d (of %d; each row once)" % (j, dst, n_out))
+        seen.add(dst)
+        s, r, t, rot, tr = _check_params(job[2])
+        table[j, 0], table[j, 1], table[j, 2] = src, dst, (1 if rot else 0) | (2 if tr else 0)
+        as_f[j, 4:7], as_f[j, 7:16], as_f[j, 16:19] = s, r.reshape(9), t
+    return table
+
+
+def _to_device(host, dev):
+    """Pinned staging + non-blocking copy on the current stream: no synchronisation (validation.SegMetrics._offsets)."""
+    return torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
+
+
+def fixmatch_views(raw, jobs, gravity_dim=1, n_out=None):
+    """raw (S, m, 3) CUDA float32; jobs: sequence of (source row, output row, params) with params from draw_view_params (or
+    any dict with s, R, t and optionally rotate / translate, default True) -> dict(pos (n_out, m, 3), x (n_out, 3, m),
+    heights (n_out, m, 1), view_center (J, 3), view_scale (J,)); n_out defaults to len(jobs).  One launch, no host
+    synchronisation; rows of the outputs no job names stay uninitialised."""
+    raw = f32(raw, "raw", 3)
+    need(raw.shape[2] == 3 and raw.shape[0] >= 1 and raw.shape[1] >= 1, "raw must be (S>=1, m>=1, 3)")
+    need(gravity_dim in (0, 1, 2), "gravity_dim must be 0, 1 or 2")
+    rows, m = raw.shape[0], raw.shape[1]
+    n_out = len(jobs) if n_out is None else int(n_out)
+    table = pack_view_jobs(jobs, rows, n_out)
+    dev = raw.device
+    out = {"pos": torch.empty((n_out, m, 3), dtype=torch.float32, device=dev),
+           "x": torch.empty((n_out, 3, m), dtype=torch.float32, device=dev),
+           "heights": torch.empty((n_out, m, 1), dtype=torch.float32, device=dev),
+           "view_center": torch.empty((len(jobs), 3), dtype=torch.float32, device=dev),
+           "view_scale": torch.empty(len(jobs), dtype=torch.float32, device=dev)}
+    jobs_dev = _to_device(table, dev)
+    call("geot_fixmatch_views", dev, len(jobs), m, rows, n_out, int(gravity_dim), ptr(raw), ptr(jobs_dev), ptr(out["pos"]),
+         ptr(out["x"]), ptr(out["heights"]), ptr(out["view_center"]), ptr(out["view_scale"]))
+    return out
+
+
+class DeviceScanSet:
+    """The scans of one split on one device, built once: vertices concatenated (sum N, 3) float32, labels (sum N,) int32,
+    offsets (n + 1,) int64, the jaw flag of every scan `cls` (n,) int64 (tooth_dataset.py:97, 0 = lower; default 0).
+    scans / labels: sequences of (N_i, 3) / (N_i,) arrays or tensors."""
+
+    def __init__(self, scans, labels, cls=None, device=None):
+        need(len(scans) >= 1 and len(scans) == len(labels), "DeviceScanSet: one label array per scan, at least one scan")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        need(dev.type == "cuda", "DeviceScanSet: CPU not supported (the scans must live on the GPU)")
+        pts = [torch.as_tensor(p) for p in scans]
+        labs = [torch.as_tensor(l) for l in labels]
+        for p, l in zip(pts, labs):
+            need(p.dim() == 2 and p.shape[1] == 3 and p.shape[0] >= 1, "DeviceScanSet: a scan is (N>=1, 3)")
+            need(l.dim() == 1 and l.shape[0] == p.shape[0] and not l.is_floating_point(),
+                 "DeviceScanSet: one integer label per vertex")
+        self.sizes = [int(p.shape[0]) for p in pts]
+        cls = [0] * len(pts) if cls is None else [int(c) for c in cls]
+        need(len(cls) == len(pts), "DeviceScanSet: one cls entry per scan")
+        self.device = dev
+        self.points = torch.cat([p.to(dev, torch.float32) for p in pts]).contiguous()
+        self.labels = torch.cat([l.to(dev, torch.int32) for l in labs]).contiguous()
+        self.offsets = torch.tensor(np.concatenate([[0], np.cumsum(self.sizes, dtype=np.int64)]), dtype=torch.int64).to(dev)
+        self.cls = torch.tensor(cls, dtype=torch.int64).to(dev)
+
+    def __len__(self):
+        return len(self.sizes)
+
+    @classmethod
+    def _merged(cls, a, b):
+        """a's scans followed by b's, as one set (the batcher samples both splits in one sequence of launches)."""
+        need(a.device == b.device, "DeviceScanSet: both sets must be on one device (%s vs %s)" % (a.device, b.device))
+        out = cls.__new__(cls)
+        out.device, out.sizes = a.device, a.sizes + b.sizes
+        out.points, out.labels = torch.cat([a.points, b.points]), torch.cat([a.labels, b.labels])
+        out.offsets = torch.cat([a.offsets, b.offsets[1:] + a.offsets[-1:]])
+        out.cls = torch.cat([a.cls, b.cls])
+        return out
+
+
+def cloud_sample_batch(scans, scan_ids, sel, num_classes=17, check=True):
+    """geot_cloud_sample_batch: scans a DeviceScanSet; scan_ids: the set scan of every batch slot (S ints, host); sel (S, m)
+    int64 vertex indices local to each slot's scan (numpy or tensor) -> dict(raw (S, m, 3), y (S, m) int64, class_weights
+    (S, num_classes), center (S, 3), scale (S,), bad (S,) int32).  Slot by slot bit-identical to prepare_sample on that scan
+    alone.  check=True reads `bad` back (one host sync) and raises IndexError for an index outside its scan."""
+    need(isinstance(scans, DeviceScanSet), "cloud_sample_batch: scans must be a DeviceScanSet")
+    ids = np.asarray(scan_ids, dtype=np.int64).reshape(-1)
+    need(ids.size >= 1 and ids.min() >= 0 and ids.max() < len(scans), "cloud_sample_batch: scan ids must lie in [0, %d)" % len(scans))
+    dev = scans.device
+    if isinstance(sel, torch.Tensor):
+        need(sel.dtype == torch.int64 and sel.dim() == 2, "sel must be (S, m) int64")
+        sel_dev = sel.to(dev).contiguous()
+    else:
+        sel = np.ascontiguousarray(sel)
+        need(sel.dtype == np.int64 and sel.ndim == 2, "sel must be (S, m) int64")
+        sel_dev = _to_device(sel, dev)
+    s, m = sel_dev.shape
+    need(s == ids.size and m >= 1, "sel must have one row of m >= 1 indices per scan id")
+    need(1 <= num_classes <= 4096, "num_classes must be in [1, 4096]")
+    ids_dev = _to_device(ids, dev)
+    out = {"raw": torch.empty((s, m, 3), dtype=torch.float32, device=dev),
+           "y": torch.empty((s, m), dtype=torch.int64, device=dev),
+           "class_weights": torch.empty((s, num_classes), dtype=torch.float32, device=dev),
+           "center": torch.empty((s, 3), dtype=torch.float32, device=dev),
+           "scale": torch.empty(s, dtype=torch.float32, device=dev),
+           "bad": torch.empty(s, dtype=torch.int32, device=dev)}
+    nbytes = int(_lib.load().geot_cloud_sample_batch_ws_bytes(s, int(num_classes)))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    call("geot_cloud_sample_batch", dev, s, m, int(num_classes), len(scans), int(scans.points.shape[0]), ptr(scans.points),
+         ptr(scans.labels), ptr(scans.offsets), ptr(ids_dev), ptr(sel_dev), ptr(out["raw"]), ptr(out["y"]),
+         ptr(out["class_weights"]), ptr(out["center"]), ptr(out["scale"]), ptr(out["bad"]), ptr(ws), nbytes)
+    out["scan_ids"] = ids_dev
+    if check:
+        raise_bad_index(out["bad"], ids)
+    return out
+
+
+def raise_bad_index(bad, ids):
+    flags = bad.cpu().numpy()            # the one host synchronisation of check=True
+    if flags.any():
+        slot = int(np.flatnonzero(flags)[0])
+        raise IndexError("batch slot %d (scan %d): selected_idxs holds an index outside the scan" % (slot, int(ids[slot])))
+
+
+class FixMatchBatcher:
+    """Replaces the reference's two training DataLoaders: `batch(idx_l, idx_u)` returns (data, data_u) with the keys,
+    shapes and dtypes train_one_epoch works on after its `.cuda()` and `transpose` lines,
+
+        data    pos (B_l, m, 3)  x (B_l, 3, m)  heights (B_l, m, 1)  y (B_l, m) int64  cls (B_l, 1) int64  class_weights (B_l, C)
+        data_u  pos / x / raw_pos (B_u, m, 3)  y (B_u, m)  cls (B_u, 1)  class_weights (B_u, C)     (the untransformed sample)
+                pos_w, pos_s (B_u, m, 3)  x_w, x_s (B_u, 3, m)  heights_w, heights_s (B_u, m, 1)  and y / cls / class_weights
+                with _w and _s
+
+    in freshly allocated tensors (FixMatchNTMStep's look-ahead matches batches by identity and version).  Keys the reference
+    fills with equal values share one tensor here (data_u pos / x / raw_pos; y, cls, class_weights and their _w / _s forms):
+    clone before writing into one of them.  The two sets are copied into one concatenated set at construction.
+
+    stream: queue every batch on that side stream.  A batch depends on the scans alone, so it does NOT wait for what the
+    current stream has queued: it runs beside the iteration in flight.  Call `batcher.join(data, data_u)` before the
+    current stream (or a step: `next_batches=`) reads the tensors; the wait it queues sits behind the running iteration
+    and costs that iteration nothing.
+    """
+
+    def __init__(self, labelled, unlabelled, num_points, num_classes=17, kwargs=TOOTH_VIEW_KWARGS, stream=None):
+        need(isinstance(labelled, DeviceScanSet) and isinstance(unlabelled, DeviceScanSet),
+             "FixMatchBatcher: labelled and unlabelled must be DeviceScanSets")
+        need(int(num_points) >= 1, "FixMatchBatcher: num_points >= 1")
+        need(1 <= int(num_classes) <= 4096, "FixMatchBatcher: num_classes must be in [1, 4096]")
+        need(int(_kw(kwargs, "gravity_dim")) in (0, 1, 2), "FixMatchBatcher: gravity_dim must be 0, 1 or 2")
+        self.n_l, self.n_u = len(labelled), len(unlabelled)
+        self.scans = DeviceScanSet._merged(labelled, unlabelled)
+        self.device = self.scans.device
+        self.m, self.c, self.kwargs, self.stream = int(num_points), int(num_classes), kwargs, stream
+        if stream is not None:      # once: the scans are ready; a batch itself depends on nothing the current stream does
+            stream.wait_stream(torch.cuda.current_stream(self.device))
+
+    def draw(self, idx_l, idx_u, sel_l=None, sel_u=None, params=None):
+        """The host half of batch(): (sel (B_l + B_u, m) int64, params) with everything not given drawn in the reference's
+        per-item order -- per labelled item np.random.choice then the "train" draw, per unlabelled item np.random.choice then
+        "train_w" (draws nothing) and "train_s".  params: list of B_l dicts followed by B_u (weak, strong) pairs."""
+        bl, bu = len(idx_l), len(idx_u)
+
+        def given(sel, count, what):
+            if sel is None:
+                return None
+            sel = np.asarray(sel.cpu() if isinstance(sel, torch.Tensor) else sel)
+            need(sel.shape == (count, self.m) and sel.dtype.kind in "iu", "%s must be (%d, %d) integers" % (what, count, self.m))
+            return sel.astype(np.int64)
+        sel_l, sel_u = given(sel_l, bl, "sel_l"), given(sel_u, bu, "sel_u")
+        if params is not None:
+            need(len(params) == bl + bu and all(len(p) == 2 for p in params[bl:]),
+                 "params: %d labelled dicts followed by %d (weak, strong) pairs" % (bl, bu))
+        sel = np.empty((bl + bu, self.m), dtype=np.int64)
+        drawn = []
+        for slot, scan in enumerate(list(idx_l) + list(idx_u)):
+            lab = slot < bl
+            n = (self.scans.sizes[scan] if lab else self.scans.sizes[self.n_l + scan])
+            have = sel_l if lab else sel_u
+            if have is not None:
+                sel[slot] = have[slot if lab else slot - bl]
+            else:
+                sel[slot] = np.random.choice(n, self.m, replace=n < self.m)            # tooth_dataset.py:134-135, 340-341
+            if params is None:
+                drawn.append(draw_view_params("train", self.kwargs) if lab else
+                             (draw_view_params("train_w", self.kwargs), draw_view_params("train_s", self.kwargs)))
+        return sel, (drawn if params is None else list(params))
+
+    def batch(self, idx_l, idx_u, sel_l=None, sel_u=None, params=None, check=False):
+        """idx_l / idx_u: scan numbers within the labelled / unlabelled set (what the samplers would yield); sel_* (B, m)
+        vertex indices per scan and params (see draw()) default to the reference's draws.  check=True reads the bad-index
+        flags back (one host sync) and raises IndexError."""
+        idx_l, idx_u = [int(i) for i in idx_l], [int(i) for i in idx_u]
+        bl, bu = len(idx_l), len(idx_u)
+        need(bl >= 1 and bu >= 1, "FixMatchBatcher.batch: at least one labelled and one unlabelled scan")
+        need(all(0 <= i < self.n_l for i in idx_l), "idx_l must lie in [0, %d)" % self.n_l)
+        need(all(0 <= i < self.n_u for i in idx_u), "idx_u must lie in [0, %d)" % self.n_u)
+        sel, params = self.draw(idx_l, idx_u, sel_l, sel_u, params)
+        ids = idx_l + [self.n_l + i for i in idx_u]
+        # view jobs: output rows [0, B_l) labelled, [B_l, B_l + B_u) weak, then strong
+        jobs = [(i, i, params[i]) for i in range(bl)]
+        jobs += [(bl + i, bl + i, params[bl + i][0]) for i in range(bu)]
+        jobs += [(bl + i, bl + bu + i, params[bl + i][1]) for i in range(bu)]
+        pack_view_jobs(jobs, bl + bu, bl + 2 * bu)        # checks the parameters before anything is queued
+        if self.stream is None:
+            out = self._queue(ids, sel, jobs, bl, bu)
+        else:
+            with torch.cuda.stream(self.stream):
+                out = self._queue(ids, sel, jobs, bl, bu)
+        if check:
+            if self.stream is not None:
+                self.stream.synchronize()
+            raise_bad_index(out[2], ids)
+        return out[0], out[1]
+
+    def _queue(self, ids, sel, jobs, bl, bu):
+        s = cloud_sample_batch(self.scans, ids, sel, self.c, check=False)
+        v = fixmatch_views(s["raw"], jobs, int(_kw(self.kwargs, "gravity_dim")), bl + 2 * bu)
+        cls = self.scans.cls.index_select(0, s["scan_ids"]).view(-1, 1)
+        lab, unl = slice(0, bl), slice(bl, bl + bu)
+        data = {"pos": v["pos"][:bl], "x": v["x"][:bl], "heights": v["heights"][:bl], "y": s["y"][lab], "cls": cls[lab],
+                "class_weights": s["class_weights"][lab]}
+        raw_u = s["raw"][unl]
+        data_u = {"pos": raw_u, "x": raw_u, "raw_pos": raw_u}
+        for suffix in ("", "_w", "_s"):
+            data_u["y" + suffix], data_u["cls" + suffix] = s["y"][unl], cls[unl]
+            data_u["class_weights" + suffix] = s["class_weights"][unl]
+        for suffix, rows in (("_w", slice(bl, bl + bu)), ("_s", slice(bl + bu, bl + 2 * bu))):
+            for key in ("pos", "x", "heights"):
+                data_u[key + suffix] = v[key][rows]
+        return data, data_u, s["bad"]
+
+    def join(self, data, data_u):
+        """Hand a batch built on the side stream to the CURRENT stream: it waits for the side stream, and the caching
+        allocator is told that the batch's memory is in use here (train_step._join does the same for the steps' side streams)."""
+        if self.stream is None:
+            return
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_stream(self.stream)
+        for t in list(data.values()) + list(data_u.values()):
+            t.record_stream(cur)

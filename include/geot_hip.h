@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 13
+#define GEOT_ABI_VERSION 14
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -671,6 +671,53 @@ int geot_seg_confusion(int b, int c, const long long *offsets, const long long *
                        long long *counts, void *stream);
 int geot_seg_confusion_interp(int b, int c, int n, const long long *offsets, const float *prob, const int *idx,
                               const float *dist2, const long long *label, long long *counts, void *stream);
+
+/* ---- FixMatch training batches from device-resident scans (ABI 14) -------------------------------------------------------
+ * What the reference's two training loaders do per item on CPU workers (openpoints/dataset/tooth_semi/tooth_dataset.py:
+ * 116-206, 308-415, openpoints/transforms/point_transformer_gpu.py, default collation), for a whole batch, in a number of
+ * launches that does not depend on the batch; no host synchronisation.
+ *
+ * geot_cloud_sample_batch = geot_pc_norm_stats + geot_cloud_sample for s scans at once (5 launches).  The scans of a set lie
+ * concatenated: points (total, 3), labels (total); offsets (n_scans + 1) int64 ON THE DEVICE, set scan i owns vertices
+ * [offsets[i], offsets[i + 1]), 1 .. 2^31 - 1 of them.  scan_ids (s) int64 on the device names the set scan of every batch
+ * slot (NULL: slot i is set scan i; then n_scans must be >= s).  sel (s, m) int64: vertex indices LOCAL to the slot's scan.
+ * Per slot: raw (m, 3) = (points[sel] - centroid) / scale, y (m) int64, class_weights (num_classes), center (3), scale (1)
+ * -- each bit-identical to the single-scan calls on that scan alone (the same fp64 partial-sum tree per scan, the same
+ * (x^2 + y^2) + z^2 norm, IEEE divide; the maximum and the histogram do not depend on arrival order; no float atomics).
+ * bad (s) int32: set to 1 for a slot with an entry of sel outside its scan (the row is then read from vertex 0, as
+ * geot_cloud_sample does) and to 2 for a slot whose scan_ids / offsets entry is unusable (nothing of that slot is read;
+ * its outputs are zero-filled), 0 otherwise.  ws: geot_cloud_sample_batch_ws_bytes(s, num_classes) bytes.
+ * 1 <= s <= 65535, m >= 1, 1 <= num_classes <= 4096, n_scans >= 1, total >= 1, no NULL pointer but scan_ids; anything else
+ * is hipErrorInvalidValue. */
+long long geot_cloud_sample_batch_ws_bytes(int s, int num_classes);
+int geot_cloud_sample_batch(int s, int m, int num_classes, int n_scans, long long total, const float *points,
+                            const int *labels, const long long *offsets, const long long *scan_ids, const long long *sel,
+                            float *raw, long long *y, float *class_weights, float *center, float *scale, int *bad, void *ws,
+                            long long ws_bytes, void *stream);
+
+/* geot_fixmatch_views: j view jobs in ONE launch (one workgroup per job).  jobs: j records of GEOT_VIEW_JOB_WORDS 32-bit
+ * words on the device:
+ *   [0] int  row of raw (n_rows, m, 3) the view is made of      [1] int  output row in pos / x / heights (n_out rows each)
+ *   [2] int  flags: bit 0 rotate, bit 1 translate               [3] reserved (0)
+ *   [4..6] float s    [7..15] float R, row-major    [16..18] float t    [19] reserved
+ * With q = r * s (one rounding per element):
+ *   x       (n_out, 3, m) channel-first = q                (PointCloudScaling* scales data['pos'] in place and data['x'] IS
+ *                                                           that tensor: x is the scaled, un-centred cloud)
+ *   heights (n_out, m, 1) = q[:, g] - min(q[:, g]),  g = gravity_dim in 0..2
+ *   pos     (n_out, m, 3) = (q - mean(q)) / mx,  mx = max_i sqrtf((cx^2 + cy^2) + cz^2); with bit 0:
+ *           pos_k = ((p0 R[k][0] + p1 R[k][1]) + p2 R[k][2]), with bit 1: + t[k]  (un-contracted, left to right)
+ *   view_center (j, 3) = mean(q), view_scale (j) = mx         (per JOB, not per output row)
+ * Every statement is a single fp32 operation except the mean: fp64 sums in a fixed tree, rounded once.  min / max
+ * propagate NaN as torch does; m = 1 gives mx = 0 and pos = 0 / 0 = NaN, as the reference.  Results are bit-reproducible.
+ * Up to GEOT_VIEW_REG_POINTS points a job's cloud is read once and held in registers; beyond, the same workgroup streams it
+ * from memory three times (same tree, same results).  Two jobs must not name the same output row.  A job whose rows are
+ * out of range writes nothing but NaN to its view_center / view_scale.
+ * j >= 1, 1 <= m <= 357 913 941 (a row stays below 4 GB), n_rows >= 1, n_out >= 1, gravity_dim in 0..2, no NULL pointer;
+ * anything else is hipErrorInvalidValue. */
+#define GEOT_VIEW_JOB_WORDS 20
+#define GEOT_VIEW_REG_POINTS 24576
+int geot_fixmatch_views(int j, int m, int n_rows, int n_out, int gravity_dim, const float *raw, const void *jobs, float *pos,
+                        float *x, float *heights, float *view_center, float *view_scale, void *stream);
 
 #ifdef __cplusplus
 }
