@@ -137,6 +137,8 @@ PROTOTYPES["geot_seg_confusion"] = [_c_int, _c_int] + [_P] * 4 + [_c_void_p]
 PROTOTYPES["geot_seg_confusion_interp"] = [_c_int] * 3 + [_P] * 6 + [_c_void_p]
 PROTOTYPES["geot_cloud_sample_batch"] = [_c_int] * 4 + [ctypes.c_longlong] + [_P] * 12 + [ctypes.c_longlong, _c_void_p]
 PROTOTYPES["geot_fixmatch_views"] = [_c_int] * 5 + [_P] * 7 + [_c_void_p]
+PROTOTYPES["geot_scan_predict"] = ([_c_int] * 4 + [ctypes.c_longlong] + [_P] * 6 + [_c_int] + [_P] * 5 +
+                                   [ctypes.c_longlong, _c_void_p])
 VIEW_JOB_WORDS = 20       # GEOT_VIEW_JOB_WORDS: 32-bit words of one geot_fixmatch_views job record
 VIEW_REG_POINTS = 24576   # GEOT_VIEW_REG_POINTS: largest cloud geot_fixmatch_views holds in registers
 # entry points that do not follow the "(..., stream) -> hipError_t" shape
@@ -155,6 +157,7 @@ PLAIN = {
     "geot_grid_subsampling_ws_bytes": ([_c_int], ctypes.c_longlong),
     "geot_pc_norm_ws_bytes": ([], ctypes.c_longlong),
     "geot_cloud_sample_batch_ws_bytes": ([_c_int, _c_int], ctypes.c_longlong),
+    "geot_scan_predict_ws_bytes": ([_c_int, _c_int], ctypes.c_longlong),
     "geot_knn_grid_eligible": ([_c_int, _c_int, _c_int, _c_int], _c_int),
     "geot_ball_grid_eligible": ([_c_int, _c_int, _c_int, _c_float, _c_int], _c_int),
     "geot_edgeconv_eligible": ([_c_int] * 6, _c_int),
@@ -175,7 +178,7 @@ PLAIN = {
     "geot_rowdot_small_slices": ([_c_int] * 2, _c_int),
     "geot_colsum_ws_floats": ([_c_int] * 2, ctypes.c_longlong),
 }
-ABI_VERSION = 14    # include/geot_hip.h GEOT_ABI_VERSION this binding was written against
+ABI_VERSION = 15    # include/geot_hip.h GEOT_ABI_VERSION this binding was written against
 KNN_KMAX_HEAP = 1024      # GEOT_KNN_KMAX_HEAP: largest nsample of the heap-ordered kNN (knnquery_cuda, pointops.knn)
 KNN_KMAX_SORTED = 4096    # GEOT_KNN_KMAX_SORTED: largest k of the sorted kNN (knn_cuda.KNN, knn_point in 3-D)
 

@@ -1,0 +1,112 @@
+"""Validation batches built on the GPU from scans that already live there -- what the reference's validation loader does
+per item on CPU workers and in its collation (openpoints/dataset/tooth_semi/tooth_dataset.py:116-188 for split in ['val',
+'test'], the `val` list [PointsToTensor, PointCloudCenterAndNormalize] of cfgs/tooth_semi/transformer_finetune_fixmatch_ntm.yaml,
+openpoints/dataset/build.py:30-50 collate_fn_val) plus validate's `.cuda()` and `transpose` lines (train.py:731-739):
+
+    pos (B, m, 3)   x (B, 3, m)   y (B, m) int64   cls (B, 1) int64   center (B, 3)   scale (B,)
+    points / labels   lists of B views into the set's vertices (N_i, 3) fp32 and labels (N_i,) int32: nothing is copied
+    scan_ids (B,) int64 on the device, scans (the set), sizes (the B vertex counts) and mandible (validate's `cls[ii] == 0`)
+    as host values
+
+The `val` list is the weak view's list: geot_cloud_sample_batch (5 launches) and geot_fixmatch_views with the "train_w"
+parameters (1), one gather of the jaw classes, two small pinned host-to-device copies -- the same number for every batch,
+and no host synchronisation.  validation.SegMetrics.update_from_scans / predict_scans / validate_scans take such a batch; it
+also carries every key the existing validate() and get_pred_whole() read.
+
+One thing of the reference a user may not expect, kept: the dataset's pc_norm centres and scales the scan (`center`,
+`scale`), the sampled points then go through PointCloudCenterAndNormalize, which centres and scales the SAMPLE once more
+(x stays the sampled cloud: data['x'] is data['pos'] until the transform rebinds pos) -- and get_pred_whole de-normalises
+`pos` with pc_norm's center and scale alone (`point * s + c`).  The sampled points it searches are therefore not exactly
+on the scan.  validation.py reproduces that statement for statement.
+"""
+import numpy as np
+import torch
+
+from ...ext._common import need
+from .fixmatch_batch import (TOOTH_VIEW_KWARGS, DeviceScanSet, _kw, cloud_sample_batch, draw_view_params, fixmatch_views,
+                             raise_bad_index)
+
+
+def draw_val_sel(sizes, num_points):
+    """The host half of a batch: per item exactly one np.random.choice(N_i, m, replace=N_i < m) from numpy's GLOBAL
+    generator (tooth_dataset.py:134-135), in item order; the `val` transform list draws nothing -> (B, m) int64."""
+    m = int(num_points)
+    need(m >= 1, "draw_val_sel: num_points >= 1")
+    sel = np.empty((len(sizes), m), dtype=np.int64)
+    for slot, n in enumerate(sizes):
+        n = int(n)
+        need(n >= 1, "draw_val_sel: a scan has at least one vertex")
+        replace = False if n >= m else True
+        sel[slot] = np.random.choice(n, m, replace=replace)
+    return sel
+
+
+class ValBatcher:
+    """Replaces the reference's validation DataLoader: `batch(idx)` returns the dict described in the module text for the
+    scans `idx` of the set (what the sequential sampler would yield), in freshly allocated tensors.
+
+    The jaw classes are read from the device once, here.  stream: queue every batch on that side stream; it depends on
+    the scans alone, so it runs beside whatever the current stream has in flight.  Call `join(batch)` before the current
+    stream reads the tensors."""
+
+    def __init__(self, scans, num_points, num_classes=17, kwargs=TOOTH_VIEW_KWARGS, stream=None):
+        need(isinstance(scans, DeviceScanSet), "ValBatcher: scans must be a DeviceScanSet")
+        need(scans.device.type == "cuda", "ValBatcher: CPU not supported (the scans must live on the GPU)")
+        need(int(num_points) >= 1, "ValBatcher: num_points >= 1")
+        need(1 <= int(num_classes) <= 4096, "ValBatcher: num_classes must be in [1, 4096]")
+        need(int(_kw(kwargs, "gravity_dim")) in (0, 1, 2), "ValBatcher: gravity_dim must be 0, 1 or 2")
+        self.scans, self.device = scans, scans.device
+        self.m, self.c, self.kwargs, self.stream = int(num_points), int(num_classes), kwargs, stream
+        self.cls_host = [int(v) for v in scans.cls.cpu().tolist()]       # the one copy: validate's `cls[ii] == 0` per scan
+        self._points = list(torch.split(scans.points, scans.sizes))      # views
+        self._labels = list(torch.split(scans.labels, scans.sizes))
+        if stream is not None:
+            stream.wait_stream(torch.cuda.current_stream(self.device))
+
+    def __len__(self):
+        return len(self.scans)
+
+    def batch(self, idx, sel=None, check=False):
+        """idx: scan numbers within the set; sel (B, m) vertex indices per scan, default the reference's draws
+        (draw_val_sel).  check=True reads the bad-index flags back (one host sync) and raises IndexError."""
+        ids = [int(i) for i in idx]
+        need(len(ids) >= 1, "ValBatcher.batch: at least one scan")
+        need(all(0 <= i < len(self.scans) for i in ids), "ValBatcher.batch: idx must lie in [0, %d)" % len(self.scans))
+        sizes = [self.scans.sizes[i] for i in ids]
+        if sel is None:
+            sel = draw_val_sel(sizes, self.m)
+        else:
+            sel = np.asarray(sel.cpu() if isinstance(sel, torch.Tensor) else sel)
+            need(sel.shape == (len(ids), self.m) and sel.dtype.kind in "iu", "sel must be (%d, %d) integers" % (len(ids), self.m))
+            sel = sel.astype(np.int64)
+        weak = draw_view_params("train_w", self.kwargs)                   # the `val` list: nothing is drawn
+        jobs = [(i, i, weak) for i in range(len(ids))]
+        if self.stream is None:
+            out, bad = self._queue(ids, sizes, sel, jobs)
+        else:
+            with torch.cuda.stream(self.stream):
+                out, bad = self._queue(ids, sizes, sel, jobs)
+        if check:
+            if self.stream is not None:
+                self.stream.synchronize()
+            raise_bad_index(bad, ids)
+        return out
+
+    def _queue(self, ids, sizes, sel, jobs):
+        s = cloud_sample_batch(self.scans, ids, sel, self.c, check=False)
+        v = fixmatch_views(s["raw"], jobs, int(_kw(self.kwargs, "gravity_dim")), len(ids))
+        cls = self.scans.cls.index_select(0, s["scan_ids"]).view(-1, 1)
+        out = {"pos": v["pos"], "x": v["x"], "y": s["y"], "cls": cls, "center": s["center"], "scale": s["scale"],
+               "points": [self._points[i] for i in ids], "labels": [self._labels[i] for i in ids],
+               "scan_ids": s["scan_ids"], "scans": self.scans, "sizes": sizes,
+               "mandible": [self.cls_host[i] == 0 for i in ids]}
+        return out, s["bad"]
+
+    def join(self, batch):
+        """Hand a batch built on the side stream to the CURRENT stream (FixMatchBatcher.join)."""
+        if self.stream is None:
+            return
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_stream(self.stream)
+        for key in ("pos", "x", "y", "cls", "center", "scale", "scan_ids"):
+            batch[key].record_stream(cur)

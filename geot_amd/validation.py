@@ -18,6 +18,15 @@ DSC and their jaw and whole means, from integer counts made on the device (csrc/
 update_from_logits runs get_pred_whole's soft-max and three_nn, then interpolates, arg-maxes and counts in one launch per
 batch: no (C, M) probabilities, no per-vertex prediction, no host synchronisation.  read() executes the reference's torch /
 numpy statements on CPU int64 tensors built from the counts, so every value, NaN and dtype is the reference's.
+
+With the test split resident on the device (openpoints.dataset.DeviceScanSet) no loader is needed either:
+
+    out = validate_scans(model, scans, cfg)                  # validate()'s values from ValBatcher batches
+    metrics.update_from_scans(logits, batch)                 # one geot_scan_predict call per batch, whatever its size
+    preds = predict_scans(logits, batch)                     # get_pred_whole: the per-vertex labels of whole scans
+
+geot_scan_predict (csrc/scan_predict.hip) reads the vertices and labels in place from the set, finds the three nearest
+sampled points, interpolates, arg-maxes and counts / writes in one pass: no per-scan loop, no idx / dist2 in memory.
 """
 import logging
 
@@ -25,10 +34,24 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import _lib
 from .ext._common import call, knn_workspace, need, ptr
+from .openpoints.dataset.fixmatch_batch import _to_device
 from .pointnet2 import pointnet2_utils as pt_utils
 
 MAX_VERTICES = (1 << 31) - 1        # per scan (include/geot_hip.h geot_seg_confusion)
+# geot_scan_predict's work table.  A wave is serial over its vertices, so the table decides how many waves a launch has: an
+# MI355X holds 256 CUs x 4 SIMDs x 8 waves = 8192 waves of this kernel (occupancy 8), and knn_grid_kernel, which the search
+# comes from, gives every query a wave of its own.  4096 workgroups of 4 waves are two rounds of the full device; below
+# ~2.6e5 vertices the floor of 64 vertices per workgroup (16 per wave) applies instead, which at B = 2, M ~1e5 gives ~3100
+# workgroups = ~12 400 waves.  Against that stands the per-workgroup cost (clearing and flushing 4 x (C (C + 1) + 1) LDS
+# counters, one grid header).  Measured at B = 2, M ~1e5, N = 16 000 (profiles/validation_resident.txt, device time of one
+# update): 64 vertices per workgroup 0.355 ms, 32: 0.338, 16: 0.358, 128: 0.383, 256: 0.474; 2048 / 1024 / 512 groups with the
+# floor of 64: 0.364 / 0.389 / 0.531.  One run at one size: the constants stay at the values the tests and the recorded
+# verdict were run with; 32 per workgroup is the candidate.
+SCAN_GROUPS = 4096
+SCAN_CHUNK_MIN = 64
+SCAN_MAX_SLOTS = 65535              # batch slots per call (include/geot_hip.h geot_scan_predict)
 
 
 @torch.no_grad()
@@ -93,6 +116,78 @@ def seg_metrics_from_counts(counts, num_classes, mandible):
     for key, name in (("acc", "whole_macc"), ("miou", "whole_miou"), ("dsc", "whole_mdsc")):
         out[name] = (np.array(lo[key]).sum() + np.array(up[key]).sum()) / (len(lo[key]) + len(up[key]))
     return out
+
+
+def scan_work_table(sizes, groups=SCAN_GROUPS, min_chunk=SCAN_CHUNK_MIN):
+    """geot_scan_predict's work table for batch slots of `sizes` vertices -> (G, 4) int32 host array of (slot, first vertex,
+    vertex count, 0): every scan cut into chunks of one common length -- a multiple of 4 (one quarter per wave), at least
+    min_chunk, about sum(sizes) / groups -- so that ragged scans share the device evenly; the last chunk of a scan is the
+    remainder.  Every vertex of every slot lies in exactly one entry.  G <= groups + len(sizes)."""
+    sizes = [int(m) for m in sizes]
+    need(all(1 <= m <= MAX_VERTICES for m in sizes), "scan_work_table: 1 .. %d vertices per scan" % MAX_VERTICES)
+    need(int(groups) >= 1 and int(min_chunk) >= 1, "scan_work_table: groups >= 1 and min_chunk >= 1")
+    total = sum(sizes)
+    chunk = max(int(min_chunk), -(-total // int(groups)))
+    chunk = min(-(-chunk // 4) * 4, MAX_VERTICES)
+    rows = []
+    for slot, m in enumerate(sizes):
+        first = np.arange(0, m, chunk, dtype=np.int64)
+        part = np.zeros((first.size, 4), dtype=np.int64)
+        part[:, 0], part[:, 1], part[:, 2] = slot, first, np.minimum(chunk, m - first)
+        rows.append(part)
+    table = np.concatenate(rows) if rows else np.zeros((0, 4), dtype=np.int64)
+    return np.ascontiguousarray(table.astype(np.int32))
+
+
+def _scan_predict(logits, batch, num_classes, counts=None, want_pred=False, what="predict_scans"):
+    """One geot_scan_predict call for a ValBatcher batch: get_pred_whole's soft-max and de-normalisation as batched torch
+    statements (the same fp32 multiply and add per element as its per-scan `point * s + c`), then the kernel."""
+    need(isinstance(batch, dict) and all(k in batch for k in ("pos", "center", "scale", "scan_ids", "scans", "sizes")),
+         "%s: batch must come from ValBatcher.batch (pos, center, scale, scan_ids, scans, sizes)" % what)
+    scans, sizes = batch["scans"], [int(m) for m in batch["sizes"]]
+    dev = scans.device
+    c = int(num_classes)
+    need(torch.is_tensor(logits), "%s: logits must be a torch.Tensor" % what)
+    need(logits.is_cuda, "%s: CPU not supported (logits must live on the GPU)" % what)
+    need(logits.dim() == 3 and logits.shape[1] == c and logits.dtype == torch.float32, "%s: fp32 logits (B, %d, N)" % (what, c))
+    need(logits.device == dev, "%s: logits on %s, the scans on %s" % (what, logits.device, dev))
+    b, _, n = logits.shape
+    need(b == len(sizes) and 1 <= b <= SCAN_MAX_SLOTS, "%s: %d logits rows for a batch of %d scans (1 .. %d)" %
+         (what, b, len(sizes), SCAN_MAX_SLOTS))
+    need(all(torch.is_tensor(batch[k]) for k in ("pos", "center", "scale", "scan_ids")), "%s: batch pos, center, scale and scan_ids "
+         "must be tensors" % what)
+    need(n >= 1 and tuple(batch["pos"].shape) == (b, n, 3), "%s: logits (B, C, N) and batch pos (B, N, 3) must agree, N >= 1" % what)
+    need(tuple(batch["center"].shape) == (b, 3) and tuple(batch["scale"].shape) == (b,) and tuple(batch["scan_ids"].shape) == (b,),
+         "%s: batch center (B, 3), scale (B,), scan_ids (B,)" % what)
+    for key, dt in (("pos", torch.float32), ("center", torch.float32), ("scale", torch.float32), ("scan_ids", torch.int64)):
+        need(torch.is_tensor(batch[key]) and batch[key].device == dev and batch[key].dtype == dt,
+             "%s: batch %s must be a %s tensor on %s" % (what, key, dt, dev))
+    scan_ids = batch["scan_ids"].contiguous()
+    prob = F.softmax(logits, dim=1).contiguous()
+    known = (batch["pos"] * batch["scale"].view(b, 1, 1) + batch["center"].view(b, 1, 3)).contiguous()
+    work = _to_device(scan_work_table(sizes), dev)
+    pred = out_offs = None
+    ends = np.cumsum(sizes, dtype=np.int64)
+    if want_pred:
+        pred = torch.empty(int(ends[-1]), dtype=torch.int64, device=dev)
+        out_offs = _to_device(np.concatenate([[0], ends[:-1]]).astype(np.int64), dev)
+    nbytes = int(_lib.load().geot_scan_predict_ws_bytes(b, n))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    call("geot_scan_predict", dev, b, c, n, len(scans), int(scans.points.shape[0]), ptr(scans.points), ptr(scans.labels),
+         ptr(scans.offsets), ptr(scan_ids), ptr(known), ptr(prob), int(work.shape[0]), ptr(work), ptr(out_offs),
+         ptr(pred), ptr(counts), ptr(ws), nbytes)
+    if not want_pred:
+        return None
+    return [p.view(1, -1) for p in torch.split(pred, sizes)]
+
+
+@torch.no_grad()
+def predict_scans(logits, batch):
+    """The per-vertex labels of the batch's whole scans: list of (1, M_i) int64 tensors (views of one buffer), equal to
+    get_pred_whole(logits, batch["pos"], batch["points"], batch["center"], batch["scale"]).  logits (B, C, N) fp32 on the
+    scans' device, batch from ValBatcher.batch.  One geot_scan_predict call, no host synchronisation."""
+    need(torch.is_tensor(logits) and logits.dim() == 3, "predict_scans: logits must be a (B, C, N) tensor")
+    return _scan_predict(logits, batch, logits.shape[1], want_pred=True)
 
 
 def _mandible_flags(cls, b):
@@ -213,6 +308,19 @@ class SegMetrics:
                  ptr(rows))
         self.mandible += flags
 
+    def update_from_scans(self, logits, batch):
+        """Count one ValBatcher batch from the model's logits (B, C, N): update_from_logits' counts, from the scans where
+        they lie -- one geot_scan_predict call whatever B and the scans' sizes, the jaws from the batch's host flags, no
+        host synchronisation."""
+        need(isinstance(batch, dict) and "mandible" in batch, "SegMetrics.update_from_scans: batch must come from ValBatcher.batch")
+        need(batch["scans"].device == self.device, "SegMetrics.update_from_scans: the scans on %s, the counts on %s" %
+             (batch["scans"].device, self.device))
+        flags = [bool(m) for m in batch["mandible"]]
+        need(len(flags) == len(batch["sizes"]), "SegMetrics.update_from_scans: one jaw flag per scan")
+        rows = self._rows(len(flags))
+        _scan_predict(logits, batch, self.c, counts=rows, what="SegMetrics.update_from_scans")
+        self.mandible += flags
+
     def read(self):
         """The epoch so far, in one device-to-host copy: per scan "acc_list" (0-d fp32 tensors), "miou_list" / "mdsc_list"
         (numpy scalars: float32, or a float64 NaN for a scan with no label but 0), as get_seg_metrics returns them; per jaw
@@ -251,7 +359,11 @@ def validate(model, val_loader, cfg, num_votes=0, data_transform=None):
         data["x"] = data["x"].transpose(1, 2).contiguous()
         logits, _, _ = model(data)
         metrics.update_from_logits(logits, data["pos"], data["points"], data["center"], data["scale"], data["labels"], cls)
-    out = metrics.read()
+    return _report(metrics.read(), cfg)
+
+
+def _report(out, cfg):
+    """validate's three log lines and its return value."""
     epoch = "%s/%s" % (_cfg(cfg, "epoch"), _cfg(cfg, "epochs"))
     with np.printoptions(precision=2, suppress=True):
         logging.info(f"Test Epoch [{epoch}],Mandible mIoU {out['mandible_miou']:.5f}, "
@@ -261,3 +373,34 @@ def validate(model, val_loader, cfg, num_votes=0, data_transform=None):
         logging.info(f"Test Epoch [{epoch}],mIoU {out['whole_miou']:.5f}, DSC {out['whole_mdsc']:.5f}, "
                      f"ACC {out['whole_macc']:.5f}")
     return out["whole_macc"], out["whole_miou"], out["whole_mdsc"]
+
+
+@torch.no_grad()
+def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, num_votes=0, data_transform=None):
+    """validate() without a loader: scans a DeviceScanSet (or a ValBatcher built on one, reused from epoch to epoch),
+    batches of batch_size scans in the sequential sampler's order (the last, shorter batch is kept: drop_last is false for
+    `val`), or of the scans `indices` names (a rank's shard).  cfg.num_points sizes the sample, cfg.num_classes (default
+    17) the counts.  Same log lines, return value and dtypes as validate().  stream: the next batch is built on that side
+    stream while the current one runs through the model.  num_votes and data_transform are accepted and unused, as in the
+    reference."""
+    from .openpoints.dataset.val_batch import ValBatcher
+    model.eval()
+    c = _cfg(cfg, "num_classes", 17)
+    if isinstance(scans, ValBatcher):
+        batcher = scans
+        need(stream is None or stream is batcher.stream, "validate_scans: the ValBatcher was built for another stream")
+    else:
+        need(_cfg(cfg, "num_points") is not None, "validate_scans: cfg.num_points (the sample size) is missing")
+        batcher = ValBatcher(scans, _cfg(cfg, "num_points"), c, stream=stream)
+    need(int(batch_size) >= 1, "validate_scans: batch_size >= 1")
+    order = list(range(len(batcher))) if indices is None else [int(i) for i in indices]
+    parts = [order[at:at + int(batch_size)] for at in range(0, len(order), int(batch_size))]
+    metrics = SegMetrics(c, batcher.device)
+    data = batcher.batch(parts[0]) if parts else None
+    for k in range(len(parts)):
+        batcher.join(data)
+        ahead = batcher.batch(parts[k + 1]) if k + 1 < len(parts) else None     # beside the forward pass when on a side stream
+        logits, _, _ = model(data)
+        metrics.update_from_scans(logits, data)
+        data = ahead
+    return _report(metrics.read(), cfg)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 14
+#define GEOT_ABI_VERSION 15
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -718,6 +718,35 @@ int geot_cloud_sample_batch(int s, int m, int num_classes, int n_scans, long lon
 #define GEOT_VIEW_REG_POINTS 24576
 int geot_fixmatch_views(int j, int m, int n_rows, int n_out, int gravity_dim, const float *raw, const void *jobs, float *pos,
                         float *x, float *heights, float *view_center, float *view_scale, void *stream);
+
+/* ---- whole-scan prediction and validation counts from device-resident scans (ABI 15) --------------------------------------
+ * geot_scan_predict: get_pred_whole (train.py:781-800) and, optionally, get_seg_metrics' counts for b batch slots in a
+ * number of launches that does not depend on b or on the scans' sizes (six with the grid, one without); no host
+ * synchronisation; neither neighbour indices, distances nor a (c, M) probability table are written.
+ * The scans lie concatenated as for geot_cloud_sample_batch: points (total, 3) fp32, labels (total) int32, offsets
+ * (n_scans + 1) int64 on the device; scan_ids (b) int64 on the device names the set scan of every slot (a scan may occur
+ * in several slots, in any order).  known (b, n, 3): the slot's n sampled points in the scan's coordinates; prob (b, c, n):
+ * their soft-max.  For every vertex v of slot s's scan, read in place:
+ *   the three points of known[s] smallest by (d2, index), d2 = ((dx dx) + (dy dy)) + (dz dz) un-contracted -- geot_three_nn's
+ *   contract: with n < 3 the missing entries are (+inf, index 0), and a NaN vertex gets three of those;
+ *   geot_seg_confusion_interp's weights, interpolation and arg-max (first maximum, a NaN wins) on them;
+ *   pred (optional): pred[out_offsets[s] + v] = class, out_offsets (b) int64 on the device;
+ *   counts (optional; needs labels): row s of b rows of c (c + 1) + 1 int64, laid out and ADDED to as geot_seg_confusion's.
+ * Bit for bit what geot_three_nn_ws per scan followed by geot_seg_confusion_interp yields.  Integer atomics only.
+ * work: n_work records of four int32 on the device, 16-byte aligned -- (slot, first vertex, vertex count, 0) -- one
+ * workgroup each; together they must cover every vertex of every slot once (geot_amd/validation.py scan_work_table
+ * makes them from the scans' sizes).  A record whose slot, first vertex or count is out of range, and a slot whose scan_ids
+ * entry lies outside [0, n_scans) or whose offsets pair is not 0 <= lo < hi <= total with hi - lo <= 2^31 - 1, is skipped:
+ * nothing of it is read, written or counted (callers validate scan ids on the host, as for geot_cloud_sample_batch).
+ * ws: geot_scan_predict_ws_bytes(b, n) bytes, 16-byte aligned, contents irrelevant (the grid over every slot's sampled
+ * points; with n < 2048 or GEOT_NN_IMPL=basic|wave the n points are scanned instead and ws is not touched).
+ * 0 <= b <= 65535 (0: nothing to do), 1 <= c <= GEOT_NTM_MAX_C, n >= 1, n_scans >= 1, total >= 1, n_work >= 0 (0: nothing
+ * to do), pred or counts (or both) given; anything else is hipErrorInvalidValue before any launch. */
+long long geot_scan_predict_ws_bytes(int b, int n);
+int geot_scan_predict(int b, int c, int n, int n_scans, long long total, const float *points, const int *labels,
+                      const long long *offsets, const long long *scan_ids, const float *known, const float *prob,
+                      int n_work, const int *work, const long long *out_offsets, long long *pred, long long *counts,
+                      void *ws, long long ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }
