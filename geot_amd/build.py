@@ -19,14 +19,18 @@ LIB = os.path.join(HERE, "libgeot_hip.so")
 VARIANTS = {"exact": (0, LIB), "fma": (1, os.path.join(HERE, "libgeot_hip_fma.so")),
             "fma_xy": (2, os.path.join(HERE, "libgeot_hip_fma_xy.so"))}
 
-SOURCES = ["fps.hip", "neighbors.hip", "knn_grid.hip", "gather_group.hip", "tile_scatter.hip", "ntm.hip", "ntm_generic.hip", "sa_mlp.hip", "dataprep.hip", "edgeconv.hip", "bnrelu.hip", "channels_last.hip", "loss.hip", "layernorm.hip", "meters.hip", "seg_metrics.hip", "views.hip", "scan_predict.hip"]
-HEADERS = ["geot_common.h", "ntm_generic.h", "tile_scatter.h", "knn_grid.h", "seg_metrics.h", os.path.join(ROOT, "include", "geot_hip.h")]
+SOURCES = ["fps.hip", "neighbors.hip", "knn_grid.hip", "gather_group.hip", "tile_scatter.hip", "ntm.hip", "ntm_generic.hip", "sa_mlp.hip", "dataprep.hip", "edgeconv.hip", "bnrelu.hip", "channels_last.hip", "loss.hip", "layernorm.hip", "meters.hip", "seg_metrics.hip", "views.hip", "scan_predict.hip", "view_program.hip"]
+HEADERS = ["geot_common.h", "ntm_generic.h", "tile_scatter.h", "knn_grid.h", "seg_metrics.h", "views.h", os.path.join(ROOT, "include", "geot_hip.h")]
 
 # -ffp-contract=off: squared distances must be un-contracted IEEE fp32 so that
 # integer outputs match the CPU oracle bit for bit.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fvisibility=hidden", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-Wno-inline-asm",
          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
+# per-source additions.  view_program.hip keeps 48 points per thread in registers across an op loop: packed fp32 pairs (what
+# the SLP vectoriser makes of neighbouring multiplies and adds) must sit in even-aligned register pairs, which that kernel
+# cannot afford -- with them it spills to scratch, without them it fits in 256 VGPRs.
+SOURCE_FLAGS = {"view_program.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc():
@@ -62,7 +66,7 @@ def build(force=False, verbose=False, variant="exact"):
             src = os.path.join(ROOT, lab_dir, s)
         obj = os.path.join(obj_dir, s.replace(".hip", ".o"))
         if force or _stale(obj, [src] + hdrs):
-            jobs.append([hipcc] + flags + ["-c", src, "-o", obj])
+            jobs.append([hipcc] + flags + SOURCE_FLAGS.get(s, []) + ["-c", src, "-o", obj])
 
     def run(cmd):
         if verbose:

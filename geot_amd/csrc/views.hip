@@ -19,52 +19,15 @@
 // Arithmetic: every statement is one fp32 operation (the translation unit is built with -ffp-contract=off; nothing here is
 // an explicit fma) except the mean: fp64 partial sums per thread in index order, a butterfly over the wave, the 8 wave sums
 // added in wave order, one division, one rounding.  min / max propagate NaN like torch.min / torch.max.
-#include <hip/hip_runtime.h>
-
-#include "geot_common.h"
-#include "geot_hip.h"
+#include "views.h"
 
 namespace geot {
-
-constexpr int VIEW_THREADS = 512, VIEW_WAVES = VIEW_THREADS / GEOT_WAVE, VIEW_PPT = GEOT_VIEW_REG_POINTS / VIEW_THREADS;
 
 struct ViewJob {         // GEOT_VIEW_JOB_WORDS words, include/geot_hip.h
     int src_row, out_row, flags, reserved0;
     float s[3], R[9], t[3], reserved1;
 };
 static_assert(sizeof(ViewJob) == GEOT_VIEW_JOB_WORDS * 4, "job record layout");
-
-__device__ __forceinline__ float nan_min(float a, float b) { return (a != a) ? a : ((b < a || b != b) ? b : a); }
-__device__ __forceinline__ float nan_max(float a, float b) { return (a != a) ? a : ((b > a || b != b) ? b : a); }
-
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);     // butterfly: every lane ends with the same bits
-    return v;
-}
-template <bool IS_MAX>
-__device__ __forceinline__ float wave_ext_nan(float v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const float o = __shfl_xor(v, d);
-        v = IS_MAX ? nan_max(v, o) : nan_min(v, o);
-    }
-    return v;
-}
-
-// element at a 32-bit BYTE offset from a workgroup-uniform base: one address register per access instead of a 64-bit pair
-// (the entry point admits only clouds whose rows stay below 4 GB)
-__device__ __forceinline__ float view_ld(const float *base, unsigned bytes) { return *(const float *)((const char *)base + bytes); }
-__device__ __forceinline__ void view_st(float *base, unsigned bytes, float v) { *(float *)((char *)base + bytes) = v; }
-
-constexpr int VIEW_CHUNK = 4;       // rounds per step of the streaming path
-
-struct ViewRed {
-    double sum[3];
-    float mn, mx;
-};
 
 // q[c] = r * s for rounds k0 .. k0 + N - 1 of this thread (one multiply per element)
 template <int N>
@@ -188,25 +151,9 @@ __global__ __launch_bounds__(VIEW_THREADS) void fm_views_kernel(int m, int n_row
             view_phase1<VIEW_CHUNK, G>(m, tid, k0, q, out_x, r);
         }
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) r.sum[a] = wave_sum_f64(r.sum[a]);
-    r.mn = wave_ext_nan<false>(r.mn);
-    if (lane_id() == 0) {
-        red_sum[wave][0] = r.sum[0];
-        red_sum[wave][1] = r.sum[1];
-        red_sum[wave][2] = r.sum[2];
-        red_min[wave] = r.mn;
-    }
-    __syncthreads();
-    double tot[3] = {0, 0, 0};
-    float low = red_min[0];
-#pragma unroll
-    for (int w = 0; w < VIEW_WAVES; ++w) {
-        tot[0] += red_sum[w][0];
-        tot[1] += red_sum[w][1];
-        tot[2] += red_sum[w][2];
-        low = nan_min(low, red_min[w]);
-    }
+    double tot[3];
+    float low;
+    view_reduce_sum_min(r, red_sum, red_min, wave, tot, low);
     const float cx = (float)(tot[0] / (double)m), cy = (float)(tot[1] / (double)m), cz = (float)(tot[2] / (double)m);
 
     if constexpr (HOLD) {
@@ -218,12 +165,7 @@ __global__ __launch_bounds__(VIEW_THREADS) void fm_views_kernel(int m, int n_row
             view_phase2<VIEW_CHUNK, G>(m, tid, k0, q, low, cx, cy, cz, out_h, r);
         }
     }
-    r.mx = wave_ext_nan<true>(r.mx);
-    if (lane_id() == 0) red_max[wave] = r.mx;
-    __syncthreads();
-    float top = red_max[0];
-#pragma unroll
-    for (int w = 1; w < VIEW_WAVES; ++w) top = nan_max(top, red_max[w]);
+    const float top = view_reduce_ext<true>(r.mx, red_max, wave);
     if (tid == 0) {
         view_center[job * 3] = cx;
         view_center[job * 3 + 1] = cy;

@@ -27,6 +27,7 @@ import torch
 
 from ... import _lib
 from ...ext._common import call, f32, need, ptr
+from .view_program import ViewProgram, _axis_rotation, pack_program_jobs, view_program_views
 
 # cfgs/tooth_semi/transformer_finetune_fixmatch_ntm.yaml datatransforms.kwargs, the entries the three lists read.
 # `angle` is what the file says (its second entry; a yaml loader keeps the last duplicate) and NOTHING reads it:
@@ -50,13 +51,6 @@ def _kw(kwargs, key):
 def _draw_scale(bounds):
     lo, hi = np.array(bounds).astype(np.float32)
     return (torch.rand(3, dtype=torch.float32) * (hi - lo) + lo).numpy()
-
-
-def _axis_rotation(axis, theta):
-    if theta == 0:
-        return np.eye(3)                 # expm(0) exactly; the configured case needs no scipy
-    from scipy.linalg import expm, norm  # the reference's own routine: its Pade approximant is part of R's bits
-    return expm(np.cross(np.eye(3), axis / norm(axis) * theta))
 
 
 def draw_view_params(kind, kwargs=TOOTH_VIEW_KWARGS):
@@ -240,13 +234,20 @@ class FixMatchBatcher:
     fills with equal values share one tensor here (data_u pos / x / raw_pos; y, cls, class_weights and their _w / _s forms):
     clone before writing into one of them.  The two sets are copied into one concatenated set at construction.
 
+    transforms: None keeps the three configured lists on geot_fixmatch_views.  A dict {"train": [...], "train_w": [...],
+    "train_s": [...]} of the reference's transform class names routes every view through geot_view_program instead
+    (view_program.ViewProgram; each class reads `kwargs`); params are then ViewProgram.draw results.  The deep-copy quirk
+    (3) does not depend on the lists.
+
     stream: queue every batch on that side stream.  A batch depends on the scans alone, so it does NOT wait for what the
     current stream has queued: it runs beside the iteration in flight.  Call `batcher.join(data, data_u)` before the
     current stream (or a step: `next_batches=`) reads the tensors; the wait it queues sits behind the running iteration
     and costs that iteration nothing.
     """
 
-    def __init__(self, labelled, unlabelled, num_points, num_classes=17, kwargs=TOOTH_VIEW_KWARGS, stream=None):
+    programs = None          # kind -> ViewProgram when `transforms` routes the views through geot_view_program
+
+    def __init__(self, labelled, unlabelled, num_points, num_classes=17, kwargs=TOOTH_VIEW_KWARGS, stream=None, transforms=None):
         need(isinstance(labelled, DeviceScanSet) and isinstance(unlabelled, DeviceScanSet),
              "FixMatchBatcher: labelled and unlabelled must be DeviceScanSets")
         need(int(num_points) >= 1, "FixMatchBatcher: num_points >= 1")
@@ -256,8 +257,17 @@ class FixMatchBatcher:
         self.scans = DeviceScanSet._merged(labelled, unlabelled)
         self.device = self.scans.device
         self.m, self.c, self.kwargs, self.stream = int(num_points), int(num_classes), kwargs, stream
+        if transforms is not None:
+            need(isinstance(transforms, dict) and set(transforms) == set(KINDS),
+                 "FixMatchBatcher: transforms is a dict with the lists %s" % (KINDS,))
+            self.programs = {kind: ViewProgram(transforms[kind], kwargs) for kind in KINDS}
+            need(all(p.has_heights for p in self.programs.values()),
+                 "FixMatchBatcher: every list needs a PointCloudCenterAndNormalize (heights is a feature key)")
         if stream is not None:      # once: the scans are ready; a batch itself depends on nothing the current stream does
             stream.wait_stream(torch.cuda.current_stream(self.device))
+
+    def _draw_view(self, kind):
+        return draw_view_params(kind, self.kwargs) if self.programs is None else self.programs[kind].draw(self.m)
 
     def draw(self, idx_l, idx_u, sel_l=None, sel_u=None, params=None):
         """The host half of batch(): (sel (B_l + B_u, m) int64, params) with everything not given drawn in the reference's
@@ -286,8 +296,7 @@ class FixMatchBatcher:
             else:
                 sel[slot] = np.random.choice(n, self.m, replace=n < self.m)            # tooth_dataset.py:134-135, 340-341
             if params is None:
-                drawn.append(draw_view_params("train", self.kwargs) if lab else
-                             (draw_view_params("train_w", self.kwargs), draw_view_params("train_s", self.kwargs)))
+                drawn.append(self._draw_view("train") if lab else (self._draw_view("train_w"), self._draw_view("train_s")))
         return sel, (drawn if params is None else list(params))
 
     def batch(self, idx_l, idx_u, sel_l=None, sel_u=None, params=None, check=False):
@@ -305,21 +314,30 @@ class FixMatchBatcher:
         jobs = [(i, i, params[i]) for i in range(bl)]
         jobs += [(bl + i, bl + i, params[bl + i][0]) for i in range(bu)]
         jobs += [(bl + i, bl + bu + i, params[bl + i][1]) for i in range(bu)]
-        pack_view_jobs(jobs, bl + bu, bl + 2 * bu)        # checks the parameters before anything is queued
+        packed = None
+        if self.programs is None:
+            pack_view_jobs(jobs, bl + bu, bl + 2 * bu)        # checks the parameters before anything is queued
+        else:                                             # the same rows, every view through its list's program
+            progs = [self.programs["train"]] * bl + [self.programs["train_w"]] * bu + [self.programs["train_s"]] * bu
+            jobs = [(job[0], job[1], prog, job[2]) for job, prog in zip(jobs, progs)]
+            packed = pack_program_jobs(jobs, bl + bu, bl + 2 * bu, self.m)
         if self.stream is None:
-            out = self._queue(ids, sel, jobs, bl, bu)
+            out = self._queue(ids, sel, jobs, bl, bu, packed)
         else:
             with torch.cuda.stream(self.stream):
-                out = self._queue(ids, sel, jobs, bl, bu)
+                out = self._queue(ids, sel, jobs, bl, bu, packed)
         if check:
             if self.stream is not None:
                 self.stream.synchronize()
             raise_bad_index(out[2], ids)
         return out[0], out[1]
 
-    def _queue(self, ids, sel, jobs, bl, bu):
+    def _queue(self, ids, sel, jobs, bl, bu, packed=None):
         s = cloud_sample_batch(self.scans, ids, sel, self.c, check=False)
-        v = fixmatch_views(s["raw"], jobs, int(_kw(self.kwargs, "gravity_dim")), bl + 2 * bu)
+        if packed is None:
+            v = fixmatch_views(s["raw"], jobs, int(_kw(self.kwargs, "gravity_dim")), bl + 2 * bu)
+        else:
+            v = view_program_views(s["raw"], jobs, bl + 2 * bu, packed)
         cls = self.scans.cls.index_select(0, s["scan_ids"]).view(-1, 1)
         lab, unl = slice(0, bl), slice(bl, bl + bu)
         data = {"pos": v["pos"][:bl], "x": v["x"][:bl], "heights": v["heights"][:bl], "y": s["y"][lab], "cls": cls[lab],

@@ -1,0 +1,107 @@
+"""Supervised training batches built on the GPU from scans that already live there -- what the reference's labelled training
+loader does per item on CPU workers in the supervised stage (openpoints/dataset/tooth_semi/tooth_dataset.py:116-206 for
+split 'train', the `train` transform list of cfgs/tooth_semi/default.yaml, default collation) plus the `.cuda()` /
+`transpose` lines of examples/segmentation/train.py:442-445:
+
+    pos (B, m, 3)   x (B, 3, m)   heights (B, m, 1)   y (B, m) int64   cls (B, 1) int64   class_weights (B, C)
+
+A batch is geot_cloud_sample_batch (5 launches), ONE geot_view_program launch for whatever the transform list holds, one
+gather of the jaw flags and three small pinned host-to-device copies; it never synchronises with the host.  The list is
+given by the reference's class names and kwargs (view_program.ViewProgram); per item the host draws np.random.choice and
+then the list's draws, in the reference's order.
+
+Kept from the reference: data['x'] IS data['pos'] until a transform rebinds pos.  With the default list x is the SCALED,
+un-centred, un-jittered cloud (PointCloudCenterAndNormalize separates the two), and ChromaticDropGPU -- there are no colour
+channels, x[:, :3] is all of x -- zeroes it with probability color_drop.
+"""
+import numpy as np
+import torch
+
+from ...ext._common import need
+from .fixmatch_batch import DeviceScanSet, cloud_sample_batch, raise_bad_index
+from .view_program import ViewProgram, pack_program_jobs, view_program_views
+
+# cfgs/tooth_semi/default.yaml datatransforms: the `train` list and its kwargs (`angle` is read by nothing in this list)
+DEFAULT_TRAIN = ["PointsToTensor", "PointCloudScaling", "PointCloudCenterAndNormalize", "PointCloudJitter", "ChromaticDropGPU"]
+DEFAULT_TRAIN_KWARGS = {"jitter_sigma": 0.001, "jitter_clip": 0.005, "scale": [0.8, 1.2], "gravity_dim": 1, "angle": [0, 1.0, 0]}
+
+
+class SupervisedBatcher:
+    """Replaces the reference's labelled training DataLoader of the supervised stage: `batch(idx)` returns the dict of the
+    module text for the scans `idx` of the set (what the sampler would yield) in freshly allocated tensors, so the `pos`
+    handed to SupervisedStep(..., next_pos=) passes the model's identity and version check one call later.  `heights` is
+    missing when the list has no PointCloudCenterAndNormalize, as in the reference.
+
+    stream: queue every batch on that side stream.  A batch depends on the scans alone, so it does not wait for what the
+    current stream has queued; call `join(data)` before the current stream (or a step) reads the tensors."""
+
+    def __init__(self, scans, num_points, num_classes=17, transforms=DEFAULT_TRAIN, kwargs=DEFAULT_TRAIN_KWARGS, stream=None):
+        need(isinstance(scans, DeviceScanSet), "SupervisedBatcher: scans must be a DeviceScanSet")
+        need(int(num_points) >= 1, "SupervisedBatcher: num_points >= 1")
+        need(1 <= int(num_classes) <= 4096, "SupervisedBatcher: num_classes must be in [1, 4096]")
+        self.program = ViewProgram(transforms, kwargs)          # NotImplementedError for what the kernel cannot do
+        self.scans, self.device = scans, scans.device
+        self.m, self.c, self.stream = int(num_points), int(num_classes), stream
+        if stream is not None:      # once: the scans are ready; a batch itself depends on nothing the current stream does
+            stream.wait_stream(torch.cuda.current_stream(self.device))
+
+    def __len__(self):
+        return len(self.scans)
+
+    def draw(self, idx, sel=None, params=None):
+        """The host half of batch(): (sel (B, m) int64, params) with everything not given drawn in the reference's per-item
+        order -- np.random.choice (tooth_dataset.py:134-135), then the list's draws (ViewProgram.draw)."""
+        idx = [int(i) for i in idx]
+        if sel is not None:
+            sel = np.asarray(sel.cpu() if isinstance(sel, torch.Tensor) else sel)
+            need(sel.shape == (len(idx), self.m) and sel.dtype.kind in "iu", "sel must be (%d, %d) integers" % (len(idx), self.m))
+            sel = sel.astype(np.int64)
+        if params is not None:
+            need(len(params) == len(idx), "params: one entry (ViewProgram.draw) per scan")
+        out = np.empty((len(idx), self.m), dtype=np.int64)
+        drawn = []
+        for slot, scan in enumerate(idx):
+            n = self.scans.sizes[scan]
+            out[slot] = sel[slot] if sel is not None else np.random.choice(n, self.m, replace=n < self.m)
+            if params is None:
+                drawn.append(self.program.draw(self.m))
+        return out, (drawn if params is None else list(params))
+
+    def batch(self, idx, sel=None, params=None, check=False):
+        """idx: scan numbers within the set; sel (B, m) vertex indices per scan and params (one ViewProgram.draw result per
+        scan) default to the reference's draws.  check=True reads the bad-index flags back (one host sync) and raises
+        IndexError."""
+        idx = [int(i) for i in idx]
+        need(len(idx) >= 1, "SupervisedBatcher.batch: at least one scan")
+        need(all(0 <= i < len(self.scans) for i in idx), "SupervisedBatcher.batch: idx must lie in [0, %d)" % len(self.scans))
+        sel, params = self.draw(idx, sel, params)
+        jobs = [(i, i, self.program, params[i]) for i in range(len(idx))]
+        packed = pack_program_jobs(jobs, len(idx), len(idx), self.m)       # checks the parameters before anything is queued
+        if self.stream is None:
+            data, bad = self._queue(idx, sel, jobs, packed)
+        else:
+            with torch.cuda.stream(self.stream):
+                data, bad = self._queue(idx, sel, jobs, packed)
+        if check:
+            if self.stream is not None:
+                self.stream.synchronize()
+            raise_bad_index(bad, idx)
+        return data
+
+    def _queue(self, idx, sel, jobs, packed):
+        s = cloud_sample_batch(self.scans, idx, sel, self.c, check=False)
+        v = view_program_views(s["raw"], jobs, len(idx), packed)
+        data = {"pos": v["pos"], "x": v["x"], "y": s["y"], "cls": self.scans.cls.index_select(0, s["scan_ids"]).view(-1, 1),
+                "class_weights": s["class_weights"]}
+        if v["heights"] is not None:
+            data["heights"] = v["heights"]
+        return data, s["bad"]
+
+    def join(self, data):
+        """Hand a batch built on the side stream to the CURRENT stream (FixMatchBatcher.join)."""
+        if self.stream is None:
+            return
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_stream(self.stream)
+        for t in data.values():
+            t.record_stream(cur)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 15
+#define GEOT_ABI_VERSION 16
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -747,6 +747,48 @@ int geot_scan_predict(int b, int c, int n, int n_scans, long long total, const f
                       const long long *offsets, const long long *scan_ids, const float *known, const float *prob,
                       int n_work, const int *work, const long long *out_offsets, long long *pred, long long *counts,
                       void *ws, long long ws_bytes, void *stream);
+
+/* ---- transform lists as per-view programs (ABI 16) ---------------------------------------------------------------------------
+ * geot_view_program: geot_fixmatch_views for ANY list of the reference's point transforms that keeps the point count
+ * (openpoints/transforms/point_transformer_gpu.py).  The host compiles the list, with one item's random draws, into ops
+ * (geot_amd/openpoints/dataset/view_program.py); j jobs run in ONE launch, one workgroup per job, no host synchronisation.
+ * jobs: j records of GEOT_VIEW_PROGRAM_JOB_WORDS 32-bit words, once on the device (what the kernel reads) and once on the
+ * host (jobs_host, the same bytes: what this entry point checks before it launches):
+ *   [0] int row of raw (n_rows, m, 3)    [1] int output row in pos / x / heights (n_out rows each)    [2] int op count, 0 ..
+ *   GEOT_VIEW_MAX_OPS    [3] int first row of the job in noise (n_noise, m, 3)    [4] int first row of the job in mask
+ *   (n_mask, m)    [5..7] reserved    then GEOT_VIEW_MAX_OPS ops of 14 words: int kind, int arg, float f[12].
+ * With p the job's cloud (initially its row of raw), per op, every statement one fp32 operation, left to right:
+ *    1 SCALE            p *= f[0..2]
+ *    2 CENTER_NORM      arg bit 0 centring, bit 1 normalising, bits 2-3 the gravity column g:
+ *                       heights (n_out, m, 1) = p[:, g] - min(p[:, g]); p -= mean(p) if centring; p /= mx if normalising,
+ *                       mx = max_i sqrtf((p0^2 + p1^2) + p2^2) of the (centred) cloud
+ *    3 XYZ_ALIGN        arg = g:  p -= mean(p); p[:, g] -= min(p[:, g])
+ *    4 TRANSLATE        p += f[0..2]
+ *    5 SCALE_TRANSLATE  p = p * f[0..2] + f[3..5]                        (two roundings)
+ *    6 JITTER           p += noise[row [3] + arg]                         (the host finishes the noise: scaled, clamped)
+ *    7 SCALE_JITTER     p = p * f[0..2] + noise[row [3] + arg]
+ *    8 ROTATE           p_k = ((p0 f[3k] + p1 f[3k+1]) + p2 f[3k+2])      (f = R, row-major)
+ *    9 FLIP             arg = axis:  p[:, axis] = max(ALL coordinates of p) - p[:, axis]
+ *   10 ZERO             p = 0
+ *   11 MASK             p *= mask[row [4] + arg]                          (per point)
+ *   12 STORE_X          x (n_out, 3, m) channel-first = p (arg mode 0), 0 (mode 1) or p * mask[row [4] + (arg >> 2)] (mode 2);
+ *                       mode = arg & 3
+ * pos (n_out, m, 3) = p after the last op.  view_center (j, 3) / view_scale (j): the mean and mx of the job's last op 2 or 3
+ * (0 / 1 for the part it does not compute, and for a job without such an op).  The mean is fp64 sums in geot_fixmatch_views'
+ * fixed tree, rounded once; min / max propagate NaN as torch does; results are bit-reproducible, and the program SCALE,
+ * STORE_X, CENTER_NORM (centring, normalising), ROTATE, TRANSLATE produces the bits of geot_fixmatch_views.  Up to
+ * GEOT_VIEW_REG_POINTS points a job's cloud stays in registers across all ops; beyond, every op streams it through the job's
+ * pos row.  heights is written by CENTER_NORM ops alone and may be NULL when no job has one; noise / mask may be NULL when
+ * n_noise / n_mask is 0.
+ * 1 <= j <= 65535, 1 <= m <= 357 913 941, n_rows >= 1, n_out >= 1, n_noise >= 0, n_mask >= 0, no other NULL pointer, every
+ * row in range, every op count <= GEOT_VIEW_MAX_OPS, every kind and arg known, no output row named twice; anything else is
+ * hipErrorInvalidValue before any launch.  (The kernel repeats the per-job test on the device copy: a job that fails it
+ * there writes nothing but NaN to its view_center / view_scale.) */
+#define GEOT_VIEW_MAX_OPS 16
+#define GEOT_VIEW_PROGRAM_JOB_WORDS (8 + 14 * GEOT_VIEW_MAX_OPS)
+int geot_view_program(int j, int m, int n_rows, int n_out, int n_noise, int n_mask, const float *raw, const void *jobs_host,
+                      const void *jobs, const float *noise, const float *mask, float *pos, float *x, float *heights,
+                      float *view_center, float *view_scale, void *stream);
 
 #ifdef __cplusplus
 }
