@@ -133,6 +133,12 @@ PROTOTYPES.update({
 PROTOTYPES["geot_rowsum_f64"] = [ctypes.c_longlong, _c_int, _P, _P, _c_void_p]
 PROTOTYPES["geot_fixmatch_meters_count"] = [_c_int, _c_int, _c_int, _c_float] + [_P] * 5 + [_c_void_p]
 PROTOTYPES["geot_fixmatch_meters_finalize"] = [_c_int] * 5 + [_P] * 10 + [_c_void_p]
+PROTOTYPES["geot_fixmatch_meters_finalize6"] = [_c_int] * 5 + [_P] * 12 + [_c_void_p]
+PROTOTYPES["geot_ntm_feature_loss_grad_det"] = [_c_int] * 5 + [_c_float] * 2 + [_P] * 7 + [_c_void_p]
+PROTOTYPES["geot_weighted_ce"] = [_c_int] * 4 + [_c_float] + [_P] * 6 + [_c_void_p]
+PROTOTYPES["geot_weighted_ce_grad"] = [_c_int] * 4 + [_c_float] + [_P] * 7 + [_c_void_p]
+PROTOTYPES["geot_poly1_focal_beta"] = [_c_int] * 3 + [_c_float] * 3 + [_P] * 7 + [_c_void_p]
+PROTOTYPES["geot_poly1_focal_beta_grad"] = [_c_int] * 3 + [_c_float] * 3 + [_P] * 9 + [_c_void_p]
 PROTOTYPES["geot_seg_confusion"] = [_c_int, _c_int] + [_P] * 4 + [_c_void_p]
 PROTOTYPES["geot_seg_confusion_interp"] = [_c_int] * 3 + [_P] * 6 + [_c_void_p]
 PROTOTYPES["geot_cloud_sample_batch"] = [_c_int] * 4 + [ctypes.c_longlong] + [_P] * 12 + [ctypes.c_longlong, _c_void_p]
@@ -174,6 +180,7 @@ PLAIN = {
     "geot_edgeconv_ws_bytes": ([_c_int] * 5, ctypes.c_longlong),
     "geot_edgeconv_rix_ints": ([_c_int] * 4, ctypes.c_longlong),
     "geot_poly1_focal_ws_doubles": ([_c_int] * 3, ctypes.c_longlong),
+    "geot_weighted_ce_ws_doubles": ([_c_int] * 3, ctypes.c_longlong),
     "geot_res_ln_supported": ([_c_int], _c_int),
     "geot_res_ln_ws_floats": ([_c_int] * 2, ctypes.c_longlong),
     "geot_rowdot_small_slices": ([_c_int] * 2, _c_int),
@@ -181,7 +188,7 @@ PLAIN = {
 }
 VIEW_MAX_OPS = 16        # GEOT_VIEW_MAX_OPS: ops of one geot_view_program job
 VIEW_PROGRAM_JOB_WORDS = 8 + 14 * VIEW_MAX_OPS     # GEOT_VIEW_PROGRAM_JOB_WORDS
-ABI_VERSION = 16    # include/geot_hip.h GEOT_ABI_VERSION this binding was written against
+ABI_VERSION = 17    # include/geot_hip.h GEOT_ABI_VERSION this binding was written against
 KNN_KMAX_HEAP = 1024      # GEOT_KNN_KMAX_HEAP: largest nsample of the heap-ordered kNN (knnquery_cuda, pointops.knn)
 KNN_KMAX_SORTED = 4096    # GEOT_KNN_KMAX_SORTED: largest k of the sorted kNN (knn_cuda.KNN, knn_point in 3-D)
 

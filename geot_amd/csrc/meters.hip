@@ -112,6 +112,8 @@ __global__ __launch_bounds__(FM_FIN_THREADS) void fm_finalize_kernel(int b, int 
                                                                      const float *__restrict__ loss, const float *__restrict__ sup,
                                                                      const float *__restrict__ unsup,
                                                                      const float *__restrict__ threed,
+                                                                     const float *__restrict__ feat,
+                                                                     const float *__restrict__ identity,
                                                                      const float *__restrict__ ema_corr, int *__restrict__ counts,
                                                                      float *__restrict__ mf32, double *__restrict__ mf64,
                                                                      long long *__restrict__ mi64, float *__restrict__ ema_corr_out)
@@ -146,8 +148,9 @@ __global__ __launch_bounds__(FM_FIN_THREADS) void fm_finalize_kernel(int b, int 
         meter_f64(v, s, a, 0, (double)*loss, n_l + n_u, cnt_all);
         meter_f64(v, s, a, 1, (double)*sup, n_l, cnt_l);
         meter_f64(v, s, a, 2, (double)*unsup, n_u, cnt_u);
-        meter_f64(v, s, a, 3, 0.0, n_u, cnt_u);                                 // use_feat_loss off (train.py:558-562)
-        meter_f64(v, s, a, 4, 0.0, n_u, cnt_u);                                 // use_identity_loss off (:564-567)
+        // NULL: the switch is off and the reference meters torch.tensor([0.]).item() (train.py:560-568, 678-679)
+        meter_f64(v, s, a, 3, feat ? (double)*feat : 0.0, n_u, cnt_u);
+        meter_f64(v, s, a, 4, identity ? (double)*identity : 0.0, n_u, cnt_u);
         meter_f64(v, s, a, 5, (double)*threed, n_u, cnt_u);
         mi64[3] += counts[FM_BAD];
         mi64[4] += 1;
@@ -189,6 +192,19 @@ GEOT_EXPORT int geot_fixmatch_meters_finalize(int b, int n, int c, int n_l, int 
         !meters_f32 || !meters_f64 || !meters_i64 || (ema_corr && !ema_corr_out))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(fm_finalize_kernel, dim3(1), dim3(FM_FIN_THREADS), 0, (hipStream_t)stream, b, n, c, n_l, n_u, loss, sup,
-                       unsup, threed, ema_corr, counts, meters_f32, meters_f64, meters_i64, ema_corr_out);
+                       unsup, threed, nullptr, nullptr, ema_corr, counts, meters_f32, meters_f64, meters_i64, ema_corr_out);
+    return hipGetLastError();
+}
+
+GEOT_EXPORT int geot_fixmatch_meters_finalize6(int b, int n, int c, int n_l, int n_u, const float *loss, const float *sup,
+                                               const float *unsup, const float *threed, const float *feat,
+                                               const float *identity, const float *ema_corr, int *counts, float *meters_f32,
+                                               double *meters_f64, long long *meters_i64, float *ema_corr_out, void *stream)
+{
+    if (b < 1 || n < 1 || c < 1 || c > GEOT_NTM_MAX_C || n_l < 0 || n_u < 0 || !loss || !sup || !unsup || !threed || !counts ||
+        !meters_f32 || !meters_f64 || !meters_i64 || (ema_corr && !ema_corr_out))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fm_finalize_kernel, dim3(1), dim3(FM_FIN_THREADS), 0, (hipStream_t)stream, b, n, c, n_l, n_u, loss, sup,
+                       unsup, threed, feat, identity, ema_corr, counts, meters_f32, meters_f64, meters_i64, ema_corr_out);
     return hipGetLastError();
 }

@@ -662,6 +662,83 @@ __global__ __launch_bounds__(256) void threed_loss_kernel(
     }
 }
 
+// ---- feature_space_loss backward with the same bits on every run ---------------------------------
+// The scatter form above adds floats with atomics: the sum of a row depends on the arrival order.  Here every term
+// 2 w_ij (T_i - T_j) is rounded to a 2^-40 fixed-point integer first and the rows are summed with 64-bit INTEGER atomics
+// (associative: any order gives the same sum); feature_fixed_finish_kernel then writes
+// grad_T = upstream * gscale * sum / 2^40 in full.  Range: |sum| < 2^23 per element (|T_i - T_j| <= 1 for the
+// row-stochastic matrices of sig_t_mean, 2 (k + in-degree) terms); resolution 9e-13 per term.
+constexpr double FEAT_FIX = 1099511627776.0;      // 2^40
+
+__device__ __forceinline__ void feat_fixed_add(unsigned long long *dst, float v)
+{
+    atomicAdd(dst, (unsigned long long)__double2ll_rn((double)v * FEAT_FIX));     // two's complement: negative terms wrap
+}
+
+template <int R>
+__global__ __launch_bounds__(256) void feature_grad_fixed_kernel(int total_pts, int n, int k, int pd, int CC, float inv2s2,
+                                                                 const float *__restrict__ feats,
+                                                                 const int *__restrict__ labels, const float *__restrict__ T,
+                                                                 const int *__restrict__ nbr, unsigned long long *__restrict__ acc)
+{
+    const int lane = lane_id();
+    for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < total_pts; i += gridDim.x * 4) {
+        const int b = i / n;
+        const float *Ti = T + (size_t)i * CC;
+        float ti[R], gi[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            ti[r] = (lane + 64 * r < CC) ? Ti[lane + 64 * r] : 0.f;
+            gi[r] = 0.f;
+        }
+        const int li = labels[i];
+        int j = -1;
+        float w = 0.f;
+        if (lane < k) {          // lanes 0..k-1 evaluate the k signed weights, exactly as threed_loss_kernel<.., SIGNED> does
+            j = b * n + nbr[(size_t)i * k + lane];
+            const float *pi = feats + (size_t)i * pd, *pj = feats + (size_t)j * pd;
+            float d2 = 0.f;
+            for (int d = 0; d < pd; ++d) {
+                float dx = pi[d] - pj[d];
+                d2 += dx * dx;
+            }
+            const float e = __expf(-d2 * inv2s2);
+            w = labels[j] == li ? e : -e;
+        }
+        unsigned long long live = __ballot(w != 0.f);
+        while (live) {
+            const int l = __builtin_ctzll(live);
+            live &= live - 1;
+            const int jj = __builtin_amdgcn_readlane(j, l);
+            const float wj = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(w), l));
+            const float *Tj = T + (size_t)jj * CC;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int e = lane + 64 * r;
+                if (e < CC) {
+                    const float c = 2.f * wj * (ti[r] - Tj[e]);
+                    gi[r] += c;                                             // (lane order: the same on every run)
+                    feat_fixed_add(acc + (size_t)jj * CC + e, -c);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int e = lane + 64 * r;
+            if (e < CC) feat_fixed_add(acc + (size_t)i * CC + e, gi[r]);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void feature_fixed_finish_kernel(long long total, float gscale, const float *__restrict__ upstream,
+                                                                   const unsigned long long *__restrict__ acc,
+                                                                   float *__restrict__ grad_T)
+{
+    const double f = (double)gscale * (upstream ? (double)upstream[0] : 1.0) / FEAT_FIX;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long long)gridDim.x * 256)
+        grad_T[e] = (float)((double)(long long)acc[e] * f);
+}
+
 // ---- threeD_space_loss forward, G consecutive points of the spatial order per wave ------------
 // Points that follow each other in Morton order share most of their neighbours.  The wave keeps the G
 // neighbour lists in lanes, and every neighbour row it loads is applied to ALL of its points that list it
@@ -1553,6 +1630,34 @@ GEOT_EXPORT int geot_ntm_feature_loss_grad(int b, int n, int c, int k, int feat_
     if ((long long)b * n == 0) return hipSuccess;
     return launch_threed_plain<true, true>(b, n, c, k, feat_dim, sigma, grad_scale, feats, labels, ins_T, nbr, nullptr,
                                            nullptr, grad_ins_T, (hipStream_t)stream);
+}
+
+GEOT_EXPORT int geot_ntm_feature_loss_grad_det(int b, int n, int c, int k, int feat_dim, float sigma, float grad_scale,
+                                               const float *feats, const int *labels, const float *ins_T, const int *nbr,
+                                               long long *acc, const float *upstream, float *grad_ins_T, void *stream)
+{
+    if (c < 1 || c > GEN_MAXC || b < 0 || n < 0 || k < 1 || k > 64 || feat_dim < 1 || !(sigma > 0.f) || !acc || !grad_ins_T)
+        return hipErrorInvalidValue;
+    if ((long long)b * n == 0) return hipSuccess;
+    if ((long long)b * n > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    const int t = b * n, cc = c * c, r = (cc + 63) / 64;
+    int blocks = (t + 3) / 4;
+    if (blocks > 16384) blocks = 16384;
+    const float inv2s2 = 1.f / (2.f * sigma * sigma);
+#define GEOT_FEAT_FIXED(R)                                                                                               \
+    hipLaunchKernelGGL((feature_grad_fixed_kernel<R>), dim3(blocks), dim3(256), 0, s, t, n, k, feat_dim, cc, inv2s2, feats, \
+                       labels, ins_T, nbr, (unsigned long long *)acc)
+    if (r <= 2) GEOT_FEAT_FIXED(2);
+    else if (r <= 5) GEOT_FEAT_FIXED(5);
+    else if (r <= 8) GEOT_FEAT_FIXED(8);
+    else GEOT_FEAT_FIXED(16);
+#undef GEOT_FEAT_FIXED
+    const long long total = (long long)t * cc;
+    const int fb = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(feature_fixed_finish_kernel, dim3(fb), dim3(256), 0, s, total, grad_scale, upstream,
+                       (const unsigned long long *)acc, grad_ins_T);
+    return hipGetLastError();
 }
 
 GEOT_EXPORT int geot_ntm_threed_loss_grad(int b, int n, int c, int k, float sigma, float grad_scale,

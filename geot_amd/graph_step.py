@@ -285,25 +285,31 @@ class GraphedSupervisedStep(_Graphed):
         super().__init__(step, warmup, agree)
         env = os.environ.get("GEOT_GRAPH_SPLIT")
         self.split = bool(split) if split is not None else (None if env is None else env == "1")
-        self.x = None            # static (pos, cls, target)
+        self.x = None            # static (pos, cls, target[, class_weights])
         self.next_pos = None     # static coordinates P works on
 
-    def __call__(self, pos, cls, target, next_pos=None):
+    def __call__(self, pos, cls, target, next_pos=None, class_weights=None):
+        weighted = getattr(self.step, "criterion_name", None) == "Weight_CELoss"
+        if weighted and class_weights is None:
+            raise RuntimeError("graphed step: SupervisedStep(criterion='Weight_CELoss') needs the batch's class_weights")
+        batch = (pos, cls, target) + ((class_weights,) if weighted else ())
+        names = ("pos", "cls", "target", "class_weights")
         if self.x is None:
             self.device = pos.device
-            self.x = (pos.detach().clone().contiguous(), cls.detach().clone(), target.detach().clone())
+            self.x = (pos.detach().clone().contiguous(),) + tuple(t.detach().clone() for t in batch[1:])
             self.next_pos = torch.empty_like(self.x[0])
             if self.split is None:
                 self.split = pos.shape[0] >= 3
-        for dst, src, name in zip(self.x, (pos, cls, target), ("pos", "cls", "target")):
+        for dst, src, name in zip(self.x, batch, names):
             _fits(dst, src, name)
         if next_pos is not None:
             _fits(self.next_pos, next_pos, "next_pos")
         self._check_lr()
         announced_now = self._is_announced((pos,))
         self._join_pending()
-        for dst, src in zip(self.x, (pos, cls, target)):
+        for dst, src in zip(self.x, batch):
             dst.copy_(src)
+        cw = self.x[3] if weighted else None
 
         def load_next(current):
             self.next_pos.copy_(self.x[0] if current else next_pos)
@@ -312,10 +318,10 @@ class GraphedSupervisedStep(_Graphed):
             return self.step.lookahead_work(self.next_pos)
 
         def train():
-            return self.step.iteration(self.x[0], self.x[1], self.x[2], self.pre, None)[0]
+            return self.step.iteration(self.x[0], self.x[1], self.x[2], self.pre, None, cw)[0]
         if self.split:
             def head():
-                self._loss, rest = self.step.forward_backward_head(self.x[0], self.x[1], self.x[2], self.pre)
+                self._loss, rest = self.step.forward_backward_head(self.x[0], self.x[1], self.x[2], self.pre, cw)
                 return rest
 
             def rest_update(rest):
@@ -327,6 +333,12 @@ class GraphedSupervisedStep(_Graphed):
 
 _P_KEYS = (("pos",), ("pos_s", "pos_w", "x_w", "cls_w", "raw_pos"))      # what FixMatchNTMStep.lookahead_work reads
 _P_KEYS_2 = (("pos",), ("pos_s", "pos_w", "raw_pos"))                     # ... after switch_ep (no teacher forward)
+
+
+def _p_keys(self_labelling, use_3d_loss=True):
+    """... and without raw_pos when cfg use_3d_loss is off: the look-ahead then builds no kNN graph and no Morton order."""
+    keys = _P_KEYS_2 if self_labelling else _P_KEYS
+    return keys if use_3d_loss else (keys[0], tuple(k for k in keys[1] if k != "raw_pos"))
 
 
 class GraphedFixMatchStep(_Graphed):
@@ -351,13 +363,14 @@ class GraphedFixMatchStep(_Graphed):
             self.device = data["pos"].device
             self.data = {k: v.detach().clone().contiguous() for k, v in data.items() if torch.is_tensor(v)}
             self.data_u = {k: v.detach().clone().contiguous() for k, v in data_u.items() if torch.is_tensor(v) and k != "T"}
-            self.next = tuple({k: torch.empty_like(d[k]) for k in keys} for d, keys in zip((self.data, self.data_u), _P_KEYS))
+            self.next = tuple({k: torch.empty_like(d[k]) for k in keys}
+                              for d, keys in zip((self.data, self.data_u), _p_keys(False, step.cfg.get("use_3d_loss", True))))
         for dst, src, what in ((self.data, data, "data"), (self.data_u, data_u, "data_u")):
             for k, v in dst.items():
                 _fits(v, src[k], "%s[%r]" % (what, k))
         self._check_lr()
         self_labelling = step.self_labelling
-        tag, p_keys = ("@2", _P_KEYS_2) if self_labelling else ("", _P_KEYS)
+        tag, p_keys = ("@2" if self_labelling else ""), _p_keys(self_labelling, step.cfg.get("use_3d_loss", True))
         announced_now = self._is_announced([b[k] for b, keys in zip((data, data_u), p_keys) for k in keys])
         self._join_pending()
         for dst, src in ((self.data, data), (self.data_u, data_u)):

@@ -55,15 +55,19 @@ class FixMatchMeters:
         for t in (self.counts, self.f32, self.f64, self.i64):
             t.zero_()
 
-    def update(self, label_u_aug, logits_u_aug, y_u, prob_s, loss, sup, unsup, threed, ema_t_corr=None):
+    def update(self, label_u_aug, logits_u_aug, y_u, prob_s, loss, sup, unsup, threed, ema_t_corr=None, feat=None,
+               identity=None):
         """One iteration, on the current stream: label_u_aug (B_u, N) int64 pseudo labels, logits_u_aug (B_u, N) fp32 their
         confidence, y_u (B_u, N) or (B_u, N, 1) int64 ground truth (data_u["y"]), prob_s (B_u, C, N) fp32 the student's
         soft-max on the strong view; loss / sup / unsup / threed the iteration's fp32 scalar losses; ema_t_corr (C, C).
+        feat / identity: the iteration's weighted feature-space / identity losses when cfg use_feat_loss / use_identity_loss
+        are on (LOSS_NAMES[3:5]: manifold_loss_feat, insT_identity_loss; None: 0.0 is metered, as the reference does).
         Every tensor must live on the meters' GPU: anything else is refused before a kernel is launched."""
         dev = self.counts.device
-        scalars = (loss, sup, unsup, threed)
+        extra = [(name, s) for name, s in (("feat", feat), ("identity", identity)) if s is not None]
+        scalars = (loss, sup, unsup, threed) + tuple(s for _, s in extra)
         named = [("label_u_aug", label_u_aug), ("logits_u_aug", logits_u_aug), ("data_u['y']", y_u), ("prob_s", prob_s),
-                 ("loss", loss), ("sup", sup), ("unsup", unsup), ("threed", threed)]
+                 ("loss", loss), ("sup", sup), ("unsup", unsup), ("threed", threed)] + extra
         if ema_t_corr is not None:
             named.append(("ema_t_corr", ema_t_corr))
         for name, t in named:
@@ -84,9 +88,14 @@ class FixMatchMeters:
         t, conf, g, p = (x.detach().contiguous() for x in (label_u_aug, logits_u_aug, y_u, prob_s))
         call("geot_fixmatch_meters_count", dev, b, n, self.c, self.threshold, ptr(t), ptr(conf), ptr(g), ptr(p), ptr(self.counts))
         corr = None if ema_t_corr is None else ema_t_corr.detach().contiguous()
-        call("geot_fixmatch_meters_finalize", dev, b, n, self.c, self.n_l, self.n_u,
-             *(ptr(s.detach()) for s in scalars), ptr(corr), ptr(self.counts), ptr(self.f32),
-             ptr(self.f64), ptr(self.i64), ptr(self.ema_t_corr) if corr is not None else None)
+        tail = (ptr(corr), ptr(self.counts), ptr(self.f32), ptr(self.f64), ptr(self.i64),
+                ptr(self.ema_t_corr) if corr is not None else None)
+        four = tuple(ptr(s.detach()) for s in (loss, sup, unsup, threed))
+        if extra:       # the six-loss entry point only when one of the two switched losses is given
+            call("geot_fixmatch_meters_finalize6", dev, b, n, self.c, self.n_l, self.n_u, *four,
+                 ptr(feat.detach()) if feat is not None else None, ptr(identity.detach()) if identity is not None else None, *tail)
+        else:
+            call("geot_fixmatch_meters_finalize", dev, b, n, self.c, self.n_l, self.n_u, *four, *tail)
 
     def read(self, strict=False):
         """-> (dict, tuple): the epoch's averages under train_one_epoch's names, plus "val" (the last iteration's values),

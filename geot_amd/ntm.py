@@ -443,10 +443,14 @@ class _FeatureLossFn(Function):
         feats, labels, ins_T, nbr = ctx.saved_tensors
         b, n, d = feats.shape
         c, k = ins_T.shape[1], nbr.shape[2]
-        g = torch.zeros_like(ins_T)
-        call("geot_ntm_feature_loss_grad", feats.device, b, n, c, k, d, ctx.sigma, 1.0 / (b * n * k),
-             ptr(feats), ptr(labels), ptr(ins_T), ptr(nbr), ptr(g))
-        return None, None, g * grad_out.reshape(()), None, None      # upstream gradient stays on the device
+        # the run-to-run reproducible form (fixed-point integer sums instead of float atomics): a step with use_feat_loss
+        # replays and compares bit for bit; the upstream gradient stays on the device
+        acc = torch.zeros(ins_T.numel(), dtype=torch.int64, device=ins_T.device)
+        g = torch.empty_like(ins_T)
+        up = grad_out.reshape(1).float().contiguous()
+        call("geot_ntm_feature_loss_grad_det", feats.device, b, n, c, k, d, ctx.sigma, 1.0 / (b * n * k),
+             ptr(feats), ptr(labels), ptr(ins_T), ptr(nbr), ptr(acc), ptr(up), ptr(g))
+        return None, None, g, None, None
 
 
 class feature_space_loss(nn.Module):
@@ -471,8 +475,10 @@ class Idenyity_loss(nn.Module):
 
     def forward(self, insT, Identity):
         ident = Identity.reshape(1, -1)
-        diff = (insT.reshape(insT.size(0), -1) - ident).pow(2)
-        return (torch.sum(diff * ident, dim=1) / torch.sum(ident)).mean()
+        # d * d, not d.pow(2): the same values and the same gradient bits (2 (g d) either way), but pow's backward forms
+        # d.pow(1) with a device-to-device copy -- a memcpy node when the iteration is captured (geot_amd/graph_step.py)
+        d = insT.reshape(insT.size(0), -1) - ident
+        return (torch.sum((d * d) * ident, dim=1) / torch.sum(ident)).mean()
 
 
 @torch.no_grad()

@@ -23,13 +23,58 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ntm as ntm_mod
-from .openpoints.loss import Poly1FocalLoss, Poly1FocalLoss_U_corr
+from .openpoints.loss.build import SUPERVISED_CRITERIA, UNSUPERVISED_CRITERIA, criterion_class
 from .openpoints.models.segmentation import WholePartSeg
 
 NTM_CFG = dict(threshold=0.0, unsupervised_loss_weight=1.0, ema_t_decay=0.999, lambma=0.9, geo_lambma=0.999,
                threed_loss_weight=0.1, threed_k=32, threed_sigma=1.0, filter_outlier=False, lr=1e-3,
-               weight_decay=1e-4, grad_norm_clip=None, batch_size_l=2, batch_size_u=2, num_classes=17, switch_ep=50)
-# cfgs/tooth_semi/transformer_finetune_fixmatch_ntm.yaml:45-96 (+ default.yaml)
+               weight_decay=1e-4, grad_norm_clip=None, batch_size_l=2, batch_size_u=2, num_classes=17, switch_ep=50,
+               criterion="Poly1FocalLoss", criterion_u="Poly1FocalLoss_U_corr", use_3d_loss=True, use_feat_loss=False,
+               feat_loss_weight=10.0, feat_k=16, feat_sigma=1.0, use_identity_loss=False, identity_loss_weight=1.0)
+# cfgs/tooth_semi/transformer_finetune_fixmatch_ntm.yaml:45-96 (+ default.yaml); criterion / criterion_u are its
+# criterion_args.NAME / criterion_u_args.NAME (a {"NAME": ..., **constructor arguments} dict is taken too)
+
+
+def _criterion(spec, allowed, what):
+    """The criterion a cfg entry names (a NAME or a {"NAME": ..., **kwargs} dict), of the ones train_one_epoch's dispatch
+    (train.py:449-454, 576-596) has a branch for in that place.  Raises before anything touches a device."""
+    args = dict(spec) if isinstance(spec, dict) else {"NAME": spec}
+    name = args.pop("NAME", None)
+    cls = criterion_class(name)          # NotImplementedError for a registered criterion the loop has no branch for
+    if name not in allowed:
+        raise ValueError("%s=%r: train_one_epoch calls one of %s there" % (what, name, ", ".join(allowed)))
+    return name, cls(**args)
+
+
+def check_cfg(cfg):
+    """A FixMatch+NTM cfg's switches, checked on the host: -> (criterion name, criterion, criterion_u name, criterion_u)."""
+    for key in ("use_3d_loss", "use_feat_loss", "use_identity_loss"):
+        if not isinstance(cfg[key], bool):
+            raise TypeError("cfg %s must be a bool, got %r" % (key, cfg[key]))
+    if cfg["use_feat_loss"] and not (isinstance(cfg["feat_k"], int) and cfg["feat_k"] >= 1 and cfg["feat_sigma"] > 0):
+        raise ValueError("cfg use_feat_loss: feat_k must be a positive int and feat_sigma positive, got %r / %r"
+                         % (cfg["feat_k"], cfg["feat_sigma"]))
+    return (_criterion(cfg["criterion"], SUPERVISED_CRITERIA, "criterion")
+            + _criterion(cfg["criterion_u"], UNSUPERVISED_CRITERIA, "criterion_u"))
+
+
+def unused_parameters(cfg=None):
+    """Names (suffixes, as ddp(unused=...) takes them) of the student's and T_predictor's parameters that receive no
+    gradient under `cfg` (NTM_CFG's keys; missing ones at their defaults).  T_revision / T_linear never do (see
+    UNUSED_SUPERVISED); `sigma` reaches the loss only through the class-transition prior inside the corrected logits, which
+    Poly1FocalLoss_U and Weight_CELoss_U do not read; T_predictor ("fc.": every layer of Ins_T_mean / sig_t_mean) reaches it
+    through the corrected logits and the 3-D, feature and identity losses."""
+    cfg = dict(NTM_CFG, **(cfg or {}))
+    name_u = cfg["criterion_u"]["NAME"] if isinstance(cfg["criterion_u"], dict) else cfg["criterion_u"]
+    unused = ["T_revision.weight", "T_linear.weight"]
+    if name_u in _IGNORES_CORRECTION:
+        unused.append("sigma")
+        if not (cfg["use_3d_loss"] or cfg["use_feat_loss"] or cfg["use_identity_loss"]):
+            unused.append("T_predictor.*")
+    return tuple(unused)
+
+
+_IGNORES_CORRECTION = ("Poly1FocalLoss_U", "Weight_CELoss_U")      # train.py:584-590: they get the uncorrected strong logits
 
 
 # parameters the configured step never differentiates: T_revision is not used by forward() at all and the
@@ -37,7 +82,7 @@ NTM_CFG = dict(threshold=0.0, unsupervised_loss_weight=1.0, ema_t_decay=0.999, l
 # unused); `sigma` only receives a gradient through the class-transition prior of the FixMatch step.  DDP's reducer
 # must be told, or it waits for their gradients (the reference never ran its DDP path: train.py:7 pins one GPU).
 UNUSED_SUPERVISED = ("T_revision.weight", "T_linear.weight", "sigma")
-UNUSED_FIXMATCH = ("T_revision.weight", "T_linear.weight")
+UNUSED_FIXMATCH = ("T_revision.weight", "T_linear.weight")       # = unused_parameters() of the default cfg
 
 
 def ddp(module, device, sync_bn=True, unused=(), min_world=2, **kw):
@@ -192,9 +237,11 @@ def _lookahead_at_blocks(segmentor, default):
 
 
 class SupervisedStep:
-    def __init__(self, model, lr=1e-3, weight_decay=1e-4, grad_norm_clip=None, grad_sync=None):
+    def __init__(self, model, lr=1e-3, weight_decay=1e-4, grad_norm_clip=None, grad_sync=None, criterion="Poly1FocalLoss"):
+        """criterion: cfg criterion_args -- "Poly1FocalLoss" or "Weight_CELoss" (or {"NAME": ..., **kwargs}); the latter takes
+        the batch's class_weights (train.py:449-450)."""
+        self.criterion_name, self.criterion = _criterion(criterion, SUPERVISED_CRITERIA, "criterion")
         self.model = model
-        self.criterion = Poly1FocalLoss()
         self.optimizer = make_optimizer(model, lr, weight_decay)
         self.clip = grad_norm_clip
         self._geometry = None          # coordinate-only work of the next batch, queued by the previous call
@@ -206,15 +253,16 @@ class SupervisedStep:
     def sync_modules(self):
         return [self.model]
 
-    def __call__(self, pos, cls, target, next_pos=None):
+    def __call__(self, pos, cls, target, next_pos=None, class_weights=None):
         """pos (B,N,3) f32, cls (B,1) int64 jaw id, target (B,N) int64 -> detached loss.
+        class_weights (B, C) f32: data['class_weights'], required by (and only read under) criterion="Weight_CELoss".
         next_pos: the coordinates of the NEXT batch, when the loop already holds them (a data loader with one batch of
         look-ahead): their sampling / grouping / index work is queued between this batch's forward and backward
         (PointTransformer_seg_T.prefetch_geometry) and picked up by the next call -- same results, 0.6 ms less per step.
         The queued work is used only if the next call passes that very tensor, unedited (the model checks the tensor, its
         version counter and, for WholePartSeg, the tensors it was assembled from); anything else is computed in line."""
         geometry, self._geometry = self._geometry, None
-        loss, self._geometry = self.iteration(pos, cls, target, geometry, next_pos)
+        loss, self._geometry = self.iteration(pos, cls, target, geometry, next_pos, class_weights)
         return loss
 
     def lookahead_work(self, pos):
@@ -225,11 +273,14 @@ class SupervisedStep:
         inner = self.model.module if hasattr(self.model, "module") else self.model
         return inner.prefetch_geometry(pos, inline=True) if hasattr(inner, "prefetch_geometry") else None
 
-    def forward_loss(self, pos, cls, target, geometry=None):
+    def forward_loss(self, pos, cls, target, geometry=None, class_weights=None):
         """The first half of an iteration: the forward and the loss (with its autograd graph)."""
+        weighted = self.criterion_name == "Weight_CELoss"
+        if weighted and class_weights is None:
+            raise RuntimeError("SupervisedStep(criterion='Weight_CELoss'): the batch's class_weights are required")
         _mode(self.model, True)
         logits = _inner(self.model, self.grad_sync is not None)(pos, pos.transpose(1, 2).contiguous(), cls, geometry=geometry)[0]
-        return self.criterion(logits, target)
+        return self.criterion(logits, target, class_weights) if weighted else self.criterion(logits, target)
 
     def backward_update(self, loss):
         """The second half: backward, clipping, the optimizer -> the detached loss."""
@@ -242,7 +293,7 @@ class SupervisedStep:
         self.optimizer.zero_grad(set_to_none=True)
         return loss.detach()
 
-    def forward_backward_head(self, pos, cls, target, geometry=None):
+    def forward_backward_head(self, pos, cls, target, geometry=None, class_weights=None):
         """The iteration up to the point where the backward reaches the transformer blocks -- forward, loss, the backward of
         the head and the decoder -- for a model that can cut its autograd graph there (cut_at_blocks / take_cut: the
         segmentor); otherwise the whole backward.  -> (detached loss, what backward_rest_update needs)."""
@@ -251,7 +302,7 @@ class SupervisedStep:
         if can_cut:
             inner.cut_at_blocks = True
         try:
-            loss = self.forward_loss(pos, cls, target, geometry)
+            loss = self.forward_loss(pos, cls, target, geometry, class_weights)
         finally:
             if can_cut:
                 inner.cut_at_blocks = False
@@ -271,7 +322,7 @@ class SupervisedStep:
         self.optimizer.step()
         self.optimizer.zero_grad(set_to_none=True)
 
-    def iteration(self, pos, cls, target, geometry=None, next_pos=None):
+    def iteration(self, pos, cls, target, geometry=None, next_pos=None, class_weights=None):
         """One iteration -> (detached loss, the geometry queued for next_pos or None)."""
         inner = self.model.module if hasattr(self.model, "module") else self.model
         queued = [None]
@@ -282,7 +333,7 @@ class SupervisedStep:
         at_blocks = _lookahead_at_blocks(inner, "blocks")
         if queue is not None and at_blocks:
             inner.at_blocks_backward = queue          # runs inside the backward, when it reaches the transformer blocks
-        loss = self.forward_loss(pos, cls, target, geometry)
+        loss = self.forward_loss(pos, cls, target, geometry, class_weights)
         if queue is not None and not at_blocks:
             queue()                                   # (GEOT_LOOKAHEAD_AT=forward: right behind the forward)
         loss = self.backward_update(loss)
@@ -302,12 +353,18 @@ class FixMatchNTMStep:
         must then carry the ground truth data_u["y"] (B_u, N) or (B_u, N, 1)."""
         self.cfg = dict(NTM_CFG, **(cfg or {}))
         c = self.cfg["num_classes"]
+        # the cfg's switches first: a criterion the loop has no branch for is refused before anything touches a device
+        self.criterion_name, self.criterion, self.criterion_u_name, self.criterion_u = check_cfg(self.cfg)
         self.model, self.model_t, self.T_predictor = student, teacher, t_predictor
         for p in self.model_t.parameters():
             p.requires_grad = False                                                    # train.py:221-222
         dev = next(student.parameters()).device
-        self.criterion, self.criterion_u = Poly1FocalLoss(), Poly1FocalLoss_U_corr()
         self.threed_loss = ntm_mod.threeD_space_loss(self.cfg["threed_k"], self.cfg["threed_sigma"], c)
+        self.feat_S_loss = ntm_mod.feature_space_loss(self.cfg["feat_k"], self.cfg["feat_sigma"], c)      # train.py:268-269
+        self.identity_loss = ntm_mod.Idenyity_loss()
+        self.Identity_t = torch.eye(c, device=dev) if self.cfg["use_identity_loss"] else None              # train.py:430
+        # the corrected strong logits have a reader only under these two (train.py:591-596)
+        self.needs_correction = self.criterion_u_name not in _IGNORES_CORRECTION
         self.optimizer = make_optimizer(student, self.cfg["lr"], self.cfg["weight_decay"])
         self.T_optimizer = make_optimizer(t_predictor, self.cfg["lr"], self.cfg["weight_decay"])
         self.ema_t = torch.eye(c, device=dev)                                          # train.py:274
@@ -409,9 +466,11 @@ class FixMatchNTMStep:
             if not self_labelling:
                 _mode(self.model_t, False)
                 geom_t = self._teacher_geometry(inner, geom_s, data, data_u, inline=True)
-            raw = data_u["raw_pos"].contiguous()
-            nbr = self.threed_loss.neighbours(raw)
-            order = ntm_mod.spatial_order(raw)
+            nbr = order = None
+            if self.cfg["use_3d_loss"]:                   # (off: nobody reads the 3-D loss's graph)
+                raw = data_u["raw_pos"].contiguous()
+                nbr = self.threed_loss.neighbours(raw)
+                order = ntm_mod.spatial_order(raw)
         pseudo = None if self_labelling else self._pseudo_labels(data_u, geom_t)
         return {"geom_s": geom_s, "pseudo": pseudo, "knn": (nbr, order)}
 
@@ -423,7 +482,7 @@ class FixMatchNTMStep:
         # the kNN graph of the 3-D loss needs raw_pos only: build it beside the teacher / student forwards
         dev = data["pos"].device
         nbr = order = None
-        if dev.type == "cuda":
+        if dev.type == "cuda" and self.cfg["use_3d_loss"]:
             if self._side is None:
                 self._side = torch.cuda.Stream(device=dev)
             main = torch.cuda.current_stream(dev)
@@ -530,23 +589,51 @@ class FixMatchNTMStep:
         # 4. per-point matrices + corrected strong logits (train.py:547-552)
         prob_s = F.softmax(pred_u_strong, dim=1).detach()
         ins_t = _inner(self.T_predictor, self.grad_sync is not None)(prob_s, self.cm)
-        pred_u_strong_corr = ntm_mod.correct_logits(pred_u_strong, ins_t, ema_t_corr, cfg["lambma"])
+        # (Poly1FocalLoss_U / Weight_CELoss_U read the uncorrected logits: the correction would have no reader)
+        pred_u_strong_corr = ntm_mod.correct_logits(pred_u_strong, ins_t, ema_t_corr, cfg["lambma"]) \
+            if self.needs_correction else None
         if not ema_in_place:
             with torch.no_grad():      # in its buffer, never rebound: a captured replay (graph_step) holds this very tensor
                 self.ema_t.copy_(ema_next)
-        # 5. losses (train.py:570-602)
-        nbr, order = knn_graph() if callable(knn_graph) else knn_graph
-        loss_3d = self.threed_loss(data_u["raw_pos"], label_u_aug, ins_t, nbr=nbr, order=order) * cfg["threed_loss_weight"]
-        sup_loss = self.criterion(pred_l, data["y"])
-        unsup_loss = self.criterion_u(pred_u_strong_corr, label_u_aug.detach(), logits_u_aug.detach(),
-                                      thresh=cfg["threshold"])
+        # 5. losses (train.py:560-602)
+        loss_feat = loss_ident = loss_3d = None
+        if cfg["use_feat_loss"]:
+            loss_feat = self.feat_S_loss(prob_s, label_u_aug, ins_t) * cfg["feat_loss_weight"]
+        if cfg["use_identity_loss"]:
+            loss_ident = self.identity_loss(ins_t, self.Identity_t) * cfg["identity_loss_weight"]
+        if cfg["use_3d_loss"]:
+            nbr, order = knn_graph() if callable(knn_graph) else knn_graph
+            loss_3d = self.threed_loss(data_u["raw_pos"], label_u_aug, ins_t, nbr=nbr, order=order) * cfg["threed_loss_weight"]
+        if self.criterion_name == "Weight_CELoss":
+            sup_loss = self.criterion(pred_l, data["y"], data["class_weights"])
+        else:
+            sup_loss = self.criterion(pred_l, data["y"])
+        conf, thresh = logits_u_aug.detach(), cfg["threshold"]
+        if self.criterion_u_name == "Weight_CELoss_U":          # (the labelled batch's weights: train.py:585-587)
+            unsup_loss = self.criterion_u(pred_u_strong, label_u_aug.detach(), data["class_weights"], conf, thresh=thresh)
+        elif self.criterion_u_name == "Poly1FocalLoss_U":
+            unsup_loss = self.criterion_u(pred_u_strong, label_u_aug.detach(), conf, thresh=thresh)
+        elif self.criterion_u_name == "Poly1FocalLoss_U_corr":
+            unsup_loss = self.criterion_u(pred_u_strong_corr, label_u_aug.detach(), conf, thresh=thresh)
+        else:                                                   # Poly1FocalLoss_U_T
+            unsup_loss = self.criterion_u(pred_u_strong, label_u_aug.detach(), conf, self.ema_t, pred_u_strong_corr,
+                                          thresh=thresh)
         thresh_mask = logits_u_aug.ge(cfg["threshold"])
         unsup_loss = unsup_loss * (cfg["unsupervised_loss_weight"] * (bu * n) / thresh_mask.sum())
-        loss = sup_loss + unsup_loss + loss_3d
+        loss = sup_loss + unsup_loss                            # train.py:646-655, in its order
+        if loss_feat is not None:
+            loss = loss + loss_feat
+        if loss_ident is not None:
+            loss = loss + loss_ident
+        if loss_3d is not None:
+            loss = loss + loss_3d
         if self.meters is not None:
             if "y" not in data_u:
                 raise RuntimeError("FixMatchNTMStep(meters=...): the unlabelled batch carries no ground truth data_u['y']")
-            self.meters.update(label_u_aug, logits_u_aug, data_u["y"], prob_s, loss, sup_loss, unsup_loss, loss_3d, ema_t_corr)
+            # (3-D loss off: the reference meters torch.tensor([0.]).item())
+            self.meters.update(label_u_aug, logits_u_aug, data_u["y"], prob_s, loss, sup_loss, unsup_loss,
+                               loss_3d if loss_3d is not None else torch.zeros((), device=loss.device), ema_t_corr,
+                               feat=loss_feat, identity=loss_ident)
         loss.backward()
         rest_in = None if cut is None else (cut[0], [d.grad for d in cut[1]])
 
@@ -564,7 +651,12 @@ class FixMatchNTMStep:
             self.optimizer.zero_grad(set_to_none=True)
             self.T_optimizer.step()
             self.T_optimizer.zero_grad(set_to_none=True)
-        losses = {"loss": loss.detach(), "sup": sup_loss.detach(), "unsup": unsup_loss.detach(), "threed": loss_3d.detach()}
+        losses = {"loss": loss.detach(), "sup": sup_loss.detach(), "unsup": unsup_loss.detach(),
+                  "threed": loss_3d.detach() if loss_3d is not None else torch.zeros((), device=loss.device)}
+        if loss_feat is not None:
+            losses["feat"] = loss_feat.detach()
+        if loss_ident is not None:
+            losses["identity"] = loss_ident.detach()
         if defer_rest:
             return losses, rest
         rest()
@@ -582,19 +674,33 @@ def build_fixmatch(device, seg_cfg=None, cfg=None, use_ddp=True, group=None, gra
     SyncBatchNorm-converted modules + one flat gradient all-reduce (sync_only / GradSync) instead of DDP wrappers.
     meters: see FixMatchNTMStep."""
     from .openpoints.models.backbone.transformer import TOOTH_SEG_CFG
+    import torch.distributed as dist
+    check_cfg(dict(NTM_CFG, **(cfg or {})))            # a bad cfg is refused before any module goes to the device
+    unused = unused_parameters(cfg)
+    if graph_sync and ("sigma" in unused or "T_predictor.*" in unused):
+        # GradSync sizes its one flat all-reduce by the gradients that exist when it is called: a synchronised parameter
+        # that never gets one is the case in which ranks can meet with buffers of different sizes -- a hang, or corruption
+        # inside a captured graph, not an error.  The multi-rank run of the non-default switches is out of scope: refuse.
+        raise RuntimeError("build_fixmatch(graph_sync=True): under this cfg %s receive no gradient (unused_parameters(cfg)); "
+                           "the flat gradient exchange of a replayed step expects one for every synchronised parameter -- "
+                           "build the step without graph_sync (one rank, or eager DDP)"
+                           % ", ".join(u for u in unused if u in ("sigma", "T_predictor.*")))
+    world = dist.is_available() and dist.is_initialized() and dist.get_world_size() >= min_world
     seg = dict(NAME="PointTransformer_seg_T", **(seg_cfg or TOOTH_SEG_CFG))
     student = WholePartSeg(segmentor_args=seg).to(device)
     teacher = WholePartSeg(segmentor_args=seg).to(device)
     teacher.load_state_dict(student.state_dict())
     t_pred = ntm_mod.Ins_T_mean(nclasses=(cfg or NTM_CFG).get("num_classes", 17)).to(device)
     if graph_sync:
-        import torch.distributed as dist
         student = sync_only(student, min_world=min_world)
         step = FixMatchNTMStep(student, teacher, t_pred, cfg=cfg, group=group, meters=meters)
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() >= min_world:
+        if world:
             step.grad_sync = GradSync([student, t_pred], group)
         return step
     if use_ddp:
-        student = ddp(student, device, unused=UNUSED_FIXMATCH, min_world=min_world)
-        t_pred = ddp(t_pred, device, sync_bn=False, min_world=min_world)
+        student = ddp(student, device, unused=[u for u in unused if u != "T_predictor.*"], min_world=min_world)
+        if "T_predictor.*" in unused:
+            t_pred = ddp(t_pred, device, sync_bn=False, unused=[n for n, _ in t_pred.named_parameters()], min_world=min_world)
+        else:
+            t_pred = ddp(t_pred, device, sync_bn=False, min_world=min_world)
     return FixMatchNTMStep(student, teacher, t_pred, cfg=cfg, group=group, meters=meters)

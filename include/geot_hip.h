@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 16
+#define GEOT_ABI_VERSION 17
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -237,6 +237,31 @@ int geot_poly1_focal(int b, int c, int n, float alpha, float gamma, float epsilo
 int geot_poly1_focal_grad(int b, int c, int n, float alpha, float gamma, float epsilon, const float *logits,
                           const long long *labels, const unsigned char *keep, const float *out2, const float *upstream,
                           float *grad_logits, void *stream);
+/* Class-weighted soft-max cross-entropy (ABI 17; openpoints/loss/build.py:913-925 Weight_CELoss, :928-938 Weight_CELoss_U
+ * when `conf` is given) on logits (b, c, n), 1 <= c <= GEOT_NTM_MAX_C, with int64 labels (b, n) and class_weights (bw, c):
+ *   w = mean over the bw rows (a sequential fp32 sum, one division);  per point  -w[y] * log_softmax(x)[y];
+ *   out2[0] = sum / (b n) -- ignored points count in the denominator, the weights do not;  out2[1] = 1 / (b n).
+ *   conf (b, n) fp32 (may be NULL): the point is ignored when !(conf >= thresh) (NaN: ignored), when y == 0 and when y == 255.
+ *   Any other label outside [0, c) makes the loss NaN.  workspace: _ws_doubles doubles.  No atomics: the same bits every call.
+ *   _grad: grad_logits = upstream[0] * out2[1] * w[y] * (softmax - onehot), exactly 0 at ignored points, written in full. */
+long long geot_weighted_ce_ws_doubles(int b, int c, int n);
+int geot_weighted_ce(int b, int c, int n, int bw, float thresh, const float *logits, const long long *labels,
+                     const float *class_weights, const float *conf, double *workspace, float *out2, void *stream);
+int geot_weighted_ce_grad(int b, int c, int n, int bw, float thresh, const float *logits, const long long *labels,
+                          const float *class_weights, const float *conf, const float *out2, const float *upstream,
+                          float *grad_logits, void *stream);
+/* Poly-1 focal loss with a per-point factor (ABI 17; openpoints/loss/build.py:564-688 Poly1FocalLoss_U_T): l as in
+ * geot_poly1_focal, beta[b,n] = conf[b,n] / t[b, y[b,n], n] with t (b, c, n) a second logits tensor, keep (b, n) bytes:
+ *   out2[0] = sum l * beta * keep / (c sum keep + 0.001);  out2[1] = 1 / that denominator.  workspace: as geot_poly1_focal.
+ *   _grad: grad_logits = upstream[0] * out2[1] * keep * beta * dl/dx;
+ *          grad_t[b,c,n] = [c == y] * upstream[0] * out2[1] * keep * (-conf / t^2) * sum_c' l(x[b,c',n]);
+ *   both written in full (0 where keep is 0 and, for grad_t, off the label channel). */
+int geot_poly1_focal_beta(int b, int c, int n, float alpha, float gamma, float epsilon, const float *logits,
+                          const long long *labels, const unsigned char *keep, const float *conf, const float *t,
+                          double *workspace, float *out2, void *stream);
+int geot_poly1_focal_beta_grad(int b, int c, int n, float alpha, float gamma, float epsilon, const float *logits,
+                               const long long *labels, const unsigned char *keep, const float *conf, const float *t,
+                               const float *out2, const float *upstream, float *grad_logits, float *grad_t, void *stream);
 /* max over the n innermost elements of every row, x (rows, n) contiguous and 16-byte aligned, n a multiple of 4, <= 256:
  * out (rows), arg (rows) uint8 = the first maximum's slot (torch.max semantics); _grad writes dx (rows, n) in full.
  * (Encoder's max over a group's points, transformer.py:127-134; max over nsample of the SA modules.) */
@@ -601,6 +626,14 @@ int geot_ntm_feature_loss(int b, int n, int c, int k, int feat_dim, float sigma,
 int geot_ntm_feature_loss_grad(int b, int n, int c, int k, int feat_dim, float sigma, float grad_scale,
                                const float *feats, const int *labels, const float *ins_T, const int *nbr,
                                float *grad_ins_T, void *stream);
+/* (ABI 17) the same gradient with the same bits on every run, for a step that is compared or replayed bit for bit: the
+ * terms 2 w_ij (T_i - T_j) are summed as 2^-40 fixed-point integers (64-bit integer atomics: any order, one sum; exact
+ * while |sum| < 2^23 per element -- row-stochastic T), then grad_ins_T = upstream[0] * grad_scale * sum is written in
+ * full.  acc: b*n*c*c int64 of device scratch, ZERO on entry; upstream: device scalar or NULL (= 1);
+ * grad_scale = 1 / (b*n*k). */
+int geot_ntm_feature_loss_grad_det(int b, int n, int c, int k, int feat_dim, float sigma, float grad_scale,
+                                   const float *feats, const int *labels, const float *ins_T, const int *nbr,
+                                   long long *acc, const float *upstream, float *grad_ins_T, void *stream);
 
 /* ---- dataloader-side ops ---------------------------------------------------------------
  * geot_grid_subsampling replaces cpp_subsampling.compute (openpoints/cpp/subsampling/wrapper.cpp:58-285 ->
@@ -649,6 +682,12 @@ int geot_fixmatch_meters_finalize(int b, int n, int c, int n_l, int n_u, const f
                                   const float *unsup, const float *threed, const float *ema_corr, int *counts,
                                   float *meters_f32, double *meters_f64, long long *meters_i64, float *ema_corr_out,
                                   void *stream);
+/* (ABI 17) the same with the two switched losses of train.py:560-568 metered too (:678-679, n = n_u, in double): feat /
+ * identity are device fp32 scalars, NULL = the switch is off and 0.0 is metered, as geot_fixmatch_meters_finalize does. */
+int geot_fixmatch_meters_finalize6(int b, int n, int c, int n_l, int n_u, const float *loss, const float *sup,
+                                   const float *unsup, const float *threed, const float *feat, const float *identity,
+                                   const float *ema_corr, int *counts, float *meters_f32, double *meters_f64,
+                                   long long *meters_i64, float *ema_corr_out, void *stream);
 
 /* ---- validation metrics (ABI 13) ---------------------------------------------------------------------------------------
  * The counts behind examples/segmentation/train.py:802-832 get_seg_metrics (per-scan accuracy, IoU and DSC of the classes
