@@ -167,6 +167,8 @@ PLAIN = {
     "geot_scan_predict_ws_bytes": ([_c_int, _c_int], ctypes.c_longlong),
     "geot_knn_grid_eligible": ([_c_int, _c_int, _c_int, _c_int], _c_int),
     "geot_ball_grid_eligible": ([_c_int, _c_int, _c_int, _c_float, _c_int], _c_int),
+    "geot_knn_grid_plan": ([_c_int] * 4 + [ctypes.POINTER(ctypes.c_longlong), _c_int], _c_int),
+    "geot_ball_grid_plan": ([_c_int] * 3 + [_c_float, _c_int, ctypes.POINTER(ctypes.c_longlong), _c_int], _c_int),
     "geot_edgeconv_eligible": ([_c_int] * 6, _c_int),
     "geot_edgeconv_plan": ([_c_int] * 6 + [ctypes.POINTER(ctypes.c_longlong), _c_int], _c_int),
     "geot_sa_plan": ([_c_int] * 5 + [ctypes.POINTER(_c_int), _c_int, _c_int, ctypes.POINTER(ctypes.c_longlong), _c_int],
@@ -188,7 +190,7 @@ PLAIN = {
 }
 VIEW_MAX_OPS = 16        # GEOT_VIEW_MAX_OPS: ops of one geot_view_program job
 VIEW_PROGRAM_JOB_WORDS = 8 + 14 * VIEW_MAX_OPS     # GEOT_VIEW_PROGRAM_JOB_WORDS
-ABI_VERSION = 17    # include/geot_hip.h GEOT_ABI_VERSION this binding was written against
+ABI_VERSION = 18    # include/geot_hip.h GEOT_ABI_VERSION this binding was written against
 KNN_KMAX_HEAP = 1024      # GEOT_KNN_KMAX_HEAP: largest nsample of the heap-ordered kNN (knnquery_cuda, pointops.knn)
 KNN_KMAX_SORTED = 4096    # GEOT_KNN_KMAX_SORTED: largest k of the sorted kNN (knn_cuda.KNN, knn_point in 3-D)
 

@@ -485,6 +485,15 @@ GEOT_EXPORT int geot_knn_grid_eligible(int b, int nq, int nr, int k)
     return (pairs >= (1ll << 26) || (k >= 16 && nr >= 8192 && pairs >= (1ll << 22))) ? 1 : 0;
 }
 
+// Host-only: what geot_knn_sorted_ws' grid path runs with for these sizes (see include/geot_hip.h)
+GEOT_EXPORT int geot_knn_grid_plan(int b, int nq, int nr, int k, long long *out, int n_out)
+{
+    if (!geot_knn_grid_eligible(b, nq, nr, k)) return 0;
+    const long long plan[7] = {kg_target(nr, k), KG_GMAX, KG_SLOTS, KG_SEL_KMIN, KG_SEL_KMAX, KG_WAVES, RIX_SORT_MAX};
+    for (int i = 0; out && i < n_out && i < 7; ++i) out[i] = plan[i];
+    return 1;
+}
+
 GEOT_EXPORT int geot_knn_sorted_ws(int b, int nq, int nr, int k, const float *query, const float *ref, int *idx,
                                    float *dist2, void *workspace, long long ws_bytes, void *stream)
 {
@@ -544,6 +553,15 @@ GEOT_EXPORT int geot_ball_grid_eligible(int b, int n, int m, float radius, int n
     return (long long)b * m * n >= (1ll << 26) ? 1 : 0;
 }
 
+// Host-only: the constants of geot_ball_query_ws' grid path (see include/geot_hip.h)
+GEOT_EXPORT int geot_ball_grid_plan(int b, int n, int m, float radius, int nsample, long long *out, int n_out)
+{
+    if (!geot_ball_grid_eligible(b, n, m, radius, nsample)) return 0;
+    const long long plan[3] = {KG_GMAX, KG_SLOTS, KG_WAVES};
+    for (int i = 0; out && i < n_out && i < 3; ++i) out[i] = plan[i];
+    return 1;
+}
+
 // geot_ball_query through the grid (identical output); workspace: geot_knn_grid_ws_bytes(b, n) bytes.
 GEOT_EXPORT int geot_ball_query_ws(int b, int n, int m, float radius, int nsample, const float *new_xyz,
                                    const float *xyz, int *idx, void *workspace, long long ws_bytes, void *stream)
@@ -551,8 +569,9 @@ GEOT_EXPORT int geot_ball_query_ws(int b, int n, int m, float radius, int nsampl
     if (b < 0 || n < 0 || m < 0 || nsample < 0) return hipErrorInvalidValue;
     if (b == 0 || m == 0 || nsample == 0) return hipSuccess;
     if (!workspace || !geot_ball_grid_eligible(b, n, m, radius, nsample) || ws_bytes < geot_knn_grid_ws_bytes(b, n) ||
-        b > 65535 || ((uintptr_t)workspace & 15) != 0)
+        b > 65535)
         return geot_ball_query(b, n, m, radius, nsample, new_xyz, xyz, idx, stream);
+    if (((uintptr_t)workspace & 15) != 0) return hipErrorInvalidValue; // as geot_knn_sorted_ws: the records are float4
     hipStream_t s = (hipStream_t)stream;
     const KgLayout L = kg_layout(n);
     uint32_t *ws = (uint32_t *)workspace;

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 17
+#define GEOT_ABI_VERSION 18
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -142,7 +142,8 @@ int geot_three_interpolate_grad_from(int b, int c, int n, int m, const float *gr
  * the k-th distance is strictly inside the visited block).  workspace = geot_knn_grid_ws_bytes(b, nr)
  * bytes of 16-byte-aligned scratch (contents irrelevant on entry).  Falls back to the brute-force kernel
  * when workspace is NULL / too small or geot_knn_grid_eligible(b, nq, nr, k) is 0 (small problems, k > 64,
- * or GEOT_NN_IMPL=basic|wave in the environment; GEOT_NN_IMPL=grid forces the grid where it is valid). */
+ * or GEOT_NN_IMPL=basic|wave in the environment; GEOT_NN_IMPL=grid forces the grid where it is valid).  A workspace
+ * that would be used but is not 16-byte aligned is refused with hipErrorInvalidValue, nothing written (all three). */
 long long geot_knn_grid_ws_bytes(int b, int nr);
 /* geot_ball_query through the same grid (cells of edge >= 1.0001 radius; identical output). */
 int geot_ball_grid_eligible(int b, int n, int m, float radius, int nsample);
@@ -151,6 +152,17 @@ int geot_ball_query_ws(int b, int n, int m, float radius, int nsample, const flo
 int geot_knn_grid_eligible(int b, int nq, int nr, int k);
 int geot_knn_sorted_ws(int b, int nq, int nr, int k, const float *query, const float *ref, int *idx,
                        float *dist2, void *workspace, long long ws_bytes, void *stream);
+/* Host-only (ABI 18): the constants the grid searches run with, for tests that place inputs on either side of every
+ * in-kernel branch.  Each returns 1 and fills the first n_out entries of its list when the matching *_eligible call
+ * is 1, and returns 0 and leaves out alone otherwise; no kernel is started.  out is a HOST array.
+ * geot_knn_grid_plan (up to 7): cells per axis aimed at, G = floor(sqrt(3 nr / (5 k))) clamped to 1..32; the most
+ * cells per axis (32, also the grid of geot_spatial_order); the 64-record register slots of the threshold-select fast
+ * path; the smallest and the largest k that take it; queries (waves) per workgroup; the largest cell whose points
+ * geot_spatial_order returns in ascending index.
+ * geot_ball_grid_plan (up to 3): the most cells per axis; the register slots; queries per workgroup.  The cell edge
+ * is the cloud's largest extent / floor(extent / (1.0001f * radius)) cells, 1..32 of them per axis. */
+int geot_knn_grid_plan(int b, int nq, int nr, int k, long long *out, int n_out);
+int geot_ball_grid_plan(int b, int n, int m, float radius, int nsample, long long *out, int n_out);
 int geot_three_nn_ws(int b, int n, int m, const float *unknown, const float *known, float *dist2, int *idx,
                      void *workspace, long long ws_bytes, void *stream);
 

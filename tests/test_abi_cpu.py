@@ -153,6 +153,38 @@ def test_host_only_planning_entry_points(monkeypatch):
         assert lib.geot_sa_plan(*args, 256, 1, untouched, 27) == 0 and list(untouched) == [-7] * 27
 
 
+def test_grid_search_plan_entry_points(monkeypatch):
+    """geot_knn_grid_plan / geot_ball_grid_plan (ABI 18): host-only, filled exactly where the matching *_eligible call is
+    1, a prefix on request, nothing written otherwise."""
+    import ctypes
+    from geot_amd import _lib
+    lib = _lib.load()
+    monkeypatch.delenv("GEOT_NN_IMPL", raising=False)
+    out = (ctypes.c_longlong * 7)(*([-7] * 7))
+    assert lib.geot_knn_grid_plan(1, 24000, 24000, 33, out, 7) == 1
+    assert list(out) == [int((3 * 24000 / (5 * 33)) ** 0.5), 32, 12, 8, 48, 4, 1 << 22]
+    assert lib.geot_knn_grid_plan(8, 8192, 8192, 4, out, 1) == 1 and out[0] == 32 and out[1] == 32   # G clamped to the most
+    short = (ctypes.c_longlong * 7)(*([-7] * 7))
+    assert lib.geot_knn_grid_plan(1, 24000, 24000, 33, short, 2) == 1 and list(short) == [20, 32] + [-7] * 5
+    assert lib.geot_knn_grid_plan(1, 24000, 24000, 33, None, 0) == 1
+    ball = (ctypes.c_longlong * 3)(*([-7] * 3))
+    assert lib.geot_ball_grid_plan(1, 24000, 6000, 0.1, 32, ball, 3) == 1 and list(ball) == [32, 12, 4]
+    for args in ((1, 1000, 1000, 8), (1, 24000, 24000, 65), (1, 24000, 24000, 0), (0, 24000, 24000, 8)):
+        untouched = (ctypes.c_longlong * 7)(*([-7] * 7))
+        assert lib.geot_knn_grid_eligible(*args) == 0
+        assert lib.geot_knn_grid_plan(*args, untouched, 7) == 0 and list(untouched) == [-7] * 7
+    for args in ((1, 24000, 6000, 0.1, 65), (1, 24000, 6000, -1.0, 32), (1, 2047, 6000, 0.1, 32)):
+        untouched = (ctypes.c_longlong * 3)(*([-7] * 3))
+        assert lib.geot_ball_grid_eligible(*args) == 0
+        assert lib.geot_ball_grid_plan(*args, untouched, 3) == 0 and list(untouched) == [-7] * 3
+    monkeypatch.setenv("GEOT_NN_IMPL", "grid")                # the environment switch moves the plan with the dispatch
+    assert lib.geot_knn_grid_plan(1, 241, 2048, 8, out, 7) == 1 and out[0] == 12
+    assert lib.geot_ball_grid_plan(1, 2048, 241, 0.1, 32, ball, 3) == 1
+    monkeypatch.setenv("GEOT_NN_IMPL", "wave")
+    assert lib.geot_knn_grid_plan(1, 24000, 24000, 33, out, 7) == 0
+    assert lib.geot_ball_grid_plan(1, 24000, 6000, 0.1, 32, ball, 3) == 0
+
+
 def test_header_is_plain_c_and_links(tmp_path):
     """include/geot_hip.h must be consumable from C (no C++ / torch types) and every declared entry point must
     resolve at link time against the shared library -- what a maintainer's cgo / JNI / C++ forwarder would do."""
