@@ -75,7 +75,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_stats_kernel(int c, int l, cons
     if (threadIdx.x == 0) { dst[2] = p; dst[3] = (float)max(e1 - e0, 0); }
 }
 
-// out = x * scale[c] + shift[c], clamped at 0 when relu; grid (gx, C, B)
+// out = x * scale[c] + shift[c], clamped at 0 when relu (NaN stays NaN: max_nan, geot_common.h); grid (gx, C, B)
 __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(int c, int l, int relu, const float *__restrict__ x,
                                                               const float *__restrict__ scale,
                                                               const float *__restrict__ shift, float *__restrict__ out)
@@ -88,17 +88,17 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(int c, int l, int 
         const int vec = l >> 2;
         for (int v = blockIdx.x * BN_THREADS + threadIdx.x; v < vec; v += gridDim.x * BN_THREADS) {
             float4 q = reinterpret_cast<const float4 *>(x + base)[v];
-            q.x = fmaxf(fmaf(q.x, a, b), lo);
-            q.y = fmaxf(fmaf(q.y, a, b), lo);
-            q.z = fmaxf(fmaf(q.z, a, b), lo);
-            q.w = fmaxf(fmaf(q.w, a, b), lo);
+            q.x = max_nan(fmaf(q.x, a, b), lo);
+            q.y = max_nan(fmaf(q.y, a, b), lo);
+            q.z = max_nan(fmaf(q.z, a, b), lo);
+            q.w = max_nan(fmaf(q.w, a, b), lo);
             reinterpret_cast<float4 *>(out + base)[v] = q;
         }
         for (int e = (vec << 2) + blockIdx.x * BN_THREADS + threadIdx.x; e < l; e += gridDim.x * BN_THREADS)
-            out[base + e] = fmaxf(fmaf(x[base + e], a, b), lo);
+            out[base + e] = max_nan(fmaf(x[base + e], a, b), lo);
     } else {
         for (int e = blockIdx.x * BN_THREADS + threadIdx.x; e < l; e += gridDim.x * BN_THREADS)
-            out[base + e] = fmaxf(fmaf(x[base + e], a, b), lo);
+            out[base + e] = max_nan(fmaf(x[base + e], a, b), lo);
     }
 }
 
@@ -473,7 +473,7 @@ __global__ __launch_bounds__(256) void bn_pool_kernel(long long rows, int n, int
             sv = y[row * n];
         }
         const float z = fmaf(sv, a, shift[cc]);
-        out[row] = relu ? fmaxf(z, 0.f) : z;               // (NaN: fmaxf drops it; the reference's relu keeps it -- inputs are finite)
+        out[row] = relu ? max_nan(z, 0.f) : z;             // (a NaN stays a NaN, as the reference's relu keeps it)
         sel_out[row] = sv;
         arg[row] = (uint8_t)(bj == 0x7fffffff ? 0 : bj);
     }

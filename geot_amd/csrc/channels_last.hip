@@ -19,13 +19,14 @@
 //   bn_bwd_apply_cl    dx = k0 (g - c1 - xhat c2)                                      12 B
 //   bn_sums_cl         (tiles, 2, C) float partials -> (C, 2) double sums, fixed order
 // Same arithmetic per element as the channels-first kernels of bnrelu.hip (bit-identical values; the statistics differ in
-// summation order only).  The gradient of the interpolation lives in gather_group.hip (gather_rows_csr_cl_kernel).
+// summation order, and fp_front_cl accumulates its shifted sums in fp64).  The gradient of the interpolation lives in gather_group.hip (gather_rows_csr_cl_kernel).
 #include "geot_common.h"
 #include "geot_hip.h"
 
 namespace geot {
 
 typedef float cl_f4 __attribute__((ext_vector_type(4)));
+typedef double cl_d4 __attribute__((ext_vector_type(4)));
 // Row stores: the rows these kernels write are not read again before the whole tensor has gone by, so they should not
 // take L2 capacity from the rows being gathered: non-temporal (plain, sc1 and sc0 sc1 stores measured no better; the lab copy
 // tools/lab/kernels/channels_last.hip keeps the switch).
@@ -41,16 +42,33 @@ constexpr int CL_MAX_THREADS = 1024;
 // Workgroups per launch: every row costs the same, so the launch is ONE round of co-resident workgroups -- CUs x the
 // workgroups of cl_block(c4) threads a CU holds at <= 64 registers (8 waves per SIMD) -- each with one contiguous run of
 // rows (a second, partly filled round is a ~20 % tail at ~1.6 rounds: measured).  At least 16 rows per workgroup.
+//
+// Lab / test knobs, read on every call (unset: nothing changes):
+//   GEOT_CL_TILES_MULT=<k>  k rounds of co-resident workgroups instead of one
+//   GEOT_CL_TILES=<T>       T > 0 stands in for "CUs x workgroups per CU" in both tile counts below (before the 16-row cap):
+//                           the launch geometry no longer depends on the device, so a few hundred rows reach every branch
+//                           of the row deal and of the tile loops (tests/test_cl_kernels_gpu.py, tests/_cl_ref.py)
+//   GEOT_CL_GRANULE=<g>     granule of fp_front_cl's row deal (default 8; <= 0: one contiguous run per workgroup)
+// Every buffer is sized from geot_cl_tiles / geot_fp_front_cl_tiles, which go through these two functions as the launches do.
 static inline int cl_cus() { return device_cus(); }     // per device (geot_common.h)
-static inline int cl_tiles_for(long long rows, int c)
+static inline long long cl_tiles_pinned()
 {
-    const int waves = (c / 4 + 63) / 64;
-    int per_cu = 32 / waves;
-    if (per_cu < 1) per_cu = 1;
-    long long t = (long long)cl_cus() * per_cu;
+    const char *e = getenv("GEOT_CL_TILES");
+    return e && atoll(e) > 0 ? atoll(e) : 0;
+}
+static inline int cl_tiles_capped(long long t, long long rows)
+{
     if (const char *mult = getenv("GEOT_CL_TILES_MULT")) t *= atoi(mult) > 0 ? atoi(mult) : 1;   // lab
     if (t > (rows + 15) / 16) t = (rows + 15) / 16;
     return (int)(t < 1 ? 1 : t);
+}
+static inline int cl_tiles_for(long long rows, int c)
+{
+    if (const long long pinned = cl_tiles_pinned()) return cl_tiles_capped(pinned, rows);
+    const int waves = (c / 4 + 63) / 64;
+    int per_cu = 32 / waves;
+    if (per_cu < 1) per_cu = 1;
+    return cl_tiles_capped((long long)cl_cus() * per_cu, rows);
 }
 static inline bool cl_dims_ok(long long rows, int c) { return rows > 0 && c >= 4 && c % 4 == 0 && c / 4 <= CL_MAX_THREADS; }
 static inline int cl_block(int c4) { return (c4 + 63) & ~63; }
@@ -77,7 +95,7 @@ template <int CS, int U>
 __device__ __forceinline__ void fp_front_cl_rows(int i, int cnt, int c4, int q, bool on, cl_f4 *__restrict__ y,
                                                  const cl_f4 (&p)[U][3], const float (*s_w)[3],
                                                  const float (*s_sk)[CS > 0 ? CS : 1], const int *s_out, const cl_f4 *wbr,
-                                                 cl_f4 &s, cl_f4 &ss, cl_f4 &piv, int &seen)
+                                                 cl_d4 &s, cl_d4 &ss, cl_f4 &piv, int &seen)
 {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -93,7 +111,10 @@ __device__ __forceinline__ void fp_front_cl_rows(int i, int cnt, int c4, int q, 
             }
             if (seen == 0) piv = v;                       // pivot of the shifted sums: this workgroup's first row
             ++seen;
-            const cl_f4 d = v - piv;
+            // shifted sums in fp64: a workgroup takes hundreds of rows (250 at 8 x 24000 x 1536), and an fp32 chain of that
+            // length is off by ~1e-6 of sum y^2 once the pivot sits a few sigma from the mean (sum d^2 = sum y^2 + n p^2 ...):
+            // d is one fp32 rounding, everything after it exact to 2^-53; the record leaves rounded to fp32 once
+            const cl_d4 d = __builtin_convertvector(v - piv, cl_d4);
             s = s + d;
             ss = __builtin_elementwise_fma(d, d, ss);
         }
@@ -122,8 +143,11 @@ __device__ __forceinline__ ClDeal cl_deal(int R, int g)
     return d;
 }
 
+// (waves per SIMD: the fp64 sums cost 8 registers, which would take the instantiations with up to 3 skip channels -- the
+// model's upper FP stages have 3 -- from 5 waves to 4, and a quarter of the workgroups of a launch with them; the compiler
+// holds them at 5 without spilling when asked to)
 template <int CS>
-__global__ __launch_bounds__(CL_MAX_THREADS) void fp_front_cl_kernel(
+__global__ __launch_bounds__(CL_MAX_THREADS) __attribute__((amdgpu_waves_per_eu(CS <= 3 ? 5 : 4))) void fp_front_cl_kernel(
     int c4, int m, int n, int R, int granule, const cl_f4 *__restrict__ a, const int *__restrict__ idx,
     const float *__restrict__ w, const float *__restrict__ skip, const float *__restrict__ wb,
     const int *__restrict__ order, cl_f4 *__restrict__ y, cl_f4 *__restrict__ partial)
@@ -145,7 +169,8 @@ __global__ __launch_bounds__(CL_MAX_THREADS) void fp_front_cl_kernel(
         wbr[k].z = wb[(size_t)(4 * q + 2) * CS + k];
         wbr[k].w = wb[(size_t)(4 * q + 3) * CS + k];
     }
-    cl_f4 s = {0.f, 0.f, 0.f, 0.f}, ss = {0.f, 0.f, 0.f, 0.f}, piv = {0.f, 0.f, 0.f, 0.f};
+    cl_d4 s = {0.0, 0.0, 0.0, 0.0}, ss = {0.0, 0.0, 0.0, 0.0};
+    cl_f4 piv = {0.f, 0.f, 0.f, 0.f};
     int seen = 0;
     for (int base = 0;; base += CL_STAGE) {
         __syncthreads();                                   // the previous run has been consumed
@@ -189,8 +214,8 @@ __global__ __launch_bounds__(CL_MAX_THREADS) void fp_front_cl_kernel(
     }
     if (on) {                                              // (s1, s2, pivot) rows of this tile + its row count
         cl_f4 *P = partial + (size_t)blockIdx.x * 3 * c4;
-        P[q] = s;
-        P[c4 + q] = ss;
+        P[q] = __builtin_convertvector(s, cl_f4);
+        P[c4 + q] = __builtin_convertvector(ss, cl_f4);
         P[2 * c4 + q] = piv;
         if (q == 0) reinterpret_cast<float *>(partial + (size_t)gridDim.x * 3 * c4)[blockIdx.x] = (float)seen;
     }
@@ -272,7 +297,9 @@ __global__ __launch_bounds__(CL_MAX_THREADS) void bn_apply_cl_kernel(
     if (MODE == 1) { mu = mean[q]; rs = rstd[q]; kk = k0[q]; m1 = c1[q]; m2 = c2[q]; }
     const float lo = relu ? 0.f : -INFINITY;
     auto one = [&](float xv, float gv, float av, float bv, float mv, float rv, float kv, float p1, float p2) {
-        if (MODE == 0) return fmaxf(fmaf(xv, av, bv), lo);
+        if (MODE == 0) return max_nan(fmaf(xv, av, bv), lo);     // NaN stays NaN (geot_common.h)
+        // (a NaN input fails `> 0`: its upstream gradient is dropped here and in the reduce kernels, where torch's ReLU
+        // backward passes it on; under batch statistics the channel's gradient is NaN either way, through xhat)
         const float g = (!relu || fmaf(xv, av, bv) > 0.f) ? gv : 0.f;
         return kv * (g - p1 - (xv - mv) * rv * p2);
     };
@@ -465,6 +492,7 @@ static int fp_front_cl_blocks_of(int block)
 }
 static int fp_front_cl_tiles(long long rows, int c, int cs)
 {
+    if (const long long pinned = cl_tiles_pinned()) return cl_tiles_capped(pinned, rows);
     static int cache[GEOT_DEV_SLOTS][CL_MAX_SKIP + 1][CL_MAX_THREADS / 64 + 1];   // [device][cs][waves] -> workgroups per CU
     const int block = cl_block(c / 4), waves = block / 64;
     int &per_cu = cache[device_slot()][cs][waves];
@@ -481,10 +509,7 @@ static int fp_front_cl_tiles(long long rows, int c, int cs)
         default: per_cu = fp_front_cl_blocks_of<8>(block); break;
         }
     }
-    long long t = (long long)cl_cus() * per_cu;
-    if (const char *mult = getenv("GEOT_CL_TILES_MULT")) t *= atoi(mult) > 0 ? atoi(mult) : 1;   // lab
-    if (t > (rows + 15) / 16) t = (rows + 15) / 16;
-    return (int)(t < 1 ? 1 : t);
+    return cl_tiles_capped((long long)cl_cus() * per_cu, rows);
 }
 GEOT_EXPORT int geot_fp_front_cl_tiles(int b, int c, int n, int cs)
 {

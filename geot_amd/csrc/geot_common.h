@@ -137,6 +137,11 @@ __device__ __forceinline__ float wave_min_f32(float v)
 }
 __device__ __forceinline__ float wave_max_f32(float v) { return -wave_min_f32(-v); }
 
+// max that propagates NaN like torch.relu / torch.clamp_min (fmaxf returns the OTHER operand: relu(NaN) = 0, and with a
+// floor of -inf, NaN -> -inf): llvm.maximum, one VALU instruction on gfx950.  For the activations after a BatchNorm: one
+// NaN in a batch makes the channel's statistics NaN, and the whole channel must stay NaN, not come out as zeros.
+__device__ __forceinline__ float max_nan(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
 

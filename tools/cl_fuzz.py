@@ -12,7 +12,10 @@ import sys
 import numpy as np
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from _cl_ref import NODE_FORWARD_TOLERANCE, node_grad_tolerance, node_ref64  # noqa: E402  (the suite's referee and bounds)
 from geot_amd import fused_norm as fn  # noqa: E402
 from geot_amd.synth import make_batch  # noqa: E402
 from geot_amd.pointnet2 import pointnet2_utils as pu  # noqa: E402
@@ -28,25 +31,8 @@ def rel(got, want):
 
 
 def ref64(a_cl, idx, w, skip, wb, bn, relu, up):
-    a64 = a_cl.double().cpu().requires_grad_(True)
-    wb64 = None if wb is None else wb.double().cpu().requires_grad_(True)
-    b, m, c = a64.shape
-    n = idx.shape[1]
-    g = torch.gather(a64, 1, idx.cpu().long().reshape(b, n * 3, 1).expand(-1, -1, c)).view(b, n, 3, c)
-    y = (g * w.double().cpu().unsqueeze(-1)).sum(2)
-    if skip is not None:
-        y = y + torch.matmul(skip.double().cpu().transpose(1, 2), wb64.t())
-    bn64 = torch.nn.BatchNorm1d(c).double()
-    bn64.load_state_dict({k: v.double().cpu() if v.dtype.is_floating_point else v.cpu() for k, v in bn.state_dict().items()})
-    bn64.train(bn.training)
-    pre = bn64(y.transpose(1, 2)).transpose(1, 2)
-    z = torch.relu(pre) if relu else pre
-    # a ReLU input within fp32 rounding of zero has no defined mask at this precision (any two fp32 evaluations may disagree
-    # and move a whole gradient element): those elements get no upstream gradient, in the referee and on the GPU alike
-    keep = (pre.detach().abs() > 1e-5) if relu else torch.ones_like(pre, dtype=torch.bool)
-    up64 = up.double().cpu() * keep
-    (z * up64).sum().backward()
-    return z.detach(), a64.grad, None if wb64 is None else wb64.grad, bn64.weight.grad, bn64.bias.grad, bn64, keep
+    """the whole node in float64 on the CPU, with the rule for ReLU inputs within fp32 rounding of zero (tests/_cl_ref.py)"""
+    return node_ref64(a_cl, idx, w, skip, wb, bn, relu, up)
 
 
 worst = {}
@@ -129,9 +115,8 @@ while done < CASES:
     # reproducible bit for bit; geot_common.h)
     longest = int(torch.bincount((idx.long() + torch.arange(b, device=DEV).view(b, 1, 1) * m).reshape(-1), minlength=b * m).max())
     same = torch.equal(z2, res["fused"][0]) and (longest > 4096 or torch.equal(a_r.grad, res["fused"][1]))
-    # a list of N pairs is summed in fp32 in list order: error grows like sqrt(N) eps x (sum |terms| / |result|)
-    tol = 1e-4 if longest > 2000 else (5e-5 if longest > 256 else 2e-5)
-    bad = {k: v for k, v in errs.items() if v > (1e-5 if k.endswith(" z") else tol)}
+    tol = node_grad_tolerance(longest)
+    bad = {k: v for k, v in errs.items() if v > (NODE_FORWARD_TOLERANCE if k.endswith(" z") else tol)}
     for k, v in errs.items():
         key = k.split(" ", 1)[1]
         worst[key] = max(worst.get(key, 0.0), v)
