@@ -21,7 +21,7 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from . import _lib
-from .ext._common import f32, i32, same_device, need, call, ptr
+from .ext._common import f32, i32, same_device, need, call, ptr, check_index
 from .knn_cuda import knn_sorted
 
 LABEL_PROJ = [0, 8, 7, 6, 5, 4, 3, 2, 1, 9, 10, 11, 12, 13, 14, 15, 16]  # train.py:48
@@ -332,6 +332,7 @@ class _ThreeDLossFn(Function):
         need(tuple(ins_T.shape) == (b * n, c, c) and tuple(labels.shape) == (b, n) and tuple(nbr.shape) == (b, n, k),
              "threeD_space_loss shape mismatch")
         _need_ntm_classes(c, "threeD_space_loss")
+        check_index(nbr, n, "threeD_space_loss nbr")      # GEOT_DEBUG=1 only: the kernels read rows nbr points at
         per_point = torch.empty(b * n, dtype=torch.float32, device=dev)
         if order is None:
             order = spatial_order(positions)      # processing order only: neighbour rows then hit L2
@@ -395,7 +396,14 @@ def spatial_order(positions):
 class threeD_space_loss(nn.Module):
     """utils/insT_loss.py:61-110.  forward(positions (B,N,3), labels (B,N), ins_T (B*N,C,C)) -> scalar.
     Neighbours = the k nearest other points (reference: knn_point(k+1)[..., 1:], i.e. the nearest hit
-    is dropped as "self"); the N x N distance matrix and the (BN, k, C*C) gathers are never built."""
+    is dropped as "self"); the N x N distance matrix and the (BN, k, C*C) gathers are never built.
+    A caller's own `nbr` holds k distinct ids per point: a repeated id inside one list is outside the contract (topk never
+    produces one), and the kernels differ on it -- the grouped ones apply a repeated row once, the one-point-per-wave ones
+    once per slot.
+    k + 1 > N: the reference's knn_point(k + 1) makes torch.topk raise.  The sorted kNN kernels (knn_wave_kernel,
+    knn_grid_kernel, the long-list selection) leave (distance inf, id 0) in the slots past the N references: in range, never
+    undefined, but point 0 would then sit several times in every list -- the repeated ids above -- so `neighbours` refuses
+    k >= N as the reference does."""
 
     def __init__(self, k=7, sigma=1.0, num_classes=17):
         super().__init__()
@@ -405,6 +413,8 @@ class threeD_space_loss(nn.Module):
 
     @torch.no_grad()
     def neighbours(self, positions):
+        need(self.k < positions.shape[1], "threeD_space_loss: k = %d neighbours need more than %d points per cloud, got %d"
+             % (self.k, self.k, positions.shape[1]))
         _, idx = knn_sorted(positions.contiguous().float(), positions.contiguous().float(), self.k + 1)
         return idx[:, :, 1:].contiguous()
 
@@ -431,6 +441,7 @@ class _FeatureLossFn(Function):
         need(tuple(ins_T.shape) == (b * n, c, c) and tuple(labels.shape) == (b, n) and tuple(nbr.shape) == (b, n, k),
              "feature_space_loss shape mismatch")
         _need_ntm_classes(c, "feature_space_loss")
+        check_index(nbr, n, "feature_space_loss nbr")     # GEOT_DEBUG=1 only
         per_point = torch.empty(b * n, dtype=torch.float32, device=dev)
         call("geot_ntm_feature_loss", dev, b, n, c, k, d, float(sigma), ptr(feats), ptr(labels), ptr(ins_T),
              ptr(nbr), ptr(per_point))
@@ -466,6 +477,9 @@ class feature_space_loss(nn.Module):
         feats = logits.detach().permute(0, 2, 1).contiguous()
         if nbr is None:
             from .openpoints.models.layers.knn import knn_point
+            # as in threeD_space_loss.neighbours: past the N references the kNN leaves id 0, a repeated id
+            need(self.k < feats.shape[1], "feature_space_loss: k = %d neighbours need more than %d points per cloud, got %d"
+                 % (self.k, self.k, feats.shape[1]))
             nbr = knn_point(self.k + 1, feats, feats)[1][:, :, 1:]
         return _FeatureLossFn.apply(feats, labels.to(torch.int32), ins_T, nbr.to(torch.int32), self.sigma)
 
