@@ -326,23 +326,7 @@ __global__ void pn_weights_kernel(int num_classes, const int *__restrict__ hist,
 // blockIdx.y = batch slot.  Every per-scan statement above is kept as it is -- the fp64 tree of pn_sum_kernel with its
 // PN_BLOCKS x PN_THREADS layout, the centroid's serial sum over the blocks, the fp32 norm, the divide -- so a slot's results
 // carry the bits of the single-scan calls.  The sizes live on the device (offsets), so no grid depends on them.
-struct PnScan {
-    long long base;      // first vertex of the slot's scan in the concatenated arrays
-    int n;               // its vertex count; 0: the slot's table entries are unusable
-};
-__device__ __forceinline__ PnScan pnb_scan(int slot, int n_scans, long long total, const long long *__restrict__ offsets,
-                                           const long long *__restrict__ scan_ids)
-{
-    PnScan r = {0, 0};
-    const long long id = scan_ids ? scan_ids[slot] : (long long)slot;
-    if (id < 0 || id >= n_scans) return r;
-    const long long a = offsets[id], b = offsets[id + 1];
-    if (a < 0 || b > total || b <= a || b - a > 0x7fffffffLL) return r;
-    r.base = a;
-    r.n = (int)(b - a);
-    return r;
-}
-
+// (PnScan / pnb_scan, a slot's entry of the scan table: geot_common.h -- geot_sample_draw reads the table by the same rules)
 __global__ __launch_bounds__(PN_THREADS) void pnb_sum_kernel(int n_scans, long long total, const float *__restrict__ points,
                                                              const long long *__restrict__ offsets,
                                                              const long long *__restrict__ scan_ids, double *__restrict__ partial)

@@ -304,4 +304,23 @@ static inline int device_slot()
     return dev % GEOT_DEV_SLOTS;
 }
 
+// (4) a batch slot's scan in a concatenated scan set (geot_cloud_sample_batch, geot_sample_draw): offsets (n_scans + 1) and
+// scan_ids (one per slot, NULL: slot i is scan i) live on the device, so the entry is checked where it is read.
+struct PnScan {
+    long long base;      // first vertex of the slot's scan in the concatenated arrays
+    int n;               // its vertex count; 0: the slot's table entries are unusable
+};
+__device__ __forceinline__ PnScan pnb_scan(int slot, int n_scans, long long total, const long long *__restrict__ offsets,
+                                           const long long *__restrict__ scan_ids)
+{
+    PnScan r = {0, 0};
+    const long long id = scan_ids ? scan_ids[slot] : (long long)slot;
+    if (id < 0 || id >= n_scans) return r;
+    const long long a = offsets[id], b = offsets[id + 1];
+    if (a < 0 || b > total || b <= a || b - a > 0x7fffffffLL) return r;
+    r.base = a;
+    r.n = (int)(b - a);
+    return r;
+}
+
 } // namespace geot

@@ -8,9 +8,11 @@ in openpoints/dataset/build.py:128-189) plus the `.cuda()` / `transpose` lines o
     strong     PointCloudScaling_s, PointCloudCenterAndNormalize, PointCloudRotation_s, PointCloudTranslation_s   "train_s"
 
 A batch costs a constant number of launches (geot_cloud_sample_batch: 5, geot_fixmatch_views: 1, one gather of the jaw flags,
-three small pinned host-to-device copies) and never synchronises with the host.  The random numbers stay on the host and are
-drawn with the reference's statements in the reference's order (draw_view_params), so a caller who seeds numpy and torch as
-the reference's worker did gets the reference's views.
+three small pinned host-to-device copies) and never synchronises with the host.  By default the random numbers stay on the
+host and are drawn with the reference's statements in the reference's order (draw_view_params), so a caller who seeds numpy
+and torch as the reference's worker did gets the reference's views.  `draws=DeviceDraws(seed)` moves the one expensive draw,
+the np.random.choice of every item, into one more launch (sample_draw.py: geot_sample_draw; not numpy's stream); the view
+parameters, a handful of scalars per item, stay host draws in both modes.
 
 Three things of the reference a user may not expect, all kept:
 
@@ -27,6 +29,7 @@ import torch
 
 from ... import _lib
 from ...ext._common import call, f32, need, ptr
+from .sample_draw import draw_batch_sel, on_stream
 from .view_program import ViewProgram, _axis_rotation, pack_program_jobs, view_program_views
 
 # cfgs/tooth_semi/transformer_finetune_fixmatch_ntm.yaml datatransforms.kwargs, the entries the three lists read.
@@ -177,11 +180,12 @@ class DeviceScanSet:
         return out
 
 
-def cloud_sample_batch(scans, scan_ids, sel, num_classes=17, check=True):
+def cloud_sample_batch(scans, scan_ids, sel, num_classes=17, check=True, ids_dev=None):
     """geot_cloud_sample_batch: scans a DeviceScanSet; scan_ids: the set scan of every batch slot (S ints, host); sel (S, m)
     int64 vertex indices local to each slot's scan (numpy or tensor) -> dict(raw (S, m, 3), y (S, m) int64, class_weights
     (S, num_classes), center (S, 3), scale (S,), bad (S,) int32).  Slot by slot bit-identical to prepare_sample on that scan
-    alone.  check=True reads `bad` back (one host sync) and raises IndexError for an index outside its scan."""
+    alone.  check=True reads `bad` back (one host sync) and raises IndexError for an index outside its scan.  ids_dev:
+    scan_ids as an (S,) int64 tensor already on the device (the batchers upload them once for the draw and the sampling)."""
     need(isinstance(scans, DeviceScanSet), "cloud_sample_batch: scans must be a DeviceScanSet")
     ids = np.asarray(scan_ids, dtype=np.int64).reshape(-1)
     need(ids.size >= 1 and ids.min() >= 0 and ids.max() < len(scans), "cloud_sample_batch: scan ids must lie in [0, %d)" % len(scans))
@@ -196,7 +200,8 @@ def cloud_sample_batch(scans, scan_ids, sel, num_classes=17, check=True):
     s, m = sel_dev.shape
     need(s == ids.size and m >= 1, "sel must have one row of m >= 1 indices per scan id")
     need(1 <= num_classes <= 4096, "num_classes must be in [1, 4096]")
-    ids_dev = _to_device(ids, dev)
+    if ids_dev is None:
+        ids_dev = _to_device(ids, dev)
     out = {"raw": torch.empty((s, m, 3), dtype=torch.float32, device=dev),
            "y": torch.empty((s, m), dtype=torch.int64, device=dev),
            "class_weights": torch.empty((s, num_classes), dtype=torch.float32, device=dev),
@@ -243,11 +248,18 @@ class FixMatchBatcher:
     current stream has queued: it runs beside the iteration in flight.  Call `batcher.join(data, data_u)` before the
     current stream (or a step: `next_batches=`) reads the tensors; the wait it queues sits behind the running iteration
     and costs that iteration nothing.
+
+    draws: None keeps the reference's per-item np.random.choice on the host (numpy's global stream, milliseconds per item).
+    A sample_draw.DeviceDraws draws every slot's vertex sample in one geot_sample_draw launch on the batcher's stream
+    instead -- one draw id per slot, the labelled slots first -- and np.random.choice is not called; given here it serves
+    every batch, given to batch() / draw() that call.  Explicit sel_l / sel_u rows still win.
     """
 
     programs = None          # kind -> ViewProgram when `transforms` routes the views through geot_view_program
+    stream = draws = None    # (the constructor's; None: the current stream, the reference's host draws)
 
-    def __init__(self, labelled, unlabelled, num_points, num_classes=17, kwargs=TOOTH_VIEW_KWARGS, stream=None, transforms=None):
+    def __init__(self, labelled, unlabelled, num_points, num_classes=17, kwargs=TOOTH_VIEW_KWARGS, stream=None, transforms=None,
+                 draws=None):
         need(isinstance(labelled, DeviceScanSet) and isinstance(unlabelled, DeviceScanSet),
              "FixMatchBatcher: labelled and unlabelled must be DeviceScanSets")
         need(int(num_points) >= 1, "FixMatchBatcher: num_points >= 1")
@@ -256,7 +268,7 @@ class FixMatchBatcher:
         self.n_l, self.n_u = len(labelled), len(unlabelled)
         self.scans = DeviceScanSet._merged(labelled, unlabelled)
         self.device = self.scans.device
-        self.m, self.c, self.kwargs, self.stream = int(num_points), int(num_classes), kwargs, stream
+        self.m, self.c, self.kwargs, self.stream, self.draws = int(num_points), int(num_classes), kwargs, stream, draws
         if transforms is not None:
             need(isinstance(transforms, dict) and set(transforms) == set(KINDS),
                  "FixMatchBatcher: transforms is a dict with the lists %s" % (KINDS,))
@@ -269,11 +281,18 @@ class FixMatchBatcher:
     def _draw_view(self, kind):
         return draw_view_params(kind, self.kwargs) if self.programs is None else self.programs[kind].draw(self.m)
 
-    def draw(self, idx_l, idx_u, sel_l=None, sel_u=None, params=None):
+    def draw(self, idx_l, idx_u, sel_l=None, sel_u=None, params=None, draws=None):
         """The host half of batch(): (sel (B_l + B_u, m) int64, params) with everything not given drawn in the reference's
         per-item order -- per labelled item np.random.choice then the "train" draw, per unlabelled item np.random.choice then
-        "train_w" (draws nothing) and "train_s".  params: list of B_l dicts followed by B_u (weak, strong) pairs."""
+        "train_w" (draws nothing) and "train_s".  params: list of B_l dicts followed by B_u (weak, strong) pairs.
+        With draws (a DeviceDraws; default: the constructor's) the rows not given are drawn by geot_sample_draw, queued on
+        the batcher's stream, and sel is that (B_l + B_u, m) int64 DEVICE tensor; only the view parameters are host draws."""
+        return self._draw(idx_l, idx_u, sel_l, sel_u, params, draws)[:2]
+
+    def _draw(self, idx_l, idx_u, sel_l, sel_u, params, draws):
+        """draw() and, third, the scan ids on the device when the device drew (None otherwise)."""
         bl, bu = len(idx_l), len(idx_u)
+        draws = self.draws if draws is None else draws
 
         def given(sel, count, what):
             if sel is None:
@@ -285,30 +304,40 @@ class FixMatchBatcher:
         if params is not None:
             need(len(params) == bl + bu and all(len(p) == 2 for p in params[bl:]),
                  "params: %d labelled dicts followed by %d (weak, strong) pairs" % (bl, bu))
-        sel = np.empty((bl + bu, self.m), dtype=np.int64)
+        ids_dev = None
+        on_device = draws is not None and (sel_l is None or sel_u is None)
+        if on_device:
+            ids = [int(i) for i in idx_l] + [self.n_l + int(i) for i in idx_u]
+            with on_stream(self.stream):
+                sel, ids_dev = draw_batch_sel(self.scans, ids, self.m, draws, ((0, sel_l), (bl, sel_u)))
+        else:
+            sel = np.empty((bl + bu, self.m), dtype=np.int64)
         drawn = []
         for slot, scan in enumerate(list(idx_l) + list(idx_u)):
             lab = slot < bl
             n = (self.scans.sizes[scan] if lab else self.scans.sizes[self.n_l + scan])
             have = sel_l if lab else sel_u
-            if have is not None:
+            if on_device:                                                              # drawn (or copied) above
+                pass
+            elif have is not None:
                 sel[slot] = have[slot if lab else slot - bl]
             else:
                 sel[slot] = np.random.choice(n, self.m, replace=n < self.m)            # tooth_dataset.py:134-135, 340-341
             if params is None:
                 drawn.append(self._draw_view("train") if lab else (self._draw_view("train_w"), self._draw_view("train_s")))
-        return sel, (drawn if params is None else list(params))
+        return sel, (drawn if params is None else list(params)), ids_dev
 
-    def batch(self, idx_l, idx_u, sel_l=None, sel_u=None, params=None, check=False):
+    def batch(self, idx_l, idx_u, sel_l=None, sel_u=None, params=None, check=False, draws=None):
         """idx_l / idx_u: scan numbers within the labelled / unlabelled set (what the samplers would yield); sel_* (B, m)
-        vertex indices per scan and params (see draw()) default to the reference's draws.  check=True reads the bad-index
-        flags back (one host sync) and raises IndexError."""
+        vertex indices per scan and params (see draw()) default to the reference's draws; draws: a DeviceDraws for this
+        call (default: the constructor's; see the class text).  check=True reads the bad-index flags back (one host sync)
+        and raises IndexError."""
         idx_l, idx_u = [int(i) for i in idx_l], [int(i) for i in idx_u]
         bl, bu = len(idx_l), len(idx_u)
         need(bl >= 1 and bu >= 1, "FixMatchBatcher.batch: at least one labelled and one unlabelled scan")
         need(all(0 <= i < self.n_l for i in idx_l), "idx_l must lie in [0, %d)" % self.n_l)
         need(all(0 <= i < self.n_u for i in idx_u), "idx_u must lie in [0, %d)" % self.n_u)
-        sel, params = self.draw(idx_l, idx_u, sel_l, sel_u, params)
+        sel, params, ids_dev = self._draw(idx_l, idx_u, sel_l, sel_u, params, draws)
         ids = idx_l + [self.n_l + i for i in idx_u]
         # view jobs: output rows [0, B_l) labelled, [B_l, B_l + B_u) weak, then strong
         jobs = [(i, i, params[i]) for i in range(bl)]
@@ -321,19 +350,16 @@ class FixMatchBatcher:
             progs = [self.programs["train"]] * bl + [self.programs["train_w"]] * bu + [self.programs["train_s"]] * bu
             jobs = [(job[0], job[1], prog, job[2]) for job, prog in zip(jobs, progs)]
             packed = pack_program_jobs(jobs, bl + bu, bl + 2 * bu, self.m)
-        if self.stream is None:
-            out = self._queue(ids, sel, jobs, bl, bu, packed)
-        else:
-            with torch.cuda.stream(self.stream):
-                out = self._queue(ids, sel, jobs, bl, bu, packed)
+        with on_stream(self.stream):
+            out = self._queue(ids, sel, jobs, bl, bu, packed, ids_dev)
         if check:
             if self.stream is not None:
                 self.stream.synchronize()
             raise_bad_index(out[2], ids)
         return out[0], out[1]
 
-    def _queue(self, ids, sel, jobs, bl, bu, packed=None):
-        s = cloud_sample_batch(self.scans, ids, sel, self.c, check=False)
+    def _queue(self, ids, sel, jobs, bl, bu, packed=None, ids_dev=None):
+        s = cloud_sample_batch(self.scans, ids, sel, self.c, check=False, ids_dev=ids_dev)
         if packed is None:
             v = fixmatch_views(s["raw"], jobs, int(_kw(self.kwargs, "gravity_dim")), bl + 2 * bu)
         else:

@@ -8,7 +8,8 @@ split 'train', the `train` transform list of cfgs/tooth_semi/default.yaml, defau
 A batch is geot_cloud_sample_batch (5 launches), ONE geot_view_program launch for whatever the transform list holds, one
 gather of the jaw flags and three small pinned host-to-device copies; it never synchronises with the host.  The list is
 given by the reference's class names and kwargs (view_program.ViewProgram); per item the host draws np.random.choice and
-then the list's draws, in the reference's order.
+then the list's draws, in the reference's order.  With `draws=DeviceDraws(seed)` the np.random.choice of every item is one
+geot_sample_draw launch in front of the five instead (sample_draw.py; not numpy's stream); the list's draws stay on the host.
 
 Kept from the reference: data['x'] IS data['pos'] until a transform rebinds pos.  With the default list x is the SCALED,
 un-centred, un-jittered cloud (PointCloudCenterAndNormalize separates the two), and ChromaticDropGPU -- there are no colour
@@ -19,6 +20,7 @@ import torch
 
 from ...ext._common import need
 from .fixmatch_batch import DeviceScanSet, cloud_sample_batch, raise_bad_index
+from .sample_draw import draw_batch_sel, on_stream
 from .view_program import ViewProgram, pack_program_jobs, view_program_views
 
 # cfgs/tooth_semi/default.yaml datatransforms: the `train` list and its kwargs (`angle` is read by nothing in this list)
@@ -33,63 +35,81 @@ class SupervisedBatcher:
     missing when the list has no PointCloudCenterAndNormalize, as in the reference.
 
     stream: queue every batch on that side stream.  A batch depends on the scans alone, so it does not wait for what the
-    current stream has queued; call `join(data)` before the current stream (or a step) reads the tensors."""
+    current stream has queued; call `join(data)` before the current stream (or a step) reads the tensors.
 
-    def __init__(self, scans, num_points, num_classes=17, transforms=DEFAULT_TRAIN, kwargs=DEFAULT_TRAIN_KWARGS, stream=None):
+    draws: None keeps the reference's np.random.choice per item on the host; a sample_draw.DeviceDraws draws the vertex
+    samples of a batch in one geot_sample_draw launch on the batcher's stream (one draw id per slot) and np.random.choice
+    is not called.  Given here it serves every batch, given to batch() / draw() that call; an explicit sel= still wins."""
+
+    stream = draws = None    # (the constructor's; None: the current stream, the reference's host draws)
+
+    def __init__(self, scans, num_points, num_classes=17, transforms=DEFAULT_TRAIN, kwargs=DEFAULT_TRAIN_KWARGS, stream=None,
+                 draws=None):
         need(isinstance(scans, DeviceScanSet), "SupervisedBatcher: scans must be a DeviceScanSet")
         need(int(num_points) >= 1, "SupervisedBatcher: num_points >= 1")
         need(1 <= int(num_classes) <= 4096, "SupervisedBatcher: num_classes must be in [1, 4096]")
         self.program = ViewProgram(transforms, kwargs)          # NotImplementedError for what the kernel cannot do
         self.scans, self.device = scans, scans.device
-        self.m, self.c, self.stream = int(num_points), int(num_classes), stream
+        self.m, self.c, self.stream, self.draws = int(num_points), int(num_classes), stream, draws
         if stream is not None:      # once: the scans are ready; a batch itself depends on nothing the current stream does
             stream.wait_stream(torch.cuda.current_stream(self.device))
 
     def __len__(self):
         return len(self.scans)
 
-    def draw(self, idx, sel=None, params=None):
+    def draw(self, idx, sel=None, params=None, draws=None):
         """The host half of batch(): (sel (B, m) int64, params) with everything not given drawn in the reference's per-item
-        order -- np.random.choice (tooth_dataset.py:134-135), then the list's draws (ViewProgram.draw)."""
+        order -- np.random.choice (tooth_dataset.py:134-135), then the list's draws (ViewProgram.draw).  With draws (a
+        DeviceDraws; default: the constructor's) and no sel, geot_sample_draw draws the rows on the batcher's stream and sel
+        is that (B, m) int64 DEVICE tensor."""
+        return self._draw(idx, sel, params, draws)[:2]
+
+    def _draw(self, idx, sel, params, draws):
+        """draw() and, third, the scan ids on the device when the device drew (None otherwise)."""
         idx = [int(i) for i in idx]
+        draws = self.draws if draws is None else draws
         if sel is not None:
             sel = np.asarray(sel.cpu() if isinstance(sel, torch.Tensor) else sel)
             need(sel.shape == (len(idx), self.m) and sel.dtype.kind in "iu", "sel must be (%d, %d) integers" % (len(idx), self.m))
             sel = sel.astype(np.int64)
         if params is not None:
             need(len(params) == len(idx), "params: one entry (ViewProgram.draw) per scan")
-        out = np.empty((len(idx), self.m), dtype=np.int64)
+        ids_dev = None
+        on_device = draws is not None and sel is None
+        if on_device:
+            with on_stream(self.stream):
+                out, ids_dev = draw_batch_sel(self.scans, idx, self.m, draws)
+        else:
+            out = np.empty((len(idx), self.m), dtype=np.int64)
         drawn = []
         for slot, scan in enumerate(idx):
             n = self.scans.sizes[scan]
-            out[slot] = sel[slot] if sel is not None else np.random.choice(n, self.m, replace=n < self.m)
+            if not on_device:
+                out[slot] = sel[slot] if sel is not None else np.random.choice(n, self.m, replace=n < self.m)
             if params is None:
                 drawn.append(self.program.draw(self.m))
-        return out, (drawn if params is None else list(params))
+        return out, (drawn if params is None else list(params)), ids_dev
 
-    def batch(self, idx, sel=None, params=None, check=False):
+    def batch(self, idx, sel=None, params=None, check=False, draws=None):
         """idx: scan numbers within the set; sel (B, m) vertex indices per scan and params (one ViewProgram.draw result per
-        scan) default to the reference's draws.  check=True reads the bad-index flags back (one host sync) and raises
-        IndexError."""
+        scan) default to the reference's draws; draws: a DeviceDraws for this call (default: the constructor's).
+        check=True reads the bad-index flags back (one host sync) and raises IndexError."""
         idx = [int(i) for i in idx]
         need(len(idx) >= 1, "SupervisedBatcher.batch: at least one scan")
         need(all(0 <= i < len(self.scans) for i in idx), "SupervisedBatcher.batch: idx must lie in [0, %d)" % len(self.scans))
-        sel, params = self.draw(idx, sel, params)
+        sel, params, ids_dev = self._draw(idx, sel, params, draws)
         jobs = [(i, i, self.program, params[i]) for i in range(len(idx))]
         packed = pack_program_jobs(jobs, len(idx), len(idx), self.m)       # checks the parameters before anything is queued
-        if self.stream is None:
-            data, bad = self._queue(idx, sel, jobs, packed)
-        else:
-            with torch.cuda.stream(self.stream):
-                data, bad = self._queue(idx, sel, jobs, packed)
+        with on_stream(self.stream):
+            data, bad = self._queue(idx, sel, jobs, packed, ids_dev)
         if check:
             if self.stream is not None:
                 self.stream.synchronize()
             raise_bad_index(bad, idx)
         return data
 
-    def _queue(self, idx, sel, jobs, packed):
-        s = cloud_sample_batch(self.scans, idx, sel, self.c, check=False)
+    def _queue(self, idx, sel, jobs, packed, ids_dev=None):
+        s = cloud_sample_batch(self.scans, idx, sel, self.c, check=False, ids_dev=ids_dev)
         v = view_program_views(s["raw"], jobs, len(idx), packed)
         data = {"pos": v["pos"], "x": v["x"], "y": s["y"], "cls": self.scans.cls.index_select(0, s["scan_ids"]).view(-1, 1),
                 "class_weights": s["class_weights"]}

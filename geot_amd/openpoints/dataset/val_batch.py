@@ -10,7 +10,8 @@ openpoints/dataset/build.py:30-50 collate_fn_val) plus validate's `.cuda()` and 
 
 The `val` list is the weak view's list: geot_cloud_sample_batch (5 launches) and geot_fixmatch_views with the "train_w"
 parameters (1), one gather of the jaw classes, two small pinned host-to-device copies -- the same number for every batch,
-and no host synchronisation.  validation.SegMetrics.update_from_scans / predict_scans / validate_scans take such a batch; it
+and no host synchronisation.  With `draws=DeviceDraws(seed)` the per-item np.random.choice becomes one geot_sample_draw launch
+in front of them (sample_draw.py; not numpy's stream).  validation.SegMetrics.update_from_scans / predict_scans / validate_scans take such a batch; it
 also carries every key the existing validate() and get_pred_whole() read.
 
 One thing of the reference a user may not expect, kept: the dataset's pc_norm centres and scales the scan (`center`,
@@ -25,6 +26,7 @@ import torch
 from ...ext._common import need
 from .fixmatch_batch import (TOOTH_VIEW_KWARGS, DeviceScanSet, _kw, cloud_sample_batch, draw_view_params, fixmatch_views,
                              raise_bad_index)
+from .sample_draw import draw_batch_sel, on_stream
 
 
 def draw_val_sel(sizes, num_points):
@@ -47,16 +49,20 @@ class ValBatcher:
 
     The jaw classes are read from the device once, here.  stream: queue every batch on that side stream; it depends on
     the scans alone, so it runs beside whatever the current stream has in flight.  Call `join(batch)` before the current
-    stream reads the tensors."""
+    stream reads the tensors.
 
-    def __init__(self, scans, num_points, num_classes=17, kwargs=TOOTH_VIEW_KWARGS, stream=None):
+    draws: None keeps the reference's np.random.choice per item on the host (draw_val_sel); a sample_draw.DeviceDraws draws
+    the vertex samples of a batch in one geot_sample_draw launch on the batcher's stream (one draw id per slot) and
+    np.random.choice is not called.  Given here it serves every batch, given to batch() that call; sel= still wins."""
+
+    def __init__(self, scans, num_points, num_classes=17, kwargs=TOOTH_VIEW_KWARGS, stream=None, draws=None):
         need(isinstance(scans, DeviceScanSet), "ValBatcher: scans must be a DeviceScanSet")
         need(scans.device.type == "cuda", "ValBatcher: CPU not supported (the scans must live on the GPU)")
         need(int(num_points) >= 1, "ValBatcher: num_points >= 1")
         need(1 <= int(num_classes) <= 4096, "ValBatcher: num_classes must be in [1, 4096]")
         need(int(_kw(kwargs, "gravity_dim")) in (0, 1, 2), "ValBatcher: gravity_dim must be 0, 1 or 2")
         self.scans, self.device = scans, scans.device
-        self.m, self.c, self.kwargs, self.stream = int(num_points), int(num_classes), kwargs, stream
+        self.m, self.c, self.kwargs, self.stream, self.draws = int(num_points), int(num_classes), kwargs, stream, draws
         self.cls_host = [int(v) for v in scans.cls.cpu().tolist()]       # the one copy: validate's `cls[ii] == 0` per scan
         self._points = list(torch.split(scans.points, scans.sizes))      # views
         self._labels = list(torch.split(scans.labels, scans.sizes))
@@ -66,14 +72,20 @@ class ValBatcher:
     def __len__(self):
         return len(self.scans)
 
-    def batch(self, idx, sel=None, check=False):
+    def batch(self, idx, sel=None, check=False, draws=None):
         """idx: scan numbers within the set; sel (B, m) vertex indices per scan, default the reference's draws
-        (draw_val_sel).  check=True reads the bad-index flags back (one host sync) and raises IndexError."""
+        (draw_val_sel) or, with draws (a DeviceDraws; default: the constructor's), geot_sample_draw's.  check=True reads the
+        bad-index flags back (one host sync) and raises IndexError."""
         ids = [int(i) for i in idx]
         need(len(ids) >= 1, "ValBatcher.batch: at least one scan")
         need(all(0 <= i < len(self.scans) for i in ids), "ValBatcher.batch: idx must lie in [0, %d)" % len(self.scans))
         sizes = [self.scans.sizes[i] for i in ids]
-        if sel is None:
+        draws = self.draws if draws is None else draws
+        ids_dev = None
+        if sel is None and draws is not None:
+            with on_stream(self.stream):
+                sel, ids_dev = draw_batch_sel(self.scans, ids, self.m, draws)
+        elif sel is None:
             sel = draw_val_sel(sizes, self.m)
         else:
             sel = np.asarray(sel.cpu() if isinstance(sel, torch.Tensor) else sel)
@@ -81,19 +93,16 @@ class ValBatcher:
             sel = sel.astype(np.int64)
         weak = draw_view_params("train_w", self.kwargs)                   # the `val` list: nothing is drawn
         jobs = [(i, i, weak) for i in range(len(ids))]
-        if self.stream is None:
-            out, bad = self._queue(ids, sizes, sel, jobs)
-        else:
-            with torch.cuda.stream(self.stream):
-                out, bad = self._queue(ids, sizes, sel, jobs)
+        with on_stream(self.stream):
+            out, bad = self._queue(ids, sizes, sel, jobs, ids_dev)
         if check:
             if self.stream is not None:
                 self.stream.synchronize()
             raise_bad_index(bad, ids)
         return out
 
-    def _queue(self, ids, sizes, sel, jobs):
-        s = cloud_sample_batch(self.scans, ids, sel, self.c, check=False)
+    def _queue(self, ids, sizes, sel, jobs, ids_dev=None):
+        s = cloud_sample_batch(self.scans, ids, sel, self.c, check=False, ids_dev=ids_dev)
         v = fixmatch_views(s["raw"], jobs, int(_kw(self.kwargs, "gravity_dim")), len(ids))
         cls = self.scans.cls.index_select(0, s["scan_ids"]).view(-1, 1)
         out = {"pos": v["pos"], "x": v["x"], "y": s["y"], "cls": cls, "center": s["center"], "scale": s["scale"],

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 18
+#define GEOT_ABI_VERSION 19
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -840,6 +840,34 @@ int geot_scan_predict(int b, int c, int n, int n_scans, long long total, const f
 int geot_view_program(int j, int m, int n_rows, int n_out, int n_noise, int n_mask, const float *raw, const void *jobs_host,
                       const void *jobs, const float *noise, const float *mask, float *pos, float *x, float *heights,
                       float *view_center, float *view_scale, void *stream);
+
+/* ---- the batchers' vertex sample drawn on the device (ABI 19) --------------------------------------------------------------------
+ * geot_sample_draw: what the reference draws per item on the host, np.random.choice(N, m, replace=N < m)
+ * (openpoints/dataset/tooth_semi/tooth_dataset.py:134-135, 340-341), for the s slots of a batch in ONE launch -- grid
+ * (ceil(m / 256), s), one thread per output element, no workspace, no host synchronisation.  NOT numpy's stream: a
+ * counter-based generator, so sel depends on (seed, draw id, position) alone and is the same in every process.
+ * The scans are those of geot_cloud_sample_batch: offsets (n_scans + 1) int64 on the device, scan_ids (s) int64 on the device
+ * or NULL (slot i is set scan i); slot i works on n = the size of its scan, read on the device and checked as there
+ * (scan id in [0, n_scans), 0 <= lo < hi <= total, hi - lo <= 2^31 - 1).  sel (s, m) int64, indices LOCAL to the slot's scan:
+ * what geot_cloud_sample_batch takes as sel.  bad (s) int32: 2 for a slot whose table entry is unusable (its row of sel is
+ * zeros), 0 otherwise.  Slot i draws with the draw id d = draw_base + i (mod 2^64); a caller that never hands out an id
+ * twice never repeats a row.
+ * Generator: Philox4x32-10 -- multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, ten rounds,
+ * the key bumped between rounds -- with the key (seed lo, seed hi); counter words are written (c0, c1, c2, c3) below.
+ *   n >= m  (replace=False): sel[i][j] = pi_d(j), pi_d a keyed bijection on [0, 2^b) walked back into [0, n): while the
+ *           value is >= n, pi_d is applied again.  b = max(10, bit length of n - 1), lb = b / 2 (floor), rb = b - lb,
+ *           x = (L << rb) | R; eight rounds r = 0..7: even r  L ^= F(R, r) & (2^lb - 1), odd r  R ^= F(L, r) & (2^rb - 1),
+ *           F(v, r) = word 0 of Philox on (v, r, d lo, d hi).  A row is m distinct indices; from n = 512 on fewer than two
+ *           applications are expected per element, below the 10-bit floor costs up to 1024 / n (it is there for the
+ *           quality of the small permutations, which the natural width does not mix).
+ *   n <  m  (replace=True): sel[i][j] = the high 64 bits of (w0 | w1 << 32) * n, (w0, w1) = words 0 and 1 of Philox on
+ *           (j, 0xFFFFFFFF, d lo, d hi).
+ * Integer arithmetic only, no atomics, no dependence on arrival order: bit-reproducible (tests/_sample_draw_ref.py restates
+ * it in numpy).
+ * 1 <= s <= 65535, m >= 1, n_scans >= 1, total >= 1, offsets, sel and bad not NULL; anything else is hipErrorInvalidValue
+ * before any launch. */
+int geot_sample_draw(int s, int m, int n_scans, long long total, const long long *offsets, const long long *scan_ids,
+                     unsigned long long seed, unsigned long long draw_base, long long *sel, int *bad, void *stream);
 
 #ifdef __cplusplus
 }
