@@ -19,8 +19,8 @@ LIB = os.path.join(HERE, "libgeot_hip.so")
 VARIANTS = {"exact": (0, LIB), "fma": (1, os.path.join(HERE, "libgeot_hip_fma.so")),
             "fma_xy": (2, os.path.join(HERE, "libgeot_hip_fma_xy.so"))}
 
-SOURCES = ["fps.hip", "neighbors.hip", "knn_grid.hip", "gather_group.hip", "tile_scatter.hip", "ntm.hip", "ntm_generic.hip", "sa_mlp.hip", "dataprep.hip", "edgeconv.hip", "bnrelu.hip", "channels_last.hip", "loss.hip", "layernorm.hip", "meters.hip", "seg_metrics.hip", "views.hip", "scan_predict.hip", "view_program.hip", "sample_draw.hip"]
-HEADERS = ["geot_common.h", "ntm_generic.h", "tile_scatter.h", "knn_grid.h", "seg_metrics.h", "views.h", os.path.join(ROOT, "include", "geot_hip.h")]
+SOURCES = ["fps.hip", "neighbors.hip", "knn_grid.hip", "gather_group.hip", "tile_scatter.hip", "ntm.hip", "ntm_generic.hip", "sa_mlp.hip", "dataprep.hip", "edgeconv.hip", "bnrelu.hip", "channels_last.hip", "loss.hip", "layernorm.hip", "meters.hip", "seg_metrics.hip", "views.hip", "scan_predict.hip", "view_program.hip", "sample_draw.hip", "view_draw.hip"]
+HEADERS = ["geot_common.h", "ntm_generic.h", "tile_scatter.h", "knn_grid.h", "seg_metrics.h", "views.h", "philox.h", "view_draw.h", os.path.join(ROOT, "include", "geot_hip.h")]
 
 # -ffp-contract=off: squared distances must be un-contracted IEEE fp32 so that
 # integer outputs match the CPU oracle bit for bit.
@@ -59,6 +59,12 @@ def build(force=False, verbose=False, variant="exact"):
     # lab sweeps (tools/lab/*.sh): GEOT_LAB_KERNELS=tools/lab/kernels takes a file from there when it exists -- the copies that
     # still carry the knock-out / tuning switches the product sources no longer have
     lab_dir = os.environ.get("GEOT_LAB_KERNELS")
+    # a tree that travelled without its object files (they are build products, the library went along): a library newer than
+    # every source and header it is made of needs none of them
+    if (not force and not lab_dir and "GEOT_EXTRA_HIPCC_FLAGS" not in os.environ and os.path.exists(lib_path)
+            and not all(os.path.exists(os.path.join(obj_dir, s.replace(".hip", ".o"))) for s in srcs)
+            and not _stale(lib_path, [os.path.join(CSRC, s) for s in srcs] + hdrs)):
+        return lib_path
     jobs = []
     for s in srcs:
         src = os.path.join(CSRC, s)

@@ -17,33 +17,13 @@
 
 #include "geot_common.h"
 #include "geot_hip.h"
+#include "philox.h"
 
 namespace geot {
 
 typedef unsigned long long u64;
 
-constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u, PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
 constexpr int SD_THREADS = 256, SD_ROUNDS = 8, SD_MIN_BITS = 10;
-
-struct Philox4 {
-    uint32_t w[4];
-};
-
-__device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const u64 p0 = (u64)PHILOX_M0 * c0, p1 = (u64)PHILOX_M1 * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1;
-        c3 = (uint32_t)p0;
-        c0 = n0;
-        c2 = n2;
-        k0 += PHILOX_W0;
-        k1 += PHILOX_W1;
-    }
-    return Philox4{{c0, c1, c2, c3}};
-}
 
 // pi_d on [0, 2^(lb + rb)): x = (L << rb) | R
 __device__ __forceinline__ uint32_t sd_permute(uint32_t x, int rb, uint32_t mask_l, uint32_t mask_r, uint32_t d_lo, uint32_t d_hi,

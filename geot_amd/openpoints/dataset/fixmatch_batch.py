@@ -12,7 +12,8 @@ three small pinned host-to-device copies) and never synchronises with the host. 
 host and are drawn with the reference's statements in the reference's order (draw_view_params), so a caller who seeds numpy
 and torch as the reference's worker did gets the reference's views.  `draws=DeviceDraws(seed)` moves the one expensive draw,
 the np.random.choice of every item, into one more launch (sample_draw.py: geot_sample_draw; not numpy's stream); the view
-parameters, a handful of scalars per item, stay host draws in both modes.
+parameters, a handful of scalars per item, stay host draws unless it is a DeviceDraws(seed, views=True): then one
+geot_view_draw launch (view_draw.py) draws them from the slots' own draw ids and every view runs on geot_view_program.
 
 Three things of the reference a user may not expect, all kept:
 
@@ -29,7 +30,7 @@ import torch
 
 from ... import _lib
 from ...ext._common import call, f32, need, ptr
-from .sample_draw import draw_batch_sel, on_stream
+from .sample_draw import DeviceDraws, ViewDrawHandle, draw_batch_sel, on_stream
 from .view_program import ViewProgram, _axis_rotation, pack_program_jobs, view_program_views
 
 # cfgs/tooth_semi/transformer_finetune_fixmatch_ntm.yaml datatransforms.kwargs, the entries the three lists read.
@@ -43,6 +44,11 @@ TOOTH_VIEW_KWARGS = {
     "angle": [1, 1, 1],
 }
 KINDS = ("train", "train_w", "train_s")
+# the three configured lists as ViewProgram takes them: the same bits as geot_fixmatch_views (tests/test_view_program_gpu.py)
+CONFIGURED_LISTS = {"train": ["PointCloudScaling", "PointCloudCenterAndNormalize"],
+                    "train_w": ["PointCloudCenterAndNormalize"],
+                    "train_s": ["PointCloudScaling_s", "PointCloudCenterAndNormalize", "PointCloudRotation_s",
+                                "PointCloudTranslation_s"]}
 _DEFAULTS = {"scale": [2. / 3, 3. / 2], "scale_s": [2. / 3, 3. / 2], "shift_s": [0.2, 0.2, 0.], "angle_s": [0, 0, 0],
              "gravity_dim": 2}         # the transform classes' own defaults for absent keywords
 
@@ -253,6 +259,10 @@ class FixMatchBatcher:
     A sample_draw.DeviceDraws draws every slot's vertex sample in one geot_sample_draw launch on the batcher's stream
     instead -- one draw id per slot, the labelled slots first -- and np.random.choice is not called; given here it serves
     every batch, given to batch() / draw() that call.  Explicit sel_l / sel_u rows still win.
+    With DeviceDraws(seed, views=True) the view parameters are device draws too (geot_view_draw, from the slot's own draw
+    id: view 0 labelled, 1 weak, 2 strong), no host generator is read, and with transforms=None the three configured lists
+    run as ViewPrograms, which give the bits of geot_fixmatch_views.  draw() then returns a ViewDrawHandle in place of the
+    parameters, batch(params=handle) replays it, and explicit params= still win.
     """
 
     programs = None          # kind -> ViewProgram when `transforms` routes the views through geot_view_program
@@ -269,6 +279,7 @@ class FixMatchBatcher:
         self.scans = DeviceScanSet._merged(labelled, unlabelled)
         self.device = self.scans.device
         self.m, self.c, self.kwargs, self.stream, self.draws = int(num_points), int(num_classes), kwargs, stream, draws
+        self._layouts, self._draw_programs = {}, None      # (B_l, B_u) -> DrawLayout; the lists device view draws run on
         if transforms is not None:
             need(isinstance(transforms, dict) and set(transforms) == set(KINDS),
                  "FixMatchBatcher: transforms is a dict with the lists %s" % (KINDS,))
@@ -301,15 +312,22 @@ class FixMatchBatcher:
             need(sel.shape == (count, self.m) and sel.dtype.kind in "iu", "%s must be (%d, %d) integers" % (what, count, self.m))
             return sel.astype(np.int64)
         sel_l, sel_u = given(sel_l, bl, "sel_l"), given(sel_u, bu, "sel_u")
-        if params is not None:
+        need(draws is None or isinstance(draws, DeviceDraws), "draws must be a DeviceDraws (or None: the reference's host draws)")
+        if isinstance(params, ViewDrawHandle):
+            need(params.count == bl + bu, "params: the handle was drawn for %d slots" % params.count)
+        elif params is not None:
             need(len(params) == bl + bu and all(len(p) == 2 for p in params[bl:]),
                  "params: %d labelled dicts followed by %d (weak, strong) pairs" % (bl, bu))
         ids_dev = None
         on_device = draws is not None and (sel_l is None or sel_u is None)
+        device_views = draws is not None and draws.views and params is None
+        base = draws.take(bl + bu) if on_device or device_views else None           # one id per slot, whatever it serves
+        if device_views:
+            params = ViewDrawHandle(draws.seed, base, bl + bu)
         if on_device:
             ids = [int(i) for i in idx_l] + [self.n_l + int(i) for i in idx_u]
             with on_stream(self.stream):
-                sel, ids_dev = draw_batch_sel(self.scans, ids, self.m, draws, ((0, sel_l), (bl, sel_u)))
+                sel, ids_dev = draw_batch_sel(self.scans, ids, self.m, draws, ((0, sel_l), (bl, sel_u)), base=base)
         else:
             sel = np.empty((bl + bu, self.m), dtype=np.int64)
         drawn = []
@@ -325,7 +343,24 @@ class FixMatchBatcher:
                 sel[slot] = np.random.choice(n, self.m, replace=n < self.m)            # tooth_dataset.py:134-135, 340-341
             if params is None:
                 drawn.append(self._draw_view("train") if lab else (self._draw_view("train_w"), self._draw_view("train_s")))
+        if isinstance(params, ViewDrawHandle):
+            return sel, params, ids_dev
         return sel, (drawn if params is None else list(params)), ids_dev
+
+    def _layout(self, bl, bu):
+        """The templates and plans of a (B_l, B_u) batch, on the device: output rows [0, B_l) labelled, then weak, then
+        strong; a slot's two views draw under the slot's id as views 1 and 2."""
+        from .view_draw import DrawLayout
+        if (bl, bu) not in self._layouts:
+            if self._draw_programs is None:
+                self._draw_programs = self.programs or {k: ViewProgram(CONFIGURED_LISTS[k], self.kwargs) for k in KINDS}
+            pr = self._draw_programs
+            jobs = [(i, i, pr["train"]) for i in range(bl)] + [(bl + i, bl + i, pr["train_w"]) for i in range(bu)]
+            jobs += [(bl + i, bl + bu + i, pr["train_s"]) for i in range(bu)]
+            slots = list(range(bl)) + 2 * list(range(bl, bl + bu))
+            self._layouts[(bl, bu)] = DrawLayout(jobs, bl + bu, bl + 2 * bu, self.m, self.device,
+                                                 [0] * bl + [1] * bu + [2] * bu, slots)
+        return self._layouts[(bl, bu)]
 
     def batch(self, idx_l, idx_u, sel_l=None, sel_u=None, params=None, check=False, draws=None):
         """idx_l / idx_u: scan numbers within the labelled / unlabelled set (what the samplers would yield); sel_* (B, m)
@@ -339,6 +374,14 @@ class FixMatchBatcher:
         need(all(0 <= i < self.n_u for i in idx_u), "idx_u must lie in [0, %d)" % self.n_u)
         sel, params, ids_dev = self._draw(idx_l, idx_u, sel_l, sel_u, params, draws)
         ids = idx_l + [self.n_l + i for i in idx_u]
+        if isinstance(params, ViewDrawHandle):
+            with on_stream(self.stream):
+                out = self._queue(ids, sel, None, bl, bu, self._layout(bl, bu), ids_dev, params)
+            if check:
+                if self.stream is not None:
+                    self.stream.synchronize()
+                raise_bad_index(out[2], ids)
+            return out[0], out[1]
         # view jobs: output rows [0, B_l) labelled, [B_l, B_l + B_u) weak, then strong
         jobs = [(i, i, params[i]) for i in range(bl)]
         jobs += [(bl + i, bl + i, params[bl + i][0]) for i in range(bu)]
@@ -358,9 +401,12 @@ class FixMatchBatcher:
             raise_bad_index(out[2], ids)
         return out[0], out[1]
 
-    def _queue(self, ids, sel, jobs, bl, bu, packed=None, ids_dev=None):
+    def _queue(self, ids, sel, jobs, bl, bu, packed=None, ids_dev=None, handle=None):
         s = cloud_sample_batch(self.scans, ids, sel, self.c, check=False, ids_dev=ids_dev)
-        if packed is None:
+        if handle is not None:      # packed is the DrawLayout: the parameters are drawn where they are used
+            from .view_draw import view_program_draw, view_program_views_drawn
+            v = view_program_views_drawn(s["raw"], packed, view_program_draw(packed, handle.seed, handle.base))
+        elif packed is None:
             v = fixmatch_views(s["raw"], jobs, int(_kw(self.kwargs, "gravity_dim")), bl + 2 * bu)
         else:
             v = view_program_views(s["raw"], jobs, bl + 2 * bu, packed)

@@ -54,10 +54,16 @@ class DeviceDraws:
     has not wrapped (2^64 ids).
 
     take(count) returns the current counter and advances it by count; state() / set_state() save and restore
-    (seed, counter), e.g. in a checkpoint, so that a resumed run continues the sequence."""
+    (seed, counter), e.g. in a checkpoint, so that a resumed run continues the sequence.
 
-    def __init__(self, seed, counter=0):
-        self.seed, self.counter = int(seed) & _MASK64, int(counter) & _MASK64
+    views=True: the batchers draw the transform lists' parameters on the device too (view_draw.py: geot_view_draw) --
+    every view parameter, jitter noise row and per-point colour mask of slot i comes from the SAME draw id as its vertex
+    sample, under counter words of their own, so a batch depends on (seed, counter) alone and no host generator is read.
+    The counter advances as without the flag: one id per slot.  views=False (the default) is the vertex sample alone.
+    state() carries the flag when it is set; set_state() takes either form."""
+
+    def __init__(self, seed, counter=0, views=False):
+        self.seed, self.counter, self.views = int(seed) & _MASK64, int(counter) & _MASK64, bool(views)
 
     def take(self, count):
         count = int(count)
@@ -67,10 +73,25 @@ class DeviceDraws:
         return base
 
     def state(self):
-        return {"seed": self.seed, "counter": self.counter}
+        out = {"seed": self.seed, "counter": self.counter}
+        if self.views:
+            out["views"] = True
+        return out
 
     def set_state(self, state):
         self.seed, self.counter = int(state["seed"]) & _MASK64, int(state["counter"]) & _MASK64
+        self.views = bool(state.get("views", False))
+
+
+class ViewDrawHandle:
+    """What a batcher's draw() returns in place of host parameters under DeviceDraws(views=True): the seed, the first
+    draw id and the number of slots.  batch(params=handle) draws the very same view parameters again (on the device)."""
+
+    def __init__(self, seed, base, count):
+        self.seed, self.base, self.count = int(seed) & _MASK64, int(base) & _MASK64, int(count)
+
+    def __repr__(self):
+        return "ViewDrawHandle(seed=%d, base=%d, count=%d)" % (self.seed, self.base, self.count)
 
 
 def on_stream(stream):
@@ -78,14 +99,15 @@ def on_stream(stream):
     return contextlib.nullcontext() if stream is None else torch.cuda.stream(stream)
 
 
-def draw_batch_sel(scans, ids, m, draws, given=()):
+def draw_batch_sel(scans, ids, m, draws, given=(), base=None):
     """The device half of a batcher's sampling: one id per slot taken from `draws`, one geot_sample_draw launch on the
     current stream -> (sel (S, m) int64 on the device, the scan ids on the device).  given: (first slot, host rows or None)
-    pairs -- rows a caller passed explicitly replace the drawn ones (pinned copy, no synchronisation)."""
+    pairs -- rows a caller passed explicitly replace the drawn ones (pinned copy, no synchronisation).  base: the first
+    draw id when the caller has taken the ids itself."""
     need(isinstance(draws, DeviceDraws), "draws must be a DeviceDraws (or None: the reference's host draws)")
     ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
     ids_dev = torch.from_numpy(ids).pin_memory().to(scans.device, non_blocking=True)
-    sel, _ = sample_draw(scans, ids_dev, m, draws.seed, draws.take(ids.size))
+    sel, _ = sample_draw(scans, ids_dev, m, draws.seed, draws.take(ids.size) if base is None else base)
     for first, rows in given:
         if rows is not None and len(rows):
             host = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).pin_memory()

@@ -9,7 +9,9 @@ A batch is geot_cloud_sample_batch (5 launches), ONE geot_view_program launch fo
 gather of the jaw flags and three small pinned host-to-device copies; it never synchronises with the host.  The list is
 given by the reference's class names and kwargs (view_program.ViewProgram); per item the host draws np.random.choice and
 then the list's draws, in the reference's order.  With `draws=DeviceDraws(seed)` the np.random.choice of every item is one
-geot_sample_draw launch in front of the five instead (sample_draw.py; not numpy's stream); the list's draws stay on the host.
+geot_sample_draw launch in front of the five instead (sample_draw.py; not numpy's stream); the list's draws stay on the host
+unless it is a DeviceDraws(seed, views=True): then ONE geot_view_draw launch (view_draw.py) draws every scale, jitter noise
+row and drop of the batch on the device, from the slots' own draw ids, and nothing but the scan ids is copied from the host.
 
 Kept from the reference: data['x'] IS data['pos'] until a transform rebinds pos.  With the default list x is the SCALED,
 un-centred, un-jittered cloud (PointCloudCenterAndNormalize separates the two), and ChromaticDropGPU -- there are no colour
@@ -20,7 +22,8 @@ import torch
 
 from ...ext._common import need
 from .fixmatch_batch import DeviceScanSet, cloud_sample_batch, raise_bad_index
-from .sample_draw import draw_batch_sel, on_stream
+from .sample_draw import DeviceDraws, ViewDrawHandle, draw_batch_sel, on_stream
+from .view_draw import DrawLayout, view_program_draw, view_program_views_drawn
 from .view_program import ViewProgram, pack_program_jobs, view_program_views
 
 # cfgs/tooth_semi/default.yaml datatransforms: the `train` list and its kwargs (`angle` is read by nothing in this list)
@@ -39,7 +42,9 @@ class SupervisedBatcher:
 
     draws: None keeps the reference's np.random.choice per item on the host; a sample_draw.DeviceDraws draws the vertex
     samples of a batch in one geot_sample_draw launch on the batcher's stream (one draw id per slot) and np.random.choice
-    is not called.  Given here it serves every batch, given to batch() / draw() that call; an explicit sel= still wins."""
+    is not called.  Given here it serves every batch, given to batch() / draw() that call; an explicit sel= still wins.
+    With DeviceDraws(seed, views=True) the list's parameters are device draws too: no host generator is read, draw()
+    returns a ViewDrawHandle in place of the parameters, and batch(params=handle) replays it; an explicit params= wins."""
 
     stream = draws = None    # (the constructor's; None: the current stream, the reference's host draws)
 
@@ -51,6 +56,7 @@ class SupervisedBatcher:
         self.program = ViewProgram(transforms, kwargs)          # NotImplementedError for what the kernel cannot do
         self.scans, self.device = scans, scans.device
         self.m, self.c, self.stream, self.draws = int(num_points), int(num_classes), stream, draws
+        self._layouts = {}          # batch size -> DrawLayout (templates and plans on the device, built once)
         if stream is not None:      # once: the scans are ready; a batch itself depends on nothing the current stream does
             stream.wait_stream(torch.cuda.current_stream(self.device))
 
@@ -72,13 +78,20 @@ class SupervisedBatcher:
             sel = np.asarray(sel.cpu() if isinstance(sel, torch.Tensor) else sel)
             need(sel.shape == (len(idx), self.m) and sel.dtype.kind in "iu", "sel must be (%d, %d) integers" % (len(idx), self.m))
             sel = sel.astype(np.int64)
-        if params is not None:
+        need(draws is None or isinstance(draws, DeviceDraws), "draws must be a DeviceDraws (or None: the reference's host draws)")
+        if isinstance(params, ViewDrawHandle):
+            need(params.count == len(idx), "params: the handle was drawn for %d scans" % params.count)
+        elif params is not None:
             need(len(params) == len(idx), "params: one entry (ViewProgram.draw) per scan")
         ids_dev = None
         on_device = draws is not None and sel is None
+        device_views = draws is not None and draws.views and params is None
+        base = draws.take(len(idx)) if on_device or device_views else None          # one id per slot, whatever it serves
+        if device_views:
+            params = ViewDrawHandle(draws.seed, base, len(idx))
         if on_device:
             with on_stream(self.stream):
-                out, ids_dev = draw_batch_sel(self.scans, idx, self.m, draws)
+                out, ids_dev = draw_batch_sel(self.scans, idx, self.m, draws, base=base)
         else:
             out = np.empty((len(idx), self.m), dtype=np.int64)
         drawn = []
@@ -88,6 +101,8 @@ class SupervisedBatcher:
                 out[slot] = sel[slot] if sel is not None else np.random.choice(n, self.m, replace=n < self.m)
             if params is None:
                 drawn.append(self.program.draw(self.m))
+        if isinstance(params, ViewDrawHandle):
+            return out, params, ids_dev
         return out, (drawn if params is None else list(params)), ids_dev
 
     def batch(self, idx, sel=None, params=None, check=False, draws=None):
@@ -98,19 +113,30 @@ class SupervisedBatcher:
         need(len(idx) >= 1, "SupervisedBatcher.batch: at least one scan")
         need(all(0 <= i < len(self.scans) for i in idx), "SupervisedBatcher.batch: idx must lie in [0, %d)" % len(self.scans))
         sel, params, ids_dev = self._draw(idx, sel, params, draws)
-        jobs = [(i, i, self.program, params[i]) for i in range(len(idx))]
-        packed = pack_program_jobs(jobs, len(idx), len(idx), self.m)       # checks the parameters before anything is queued
         with on_stream(self.stream):
-            data, bad = self._queue(idx, sel, jobs, packed, ids_dev)
+            if isinstance(params, ViewDrawHandle):
+                data, bad = self._queue(idx, sel, None, self._layout(len(idx)), ids_dev, params)
+            else:
+                jobs = [(i, i, self.program, params[i]) for i in range(len(idx))]
+                packed = pack_program_jobs(jobs, len(idx), len(idx), self.m)   # checks the parameters before anything is queued
+                data, bad = self._queue(idx, sel, jobs, packed, ids_dev)
         if check:
             if self.stream is not None:
                 self.stream.synchronize()
             raise_bad_index(bad, idx)
         return data
 
-    def _queue(self, idx, sel, jobs, packed, ids_dev=None):
+    def _layout(self, b):
+        if b not in self._layouts:
+            self._layouts[b] = DrawLayout([(i, i, self.program) for i in range(b)], b, b, self.m, self.device)
+        return self._layouts[b]
+
+    def _queue(self, idx, sel, jobs, packed, ids_dev=None, handle=None):
         s = cloud_sample_batch(self.scans, idx, sel, self.c, check=False, ids_dev=ids_dev)
-        v = view_program_views(s["raw"], jobs, len(idx), packed)
+        if handle is not None:      # packed is the DrawLayout: the parameters are drawn where they are used
+            v = view_program_views_drawn(s["raw"], packed, view_program_draw(packed, handle.seed, handle.base))
+        else:
+            v = view_program_views(s["raw"], jobs, len(idx), packed)
         data = {"pos": v["pos"], "x": v["x"], "y": s["y"], "cls": self.scans.cls.index_select(0, s["scan_ids"]).view(-1, 1),
                 "class_weights": s["class_weights"]}
         if v["heights"] is not None:

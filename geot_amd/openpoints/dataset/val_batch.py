@@ -53,7 +53,8 @@ class ValBatcher:
 
     draws: None keeps the reference's np.random.choice per item on the host (draw_val_sel); a sample_draw.DeviceDraws draws
     the vertex samples of a batch in one geot_sample_draw launch on the batcher's stream (one draw id per slot) and
-    np.random.choice is not called.  Given here it serves every batch, given to batch() that call; sel= still wins."""
+    np.random.choice is not called.  Given here it serves every batch, given to batch() that call; sel= still wins.
+    DeviceDraws(seed, views=True) is accepted and changes nothing: the `val` list draws no view parameter."""
 
     def __init__(self, scans, num_points, num_classes=17, kwargs=TOOTH_VIEW_KWARGS, stream=None, draws=None):
         need(isinstance(scans, DeviceScanSet), "ValBatcher: scans must be a DeviceScanSet")

@@ -29,7 +29,8 @@ alone -- so x is written exactly ONCE, by a STORE_X op in front of the separatin
 into that store.  A list that never rebinds has x = the final pos: the chromatic transforms then act on pos at their place
 in the list and STORE_X is the last op.
 
-The random numbers stay on the host.  draw() consumes the GLOBAL torch-CPU, numpy and python `random` generators exactly as
+By default the random numbers stay on the host (view_draw.py draws them on the device instead: compile_fixed below is the
+layout it fills in).  draw() consumes the GLOBAL torch-CPU, numpy and python `random` generators exactly as
 the classes do; noise and per-point masks are finished on the host with torch's own randn_like / rand, multiply and clamp_
 and travel as (m, 3) / (m,) fp32 rows, together with the job records, through one pinned staging buffer per launch.
 """
@@ -95,6 +96,7 @@ class _Step:
             self.noise_std, self.noise_clip = kw("jitter_sigma" + sfx, 0.01), kw("jitter_clip" + sfx, 0.05)
         if base == "PointCloudRotation":
             self.angle = np.array(kw("angle" + sfx, [0, 0, 0])) * np.pi
+            self.angle_pi = np.array(kw("angle" + sfx, [0, 0, 0]), dtype=np.float32)     # the bound in units of pi (view_draw)
             need(self.angle.shape == (3,), "%s: angle has three entries" % name)
         if base in ("PointCloudCenterAndNormalize", "PointCloudXYZAlign"):
             self.gravity_dim = int(kw("gravity_dim", 2))
@@ -276,6 +278,103 @@ class ViewProgram:
         need(len(ops) <= _lib.VIEW_MAX_OPS, "ViewProgram: %d ops, the kernel takes %d" % (len(ops), _lib.VIEW_MAX_OPS))
         return ops, noise, masks
 
+    def compile_fixed(self, params=None, m=None):
+        """The list in the FIXED layout geot_view_draw works on (view_draw.py): one op sequence for every draw, so that
+        the device can fill it in.  Against compile(): every RandomHorizontalFlip is two ops (FLIP, or SCALE by 1 when that
+        axis is not flipped), a ChromaticDropGPU on pos is one op (ZERO, or SCALE by 1), and when a per-point mask can reach
+        x the combined mask row exists whether or not a drop overrides it -- SCALE by (1, 1, 1) is a bit-exact no-op, so the
+        views equal compile()'s.  params None: the TEMPLATE -- the worst case (both flips, the zeroing, the masked store)
+        with every drawn float neutral -- else the record a view with these draws has.
+        -> dict(ops, n_noise, n_mask, noise, masks, store_at, steps); steps: the draw plan, tuples (kind, op index or -1,
+        position in the list, flags, constants) in the layout of include/geot_hip.h geot_view_draw."""
+        tmpl = params is None
+        if not tmpl:
+            need(len(params) == len(self.steps), "ViewProgram: parameters are a list with one dict per transform")
+        one, zero3 = np.ones(3, np.float32), np.zeros(3, np.float32)
+        ops, steps, noise, masks, x_masks = [], [], [], [], []
+        aliased, store_at, x_zero, n_noise, n_mask = True, -1, False, 0, 0
+
+        def scale_step(step, op, form):
+            flags = (1 if step.anisotropic else 0) | sum(2 << k for k in range(3) if step.scale_xyz[k]) | (form << 4)
+            mirror = step.mirror.to(torch.float32).numpy()
+            return (1, op, pos, flags, [step.scale_min, np.float32(step.scale_max - step.scale_min)] + list(mirror))
+        for pos, step in enumerate(self.steps):
+            base, p = step.base, (None if tmpl else params[pos])
+            if step.rebinds and aliased:
+                store_at, aliased = len(ops), False
+                ops.append(None)
+            at = len(ops)
+            if base == "PointCloudScaling":
+                ops.append((SCALE, 0, one if tmpl else _vec3(p, "scale", step.name)))
+                steps.append(scale_step(step, at, 1 if step.use_mirroring else 0))
+            elif base == "PointCloudCenterAndNormalize":
+                ops.append((CENTER_NORM, (1 if step.centering else 0) | (2 if step.normalize else 0) | (step.gravity_dim << 2), []))
+            elif base == "PointCloudXYZAlign":
+                ops.append((XYZ_ALIGN, step.gravity_dim, []))
+            elif base == "PointCloudTranslation":
+                ops.append((TRANSLATE, 0, zero3 if tmpl else _vec3(p, "t", step.name)))
+                steps.append((2, at, pos, 0, list(step.shift.numpy())))
+            elif base == "PointCloudScaleAndTranslate":
+                ops.append((SCALE_TRANSLATE, 0, np.concatenate([one, zero3]) if tmpl else
+                            np.concatenate([_vec3(p, "scale", step.name), _vec3(p, "t", step.name)])))
+                steps.append(scale_step(step, at, 1 if step.use_mirroring else 0))
+                steps.append((2, at, pos, 1, list(step.shift.numpy())))
+            elif base in ("PointCloudJitter", "PointCloudScaleAndJitter"):
+                if base == "PointCloudJitter":
+                    ops.append((JITTER, n_noise, []))
+                else:
+                    ops.append((SCALE_JITTER, n_noise, one if tmpl else _vec3(p, "scale", step.name)))
+                    steps.append(scale_step(step, at, 2))
+                steps.append((3, at, pos, 0, [step.noise_std, step.noise_clip]))
+                n_noise += 1
+                if not tmpl:
+                    noise.append(np.ascontiguousarray(p["noise"], dtype=np.float32))
+            elif base == "PointCloudRotation":
+                ops.append((ROTATE, 0, np.eye(3, dtype=np.float32).reshape(9) if tmpl else
+                            np.asarray(p["R"], dtype=np.float32).reshape(9)))
+                steps.append((4, at, pos, 0, list(step.angle_pi)))
+            elif base == "RandomHorizontalFlip":
+                for ax in step.horz_axes:
+                    ops.append((FLIP, int(ax), []) if tmpl or ax in p["flip"] else (SCALE, 0, one))
+                steps.append((5, at, pos, 0, [step.aug_prob]))
+            elif base == "ChromaticDropGPU":
+                if aliased:
+                    ops.append((ZERO, 0, []) if tmpl or p["drop"] else (SCALE, 0, one))
+                    steps.append((6, at, pos, 0, [step.color_drop]))
+                else:
+                    x_zero = x_zero or (not tmpl and bool(p["drop"]))
+                    steps.append((6, -1, pos, 0, [step.color_drop]))
+            elif base == "ChromaticPerDropGPU":
+                if aliased:
+                    ops.append((MASK, n_mask, []))
+                    n_mask += 1
+                    if not tmpl:
+                        masks.append(np.ascontiguousarray(p["mask"], dtype=np.float32))
+                else:
+                    at = -1
+                    if not tmpl:
+                        x_masks.append(np.ascontiguousarray(p["mask"], dtype=np.float32))
+                steps.append((7, at, pos, 0, [step.color_drop]))
+        masked_x = any(s[0] == 7 and s[1] == -1 for s in steps)
+        if aliased:
+            store_at = len(ops)
+            ops.append((STORE_X, 0, []))
+        else:
+            ops[store_at] = (STORE_X, 1 if x_zero else (2 | (n_mask << 2)) if masked_x else 0, [])
+        if masked_x:
+            n_mask += 1
+            if not tmpl:
+                combined = x_masks[0]
+                for extra in x_masks[1:]:
+                    combined = combined * extra
+                masks.append(combined)
+        need(len(ops) <= _lib.VIEW_MAX_OPS, "ViewProgram: %d ops, the kernel takes %d" % (len(ops), _lib.VIEW_MAX_OPS))
+        need(len(steps) <= _lib.VIEW_DRAW_MAX_STEPS, "ViewProgram: the list draws %d quantities, geot_view_draw takes %d"
+             % (len(steps), _lib.VIEW_DRAW_MAX_STEPS))
+        need(len(self.steps) <= 4096, "ViewProgram: geot_view_draw takes lists of up to 4096 transforms")
+        return {"ops": ops, "n_noise": n_noise, "n_mask": n_mask, "noise": noise, "masks": masks,
+                "store_at": -1 if aliased else store_at, "steps": steps}
+
     def pack(self, jobs, n_rows, n_out, m):
         """jobs: sequence of (source row, output row, params) of THIS program -> pack_program_jobs."""
         need(all(len(job) == 3 for job in jobs), "ViewProgram.pack: a job is (source row, output row, params)")
@@ -309,6 +408,52 @@ def pack_program_jobs(jobs, n_rows, n_out, m):
     noise = np.stack(noise) if noise else np.zeros((0, m, 3), np.float32)
     masks = np.stack(masks) if masks else np.zeros((0, m), np.float32)
     return table, noise, masks
+
+
+def _write_ops(table, j, ops):
+    as_f = table.view(np.float32)
+    for o, (kind, arg, floats) in enumerate(ops):
+        at = _HEADER_WORDS + o * _OP_WORDS
+        table[j, at], table[j, at + 1] = kind, arg
+        as_f[j, at + 2:at + 2 + len(floats)] = floats
+
+
+def pack_fixed_jobs(jobs, n_rows, n_out, m, views=None, slots=None):
+    """jobs: sequence of (source row, output row, program, params or None) in ViewProgram.compile_fixed's layout ->
+    (table (J, VIEW_PROGRAM_JOB_WORDS) int32, plans (J, VIEW_DRAW_PLAN_WORDS) int32, noise (n_noise, m, 3), mask (n_mask, m)
+    float32): with params None the template table geot_view_draw starts from (noise and mask rows zero), else the records and
+    rows these draws give.  views / slots: per job the view of its slot (0 only or labelled, 1 weak, 2 strong) and the slot
+    whose draw id it uses; default 0 and the job's number."""
+    need(len(jobs) >= 1, "view_draw: at least one job")
+    m = int(m)
+    need(m >= 1, "view_draw: m >= 1")
+    table = np.zeros((len(jobs), _lib.VIEW_PROGRAM_JOB_WORDS), dtype=np.int32)
+    plans = np.zeros((len(jobs), _lib.VIEW_DRAW_PLAN_WORDS), dtype=np.int32)
+    plans_f = plans.view(np.float32)
+    noise, masks, n_noise, n_mask, seen = [], [], 0, 0, set()
+    for j, job in enumerate(jobs):
+        need(len(job) == 4 and isinstance(job[2], ViewProgram), "view_draw: a job is (source row, output row, program, params)")
+        src, dst = int(job[0]), int(job[1])
+        need(0 <= src < n_rows, "view_draw: job %d reads row %d of %d" % (j, src, n_rows))
+        need(0 <= dst < n_out and dst not in seen, "view_draw: job %d writes row %d (of %d; each row once)" % (j, dst, n_out))
+        seen.add(dst)
+        fixed = job[2].compile_fixed(job[3], m)
+        table[j, :5] = src, dst, len(fixed["ops"]), n_noise, n_mask
+        _write_ops(table, j, fixed["ops"])
+        view, slot = (0 if views is None else int(views[j])), (j if slots is None else int(slots[j]))
+        need(view in (0, 1, 2) and 0 <= slot < 2 ** 31, "view_draw: a view is 0, 1 or 2, a slot a non-negative int")
+        plans[j, :4] = view, slot, len(fixed["steps"]), fixed["store_at"]
+        for k, (kind, op, pos, flags, consts) in enumerate(fixed["steps"]):
+            at = 8 + 12 * k
+            plans[j, at:at + 4] = kind, op, pos, flags
+            plans_f[j, at + 4:at + 4 + len(consts)] = np.asarray(consts, dtype=np.float32)
+        n_noise += fixed["n_noise"]
+        n_mask += fixed["n_mask"]
+        noise += fixed["noise"] if job[3] is not None else [np.zeros((m, 3), np.float32)] * fixed["n_noise"]
+        masks += fixed["masks"] if job[3] is not None else [np.zeros(m, np.float32)] * fixed["n_mask"]
+    noise = np.stack(noise) if noise else np.zeros((0, m, 3), np.float32)
+    masks = np.stack(masks) if masks else np.zeros((0, m), np.float32)
+    return table, plans, noise, masks
 
 
 def view_program_views(raw, jobs, n_out=None, packed=None):

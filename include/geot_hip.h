@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 19
+#define GEOT_ABI_VERSION 20
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -868,6 +868,60 @@ int geot_view_program(int j, int m, int n_rows, int n_out, int n_noise, int n_ma
  * before any launch. */
 int geot_sample_draw(int s, int m, int n_scans, long long total, const long long *offsets, const long long *scan_ids,
                      unsigned long long seed, unsigned long long draw_base, long long *sel, int *bad, void *stream);
+
+/* ---- the batchers' view parameters, jitter noise and colour masks drawn on the device (ABI 20) -----------------------------------
+ * geot_view_draw: what ViewProgram.draw draws per item on the host (a handful of scalars per view; an (m, 3) normal row per
+ * jittering transform and an (m,) uniform row per ChromaticPerDropGPU) for the j jobs of a batch in ONE launch in front of
+ * geot_view_program -- grid (ceil(m / 256), j), no workspace, no atomics, no host synchronisation.  It writes jobs (j
+ * records of GEOT_VIEW_PROGRAM_JOB_WORDS words), noise (n_noise, m, 3) and mask (n_mask, m), all on the device and all in
+ * geot_view_program's layout, from two tables the host compiles once per (list, batch layout), with nothing random in them,
+ * each once on the device (tmpl, plans: what the kernel reads) and once on the host (tmpl_host, plans_host, the same bytes:
+ * what this entry point checks):
+ *   tmpl   j geot_view_program job records whose op lists are the lists' WORST case -- every RandomHorizontalFlip is two
+ *          FLIP ops, every ChromaticDropGPU acting on pos a ZERO op, STORE_X in mode 2 when a per-point mask can reach x --
+ *          with every drawn float at its neutral value.  Hand the same table to geot_view_program as jobs_host.
+ *   plans  j records of GEOT_VIEW_DRAW_PLAN_WORDS words: [0] int view of the slot (0 only / labelled, 1 weak, 2 strong)
+ *          [1] int slot: the job draws with the draw id d = draw_base + slot (mod 2^64)    [2] int step count, 0 ..
+ *          GEOT_VIEW_DRAW_MAX_STEPS    [3] int index of the template's STORE_X op the x-side colour drops act on, or -1
+ *          [4..7] reserved    then GEOT_VIEW_DRAW_MAX_STEPS steps of 12 words: int kind, int op (index into the template's
+ *          ops, -1: the STORE_X op of [3]), int pos (place of the transform in its list, < 4096), int flags, float c[8].
+ * A job's record is its template with the drawn fields overwritten.  Step kinds, u = a uniform, every statement ONE correctly
+ * rounded fp32 operation, left to right:
+ *   1 SCALE    op: SCALE / SCALE_TRANSLATE / SCALE_JITTER, f[0..2].  flags bit 0 anisotropic (unset: ONE draw serves the
+ *              three), bits 1-3 scale_xyz, bits 4-5 mirror form.  v_k = u_k * c[1] + c[0] (c[0] = lo, c[1] = hi - lo);
+ *              form 1: v_k *= (u'_k > c[2+k] ? 1 : -1); form 2: v_k *= (u'_k > 0.5 ? 1 : -1) * c[2+k] + (1 - c[2+k]);
+ *              scale_xyz bit k unset: v_k = 1 (without anisotropy bit 0 decides for all three, as scale[0] = 1 does)
+ *   2 SHIFT    op: TRANSLATE f[0..2] or SCALE_TRANSLATE f[3..5].  u_k * c[k], or with flags bit 0 ((u_k - 0.5) * 2) * c[k]
+ *   3 NOISE    op: JITTER / SCALE_JITTER; fills that op's noise row.  Per point ONE generator call (w0..w3): r = sqrt(-2 ln
+ *              u1), u1 = ((w >> 8) + 1) 2^-24; z = (r(w0) cos(w1), r(w0) sin(w1), r(w2) cos(w3)) with the angle u(w) turns;
+ *              noise = min(max(z * c[0], -c[1]), c[1])  (c[0] = sigma, c[1] = clip)
+ *   4 ROTATE   op: ROTATE f[0..8].  Per axis k: t = (c[k] * (u_k * 2 - 1)) * 0.5 turns (c = the angle bound in units of pi,
+ *              |c[k]| <= 1024), the axis rotation by t; the three in the order number ((w3 >> 8) * 6) >> 24 of the six
+ *              lexicographic orders; R = (A B) C, every entry (a0 b0 + a1 b1) + a2 b2; -sin is 0 - sin
+ *   5 FLIP     ops op and op + 1, both FLIP.  any = u0 < c[0]; FLIP op stays when any and u1 < 0.5, FLIP op + 1 when any
+ *              and u2 < 0.5; otherwise the op becomes SCALE by (1, 1, 1)
+ *   6 DROP     u < c[0].  op a ZERO op: it becomes SCALE by (1, 1, 1) when NOT drawn; op -1: STORE_X's arg becomes 1 when drawn
+ *   7 PERMASK  per point u > c[0] ? 1 : 0 into the mask row of op (a MASK op) or, op -1, of the STORE_X op (mode 2).  Steps
+ *              that name one row write their product.
+ * ln is the exponent of the 24-bit integer times fp32 ln 2 plus 2 atanh((f - 1) / (f + 1)) to the 11th power on the mantissa
+ * f in [sqrt(1/2), sqrt 2); cos / sin reduce 4 t to the nearest integer exactly and use Taylor polynomials of degree 9 / 10
+ * on [-pi/4, pi/4]: fp32 add, multiply, divide and square root only, NO math-library call, so the results do not change
+ * with the toolchain and tests/_view_draw_ref.py reproduces every bit in numpy float32.  t = 0 gives cos 1, sin +0
+ * exactly: an angle bound of 0 is R = I.
+ * Generator: Philox4x32-10 as in geot_sample_draw, key (seed lo, seed hi), counter (element, tag, d lo, d hi); element = the
+ * point for kinds 3 and 7, 0 otherwise; tag = 0x40000000 | view << 24 | pos << 8 | quantity with quantity 0 scale, 1 mirror,
+ * 2 shift, 3 rotate, 4 flip, 5 drop, 6 noise, 7 per-point mask.  Bit 30 set and bit 31 clear: no tag equals a second counter
+ * word of geot_sample_draw (0..7, 0xFFFFFFFF), so a slot's views share the slot's draw id with its vertex sample.
+ * 1 <= j <= 65535, 1 <= m <= 357 913 941, n_noise >= 0, n_mask >= 0, no NULL pointer (noise / mask may be NULL when their
+ * count is 0); every plan is checked against its template -- view, step count, kinds, pos, every op index in range and of a
+ * kind the step may write, every noise and mask row inside the buffers, angle bounds finite -- anything else is
+ * hipErrorInvalidValue before any launch.  The kernel repeats the test on the device copies; a job that fails it there
+ * writes nothing. */
+#define GEOT_VIEW_DRAW_MAX_STEPS 24
+#define GEOT_VIEW_DRAW_PLAN_WORDS (8 + 12 * GEOT_VIEW_DRAW_MAX_STEPS)
+int geot_view_draw(int j, int m, int n_noise, int n_mask, const void *tmpl_host, const void *plans_host, const void *tmpl,
+                   const void *plans, unsigned long long seed, unsigned long long draw_base, void *jobs, float *noise,
+                   float *mask, void *stream);
 
 #ifdef __cplusplus
 }
