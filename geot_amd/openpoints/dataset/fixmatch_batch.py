@@ -30,8 +30,10 @@ import torch
 
 from ... import _lib
 from ...ext._common import call, f32, need, ptr
-from .sample_draw import DeviceDraws, ViewDrawHandle, draw_batch_sel, on_stream
-from .view_program import ViewProgram, _axis_rotation, pack_program_jobs, view_program_views
+from .batcher import Batcher
+from .sample_draw import DeviceDraws, ViewDrawHandle, draw_batch_sel, on_stream  # noqa: F401  (importable from here, as ever)
+from .scan_set import DeviceScanSet, _to_device, cloud_sample_batch, raise_bad_index  # noqa: F401
+from .view_program import ViewProgram, _axis_rotation, pack_program_jobs, view_program_views  # noqa: F401
 
 # cfgs/tooth_semi/transformer_finetune_fixmatch_ntm.yaml datatransforms.kwargs, the entries the three lists read.
 # `angle` is what the file says (its second entry; a yaml loader keeps the last duplicate) and NOTHING reads it:
@@ -119,10 +121,6 @@ def pack_view_jobs(jobs, n_rows, n_out):
     return table
 
 
-def _to_device(host, dev):
-    """Pinned staging + non-blocking copy on the current stream: no synchronisation (validation.SegMetrics._offsets)."""
-    return torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
-
 
 def fixmatch_views(raw, jobs, gravity_dim=1, n_out=None):
     """raw (S, m, 3) CUDA float32; jobs: sequence of (source row, output row, params) with params from draw_view_params (or
@@ -147,92 +145,8 @@ def fixmatch_views(raw, jobs, gravity_dim=1, n_out=None):
     return out
 
 
-class DeviceScanSet:
-    """The scans of one split on one device, built once: vertices concatenated (sum N, 3) float32, labels (sum N,) int32,
-    offsets (n + 1,) int64, the jaw flag of every scan `cls` (n,) int64 (tooth_dataset.py:97, 0 = lower; default 0).
-    scans / labels: sequences of (N_i, 3) / (N_i,) arrays or tensors."""
 
-    def __init__(self, scans, labels, cls=None, device=None):
-        need(len(scans) >= 1 and len(scans) == len(labels), "DeviceScanSet: one label array per scan, at least one scan")
-        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        need(dev.type == "cuda", "DeviceScanSet: CPU not supported (the scans must live on the GPU)")
-        pts = [torch.as_tensor(p) for p in scans]
-        labs = [torch.as_tensor(l) for l in labels]
-        for p, l in zip(pts, labs):
-            need(p.dim() == 2 and p.shape[1] == 3 and p.shape[0] >= 1, "DeviceScanSet: a scan is (N>=1, 3)")
-            need(l.dim() == 1 and l.shape[0] == p.shape[0] and not l.is_floating_point(),
-                 "DeviceScanSet: one integer label per vertex")
-        self.sizes = [int(p.shape[0]) for p in pts]
-        cls = [0] * len(pts) if cls is None else [int(c) for c in cls]
-        need(len(cls) == len(pts), "DeviceScanSet: one cls entry per scan")
-        self.device = dev
-        self.points = torch.cat([p.to(dev, torch.float32) for p in pts]).contiguous()
-        self.labels = torch.cat([l.to(dev, torch.int32) for l in labs]).contiguous()
-        self.offsets = torch.tensor(np.concatenate([[0], np.cumsum(self.sizes, dtype=np.int64)]), dtype=torch.int64).to(dev)
-        self.cls = torch.tensor(cls, dtype=torch.int64).to(dev)
-
-    def __len__(self):
-        return len(self.sizes)
-
-    @classmethod
-    def _merged(cls, a, b):
-        """a's scans followed by b's, as one set (the batcher samples both splits in one sequence of launches)."""
-        need(a.device == b.device, "DeviceScanSet: both sets must be on one device (%s vs %s)" % (a.device, b.device))
-        out = cls.__new__(cls)
-        out.device, out.sizes = a.device, a.sizes + b.sizes
-        out.points, out.labels = torch.cat([a.points, b.points]), torch.cat([a.labels, b.labels])
-        out.offsets = torch.cat([a.offsets, b.offsets[1:] + a.offsets[-1:]])
-        out.cls = torch.cat([a.cls, b.cls])
-        return out
-
-
-def cloud_sample_batch(scans, scan_ids, sel, num_classes=17, check=True, ids_dev=None):
-    """geot_cloud_sample_batch: scans a DeviceScanSet; scan_ids: the set scan of every batch slot (S ints, host); sel (S, m)
-    int64 vertex indices local to each slot's scan (numpy or tensor) -> dict(raw (S, m, 3), y (S, m) int64, class_weights
-    (S, num_classes), center (S, 3), scale (S,), bad (S,) int32).  Slot by slot bit-identical to prepare_sample on that scan
-    alone.  check=True reads `bad` back (one host sync) and raises IndexError for an index outside its scan.  ids_dev:
-    scan_ids as an (S,) int64 tensor already on the device (the batchers upload them once for the draw and the sampling)."""
-    need(isinstance(scans, DeviceScanSet), "cloud_sample_batch: scans must be a DeviceScanSet")
-    ids = np.asarray(scan_ids, dtype=np.int64).reshape(-1)
-    need(ids.size >= 1 and ids.min() >= 0 and ids.max() < len(scans), "cloud_sample_batch: scan ids must lie in [0, %d)" % len(scans))
-    dev = scans.device
-    if isinstance(sel, torch.Tensor):
-        need(sel.dtype == torch.int64 and sel.dim() == 2, "sel must be (S, m) int64")
-        sel_dev = sel.to(dev).contiguous()
-    else:
-        sel = np.ascontiguousarray(sel)
-        need(sel.dtype == np.int64 and sel.ndim == 2, "sel must be (S, m) int64")
-        sel_dev = _to_device(sel, dev)
-    s, m = sel_dev.shape
-    need(s == ids.size and m >= 1, "sel must have one row of m >= 1 indices per scan id")
-    need(1 <= num_classes <= 4096, "num_classes must be in [1, 4096]")
-    if ids_dev is None:
-        ids_dev = _to_device(ids, dev)
-    out = {"raw": torch.empty((s, m, 3), dtype=torch.float32, device=dev),
-           "y": torch.empty((s, m), dtype=torch.int64, device=dev),
-           "class_weights": torch.empty((s, num_classes), dtype=torch.float32, device=dev),
-           "center": torch.empty((s, 3), dtype=torch.float32, device=dev),
-           "scale": torch.empty(s, dtype=torch.float32, device=dev),
-           "bad": torch.empty(s, dtype=torch.int32, device=dev)}
-    nbytes = int(_lib.load().geot_cloud_sample_batch_ws_bytes(s, int(num_classes)))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    call("geot_cloud_sample_batch", dev, s, m, int(num_classes), len(scans), int(scans.points.shape[0]), ptr(scans.points),
-         ptr(scans.labels), ptr(scans.offsets), ptr(ids_dev), ptr(sel_dev), ptr(out["raw"]), ptr(out["y"]),
-         ptr(out["class_weights"]), ptr(out["center"]), ptr(out["scale"]), ptr(out["bad"]), ptr(ws), nbytes)
-    out["scan_ids"] = ids_dev
-    if check:
-        raise_bad_index(out["bad"], ids)
-    return out
-
-
-def raise_bad_index(bad, ids):
-    flags = bad.cpu().numpy()            # the one host synchronisation of check=True
-    if flags.any():
-        slot = int(np.flatnonzero(flags)[0])
-        raise IndexError("batch slot %d (scan %d): selected_idxs holds an index outside the scan" % (slot, int(ids[slot])))
-
-
-class FixMatchBatcher:
+class FixMatchBatcher(Batcher):
     """Replaces the reference's two training DataLoaders: `batch(idx_l, idx_u)` returns (data, data_u) with the keys,
     shapes and dtypes train_one_epoch works on after its `.cuda()` and `transpose` lines,
 
@@ -248,7 +162,9 @@ class FixMatchBatcher:
     transforms: None keeps the three configured lists on geot_fixmatch_views.  A dict {"train": [...], "train_w": [...],
     "train_s": [...]} of the reference's transform class names routes every view through geot_view_program instead
     (view_program.ViewProgram; each class reads `kwargs`); params are then ViewProgram.draw results.  The deep-copy quirk
-    (3) does not depend on the lists.
+    (3) does not depend on the lists.  Given the configured lists the program kernel produces the hard-wired kernel's bits
+    but takes 1.7 times its time at m = 16 000 and 24 000 and 2.1 times at m = 30 000 (a whole batch: 1.2 times;
+    profiles/view_program_timing.txt), which is why None keeps the hard-wired kernel.
 
     stream: queue every batch on that side stream.  A batch depends on the scans alone, so it does NOT wait for what the
     current stream has queued: it runs beside the iteration in flight.  Call `batcher.join(data, data_u)` before the
@@ -266,28 +182,21 @@ class FixMatchBatcher:
     """
 
     programs = None          # kind -> ViewProgram when `transforms` routes the views through geot_view_program
-    stream = draws = None    # (the constructor's; None: the current stream, the reference's host draws)
 
     def __init__(self, labelled, unlabelled, num_points, num_classes=17, kwargs=TOOTH_VIEW_KWARGS, stream=None, transforms=None,
                  draws=None):
         need(isinstance(labelled, DeviceScanSet) and isinstance(unlabelled, DeviceScanSet),
              "FixMatchBatcher: labelled and unlabelled must be DeviceScanSets")
-        need(int(num_points) >= 1, "FixMatchBatcher: num_points >= 1")
-        need(1 <= int(num_classes) <= 4096, "FixMatchBatcher: num_classes must be in [1, 4096]")
         need(int(_kw(kwargs, "gravity_dim")) in (0, 1, 2), "FixMatchBatcher: gravity_dim must be 0, 1 or 2")
-        self.n_l, self.n_u = len(labelled), len(unlabelled)
-        self.scans = DeviceScanSet._merged(labelled, unlabelled)
-        self.device = self.scans.device
-        self.m, self.c, self.kwargs, self.stream, self.draws = int(num_points), int(num_classes), kwargs, stream, draws
-        self._layouts, self._draw_programs = {}, None      # (B_l, B_u) -> DrawLayout; the lists device view draws run on
+        self.n_l, self.n_u, self.kwargs = len(labelled), len(unlabelled), kwargs
         if transforms is not None:
             need(isinstance(transforms, dict) and set(transforms) == set(KINDS),
                  "FixMatchBatcher: transforms is a dict with the lists %s" % (KINDS,))
             self.programs = {kind: ViewProgram(transforms[kind], kwargs) for kind in KINDS}
             need(all(p.has_heights for p in self.programs.values()),
                  "FixMatchBatcher: every list needs a PointCloudCenterAndNormalize (heights is a feature key)")
-        if stream is not None:      # once: the scans are ready; a batch itself depends on nothing the current stream does
-            stream.wait_stream(torch.cuda.current_stream(self.device))
+        self._draw_programs = self.programs      # the lists device view draws run on (None: built when first needed)
+        super().__init__(DeviceScanSet._merged(labelled, unlabelled), num_points, num_classes, stream, draws)
 
     def _draw_view(self, kind):
         return draw_view_params(kind, self.kwargs) if self.programs is None else self.programs[kind].draw(self.m)
@@ -298,69 +207,43 @@ class FixMatchBatcher:
         "train_w" (draws nothing) and "train_s".  params: list of B_l dicts followed by B_u (weak, strong) pairs.
         With draws (a DeviceDraws; default: the constructor's) the rows not given are drawn by geot_sample_draw, queued on
         the batcher's stream, and sel is that (B_l + B_u, m) int64 DEVICE tensor; only the view parameters are host draws."""
-        return self._draw(idx_l, idx_u, sel_l, sel_u, params, draws)[:2]
+        return self._draw_slots(idx_l, idx_u, sel_l, sel_u, params, draws)[:2]
 
-    def _draw(self, idx_l, idx_u, sel_l, sel_u, params, draws):
+    def _draw_slots(self, idx_l, idx_u, sel_l, sel_u, params, draws):
         """draw() and, third, the scan ids on the device when the device drew (None otherwise)."""
         bl, bu = len(idx_l), len(idx_u)
-        draws = self.draws if draws is None else draws
-
-        def given(sel, count, what):
-            if sel is None:
-                return None
-            sel = np.asarray(sel.cpu() if isinstance(sel, torch.Tensor) else sel)
-            need(sel.shape == (count, self.m) and sel.dtype.kind in "iu", "%s must be (%d, %d) integers" % (what, count, self.m))
-            return sel.astype(np.int64)
-        sel_l, sel_u = given(sel_l, bl, "sel_l"), given(sel_u, bu, "sel_u")
-        need(draws is None or isinstance(draws, DeviceDraws), "draws must be a DeviceDraws (or None: the reference's host draws)")
-        if isinstance(params, ViewDrawHandle):
-            need(params.count == bl + bu, "params: the handle was drawn for %d slots" % params.count)
-        elif params is not None:
+        if params is not None and not isinstance(params, ViewDrawHandle):
             need(len(params) == bl + bu and all(len(p) == 2 for p in params[bl:]),
                  "params: %d labelled dicts followed by %d (weak, strong) pairs" % (bl, bu))
-        ids_dev = None
-        on_device = draws is not None and (sel_l is None or sel_u is None)
-        device_views = draws is not None and draws.views and params is None
-        base = draws.take(bl + bu) if on_device or device_views else None           # one id per slot, whatever it serves
-        if device_views:
-            params = ViewDrawHandle(draws.seed, base, bl + bu)
-        if on_device:
-            ids = [int(i) for i in idx_l] + [self.n_l + int(i) for i in idx_u]
-            with on_stream(self.stream):
-                sel, ids_dev = draw_batch_sel(self.scans, ids, self.m, draws, ((0, sel_l), (bl, sel_u)), base=base)
-        else:
-            sel = np.empty((bl + bu, self.m), dtype=np.int64)
-        drawn = []
-        for slot, scan in enumerate(list(idx_l) + list(idx_u)):
-            lab = slot < bl
-            n = (self.scans.sizes[scan] if lab else self.scans.sizes[self.n_l + scan])
-            have = sel_l if lab else sel_u
-            if on_device:                                                              # drawn (or copied) above
-                pass
-            elif have is not None:
-                sel[slot] = have[slot if lab else slot - bl]
-            else:
-                sel[slot] = np.random.choice(n, self.m, replace=n < self.m)            # tooth_dataset.py:134-135, 340-341
-            if params is None:
-                drawn.append(self._draw_view("train") if lab else (self._draw_view("train_w"), self._draw_view("train_s")))
-        if isinstance(params, ViewDrawHandle):
-            return sel, params, ids_dev
-        return sel, (drawn if params is None else list(params)), ids_dev
+        ids = [int(i) for i in idx_l] + [self.n_l + int(i) for i in idx_u]
+        return self._draw(ids, (("sel_l", sel_l, bl), ("sel_u", sel_u, bu)), params, draws, lambda slot: self._draw_view(
+            "train") if slot < bl else (self._draw_view("train_w"), self._draw_view("train_s")))
 
-    def _layout(self, bl, bu):
-        """The templates and plans of a (B_l, B_u) batch, on the device: output rows [0, B_l) labelled, then weak, then
-        strong; a slot's two views draw under the slot's id as views 1 and 2."""
-        from .view_draw import DrawLayout
-        if (bl, bu) not in self._layouts:
-            if self._draw_programs is None:
-                self._draw_programs = self.programs or {k: ViewProgram(CONFIGURED_LISTS[k], self.kwargs) for k in KINDS}
-            pr = self._draw_programs
-            jobs = [(i, i, pr["train"]) for i in range(bl)] + [(bl + i, bl + i, pr["train_w"]) for i in range(bu)]
-            jobs += [(bl + i, bl + bu + i, pr["train_s"]) for i in range(bu)]
-            slots = list(range(bl)) + 2 * list(range(bl, bl + bu))
-            self._layouts[(bl, bu)] = DrawLayout(jobs, bl + bu, bl + 2 * bu, self.m, self.device,
-                                                 [0] * bl + [1] * bu + [2] * bu, slots)
-        return self._layouts[(bl, bu)]
+    @staticmethod
+    def _rows(bl, bu):
+        """(source row, output row, list) per view job: output rows [0, B_l) labelled, [B_l, B_l + B_u) weak, then strong."""
+        rows = [(i, i, "train") for i in range(bl)] + [(bl + i, bl + i, "train_w") for i in range(bu)]
+        return rows + [(bl + i, bl + bu + i, "train_s") for i in range(bu)]
+
+    def _jobs(self, bl, bu):
+        """A slot's two views draw under the slot's id as views 1 and 2."""
+        if self._draw_programs is None:           # the configured lists as programs: the bits of geot_fixmatch_views
+            self._draw_programs = {k: ViewProgram(CONFIGURED_LISTS[k], self.kwargs) for k in KINDS}
+        jobs = [(src, dst, self._draw_programs[kind]) for src, dst, kind in self._rows(bl, bu)]
+        return jobs, bl + bu, bl + 2 * bu, [0] * bl + [1] * bu + [2] * bu, list(range(bl)) + 2 * list(range(bl, bl + bu))
+
+    def _pack(self, shape, params):
+        if self.programs is not None:
+            return super()._pack(shape, params)
+        bl, bu = shape
+        jobs = [(src, dst, p) for (src, dst, _), p in zip(self._rows(bl, bu), params)]
+        pack_view_jobs(jobs, bl + bu, bl + 2 * bu)        # checks the parameters before anything is queued
+        return jobs, bl + 2 * bu, None
+
+    def _views(self, raw, packed):
+        if self.programs is not None:
+            return super()._views(raw, packed)
+        return fixmatch_views(raw, packed[0], int(_kw(self.kwargs, "gravity_dim")), packed[1])
 
     def batch(self, idx_l, idx_u, sel_l=None, sel_u=None, params=None, check=False, draws=None):
         """idx_l / idx_u: scan numbers within the labelled / unlabelled set (what the samplers would yield); sel_* (B, m)
@@ -372,45 +255,12 @@ class FixMatchBatcher:
         need(bl >= 1 and bu >= 1, "FixMatchBatcher.batch: at least one labelled and one unlabelled scan")
         need(all(0 <= i < self.n_l for i in idx_l), "idx_l must lie in [0, %d)" % self.n_l)
         need(all(0 <= i < self.n_u for i in idx_u), "idx_u must lie in [0, %d)" % self.n_u)
-        sel, params, ids_dev = self._draw(idx_l, idx_u, sel_l, sel_u, params, draws)
-        ids = idx_l + [self.n_l + i for i in idx_u]
-        if isinstance(params, ViewDrawHandle):
-            with on_stream(self.stream):
-                out = self._queue(ids, sel, None, bl, bu, self._layout(bl, bu), ids_dev, params)
-            if check:
-                if self.stream is not None:
-                    self.stream.synchronize()
-                raise_bad_index(out[2], ids)
-            return out[0], out[1]
-        # view jobs: output rows [0, B_l) labelled, [B_l, B_l + B_u) weak, then strong
-        jobs = [(i, i, params[i]) for i in range(bl)]
-        jobs += [(bl + i, bl + i, params[bl + i][0]) for i in range(bu)]
-        jobs += [(bl + i, bl + bu + i, params[bl + i][1]) for i in range(bu)]
-        packed = None
-        if self.programs is None:
-            pack_view_jobs(jobs, bl + bu, bl + 2 * bu)        # checks the parameters before anything is queued
-        else:                                             # the same rows, every view through its list's program
-            progs = [self.programs["train"]] * bl + [self.programs["train_w"]] * bu + [self.programs["train_s"]] * bu
-            jobs = [(job[0], job[1], prog, job[2]) for job, prog in zip(jobs, progs)]
-            packed = pack_program_jobs(jobs, bl + bu, bl + 2 * bu, self.m)
-        with on_stream(self.stream):
-            out = self._queue(ids, sel, jobs, bl, bu, packed, ids_dev)
-        if check:
-            if self.stream is not None:
-                self.stream.synchronize()
-            raise_bad_index(out[2], ids)
-        return out[0], out[1]
+        sel, params, ids_dev = self._draw_slots(idx_l, idx_u, sel_l, sel_u, params, draws)
+        if not isinstance(params, ViewDrawHandle):        # per job: the labelled views, the weak ones, the strong ones
+            params = params[:bl] + [p[0] for p in params[bl:]] + [p[1] for p in params[bl:]]
+        return self._batch(idx_l + [self.n_l + i for i in idx_u], (bl, bu), sel, params, ids_dev, check)
 
-    def _queue(self, ids, sel, jobs, bl, bu, packed=None, ids_dev=None, handle=None):
-        s = cloud_sample_batch(self.scans, ids, sel, self.c, check=False, ids_dev=ids_dev)
-        if handle is not None:      # packed is the DrawLayout: the parameters are drawn where they are used
-            from .view_draw import view_program_draw, view_program_views_drawn
-            v = view_program_views_drawn(s["raw"], packed, view_program_draw(packed, handle.seed, handle.base))
-        elif packed is None:
-            v = fixmatch_views(s["raw"], jobs, int(_kw(self.kwargs, "gravity_dim")), bl + 2 * bu)
-        else:
-            v = view_program_views(s["raw"], jobs, bl + 2 * bu, packed)
-        cls = self.scans.cls.index_select(0, s["scan_ids"]).view(-1, 1)
+    def _result(self, s, v, cls, ids, bl, bu):
         lab, unl = slice(0, bl), slice(bl, bl + bu)
         data = {"pos": v["pos"][:bl], "x": v["x"][:bl], "heights": v["heights"][:bl], "y": s["y"][lab], "cls": cls[lab],
                 "class_weights": s["class_weights"][lab]}
@@ -422,14 +272,8 @@ class FixMatchBatcher:
         for suffix, rows in (("_w", slice(bl, bl + bu)), ("_s", slice(bl + bu, bl + 2 * bu))):
             for key in ("pos", "x", "heights"):
                 data_u[key + suffix] = v[key][rows]
-        return data, data_u, s["bad"]
+        return data, data_u
 
     def join(self, data, data_u):
-        """Hand a batch built on the side stream to the CURRENT stream: it waits for the side stream, and the caching
-        allocator is told that the batch's memory is in use here (train_step._join does the same for the steps' side streams)."""
-        if self.stream is None:
-            return
-        cur = torch.cuda.current_stream(self.device)
-        cur.wait_stream(self.stream)
-        for t in list(data.values()) + list(data_u.values()):
-            t.record_stream(cur)
+        """Hand a batch built on the side stream to the CURRENT stream (Batcher._join)."""
+        self._join(list(data.values()) + list(data_u.values()))

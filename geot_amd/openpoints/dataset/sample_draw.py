@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from ...ext._common import call, need, ptr
+from .scan_set import DeviceScanSet
 
 _MASK64 = (1 << 64) - 1
 
@@ -23,7 +24,6 @@ def sample_draw(scans, scan_ids, m, seed, draw_base):
     of its scan with the draw id draw_base + i -> (sel (S, m) int64, bad (S,) int32), both on the device, queued on the
     current stream without a host synchronisation.  A slot whose id lies outside the set gets a row of zeros and bad = 2
     (nothing is checked on the host: the sizes live on the device)."""
-    from .fixmatch_batch import DeviceScanSet
     need(isinstance(scans, DeviceScanSet), "sample_draw: scans must be a DeviceScanSet")
     dev = scans.device
     if scan_ids is None:

@@ -1,0 +1,100 @@
+"""Scans that live on the GPU and the batch sampling on them: what every batcher of this package (batcher.py and the three
+modules built on it) starts from.  DeviceScanSet holds the scans of one split; cloud_sample_batch (geot_cloud_sample_batch,
+csrc/dataprep.hip) draws nothing itself: it gathers the given vertex indices of every batch slot and normalises them as the
+reference's dataset does per item (openpoints/dataset/tooth_semi/tooth_dataset.py:116-147)."""
+import numpy as np
+import torch
+
+from ... import _lib
+from ...ext._common import call, need, ptr
+
+
+def _to_device(host, dev):
+    """Pinned staging + non-blocking copy on the current stream: no synchronisation (validation.SegMetrics._offsets)."""
+    return torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
+
+
+class DeviceScanSet:
+    """The scans of one split on one device, built once: vertices concatenated (sum N, 3) float32, labels (sum N,) int32,
+    offsets (n + 1,) int64, the jaw flag of every scan `cls` (n,) int64 (tooth_dataset.py:97, 0 = lower; default 0).
+    scans / labels: sequences of (N_i, 3) / (N_i,) arrays or tensors."""
+
+    def __init__(self, scans, labels, cls=None, device=None):
+        need(len(scans) >= 1 and len(scans) == len(labels), "DeviceScanSet: one label array per scan, at least one scan")
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        need(dev.type == "cuda", "DeviceScanSet: CPU not supported (the scans must live on the GPU)")
+        pts = [torch.as_tensor(p) for p in scans]
+        labs = [torch.as_tensor(l) for l in labels]
+        for p, l in zip(pts, labs):
+            need(p.dim() == 2 and p.shape[1] == 3 and p.shape[0] >= 1, "DeviceScanSet: a scan is (N>=1, 3)")
+            need(l.dim() == 1 and l.shape[0] == p.shape[0] and not l.is_floating_point(),
+                 "DeviceScanSet: one integer label per vertex")
+        self.sizes = [int(p.shape[0]) for p in pts]
+        cls = [0] * len(pts) if cls is None else [int(c) for c in cls]
+        need(len(cls) == len(pts), "DeviceScanSet: one cls entry per scan")
+        self.device = dev
+        self.points = torch.cat([p.to(dev, torch.float32) for p in pts]).contiguous()
+        self.labels = torch.cat([l.to(dev, torch.int32) for l in labs]).contiguous()
+        self.offsets = torch.tensor(np.concatenate([[0], np.cumsum(self.sizes, dtype=np.int64)]), dtype=torch.int64).to(dev)
+        self.cls = torch.tensor(cls, dtype=torch.int64).to(dev)
+
+    def __len__(self):
+        return len(self.sizes)
+
+    @classmethod
+    def _merged(cls, a, b):
+        """a's scans followed by b's, as one set (the batcher samples both splits in one sequence of launches)."""
+        need(a.device == b.device, "DeviceScanSet: both sets must be on one device (%s vs %s)" % (a.device, b.device))
+        out = cls.__new__(cls)
+        out.device, out.sizes = a.device, a.sizes + b.sizes
+        out.points, out.labels = torch.cat([a.points, b.points]), torch.cat([a.labels, b.labels])
+        out.offsets = torch.cat([a.offsets, b.offsets[1:] + a.offsets[-1:]])
+        out.cls = torch.cat([a.cls, b.cls])
+        return out
+
+
+def cloud_sample_batch(scans, scan_ids, sel, num_classes=17, check=True, ids_dev=None):
+    """geot_cloud_sample_batch: scans a DeviceScanSet; scan_ids: the set scan of every batch slot (S ints, host); sel (S, m)
+    int64 vertex indices local to each slot's scan (numpy or tensor) -> dict(raw (S, m, 3), y (S, m) int64, class_weights
+    (S, num_classes), center (S, 3), scale (S,), bad (S,) int32).  Slot by slot bit-identical to prepare_sample on that scan
+    alone.  check=True reads `bad` back (one host sync) and raises IndexError for an index outside its scan.  ids_dev:
+    scan_ids as an (S,) int64 tensor already on the device (the batchers upload them once for the draw and the sampling)."""
+    need(isinstance(scans, DeviceScanSet), "cloud_sample_batch: scans must be a DeviceScanSet")
+    ids = np.asarray(scan_ids, dtype=np.int64).reshape(-1)
+    need(ids.size >= 1 and ids.min() >= 0 and ids.max() < len(scans), "cloud_sample_batch: scan ids must lie in [0, %d)" % len(scans))
+    dev = scans.device
+    if isinstance(sel, torch.Tensor):
+        need(sel.dtype == torch.int64 and sel.dim() == 2, "sel must be (S, m) int64")
+        sel_dev = sel.to(dev).contiguous()
+    else:
+        sel = np.ascontiguousarray(sel)
+        need(sel.dtype == np.int64 and sel.ndim == 2, "sel must be (S, m) int64")
+        sel_dev = _to_device(sel, dev)
+    s, m = sel_dev.shape
+    need(s == ids.size and m >= 1, "sel must have one row of m >= 1 indices per scan id")
+    need(1 <= num_classes <= 4096, "num_classes must be in [1, 4096]")
+    if ids_dev is None:
+        ids_dev = _to_device(ids, dev)
+    out = {"raw": torch.empty((s, m, 3), dtype=torch.float32, device=dev),
+           "y": torch.empty((s, m), dtype=torch.int64, device=dev),
+           "class_weights": torch.empty((s, num_classes), dtype=torch.float32, device=dev),
+           "center": torch.empty((s, 3), dtype=torch.float32, device=dev),
+           "scale": torch.empty(s, dtype=torch.float32, device=dev),
+           "bad": torch.empty(s, dtype=torch.int32, device=dev)}
+    nbytes = int(_lib.load().geot_cloud_sample_batch_ws_bytes(s, int(num_classes)))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    call("geot_cloud_sample_batch", dev, s, m, int(num_classes), len(scans), int(scans.points.shape[0]), ptr(scans.points),
+         ptr(scans.labels), ptr(scans.offsets), ptr(ids_dev), ptr(sel_dev), ptr(out["raw"]), ptr(out["y"]),
+         ptr(out["class_weights"]), ptr(out["center"]), ptr(out["scale"]), ptr(out["bad"]), ptr(ws), nbytes)
+    out["scan_ids"] = ids_dev
+    if check:
+        raise_bad_index(out["bad"], ids)
+    return out
+
+
+def raise_bad_index(bad, ids):
+    flags = bad.cpu().numpy()            # the one host synchronisation of check=True
+    if flags.any():
+        slot = int(np.flatnonzero(flags)[0])
+        raise IndexError("batch slot %d (scan %d): selected_idxs holds an index outside the scan" % (slot, int(ids[slot])))
+

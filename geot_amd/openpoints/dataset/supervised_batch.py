@@ -17,21 +17,16 @@ Kept from the reference: data['x'] IS data['pos'] until a transform rebinds pos.
 un-centred, un-jittered cloud (PointCloudCenterAndNormalize separates the two), and ChromaticDropGPU -- there are no colour
 channels, x[:, :3] is all of x -- zeroes it with probability color_drop.
 """
-import numpy as np
-import torch
-
 from ...ext._common import need
-from .fixmatch_batch import DeviceScanSet, cloud_sample_batch, raise_bad_index
-from .sample_draw import DeviceDraws, ViewDrawHandle, draw_batch_sel, on_stream
-from .view_draw import DrawLayout, view_program_draw, view_program_views_drawn
-from .view_program import ViewProgram, pack_program_jobs, view_program_views
+from .batcher import Batcher
+from .view_program import ViewProgram
 
 # cfgs/tooth_semi/default.yaml datatransforms: the `train` list and its kwargs (`angle` is read by nothing in this list)
 DEFAULT_TRAIN = ["PointsToTensor", "PointCloudScaling", "PointCloudCenterAndNormalize", "PointCloudJitter", "ChromaticDropGPU"]
 DEFAULT_TRAIN_KWARGS = {"jitter_sigma": 0.001, "jitter_clip": 0.005, "scale": [0.8, 1.2], "gravity_dim": 1, "angle": [0, 1.0, 0]}
 
 
-class SupervisedBatcher:
+class SupervisedBatcher(Batcher):
     """Replaces the reference's labelled training DataLoader of the supervised stage: `batch(idx)` returns the dict of the
     module text for the scans `idx` of the set (what the sampler would yield) in freshly allocated tensors, so the `pos`
     handed to SupervisedStep(..., next_pos=) passes the model's identity and version check one call later.  `heights` is
@@ -46,19 +41,10 @@ class SupervisedBatcher:
     With DeviceDraws(seed, views=True) the list's parameters are device draws too: no host generator is read, draw()
     returns a ViewDrawHandle in place of the parameters, and batch(params=handle) replays it; an explicit params= wins."""
 
-    stream = draws = None    # (the constructor's; None: the current stream, the reference's host draws)
-
     def __init__(self, scans, num_points, num_classes=17, transforms=DEFAULT_TRAIN, kwargs=DEFAULT_TRAIN_KWARGS, stream=None,
                  draws=None):
-        need(isinstance(scans, DeviceScanSet), "SupervisedBatcher: scans must be a DeviceScanSet")
-        need(int(num_points) >= 1, "SupervisedBatcher: num_points >= 1")
-        need(1 <= int(num_classes) <= 4096, "SupervisedBatcher: num_classes must be in [1, 4096]")
         self.program = ViewProgram(transforms, kwargs)          # NotImplementedError for what the kernel cannot do
-        self.scans, self.device = scans, scans.device
-        self.m, self.c, self.stream, self.draws = int(num_points), int(num_classes), stream, draws
-        self._layouts = {}          # batch size -> DrawLayout (templates and plans on the device, built once)
-        if stream is not None:      # once: the scans are ready; a batch itself depends on nothing the current stream does
-            stream.wait_stream(torch.cuda.current_stream(self.device))
+        super().__init__(scans, num_points, num_classes, stream, draws)
 
     def __len__(self):
         return len(self.scans)
@@ -68,42 +54,12 @@ class SupervisedBatcher:
         order -- np.random.choice (tooth_dataset.py:134-135), then the list's draws (ViewProgram.draw).  With draws (a
         DeviceDraws; default: the constructor's) and no sel, geot_sample_draw draws the rows on the batcher's stream and sel
         is that (B, m) int64 DEVICE tensor."""
-        return self._draw(idx, sel, params, draws)[:2]
+        return self._draw_slots(idx, sel, params, draws)[:2]
 
-    def _draw(self, idx, sel, params, draws):
+    def _draw_slots(self, idx, sel, params, draws):
         """draw() and, third, the scan ids on the device when the device drew (None otherwise)."""
         idx = [int(i) for i in idx]
-        draws = self.draws if draws is None else draws
-        if sel is not None:
-            sel = np.asarray(sel.cpu() if isinstance(sel, torch.Tensor) else sel)
-            need(sel.shape == (len(idx), self.m) and sel.dtype.kind in "iu", "sel must be (%d, %d) integers" % (len(idx), self.m))
-            sel = sel.astype(np.int64)
-        need(draws is None or isinstance(draws, DeviceDraws), "draws must be a DeviceDraws (or None: the reference's host draws)")
-        if isinstance(params, ViewDrawHandle):
-            need(params.count == len(idx), "params: the handle was drawn for %d scans" % params.count)
-        elif params is not None:
-            need(len(params) == len(idx), "params: one entry (ViewProgram.draw) per scan")
-        ids_dev = None
-        on_device = draws is not None and sel is None
-        device_views = draws is not None and draws.views and params is None
-        base = draws.take(len(idx)) if on_device or device_views else None          # one id per slot, whatever it serves
-        if device_views:
-            params = ViewDrawHandle(draws.seed, base, len(idx))
-        if on_device:
-            with on_stream(self.stream):
-                out, ids_dev = draw_batch_sel(self.scans, idx, self.m, draws, base=base)
-        else:
-            out = np.empty((len(idx), self.m), dtype=np.int64)
-        drawn = []
-        for slot, scan in enumerate(idx):
-            n = self.scans.sizes[scan]
-            if not on_device:
-                out[slot] = sel[slot] if sel is not None else np.random.choice(n, self.m, replace=n < self.m)
-            if params is None:
-                drawn.append(self.program.draw(self.m))
-        if isinstance(params, ViewDrawHandle):
-            return out, params, ids_dev
-        return out, (drawn if params is None else list(params)), ids_dev
+        return self._draw(idx, (("sel", sel, len(idx)),), params, draws, lambda slot: self.program.draw(self.m))
 
     def batch(self, idx, sel=None, params=None, check=False, draws=None):
         """idx: scan numbers within the set; sel (B, m) vertex indices per scan and params (one ViewProgram.draw result per
@@ -112,42 +68,18 @@ class SupervisedBatcher:
         idx = [int(i) for i in idx]
         need(len(idx) >= 1, "SupervisedBatcher.batch: at least one scan")
         need(all(0 <= i < len(self.scans) for i in idx), "SupervisedBatcher.batch: idx must lie in [0, %d)" % len(self.scans))
-        sel, params, ids_dev = self._draw(idx, sel, params, draws)
-        with on_stream(self.stream):
-            if isinstance(params, ViewDrawHandle):
-                data, bad = self._queue(idx, sel, None, self._layout(len(idx)), ids_dev, params)
-            else:
-                jobs = [(i, i, self.program, params[i]) for i in range(len(idx))]
-                packed = pack_program_jobs(jobs, len(idx), len(idx), self.m)   # checks the parameters before anything is queued
-                data, bad = self._queue(idx, sel, jobs, packed, ids_dev)
-        if check:
-            if self.stream is not None:
-                self.stream.synchronize()
-            raise_bad_index(bad, idx)
-        return data
+        sel, params, ids_dev = self._draw_slots(idx, sel, params, draws)
+        return self._batch(idx, (len(idx),), sel, params, ids_dev, check)
 
-    def _layout(self, b):
-        if b not in self._layouts:
-            self._layouts[b] = DrawLayout([(i, i, self.program) for i in range(b)], b, b, self.m, self.device)
-        return self._layouts[b]
+    def _jobs(self, b):
+        return [(i, i, self.program) for i in range(b)], b, b, None, None
 
-    def _queue(self, idx, sel, jobs, packed, ids_dev=None, handle=None):
-        s = cloud_sample_batch(self.scans, idx, sel, self.c, check=False, ids_dev=ids_dev)
-        if handle is not None:      # packed is the DrawLayout: the parameters are drawn where they are used
-            v = view_program_views_drawn(s["raw"], packed, view_program_draw(packed, handle.seed, handle.base))
-        else:
-            v = view_program_views(s["raw"], jobs, len(idx), packed)
-        data = {"pos": v["pos"], "x": v["x"], "y": s["y"], "cls": self.scans.cls.index_select(0, s["scan_ids"]).view(-1, 1),
-                "class_weights": s["class_weights"]}
+    def _result(self, s, v, cls, ids, b):
+        data = {"pos": v["pos"], "x": v["x"], "y": s["y"], "cls": cls, "class_weights": s["class_weights"]}
         if v["heights"] is not None:
             data["heights"] = v["heights"]
-        return data, s["bad"]
+        return data
 
     def join(self, data):
-        """Hand a batch built on the side stream to the CURRENT stream (FixMatchBatcher.join)."""
-        if self.stream is None:
-            return
-        cur = torch.cuda.current_stream(self.device)
-        cur.wait_stream(self.stream)
-        for t in data.values():
-            t.record_stream(cur)
+        """Hand a batch built on the side stream to the CURRENT stream (Batcher._join)."""
+        self._join(data.values())

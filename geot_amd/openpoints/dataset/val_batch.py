@@ -24,9 +24,8 @@ import numpy as np
 import torch
 
 from ...ext._common import need
-from .fixmatch_batch import (TOOTH_VIEW_KWARGS, DeviceScanSet, _kw, cloud_sample_batch, draw_view_params, fixmatch_views,
-                             raise_bad_index)
-from .sample_draw import draw_batch_sel, on_stream
+from .batcher import Batcher
+from .fixmatch_batch import TOOTH_VIEW_KWARGS, _kw, draw_view_params, fixmatch_views
 
 
 def draw_val_sel(sizes, num_points):
@@ -43,7 +42,7 @@ def draw_val_sel(sizes, num_points):
     return sel
 
 
-class ValBatcher:
+class ValBatcher(Batcher):
     """Replaces the reference's validation DataLoader: `batch(idx)` returns the dict described in the module text for the
     scans `idx` of the set (what the sequential sampler would yield), in freshly allocated tensors.
 
@@ -57,66 +56,39 @@ class ValBatcher:
     DeviceDraws(seed, views=True) is accepted and changes nothing: the `val` list draws no view parameter."""
 
     def __init__(self, scans, num_points, num_classes=17, kwargs=TOOTH_VIEW_KWARGS, stream=None, draws=None):
-        need(isinstance(scans, DeviceScanSet), "ValBatcher: scans must be a DeviceScanSet")
-        need(scans.device.type == "cuda", "ValBatcher: CPU not supported (the scans must live on the GPU)")
-        need(int(num_points) >= 1, "ValBatcher: num_points >= 1")
-        need(1 <= int(num_classes) <= 4096, "ValBatcher: num_classes must be in [1, 4096]")
+        super().__init__(scans, num_points, num_classes, stream, draws)
         need(int(_kw(kwargs, "gravity_dim")) in (0, 1, 2), "ValBatcher: gravity_dim must be 0, 1 or 2")
-        self.scans, self.device = scans, scans.device
-        self.m, self.c, self.kwargs, self.stream, self.draws = int(num_points), int(num_classes), kwargs, stream, draws
+        self.kwargs = kwargs
         self.cls_host = [int(v) for v in scans.cls.cpu().tolist()]       # the one copy: validate's `cls[ii] == 0` per scan
         self._points = list(torch.split(scans.points, scans.sizes))      # views
         self._labels = list(torch.split(scans.labels, scans.sizes))
-        if stream is not None:
-            stream.wait_stream(torch.cuda.current_stream(self.device))
 
     def __len__(self):
         return len(self.scans)
 
     def batch(self, idx, sel=None, check=False, draws=None):
         """idx: scan numbers within the set; sel (B, m) vertex indices per scan, default the reference's draws
-        (draw_val_sel) or, with draws (a DeviceDraws; default: the constructor's), geot_sample_draw's.  check=True reads the
-        bad-index flags back (one host sync) and raises IndexError."""
+        (draw_val_sel's statements) or, with draws (a DeviceDraws; default: the constructor's), geot_sample_draw's.
+        check=True reads the bad-index flags back (one host sync) and raises IndexError."""
         ids = [int(i) for i in idx]
         need(len(ids) >= 1, "ValBatcher.batch: at least one scan")
         need(all(0 <= i < len(self.scans) for i in ids), "ValBatcher.batch: idx must lie in [0, %d)" % len(self.scans))
-        sizes = [self.scans.sizes[i] for i in ids]
-        draws = self.draws if draws is None else draws
-        ids_dev = None
-        if sel is None and draws is not None:
-            with on_stream(self.stream):
-                sel, ids_dev = draw_batch_sel(self.scans, ids, self.m, draws)
-        elif sel is None:
-            sel = draw_val_sel(sizes, self.m)
-        else:
-            sel = np.asarray(sel.cpu() if isinstance(sel, torch.Tensor) else sel)
-            need(sel.shape == (len(ids), self.m) and sel.dtype.kind in "iu", "sel must be (%d, %d) integers" % (len(ids), self.m))
-            sel = sel.astype(np.int64)
         weak = draw_view_params("train_w", self.kwargs)                   # the `val` list: nothing is drawn
-        jobs = [(i, i, weak) for i in range(len(ids))]
-        with on_stream(self.stream):
-            out, bad = self._queue(ids, sizes, sel, jobs, ids_dev)
-        if check:
-            if self.stream is not None:
-                self.stream.synchronize()
-            raise_bad_index(bad, ids)
-        return out
+        sel, params, ids_dev = self._draw(ids, (("sel", sel, len(ids)),), [weak] * len(ids), draws, None)
+        return self._batch(ids, (len(ids),), sel, params, ids_dev, check)
 
-    def _queue(self, ids, sizes, sel, jobs, ids_dev=None):
-        s = cloud_sample_batch(self.scans, ids, sel, self.c, check=False, ids_dev=ids_dev)
-        v = fixmatch_views(s["raw"], jobs, int(_kw(self.kwargs, "gravity_dim")), len(ids))
-        cls = self.scans.cls.index_select(0, s["scan_ids"]).view(-1, 1)
-        out = {"pos": v["pos"], "x": v["x"], "y": s["y"], "cls": cls, "center": s["center"], "scale": s["scale"],
-               "points": [self._points[i] for i in ids], "labels": [self._labels[i] for i in ids],
-               "scan_ids": s["scan_ids"], "scans": self.scans, "sizes": sizes,
-               "mandible": [self.cls_host[i] == 0 for i in ids]}
-        return out, s["bad"]
+    def _pack(self, shape, params):
+        return [(i, i, p) for i, p in enumerate(params)]
+
+    def _views(self, raw, jobs):
+        return fixmatch_views(raw, jobs, int(_kw(self.kwargs, "gravity_dim")), len(jobs))
+
+    def _result(self, s, v, cls, ids, b):
+        return {"pos": v["pos"], "x": v["x"], "y": s["y"], "cls": cls, "center": s["center"], "scale": s["scale"],
+                "points": [self._points[i] for i in ids], "labels": [self._labels[i] for i in ids],
+                "scan_ids": s["scan_ids"], "scans": self.scans, "sizes": [self.scans.sizes[i] for i in ids],
+                "mandible": [self.cls_host[i] == 0 for i in ids]}
 
     def join(self, batch):
-        """Hand a batch built on the side stream to the CURRENT stream (FixMatchBatcher.join)."""
-        if self.stream is None:
-            return
-        cur = torch.cuda.current_stream(self.device)
-        cur.wait_stream(self.stream)
-        for key in ("pos", "x", "y", "cls", "center", "scale", "scan_ids"):
-            batch[key].record_stream(cur)
+        """Hand a batch built on the side stream to the CURRENT stream (Batcher._join)."""
+        self._join(batch[key] for key in ("pos", "x", "y", "cls", "center", "scale", "scan_ids"))

@@ -53,6 +53,7 @@ _NOTHING = ("PointsToTensor", "PointCloudToTensor")
 _REBINDING = ("PointCloudScaleAndTranslate", "PointCloudScaleAndJitter", "PointCloudRotation")
 _REFUSED = {"RandomDropout": "it changes the point count", "ChromaticNormalize": "colour statistics on real colour channels"}
 _SCALE_DEFAULT = [2. / 3, 3. / 2]
+_ONE, _ZERO3, _EYE9 = np.ones(3, np.float32), np.zeros(3, np.float32), np.eye(3, dtype=np.float32).reshape(9)   # (read only)
 
 
 def _axis_rotation(axis, theta):
@@ -169,13 +170,6 @@ class _Step:
         return {}
 
 
-def _vec3(p, key, what):
-    need(isinstance(p, dict) and key in p, "%s: the parameters lack %r (ViewProgram.draw)" % (what, key))
-    v = np.asarray(p[key], dtype=np.float32)
-    need(v.shape == (3,), "%s: %s must be (3,)" % (what, key))
-    return v
-
-
 class ViewProgram:
     """A transform list, given by the reference's class names and the kwargs dict every class receives, compiled for
     geot_view_program.  Raises NotImplementedError -- naming the transform, before any device call -- for RandomDropout,
@@ -211,72 +205,8 @@ class ViewProgram:
     def compile(self, params, m):
         """The ops of one view -> (ops, noise rows, mask rows): ops a list of (kind, arg, floats), rows lists of (m, 3) / (m,)
         float32 arrays the ops' args index.  Everything is checked here, on the host."""
-        need(isinstance(params, (list, tuple)) and len(params) == len(self.steps),
-             "ViewProgram: parameters are a list with one dict per transform (%d), see draw()" % len(self.steps))
-        ops, noise, masks = [], [], []
-        aliased, store_at, x_zero, x_masks = True, None, False, []
-
-        def rows(p, key, shape, what, into):
-            need(isinstance(p, dict) and key in p, "%s: the parameters lack %r (ViewProgram.draw)" % (what, key))
-            v = np.ascontiguousarray(p[key], dtype=np.float32)
-            need(v.shape == shape, "%s: %s must be %s, got %s" % (what, key, shape, v.shape))
-            into.append(v)
-            return len(into) - 1
-        for step, p in zip(self.steps, params):
-            base, what = step.base, step.name
-            if step.rebinds and aliased:         # x leaves pos here: it is stored once, in front of this op
-                store_at, aliased = len(ops), False
-                ops.append(None)
-            if base == "PointCloudScaling":
-                ops.append((SCALE, 0, _vec3(p, "scale", what)))
-            elif base == "PointCloudCenterAndNormalize":
-                ops.append((CENTER_NORM, (1 if step.centering else 0) | (2 if step.normalize else 0) | (step.gravity_dim << 2), []))
-            elif base == "PointCloudXYZAlign":
-                ops.append((XYZ_ALIGN, step.gravity_dim, []))
-            elif base == "PointCloudTranslation":
-                ops.append((TRANSLATE, 0, _vec3(p, "t", what)))
-            elif base == "PointCloudScaleAndTranslate":
-                ops.append((SCALE_TRANSLATE, 0, np.concatenate([_vec3(p, "scale", what), _vec3(p, "t", what)])))
-            elif base == "PointCloudJitter":
-                ops.append((JITTER, rows(p, "noise", (m, 3), what, noise), []))
-            elif base == "PointCloudScaleAndJitter":
-                ops.append((SCALE_JITTER, rows(p, "noise", (m, 3), what, noise), _vec3(p, "scale", what)))
-            elif base == "PointCloudRotation":
-                need(isinstance(p, dict) and "R" in p, "%s: the parameters lack 'R' (ViewProgram.draw)" % what)
-                r = np.asarray(p["R"], dtype=np.float32)
-                need(r.shape == (3, 3), "%s: R must be (3, 3)" % what)
-                ops.append((ROTATE, 0, r.reshape(9)))
-            elif base == "RandomHorizontalFlip":
-                need(isinstance(p, dict) and "flip" in p, "%s: the parameters lack 'flip' (ViewProgram.draw)" % what)
-                for ax in p["flip"]:
-                    need(int(ax) in step.horz_axes, "%s: axis %r is not a horizontal axis" % (what, ax))
-                    ops.append((FLIP, int(ax), []))
-            elif base == "ChromaticDropGPU":
-                need(isinstance(p, dict) and "drop" in p, "%s: the parameters lack 'drop' (ViewProgram.draw)" % what)
-                if p["drop"]:
-                    if aliased:
-                        ops.append((ZERO, 0, []))
-                    else:
-                        x_zero = True
-            elif base == "ChromaticPerDropGPU":
-                if aliased:
-                    ops.append((MASK, rows(p, "mask", (m,), what, masks), []))
-                else:
-                    rows(p, "mask", (m,), what, x_masks)
-        if aliased:
-            ops.append((STORE_X, 0, []))
-        elif x_zero:
-            ops[store_at] = (STORE_X, 1, [])
-        elif x_masks:                            # 0 / 1 masks: their product, applied once, is the chain of multiplies
-            combined = x_masks[0]
-            for extra in x_masks[1:]:
-                combined = combined * extra
-            masks.append(combined)
-            ops[store_at] = (STORE_X, 2 | ((len(masks) - 1) << 2), [])
-        else:
-            ops[store_at] = (STORE_X, 0, [])
-        need(len(ops) <= _lib.VIEW_MAX_OPS, "ViewProgram: %d ops, the kernel takes %d" % (len(ops), _lib.VIEW_MAX_OPS))
-        return ops, noise, masks
+        walked = self._walk(params, m, False)
+        return walked["ops"], walked["noise"], walked["masks"]
 
     def compile_fixed(self, params=None, m=None):
         """The list in the FIXED layout geot_view_draw works on (view_draw.py): one op sequence for every draw, so that
@@ -287,91 +217,126 @@ class ViewProgram:
         with every drawn float neutral -- else the record a view with these draws has.
         -> dict(ops, n_noise, n_mask, noise, masks, store_at, steps); steps: the draw plan, tuples (kind, op index or -1,
         position in the list, flags, constants) in the layout of include/geot_hip.h geot_view_draw."""
-        tmpl = params is None
-        if not tmpl:
-            need(len(params) == len(self.steps), "ViewProgram: parameters are a list with one dict per transform")
-        one, zero3 = np.ones(3, np.float32), np.zeros(3, np.float32)
-        ops, steps, noise, masks, x_masks = [], [], [], [], []
-        aliased, store_at, x_zero, n_noise, n_mask = True, -1, False, 0, 0
+        return self._walk(params, m, True)
 
-        def scale_step(step, op, form):
+    def _walk(self, params, m, fixed):
+        """compile() and compile_fixed(): one pass over the list that keeps the aliasing books (module text) -> the dict of
+        compile_fixed.  fixed: that layout, and the draw plan with it; params may then be None (the template)."""
+        tmpl = fixed and params is None
+        need(tmpl or (isinstance(params, (list, tuple)) and len(params) == len(self.steps)),
+             "ViewProgram: parameters are a list with one dict per transform (%d), see draw()" % len(self.steps))
+        one, zero3 = _ONE, _ZERO3
+        ops, steps, noise, masks, x_masks = [], [], [], [], []
+        aliased, store_at, x_zero, masked_x, n_noise, n_mask = True, -1, False, False, 0, 0
+
+        def vec(p, key, what, neutral, shape=(3,)):       # (the messages are formatted only when they are raised: this
+            if tmpl:                                      # runs per job of every batch)
+                return neutral
+            if not (isinstance(p, dict) and key in p):
+                need(False, "%s: the parameters lack %r (ViewProgram.draw)" % (what, key))
+            v = np.asarray(p[key], dtype=np.float32)
+            if v.shape != shape:
+                need(False, "%s: %s must be %s" % (what, key, shape))
+            return v
+
+        def row(p, key, shape, what, into):
+            if tmpl:
+                return
+            if not (isinstance(p, dict) and key in p):
+                need(False, "%s: the parameters lack %r (ViewProgram.draw)" % (what, key))
+            v = np.ascontiguousarray(p[key], dtype=np.float32)
+            if m is not None and v.shape != shape:
+                need(False, "%s: %s must be %s, got %s" % (what, key, shape, v.shape))
+            into.append(v)
+
+        def plan_scale(step, op, pos, form):
             flags = (1 if step.anisotropic else 0) | sum(2 << k for k in range(3) if step.scale_xyz[k]) | (form << 4)
             mirror = step.mirror.to(torch.float32).numpy()
-            return (1, op, pos, flags, [step.scale_min, np.float32(step.scale_max - step.scale_min)] + list(mirror))
+            steps.append((1, op, pos, flags, [step.scale_min, np.float32(step.scale_max - step.scale_min)] + list(mirror)))
+
         for pos, step in enumerate(self.steps):
-            base, p = step.base, (None if tmpl else params[pos])
-            if step.rebinds and aliased:
+            base, what, p = step.base, step.name, (None if tmpl else params[pos])
+            if step.rebinds and aliased:         # x leaves pos here: it is stored once, in front of this op
                 store_at, aliased = len(ops), False
                 ops.append(None)
             at = len(ops)
             if base == "PointCloudScaling":
-                ops.append((SCALE, 0, one if tmpl else _vec3(p, "scale", step.name)))
-                steps.append(scale_step(step, at, 1 if step.use_mirroring else 0))
+                ops.append((SCALE, 0, vec(p, "scale", what, one)))
+                if fixed:
+                    plan_scale(step, at, pos, 1 if step.use_mirroring else 0)
             elif base == "PointCloudCenterAndNormalize":
                 ops.append((CENTER_NORM, (1 if step.centering else 0) | (2 if step.normalize else 0) | (step.gravity_dim << 2), []))
             elif base == "PointCloudXYZAlign":
                 ops.append((XYZ_ALIGN, step.gravity_dim, []))
             elif base == "PointCloudTranslation":
-                ops.append((TRANSLATE, 0, zero3 if tmpl else _vec3(p, "t", step.name)))
-                steps.append((2, at, pos, 0, list(step.shift.numpy())))
+                ops.append((TRANSLATE, 0, vec(p, "t", what, zero3)))
+                if fixed:
+                    steps.append((2, at, pos, 0, list(step.shift.numpy())))
             elif base == "PointCloudScaleAndTranslate":
-                ops.append((SCALE_TRANSLATE, 0, np.concatenate([one, zero3]) if tmpl else
-                            np.concatenate([_vec3(p, "scale", step.name), _vec3(p, "t", step.name)])))
-                steps.append(scale_step(step, at, 1 if step.use_mirroring else 0))
-                steps.append((2, at, pos, 1, list(step.shift.numpy())))
+                ops.append((SCALE_TRANSLATE, 0, np.concatenate([vec(p, "scale", what, one), vec(p, "t", what, zero3)])))
+                if fixed:
+                    plan_scale(step, at, pos, 1 if step.use_mirroring else 0)
+                if fixed:
+                    steps.append((2, at, pos, 1, list(step.shift.numpy())))
             elif base in ("PointCloudJitter", "PointCloudScaleAndJitter"):
                 if base == "PointCloudJitter":
                     ops.append((JITTER, n_noise, []))
                 else:
-                    ops.append((SCALE_JITTER, n_noise, one if tmpl else _vec3(p, "scale", step.name)))
-                    steps.append(scale_step(step, at, 2))
-                steps.append((3, at, pos, 0, [step.noise_std, step.noise_clip]))
+                    ops.append((SCALE_JITTER, n_noise, vec(p, "scale", what, one)))
+                    if fixed:
+                        plan_scale(step, at, pos, 2)
+                if fixed:
+                    steps.append((3, at, pos, 0, [step.noise_std, step.noise_clip]))
+                row(p, "noise", (m, 3), what, noise)
                 n_noise += 1
-                if not tmpl:
-                    noise.append(np.ascontiguousarray(p["noise"], dtype=np.float32))
             elif base == "PointCloudRotation":
-                ops.append((ROTATE, 0, np.eye(3, dtype=np.float32).reshape(9) if tmpl else
-                            np.asarray(p["R"], dtype=np.float32).reshape(9)))
-                steps.append((4, at, pos, 0, list(step.angle_pi)))
+                ops.append((ROTATE, 0, vec(p, "R", what, _EYE9, (3, 3)).reshape(9)))
+                if fixed:
+                    steps.append((4, at, pos, 0, list(step.angle_pi)))
             elif base == "RandomHorizontalFlip":
-                for ax in step.horz_axes:
-                    ops.append((FLIP, int(ax), []) if tmpl or ax in p["flip"] else (SCALE, 0, one))
-                steps.append((5, at, pos, 0, [step.aug_prob]))
+                need(tmpl or (isinstance(p, dict) and "flip" in p), "%s: the parameters lack 'flip' (ViewProgram.draw)" % what)
+                flips = [] if tmpl else [int(ax) for ax in p["flip"]]
+                for ax in flips:
+                    need(ax in step.horz_axes, "%s: axis %r is not a horizontal axis" % (what, ax))
+                for ax in (step.horz_axes if fixed else flips):      # fixed: a place for either axis, flipped or not
+                    ops.append((FLIP, int(ax), []) if tmpl or ax in flips else (SCALE, 0, one))
+                if fixed:
+                    steps.append((5, at, pos, 0, [step.aug_prob]))
             elif base == "ChromaticDropGPU":
-                if aliased:
-                    ops.append((ZERO, 0, []) if tmpl or p["drop"] else (SCALE, 0, one))
-                    steps.append((6, at, pos, 0, [step.color_drop]))
-                else:
-                    x_zero = x_zero or (not tmpl and bool(p["drop"]))
-                    steps.append((6, -1, pos, 0, [step.color_drop]))
+                need(tmpl or (isinstance(p, dict) and "drop" in p), "%s: the parameters lack 'drop' (ViewProgram.draw)" % what)
+                drop = tmpl or bool(p["drop"])
+                if not aliased:
+                    x_zero = x_zero or (drop and not tmpl)
+                elif drop or fixed:
+                    ops.append((ZERO, 0, []) if drop else (SCALE, 0, one))
+                if fixed:
+                    steps.append((6, at if aliased else -1, pos, 0, [step.color_drop]))
             elif base == "ChromaticPerDropGPU":
                 if aliased:
                     ops.append((MASK, n_mask, []))
+                    row(p, "mask", (m,), what, masks)
                     n_mask += 1
-                    if not tmpl:
-                        masks.append(np.ascontiguousarray(p["mask"], dtype=np.float32))
                 else:
-                    at = -1
-                    if not tmpl:
-                        x_masks.append(np.ascontiguousarray(p["mask"], dtype=np.float32))
-                steps.append((7, at, pos, 0, [step.color_drop]))
-        masked_x = any(s[0] == 7 and s[1] == -1 for s in steps)
+                    masked_x = True
+                    row(p, "mask", (m,), what, x_masks)
+                if fixed:
+                    steps.append((7, at if aliased else -1, pos, 0, [step.color_drop]))
         if aliased:
-            store_at = len(ops)
             ops.append((STORE_X, 0, []))
         else:
             ops[store_at] = (STORE_X, 1 if x_zero else (2 | (n_mask << 2)) if masked_x else 0, [])
-        if masked_x:
-            n_mask += 1
-            if not tmpl:
-                combined = x_masks[0]
-                for extra in x_masks[1:]:
-                    combined = combined * extra
-                masks.append(combined)
+            if masked_x and (fixed or not x_zero):   # 0 / 1 masks: their product, applied once, is the chain of multiplies
+                n_mask += 1
+                if not tmpl:
+                    combined = x_masks[0]
+                    for extra in x_masks[1:]:
+                        combined = combined * extra
+                    masks.append(combined)
         need(len(ops) <= _lib.VIEW_MAX_OPS, "ViewProgram: %d ops, the kernel takes %d" % (len(ops), _lib.VIEW_MAX_OPS))
-        need(len(steps) <= _lib.VIEW_DRAW_MAX_STEPS, "ViewProgram: the list draws %d quantities, geot_view_draw takes %d"
-             % (len(steps), _lib.VIEW_DRAW_MAX_STEPS))
-        need(len(self.steps) <= 4096, "ViewProgram: geot_view_draw takes lists of up to 4096 transforms")
+        if fixed:
+            need(len(steps) <= _lib.VIEW_DRAW_MAX_STEPS, "ViewProgram: the list draws %d quantities, geot_view_draw takes %d"
+                 % (len(steps), _lib.VIEW_DRAW_MAX_STEPS))
+            need(len(self.steps) <= 4096, "ViewProgram: geot_view_draw takes lists of up to 4096 transforms")
         return {"ops": ops, "n_noise": n_noise, "n_mask": n_mask, "noise": noise, "masks": masks,
                 "store_at": -1 if aliased else store_at, "steps": steps}
 
@@ -381,41 +346,42 @@ class ViewProgram:
         return pack_program_jobs([(job[0], job[1], self, job[2]) for job in jobs], n_rows, n_out, m)
 
 
+def _pack_jobs(jobs, n_rows, n_out, m, who, fixed):
+    """The job and row checks and the record writer of pack_program_jobs and pack_fixed_jobs -> (table, noise, masks, what
+    ViewProgram._walk made of every job)."""
+    need(len(jobs) >= 1, "%s: at least one job" % who)
+    m = int(m)
+    need(m >= 1, "%s: m >= 1" % who)
+    table = np.zeros((len(jobs), _lib.VIEW_PROGRAM_JOB_WORDS), dtype=np.int32)
+    as_f = table.view(np.float32)
+    noise, masks, walked, n_noise, n_mask, seen = [], [], [], 0, 0, set()
+    for j, job in enumerate(jobs):
+        need(len(job) == 4 and isinstance(job[2], ViewProgram), "%s: a job is (source row, output row, program, params)" % who)
+        src, dst = int(job[0]), int(job[1])
+        need(0 <= src < n_rows, "%s: job %d reads row %d of %d" % (who, j, src, n_rows))
+        need(0 <= dst < n_out and dst not in seen, "%s: job %d writes row %d (of %d; each row once)" % (who, j, dst, n_out))
+        seen.add(dst)
+        w = job[2]._walk(job[3], m, fixed)
+        table[j, :5] = src, dst, len(w["ops"]), n_noise, n_mask
+        for o, (kind, arg, floats) in enumerate(w["ops"]):
+            at = _HEADER_WORDS + o * _OP_WORDS
+            table[j, at], table[j, at + 1] = kind, arg
+            as_f[j, at + 2:at + 2 + len(floats)] = floats
+        n_noise += w["n_noise"]
+        n_mask += w["n_mask"]
+        noise += w["noise"] if job[3] is not None else [np.zeros((m, 3), np.float32)] * w["n_noise"]      # (the template's)
+        masks += w["masks"] if job[3] is not None else [np.zeros(m, np.float32)] * w["n_mask"]
+        walked.append(w)
+    noise = np.stack(noise) if noise else np.zeros((0, m, 3), np.float32)
+    masks = np.stack(masks) if masks else np.zeros((0, m), np.float32)
+    return table, noise, masks, walked
+
+
 def pack_program_jobs(jobs, n_rows, n_out, m):
     """jobs: sequence of (source row of raw, output row, program, params) -> (table (J, VIEW_PROGRAM_JOB_WORDS) int32, noise
     (n_noise, m, 3) float32, mask (n_mask, m) float32) in the record layout of include/geot_hip.h geot_view_program.
     Everything is checked here, on the host."""
-    need(len(jobs) >= 1, "view_program_views: at least one job")
-    m = int(m)
-    need(m >= 1, "view_program_views: m >= 1")
-    table = np.zeros((len(jobs), _lib.VIEW_PROGRAM_JOB_WORDS), dtype=np.int32)
-    as_f = table.view(np.float32)
-    noise, masks, seen = [], [], set()
-    for j, job in enumerate(jobs):
-        need(len(job) == 4 and isinstance(job[2], ViewProgram), "view_program_views: a job is (source row, output row, program, params)")
-        src, dst = int(job[0]), int(job[1])
-        need(0 <= src < n_rows, "view_program_views: job %d reads row %d of %d" % (j, src, n_rows))
-        need(0 <= dst < n_out and dst not in seen, "view_program_views: job %d writes row %d (of %d; each row once)" % (j, dst, n_out))
-        seen.add(dst)
-        ops, nz, mk = job[2].compile(job[3], m)
-        table[j, :5] = src, dst, len(ops), len(noise), len(masks)
-        noise += nz
-        masks += mk
-        for o, (kind, arg, floats) in enumerate(ops):
-            at = _HEADER_WORDS + o * _OP_WORDS
-            table[j, at], table[j, at + 1] = kind, arg
-            as_f[j, at + 2:at + 2 + len(floats)] = floats
-    noise = np.stack(noise) if noise else np.zeros((0, m, 3), np.float32)
-    masks = np.stack(masks) if masks else np.zeros((0, m), np.float32)
-    return table, noise, masks
-
-
-def _write_ops(table, j, ops):
-    as_f = table.view(np.float32)
-    for o, (kind, arg, floats) in enumerate(ops):
-        at = _HEADER_WORDS + o * _OP_WORDS
-        table[j, at], table[j, at + 1] = kind, arg
-        as_f[j, at + 2:at + 2 + len(floats)] = floats
+    return _pack_jobs(jobs, n_rows, n_out, m, "view_program_views", False)[:3]
 
 
 def pack_fixed_jobs(jobs, n_rows, n_out, m, views=None, slots=None):
@@ -424,22 +390,10 @@ def pack_fixed_jobs(jobs, n_rows, n_out, m, views=None, slots=None):
     float32): with params None the template table geot_view_draw starts from (noise and mask rows zero), else the records and
     rows these draws give.  views / slots: per job the view of its slot (0 only or labelled, 1 weak, 2 strong) and the slot
     whose draw id it uses; default 0 and the job's number."""
-    need(len(jobs) >= 1, "view_draw: at least one job")
-    m = int(m)
-    need(m >= 1, "view_draw: m >= 1")
-    table = np.zeros((len(jobs), _lib.VIEW_PROGRAM_JOB_WORDS), dtype=np.int32)
+    table, noise, masks, walked = _pack_jobs(jobs, n_rows, n_out, m, "view_draw", True)
     plans = np.zeros((len(jobs), _lib.VIEW_DRAW_PLAN_WORDS), dtype=np.int32)
     plans_f = plans.view(np.float32)
-    noise, masks, n_noise, n_mask, seen = [], [], 0, 0, set()
-    for j, job in enumerate(jobs):
-        need(len(job) == 4 and isinstance(job[2], ViewProgram), "view_draw: a job is (source row, output row, program, params)")
-        src, dst = int(job[0]), int(job[1])
-        need(0 <= src < n_rows, "view_draw: job %d reads row %d of %d" % (j, src, n_rows))
-        need(0 <= dst < n_out and dst not in seen, "view_draw: job %d writes row %d (of %d; each row once)" % (j, dst, n_out))
-        seen.add(dst)
-        fixed = job[2].compile_fixed(job[3], m)
-        table[j, :5] = src, dst, len(fixed["ops"]), n_noise, n_mask
-        _write_ops(table, j, fixed["ops"])
+    for j, fixed in enumerate(walked):
         view, slot = (0 if views is None else int(views[j])), (j if slots is None else int(slots[j]))
         need(view in (0, 1, 2) and 0 <= slot < 2 ** 31, "view_draw: a view is 0, 1 or 2, a slot a non-negative int")
         plans[j, :4] = view, slot, len(fixed["steps"]), fixed["store_at"]
@@ -447,12 +401,6 @@ def pack_fixed_jobs(jobs, n_rows, n_out, m, views=None, slots=None):
             at = 8 + 12 * k
             plans[j, at:at + 4] = kind, op, pos, flags
             plans_f[j, at + 4:at + 4 + len(consts)] = np.asarray(consts, dtype=np.float32)
-        n_noise += fixed["n_noise"]
-        n_mask += fixed["n_mask"]
-        noise += fixed["noise"] if job[3] is not None else [np.zeros((m, 3), np.float32)] * fixed["n_noise"]
-        masks += fixed["masks"] if job[3] is not None else [np.zeros(m, np.float32)] * fixed["n_mask"]
-    noise = np.stack(noise) if noise else np.zeros((0, m, 3), np.float32)
-    masks = np.stack(masks) if masks else np.zeros((0, m), np.float32)
     return table, plans, noise, masks
 
 

@@ -36,7 +36,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from .ext._common import call, knn_workspace, need, ptr
-from .openpoints.dataset.fixmatch_batch import _to_device
+from .openpoints.dataset.scan_set import _to_device
 from .pointnet2 import pointnet2_utils as pt_utils
 
 MAX_VERTICES = (1 << 31) - 1        # per scan (include/geot_hip.h geot_seg_confusion)

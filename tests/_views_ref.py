@@ -64,6 +64,25 @@ def norm_f32(q, center):
         return np.sqrt((c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1]) + c[:, 2] * c[:, 2]).max()
 
 
+def mean_tree_f64(q, threads=512, wave=64):
+    """The column means as the views kernels sum them (csrc/views.h), before the one rounding to fp32: thread t adds its
+    points t, t + 512, ... in index order onto 0 in fp64, a butterfly over each 64-lane wave (v += v[lane ^ d], d = 32 .. 1),
+    the wave sums added in wave order onto 0, one division by m.  Every step is one fp64 add, so numpy repeats it exactly."""
+    q = np.asarray(q, np.float32).astype(np.float64)
+    m = q.shape[0]
+    part = np.zeros((threads, 3))
+    for k0 in range(0, m, threads):
+        chunk = q[k0:k0 + threads]
+        part[:len(chunk)] = part[:len(chunk)] + chunk
+    v, lane = part.reshape(threads // wave, wave, 3), np.arange(wave)
+    for d in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, lane ^ d]
+    tot = np.zeros(3)
+    for w in range(threads // wave):
+        tot = tot + v[w, 0]
+    return tot / m
+
+
 def rotate_f64(pre, R, t):
     """fp64 rotation and shift of a given pre-rotation pos."""
     return np.asarray(pre, np.float64) @ np.asarray(R, np.float64).T + np.asarray(t, np.float64)

@@ -21,6 +21,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _view_program_ref as vpr  # noqa: E402
+import _views_ref as vr  # noqa: E402
 from _view_program_ref import fixture_params  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -97,6 +98,55 @@ def test_configured_lists_carry_the_bits_of_fixmatch_views(m):
         assert torch.isnan(got["pos"][2::3]).all() and torch.isfinite(got["pos"][0]).all()
     if m == 1:                                                   # 0 / 0, as the reference: NaN positions, finite x and heights
         assert torch.isnan(got["pos"]).all() and torch.isfinite(got["x"]).all() and torch.isfinite(got["heights"]).all()
+
+
+def _same_bits_off_nan(got, want):
+    """The NaNs where the restatement has them (positions, not payloads), identical bits everywhere else."""
+    got, want = np.asarray(got, np.float32), np.asarray(want, np.float32)
+    nan = np.isnan(want)
+    return got.shape == want.shape and np.array_equal(np.isnan(got), nan) and np.array_equal(_bits(got)[~nan], _bits(want)[~nan])
+
+
+@pytest.mark.parametrize("m, g", ((1, 1), (5, 1), (513, 1), (768, 0), (768, 1), (768, 2), (24576, 1), (24577, 1), (30000, 1)))
+def test_configured_lists_against_numpy_alone(m, g):
+    """The nine jobs of the test above with every output pinned by numpy, no second kernel: x and heights are the fp32
+    statements, view_center the reduction tree of csrc/views.h restated in fp64 (tests/_views_ref.py mean_tree_f64) and
+    rounded once, view_scale and pos the fp32 statements given those.  m = 1 and 5 stay below one wave, 513 is the first
+    wrap of the 512 threads, 24 576 / 24 577 lie on either side of the register / streaming switch, 30 000 is 59 streaming
+    rounds with a last chunk of 3 of VIEW_CHUNK = 4; g: the gravity column.  Where the restatement has a NaN, its place is
+    compared, not its sign and payload (which IEEE 754 leaves open, and numpy's subtract and the GPU's differ on: the heights
+    of the NaN cloud at g = 1 are finite - NaN); x is the input's own NaN through one multiply and carries identical bits."""
+    from geot_amd.openpoints.dataset import TOOTH_VIEW_KWARGS, ViewProgram, draw_view_params, view_program_views
+    lists = _configured()
+    kwargs = dict(TOOTH_VIEW_KWARGS, angle_s=[1, 1, 1], gravity_dim=g)          # real rotations
+    programs = {k: ViewProgram(v, kwargs) for k, v in lists.items()}
+    rng = np.random.default_rng(m)
+    raw = (rng.standard_normal((3, m, 3)) * np.array([.3, .2, .08]) + np.array([.1, -.2, .05])).astype(np.float32)
+    if m == 768:
+        raw[2, 17, 1] = np.nan
+    _seed(m)
+    jobs = []
+    for row, kind in enumerate(("train", "train_w", "train_s", "train", "train_s", "train_w", "train_s", "train", "train_w")):
+        p = draw_view_params(kind, kwargs)
+        jobs.append((row % 3, row, programs[kind], _as_program_params(lists[kind], p)))
+    got = view_program_views(torch.from_numpy(raw).to(DEV), jobs, 9)
+    got = {k: v.cpu().numpy() for k, v in got.items()}
+    for src, row, program, params in jobs:
+        f32 = vpr.run(raw[src], program.names, kwargs, params, np.float32)
+        q = f32["x"]                                             # the scaled cloud: what the centring op sums
+        center = vr.mean_tree_f64(q).astype(np.float32)
+        scale = np.float32(vr.norm_f32(q, center))
+        want = vpr.run(raw[src], program.names, kwargs, params, np.float32, stats=(center, scale))
+        same = {"x": _same_bits(got["x"][row], q.T), "heights": _same_bits_off_nan(got["heights"][row], f32["heights"]),
+                "view_center": _same_bits_off_nan(got["view_center"][row], center),
+                "view_scale": _same_bits_off_nan(got["view_scale"][row], scale),
+                "pos": _same_bits_off_nan(got["pos"][row], want["pos"])}
+        print("m=%d g=%d job %d (%d ops): %s" % (m, g, row, len(program.names), same))
+        assert all(same.values()), (m, g, row, same)
+    if m == 768:
+        assert np.isnan(got["pos"][2::3]).all() and np.isfinite(got["pos"][0]).all()
+    if m == 1:                                                   # 0 / 0, as the reference: NaN positions, finite x and heights
+        assert np.isnan(got["pos"]).all() and np.isfinite(got["x"]).all() and np.isfinite(got["heights"]).all()
 
 
 # ------------------------------------------------------------------------------------------------ 2. the fixture

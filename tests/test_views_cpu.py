@@ -125,6 +125,21 @@ def test_restatement_reproduces_the_fixture_within_e_ref(fx, case):
         assert np.array_equal(fx[case + "_u_" + k], fx[case + "_u_" + k + "_s"])
 
 
+@pytest.mark.parametrize("m", (1, 5, 513, 768, 24577, 30000))
+def test_the_restated_reduction_tree_is_the_fp64_mean_up_to_its_last_bits(m):
+    """Two orders of summing m fp64 numbers differ by at most 2 (m - 1) 2^-53 sum|q|: for the mean, 2 m 2^-53 mean|q|."""
+    rng = np.random.default_rng(m)
+    q = (rng.standard_normal((m, 3)) * np.array([.3, .2, .08]) + np.array([.1, -.2, .05])).astype(np.float32)
+    tree, mean = vr.mean_tree_f64(q), q.astype(np.float64).mean(axis=0)
+    bound = 2 * m * 2.0 ** -53 * np.abs(q.astype(np.float64)).mean(axis=0)
+    print("m=%d: |tree - np.mean| = %s (bound %s)" % (m, np.abs(tree - mean), bound))
+    assert tree.dtype == np.float64 and (np.abs(tree - mean) <= bound).all()
+    if m == 1:
+        assert np.array_equal(tree, q[0].astype(np.float64))
+    q[m // 2, 1] = np.nan                                     # a NaN vertex reaches its column alone
+    assert np.array_equal(np.isnan(vr.mean_tree_f64(q)), [False, True, False])
+
+
 def test_fixture_is_data_with_provenance(fx):
     meta = json.loads(str(fx["meta"]))
     assert meta["generator"] == "tests/golden/make_views_golden.py" and meta["provenance"]

@@ -213,6 +213,26 @@ def test_bits_given_the_kernels_statistics(m):
             assert _same_bits(np.float32(vr.norm_f32(vr.scaled(raw[i], p["s"]), v["view_center"][row])), v["view_scale"][row])
 
 
+def test_rotate_and_translate_are_independent_flags():
+    """One cloud, the four (rotate, translate) combinations in one launch, each held bit for bit to the fp32 statements
+    with the same flags given the kernel's statistics (the other tests set both flags or neither).  m = 768: two rounds
+    of the 512 threads, the second half empty."""
+    from geot_amd.openpoints.dataset import fixmatch_views
+    rng = np.random.default_rng(768)
+    raw = (rng.standard_normal((1, 768, 3)) * np.array([.3, .2, .08]) + np.array([.1, -.2, .05])).astype(np.float32)
+    s, R, t = rng.uniform(0.8, 1.2, 3).astype(np.float32), _rotation(rng), rng.uniform(0, 0.2, 3).astype(np.float32)
+    flags = [(False, False), (True, False), (False, True), (True, True)]
+    jobs = [(0, k, {"s": s, "R": R, "t": t, "rotate": rot, "translate": tr}) for k, (rot, tr) in enumerate(flags)]
+    v = {k: a.cpu().numpy() for k, a in fixmatch_views(torch.from_numpy(raw).to(DEV), jobs, 1, 4).items()}
+    for k, (rot, tr) in enumerate(flags):
+        want = vr.pos_f32_given_stats(raw[0], s, R, t, v["view_center"][k], v["view_scale"][k], rot, tr)
+        err = float(np.abs(v["pos"][k].astype(np.float64) - want.astype(np.float64)).max())
+        print("rotate %s translate %s: bits equal %s, |pos - fp32 statements| = %.3e" % (rot, tr, _same_bits(v["pos"][k], want), err))
+        assert _same_bits(v["pos"][k], want), (rot, tr, err)
+        assert _same_bits(v["x"][k], vr.scaled(raw[0], s).T) and _same_bits(v["view_center"][k], v["view_center"][0])
+    assert not _same_bits(v["pos"][1], v["pos"][0]) and not _same_bits(v["pos"][2], v["pos"][0]) and not _same_bits(v["pos"][3], v["pos"][1])
+
+
 # ------------------------------------------------------------------------------------------------ 4. the batched sampler
 RAGGED = (1, 700, 5000, 100000, 1234)
 

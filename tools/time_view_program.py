@@ -1,6 +1,7 @@
-"""Transform lists as view programs (geot_view_program), timed.  Report only: nothing here is a gate.
+"""Transform lists as view programs (geot_view_program), timed.  A report; leg (iii) also prints the comparison that decides
+whether the hard-wired views kernel can be retired.
 
-    python tools/time_view_program.py [--reps 60] [--warmup 8] [--legs i,ii]
+    python tools/time_view_program.py [--reps 60] [--warmup 8] [--legs i,ii,iii]
 
 (i)  one supervised batch at the configured size, 8 scans x 24 000 points of ~1e5-vertex scans, default.yaml's `train` list:
      SupervisedBatcher.batch (geot_cloud_sample_batch + ONE geot_view_program launch) against the same batch composed from
@@ -10,6 +11,11 @@
 (ii) the three configured FixMatch lists, 2 labelled + 2 weak + 2 strong views (the configured batch: 6 jobs), through
      view_program_views and through fixmatch_views (geot_fixmatch_views, the kernel FixMatchBatcher keeps by default), at
      m = 16 000 and 24 000 (register-resident) and 30 000 (streaming).
+(iii) one FixMatch batch, B_l = B_u = 2 on the same scans, at m = 16 000 and 24 000: FixMatchBatcher.batch(idx_l, idx_u,
+     sel_l=, sel_u=, params=) with everything given, so the host draws nothing, once from a batcher built with
+     transforms=None (params are s / R / t dicts) and once from one built with transforms=CONFIGURED_LISTS (params are
+     ViewProgram.draw lists holding the same values).  Where the two are two kernels this is the comparison of the batch a
+     training loop pays for; the line `gate` holds the second to the first's median plus the first's own p10 .. p90 spread.
 
 The legs of a pair alternate after warm-up.  Per repetition two figures: `dev` = the time between two events recorded on the
 stream around the call (the device's view: kernels, copies and any gap the host leaves between them) and `wall` = the
@@ -27,8 +33,10 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from geot_amd.openpoints.dataset import (DEFAULT_TRAIN, DEFAULT_TRAIN_KWARGS, TOOTH_VIEW_KWARGS, DeviceScanSet, SupervisedBatcher,  # noqa: E402
-                                         ViewProgram, cloud_sample_batch, draw_view_params, fixmatch_views, view_program_views)
+from geot_amd.openpoints.dataset import (DEFAULT_TRAIN, DEFAULT_TRAIN_KWARGS, TOOTH_VIEW_KWARGS, DeviceScanSet, FixMatchBatcher,  # noqa: E402
+                                         SupervisedBatcher, ViewProgram, cloud_sample_batch, draw_view_params, fixmatch_views,
+                                         view_program_views)
+from geot_amd.openpoints.dataset.fixmatch_batch import CONFIGURED_LISTS  # noqa: E402
 
 DEV = torch.device("cuda:0")
 B, M, VERTICES = 8, 24000, (100003, 98765, 120011, 90001, 110503, 99991, 104729, 95003)
@@ -38,10 +46,10 @@ CONFIGURED = {"train": ["PointsToTensor", "PointCloudScaling", "PointCloudCenter
                           "PointCloudTranslation_s"]}
 
 
-def scans():
+def scans(part=slice(None)):
     rng = np.random.default_rng(3)
     pts = [(rng.standard_normal((n, 3)) * np.array([30, 20, 8]) + np.array([250, -400, 120])).astype(np.float32) for n in VERTICES]
-    return DeviceScanSet(pts, [rng.integers(0, 17, n).astype(np.int32) for n in VERTICES], device=DEV)
+    return DeviceScanSet(pts[part], [rng.integers(0, 17, n).astype(np.int32) for n in VERTICES][part], device=DEV)
 
 
 def measure(legs, reps, warmup):
@@ -156,6 +164,39 @@ def leg_ii(reps, warmup):
         print("  program / views (median dev): %.2f" % (p / h))
 
 
+def _as_lists(kind, p):
+    """The s / R / t dict of one view as the ViewProgram.draw list of its configured list."""
+    pick = {"PointCloudScaling": {"scale": p["s"]}, "PointCloudScaling_s": {"scale": p["s"]},
+            "PointCloudRotation_s": {"R": p["R"]}, "PointCloudTranslation_s": {"t": p["t"]}}
+    return [dict(pick.get(n, {})) for n in CONFIGURED_LISTS[kind]]
+
+
+def leg_iii(reps, warmup):
+    print("(iii) FixMatchBatcher.batch, B_l = B_u = 2, sel and params given; transforms=None against transforms=CONFIGURED_LISTS")
+    lab, unl = scans(slice(0, 4)), scans(slice(4, 8))
+    idx_l, idx_u = [0, 1], [2, 3]
+    for m in (16000, 24000):
+        none = FixMatchBatcher(lab, unl, m)
+        lists = FixMatchBatcher(lab, unl, m, transforms=CONFIGURED_LISTS)
+        np.random.seed(m)
+        torch.manual_seed(m)
+        sel, params = none.draw(idx_l, idx_u)
+        as_lists = [_as_lists("train", p) for p in params[:2]] + [(_as_lists("train_w", w), _as_lists("train_s", s)) for w, s in params[2:]]
+        hard = lambda: none.batch(idx_l, idx_u, sel_l=sel[:2], sel_u=sel[2:], params=params)         # noqa: E731
+        prog = lambda: lists.batch(idx_l, idx_u, sel_l=sel[:2], sel_u=sel[2:], params=as_lists)     # noqa: E731
+        a, b = hard(), prog()
+        torch.cuda.synchronize()
+        same = all(torch.equal(a[i][k].view(torch.int32), b[i][k].view(torch.int32)) for i in (0, 1) for k in a[i] if a[i][k].dtype == torch.float32)
+        res = measure({"none": hard, "lists": prog}, reps, warmup)
+        print("  m = %d, bits equal: %s" % (m, same))
+        line("(iii)", "transforms=None", res["none"], kernels(hard))
+        line("(iii)", "transforms=CONFIGURED_LISTS", res["lists"], kernels(prog))
+        for what, h, p in (("dev", res["none"][0], res["lists"][0]), ("wall", res["none"][1], res["lists"][1])):
+            bound = np.median(h) + np.percentile(h, 90) - np.percentile(h, 10)
+            print("  gate %-4s lists median %7.3f ms <= None median + its p10 .. p90 spread %7.3f ms: %s"
+                  % (what, np.median(p), bound, "holds" if np.median(p) <= bound else "FAILS"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=60)
@@ -167,6 +208,8 @@ def main():
         leg_i(args.reps, args.warmup)
     if "ii" in args.legs.split(","):
         leg_ii(args.reps, args.warmup)
+    if "iii" in args.legs.split(","):
+        leg_iii(args.reps, args.warmup)
 
 
 if __name__ == "__main__":
