@@ -20,6 +20,7 @@
 // Algorithmic bytes (forward): 4 (Co Nk + Co Nq) reads + 4 Nq k (indices) + Co Nq (4 + 4 + 1 + 4) writes per cloud.
 #include "geot_common.h"
 #include "geot_hip.h"
+#include "rix.h"
 
 namespace geot {
 
@@ -357,26 +358,9 @@ __global__ __launch_bounds__(256) void edge_bwd_coef_kernel(int b, int c, int gr
 //   = rstd (a_i - k s1 - s2 rstd (ysum_i - k mean)): element-wise over rows that backward 4 stages anyway, so it is written
 //   there (one more read, one write in the staging loop instead of a pass that reloads ysel and grad_out).
 
-// ---- reverse index of idx: pairs (i, j) grouped by (batch, target n) ------------------------------------------
-__global__ __launch_bounds__(256) void edge_rix_count_kernel(long long total, long long per_batch, int nk,
-                                                             const int *__restrict__ idx, int *__restrict__ cnt,
-                                                             int *__restrict__ rank)
-{
-    const long long x = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (x >= total) return;
-    const int bi = (int)(x / per_batch);
-    rank[x] = atomicAdd(&cnt[(size_t)bi * nk + idx[x]], 1);
-}
-__global__ __launch_bounds__(256) void edge_rix_fill_kernel(long long total, long long per_batch, int nk,
-                                                            const int *__restrict__ idx, const int *__restrict__ off,
-                                                            const int *__restrict__ rank, int *__restrict__ rev)
-{
-    const long long x = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (x >= total) return;
-    const int bi = (int)(x / per_batch);
-    rev[off[(size_t)bi * nk + idx[x]] + rank[x]] = (int)(x - (long long)bi * per_batch); // pair id i*k + j within the batch
-}
-// reproducible order: the pair ids of a target ascending (geot_common.h rix_sorted_position); tmp = the first fill
+// ---- reverse index of idx: pairs (i, j) grouped by (batch, target n) (rix_build_lists, csrc/rix.h) -------------
+// the payload: pair id i*k + j within the batch, the ids of a target ascending (tmp: global pair ids by list, the same
+// order within a batch; null: arrival order)
 __global__ __launch_bounds__(256) void edge_rix_place_kernel(long long total, long long per_batch, int nk,
                                                              const int *__restrict__ idx, const int *__restrict__ off,
                                                              const int *__restrict__ rank, const int *__restrict__ tmp,
@@ -386,8 +370,8 @@ __global__ __launch_bounds__(256) void edge_rix_place_kernel(long long total, lo
     if (x >= total) return;
     const int bi = (int)(x / per_batch);
     const size_t tgt = (size_t)bi * nk + idx[x];
-    const int a = off[tgt], z = off[tgt + 1], mine = (int)(x - (long long)bi * per_batch);
-    rev[a + rix_sorted_position(tmp, a, z, mine, rank[x])] = mine;
+    const int a = off[tgt], z = off[tgt + 1];
+    rev[a + rix_sorted_position(tmp, a, z, (int)x, rank[x])] = (int)(x - (long long)bi * per_batch);
 }
 
 // ---- backward 4: d/dP[b,c,n] = sum over the pairs (i,j) with idx[b,i,j] == n of dy_ij ---------------------------
@@ -713,19 +697,11 @@ static inline EcRix ec_rix_layout(int b, int nq, int nk, int k)
 static hipError_t ec_rix_build(int b, int nq, int nk, int k, const int *idx, int *ws, hipStream_t s)
 {
     const EcRix r = ec_rix_layout(b, nq, nk, k);
-    int *off = ws + r.off, *rank = ws + r.rank, *rev = ws + r.rev;
-    hipError_t e = zero_words(off, r.t + 1, s);
+    int *off = ws + r.off, *rank = ws + r.rank, *tmp = rix_reproducible() ? ws + r.tmp : nullptr;   // fixed summation order
+    hipError_t e = rix_build_lists(b, nq, nk, k, 1, nq, idx, nullptr, off, ws + r.bsum, rank, tmp, s);
     if (e != hipSuccess) return e;
-    const int pb = (int)((r.pairs + 255) / 256);
-    hipLaunchKernelGGL(edge_rix_count_kernel, dim3(pb), dim3(256), 0, s, r.pairs, (long long)nq * k, nk, idx, off, rank);
-    exclusive_scan_i32((int)r.t, off, ws + r.bsum, nullptr, s);
-    if (rix_reproducible()) {   // fill pair ids in arrival order, then place them in ascending order: fixed summation order
-        int *tmp = ws + r.tmp;
-        hipLaunchKernelGGL(edge_rix_fill_kernel, dim3(pb), dim3(256), 0, s, r.pairs, (long long)nq * k, nk, idx, off, rank, tmp);
-        hipLaunchKernelGGL(edge_rix_place_kernel, dim3(pb), dim3(256), 0, s, r.pairs, (long long)nq * k, nk, idx, off, rank, tmp, rev);
-    } else {
-        hipLaunchKernelGGL(edge_rix_fill_kernel, dim3(pb), dim3(256), 0, s, r.pairs, (long long)nq * k, nk, idx, off, rank, rev);
-    }
+    hipLaunchKernelGGL(edge_rix_place_kernel, dim3((unsigned)((r.pairs + 255) / 256)), dim3(256), 0, s, r.pairs, (long long)nq * k, nk,
+                       idx, off, rank, tmp, ws + r.rev);
     return hipGetLastError();
 }
 

@@ -17,6 +17,7 @@
 // cloud is 96 KB).
 #include "geot_common.h"
 #include "geot_hip.h"
+#include "rix.h"
 #include "tile_scatter.h"
 #include <cstdlib>
 
@@ -513,44 +514,12 @@ static hipError_t tlds_gather(const TldsPlan &p, int b, int c, int m, int L, con
 }
 // ---- gradients of the gathers as gathers: reverse index + source rows in LDS --------------------
 // grad_table[b,c,j] += sum over the (e,t) with idx[b,e,t] == j of w[b,e,t] * grad_out[b,c,e].
-// The pairs are grouped by target once per call (count with rank, exclusive scan, fill: three small
-// kernels, no atomics in the fill because the count pass already handed out the ranks); then a workgroup
-// keeps `ch` rows of grad_out (L floats each) in LDS and every thread sums one target's list from LDS:
-// no float atomics at all, and grad_out is read exactly once.  Needs L <= TLDS_FLOATS (the prop0/1/2
-// interpolations, the kNN graph features, the 512-group gather; not the 6000 x 32 SA grouping).
-// The L sources of a batch are cut into Q parts of `partlen` (Q = 1: one part); pairs are grouped by
-// (batch, part, target), so that a workgroup holding the rows of ONE part in LDS finds exactly its entries.
-__global__ __launch_bounds__(256) void rix_count_kernel(long long total, long long per_batch, int m, int nt, int Q,
-                                                        int partlen, const int *__restrict__ idx,
-                                                        int *__restrict__ cnt, int *__restrict__ rank,
-                                                        const int *__restrict__ remap = nullptr)
-{   // remap (b, m), Q == 1 only: the number under which a target is filed (the point-major walk's target order)
-    const long long x = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (x >= total) return;
-    const int bi = (int)(x / per_batch);
-    const int e = (int)((x - (long long)bi * per_batch) / nt), part = e / partlen;
-    const int j = remap ? remap[(size_t)bi * m + idx[x]] : idx[x];
-    rank[x] = atomicAdd(&cnt[((size_t)bi * Q + part) * m + j], 1);
-}
-template <bool WEIGHTED>
-__global__ __launch_bounds__(256) void rix_fill_kernel(long long total, long long per_batch, int m, int nt, int Q,
-                                                       int partlen, const int *__restrict__ idx,
-                                                       const float *__restrict__ weight, const int *__restrict__ off,
-                                                       const int *__restrict__ rank, int *__restrict__ rev,
-                                                       float *__restrict__ revw, int *__restrict__ tmp,
-                                                       const int *__restrict__ remap = nullptr)
-{
-    const long long x = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (x >= total) return;
-    const int bi = (int)(x / per_batch);
-    const int e = (int)((x - (long long)bi * per_batch) / nt), part = e / partlen;
-    const int j = remap ? remap[(size_t)bi * m + idx[x]] : idx[x];
-    const int pos = off[((size_t)bi * Q + part) * m + j] + rank[x];
-    if (tmp) { tmp[pos] = (int)x; return; } // reproducible build: pair ids first, placed by rix_place_kernel
-    rev[pos] = e - part * partlen; // source element within its part
-    if (WEIGHTED) revw[pos] = weight[x];
-}
-// second phase of the reproducible build: pair x goes to its position in ascending pair-id order within its list
+// The pairs are grouped by target once per call (rix_build_lists, csrc/rix.h: by (batch, part, target) where the L sources
+// are cut into parts); then a workgroup keeps `ch` rows of grad_out (L floats each) in LDS and every thread sums one
+// target's list from LDS: no float atomics at all, and grad_out is read exactly once.  Needs L <= TLDS_FLOATS (the
+// prop0/1/2 interpolations, the kNN graph features, the 512-group gather; not the 6000 x 32 SA grouping).
+// The list walk's payload: pair x goes to its position in ascending pair-id order within its list (tmp null,
+// GEOT_REPRODUCIBLE=0: in arrival order) as (source element within its part, weight)
 template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void rix_place_kernel(long long total, long long per_batch, int m, int nt, int Q,
                                                         int partlen, const int *__restrict__ idx,
@@ -1033,28 +1002,42 @@ static inline SellPlan sell_plan(int b, int Q, int m, int partlen, int nt)
     return p;
 }
 
+// Q > 1 parts are looped inside the workgroup (grid z = b) unless the targets are too many for its threads' registers or
+// GEOT_GATHER_IMPL=atomic asks for the per-part kernel with float atomics (A/B runs); else one launch slice per (batch, part)
+static bool csr_parts_inside(int b, int m, int Q)
+{
+    const char *env = getenv("GEOT_GATHER_IMPL");
+    return Q > 1 && m <= 16 * TLDS_THREADS && b <= 65535 && !(env && env[0] == 'a');
+}
+// every limit of scatter_via_csr: what holds here is launched there
 static bool csr_applies(int b, int c, int m, long long L, int nt, long long ws_floats)
 {
     const char *env = getenv("GEOT_GATHER_IMPL");
     if ((env && env[0] == 'p') || L < 1 || L > TLDS_FLOATS || L * c < (1 << 16)) return false;
+    const int Q = rix_plan(c, L).Q;
     return ws_floats >= rix_ws_ints(b, c, m, L, nt) && (long long)b * L * nt <= 0x7fffffffLL &&
-           (long long)b * rix_plan(c, L).Q * m <= 0x7ffffff0LL;
+           (long long)b * Q * m <= 0x7ffffff0LL && (csr_parts_inside(b, m, Q) || (long long)b * Q <= 65535);   // (grid z)
 }
 
 // Few targets with long lists (the FP modules that interpolate from the 512 group centres: 24-48 pairs per target):
 // whole rows of grad_out fit LDS (Q = 1), one lane group per target walks its list -- one writer per element, fixed order,
 // and 2x faster there than the sorted pair stream of tile_scatter.hip, which pays for a segmented sum per chunk when most
 // pairs of a tile share their target (profiles/r05_tile_scatter.txt).  The pair stream takes everything else.
+// (the shape half, which geot_scatter_grad_ws_floats sizes the workspace by: whole rows in one part, lists of 12 and more)
+static bool csr_rows_shape(int c, int m, long long L, int nt)
+{
+    return L >= 1 && L <= TLDS_FLOATS && m >= 1 && nt >= 1 && rix_plan(c, L).Q == 1 && (double)L * nt >= 12.0 * m;
+}
 static bool csr_preferred(int b, int c, int m, long long L, int nt)
 {
     const char *env = getenv("GEOT_GATHER_IMPL");
     if (env && env[0]) return env[0] != 't' && env[0] != 'p';       // forced: tiles / plain -> no; csr / sell / atomic -> as before
-    return L >= 1 && m >= 1 && rix_plan(c, L).Q == 1 && (double)L * nt >= 12.0 * m &&
-           csr_applies(b, c, m, L, nt, rix_ws_ints(b, c, m, L, nt));
+    return csr_rows_shape(c, m, L, nt) && csr_applies(b, c, m, L, nt, rix_ws_ints(b, c, m, L, nt));
 }
 
-// The form a *_grad_ws / _grad_out / _grad_from call takes for these sizes -- the one decision behind their launches,
-// geot_grad_ws_needs_zero and the host-only query geot_scatter_grad_plan.  tp receives the tile plan of GRAD_TILES.
+// The form a *_grad_ws / _grad_out / _grad_from call takes for these sizes -- the one decision behind their launches
+// (scatter_grad_dispatch), geot_grad_ws_needs_zero and the host-only query geot_scatter_grad_plan.  tp receives the tile
+// plan of GRAD_TILES.
 enum GradForm { GRAD_NONE = 0, GRAD_TILES = 1, GRAD_CSR = 2, GRAD_CL = 3 };
 static GradForm grad_form(int b, int c, int m, long long L, int nt, bool weighted, TsPlan *tp = nullptr)
 {
@@ -1067,7 +1050,7 @@ static GradForm grad_form(int b, int c, int m, long long L, int nt, bool weighte
     return csr_applies(b, c, m, L, nt, geot_scatter_grad_ws_floats(b, c, m, L, nt, weighted)) ? GRAD_CSR : GRAD_CL;
 }
 
-// returns hipErrorNotSupported when this path does not apply (caller falls back)
+// returns hipErrorNotSupported when this path does not apply (csr_applies; the caller falls back)
 template <int NT, bool WEIGHTED>
 static hipError_t scatter_via_csr(int b, int c, int m, int L, size_t src_bstride, const float *grad_out,
                                   const int *idx, const float *weight, float *grad_table, float *workspace,
@@ -1084,22 +1067,15 @@ static hipError_t scatter_via_csr(int b, int c, int m, int L, size_t src_bstride
     int *rank = bsum + scan_blocks(t);
     int *rev = rank + pairs;
     float *revw = (float *)(rev + pairs);
-    hipError_t e = zero_words(off, t + 1, s);
+    int *tmp = rix_reproducible() ? (int *)(revw + pairs) : nullptr;   // fixed list order = fixed summation order
+    hipError_t e = rix_build_lists(b, L, m, NT, Q, rp.partlen, idx, nullptr, off, bsum, rank, tmp, s);
     if (e != hipSuccess) return e;
-    const int pb = (int)((pairs + 255) / 256);
-    hipLaunchKernelGGL(rix_count_kernel, dim3(pb), dim3(256), 0, s, pairs, (long long)L * NT, m, NT, Q, rp.partlen, idx,
-                       off, rank);
-    exclusive_scan_i32((int)t, off, bsum, nullptr, s);
-    int *tmp = rix_reproducible() ? (int *)(revw + pairs) : nullptr;
-    hipLaunchKernelGGL((rix_fill_kernel<WEIGHTED>), dim3(pb), dim3(256), 0, s, pairs, (long long)L * NT, m, NT, Q,
-                       rp.partlen, idx, weight, off, rank, rev, revw, tmp);
-    if (tmp)   // fixed list order = fixed summation order: reproducible gradients
-        hipLaunchKernelGGL((rix_place_kernel<WEIGHTED>), dim3(pb), dim3(256), 0, s, pairs, (long long)L * NT, m, NT, Q,
-                           rp.partlen, idx, weight, off, rank, tmp, rev, revw);
+    hipLaunchKernelGGL((rix_place_kernel<WEIGHTED>), dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, pairs,
+                       (long long)L * NT, m, NT, Q, rp.partlen, idx, weight, off, rank, tmp, rev, revw);
     const size_t lds = (size_t)ch * rp.partlen * sizeof(float);
     const int chunks = (c + ch - 1) / ch;
-    const char *impl = getenv("GEOT_GATHER_IMPL");           // "atomic": the per-part kernel + float atomics (A/B runs)
-    const bool parts_inside = Q > 1 && m <= 16 * TLDS_THREADS && b <= 65535 && !(impl && impl[0] == 'a');
+    const char *impl = getenv("GEOT_GATHER_IMPL");
+    const bool parts_inside = csr_parts_inside(b, m, Q);
     const int set = overwrite && (parts_inside || Q == 1) ? 1 : 0;
     if (overwrite && !set) {
         e = zero_words(grad_table, (long long)b * c * m, s);
@@ -1166,7 +1142,6 @@ static hipError_t scatter_via_csr(int b, int c, int m, int L, size_t src_bstride
     long long slices = (512 + (long long)chunks * b * Q - 1) / ((long long)chunks * b * Q);
     if (slices > m / 1024) slices = m / 1024;
     if (slices < 1) slices = 1;
-    if ((long long)b * Q > 65535) return hipErrorNotSupported;
     const dim3 grid((int)slices, chunks, b * Q);
 #define GEOT_CSR_LAUNCH2(CHV, LPTV)                                                                               \
     {                                                                                                            \
@@ -1817,6 +1792,54 @@ static inline dim3 grid1(long long total)
     return dim3((unsigned)blocks);
 }
 
+// ---- the one launch behind the *_grad_ws / _grad_out / _grad_from entry points ------------------------------------------
+// grad_table (b, c, m) (+)= the pairs of idx / weight (b, L, nt) scattered from grad_out (b, c, L), in the form grad_form
+// names.  A form that refuses at launch (hipErrorNotSupported: a workspace off 8 bytes, no LDS grant) falls through, tiles
+// -> list walk -> fallback; the accumulator fallback then clears what the caller was told it need not clear.
+enum GradFallback { FALLBACK_CL, FALLBACK_ATOMIC };   // channels-last accumulator + transpose_add | geot_gather_points_grad
+struct ScatterGrad {
+    int b, c, m, L, nt;
+    bool weighted;                  // nt == 3 with weights (three_interpolate) or nt == 1 without
+    size_t src_bstride;
+    const float *grad_out;
+    const int *idx;
+    const float *weight;
+    float *grad_table, *workspace;
+    bool overwrite;                 // grad_table and the workspace arrive uninitialised, every element is written
+    GradFallback fallback;
+};
+static int scatter_grad_dispatch(const ScatterGrad &d, hipStream_t s)
+{
+    const int b = d.b, c = d.c, m = d.m, L = d.L;
+    const long long wsf = geot_scatter_grad_ws_floats(b, c, m, L, d.nt, d.weighted);
+    const GradForm f = grad_form(b, c, m, L, d.nt, d.weighted);
+    hipError_t e = hipErrorNotSupported;
+    if (f == GRAD_TILES)
+        e = scatter_via_tiles(b, c, m, L, d.nt, d.src_bstride, d.grad_out, d.idx, d.weight, d.grad_table, d.workspace, wsf, s,
+                              d.overwrite);
+    if (e == hipErrorNotSupported && f != GRAD_CL)
+        e = d.weighted ? scatter_via_csr<3, true>(b, c, m, L, d.src_bstride, d.grad_out, d.idx, d.weight, d.grad_table,
+                                                  d.workspace, wsf, s, d.overwrite)
+                       : scatter_via_csr<1, false>(b, c, m, L, d.src_bstride, d.grad_out, d.idx, nullptr, d.grad_table,
+                                                   d.workspace, wsf, s, d.overwrite);
+    if (e != hipErrorNotSupported) return e;
+    if (d.fallback == FALLBACK_ATOMIC) return geot_gather_points_grad(b, c, m, L, d.grad_out, d.idx, d.grad_table, s);
+    // the channels-last scatter accumulates in the workspace and adds into grad_table
+    e = d.overwrite ? zero_words(d.grad_table, (long long)b * c * m, s) : hipSuccess;
+    if (e == hipSuccess && (d.overwrite || f != GRAD_CL)) e = zero_words(d.workspace, (long long)b * c * m, s);
+    if (e != hipSuccess) return e;
+    const dim3 g1((unsigned)(((long long)L + SC_TILE - 1) / SC_TILE), (c + SC_TILE - 1) / SC_TILE, b);
+    const dim3 g2((m + SC_TILE - 1) / SC_TILE, g1.y, b);
+    if (d.weighted)
+        hipLaunchKernelGGL((scatter_rows_cl_kernel<3, true>), g1, dim3(256), 0, s, c, L, m, d.grad_out, d.src_bstride, d.idx,
+                           d.weight, d.workspace);
+    else
+        hipLaunchKernelGGL((scatter_rows_cl_kernel<1, false>), g1, dim3(256), 0, s, c, L, m, d.grad_out, d.src_bstride, d.idx,
+                           nullptr, d.workspace);
+    hipLaunchKernelGGL(transpose_add_kernel, g2, dim3(256), 0, s, c, m, d.workspace, d.grad_table);
+    return hipGetLastError();
+}
+
 } // namespace geot
 
 using namespace geot;
@@ -1854,17 +1877,8 @@ GEOT_EXPORT int geot_gather_points_grad_ws(int b, int c, int n, int m, const flo
 {
     if (b < 0 || c < 0 || n < 0 || m < 0 || !workspace) return hipErrorInvalidValue;
     if (b == 0 || c == 0 || m == 0 || n == 0) return hipSuccess;
-    const long long wsf = geot_scatter_grad_ws_floats(b, c, n, m, 1, 0);
-    hipError_t e = grad_form(b, c, n, m, 1, false) != GRAD_TILES
-                          ? hipErrorNotSupported
-                          : scatter_via_tiles(b, c, n, m, 1, (size_t)c * m, grad_out, idx, nullptr, grad_points, workspace, wsf,
-                                              (hipStream_t)stream, false);
-    if (e != hipErrorNotSupported) return e;
-    if (b <= 65535) {
-        e = scatter_via_csr<1, false>(b, c, n, m, (size_t)c * m, grad_out, idx, nullptr, grad_points, workspace, wsf, (hipStream_t)stream);
-        if (e != hipErrorNotSupported) return e;
-    }
-    return geot_gather_points_grad(b, c, n, m, grad_out, idx, grad_points, stream);
+    return scatter_grad_dispatch({b, c, n, m, 1, false, (size_t)c * m, grad_out, idx, nullptr, grad_points, workspace, false,
+                                  FALLBACK_ATOMIC}, (hipStream_t)stream);
 }
 
 GEOT_EXPORT int geot_group_points(int b, int c, int n, int npoints, int nsample, const float *points,
@@ -1990,8 +2004,7 @@ GEOT_EXPORT long long geot_scatter_grad_ws_floats(int b, int c, int m, long long
 {
     if (b < 1 || c < 1 || m < 1) return 0;
     const long long base = (long long)b * m * c, tiles = L > 0 && nt > 0 ? ts_ws_ints(b, c, m, L, nt, weighted != 0) : 0;
-    const long long rows = L > 0 && nt > 0 && L <= TLDS_FLOATS && rix_plan(c, L).Q == 1 && (double)L * nt >= 12.0 * m
-                               ? rix_ws_ints(b, c, m, L, nt) : 0;           // the whole-rows gather (csr_preferred)
+    const long long rows = csr_rows_shape(c, m, L, nt) ? rix_ws_ints(b, c, m, L, nt) : 0;   // the whole-rows gather (csr_preferred)
     return base > tiles ? (base > rows ? base : rows) : (tiles > rows ? tiles : rows);
 }
 
@@ -2003,27 +2016,8 @@ static int three_interpolate_grad_launch(int b, int c, int n, int m, const float
     if (b == 0 || c == 0 || m == 0) return hipSuccess;
     if (n == 0) return overwrite ? (int)zero_words(grad_points, (long long)b * c * m, s) : (int)hipSuccess;
     if (b > 65535) return hipErrorInvalidValue;
-    {
-        const long long wsf = geot_scatter_grad_ws_floats(b, c, m, n, 3, 1);
-        hipError_t e = grad_form(b, c, m, n, 3, true) != GRAD_TILES ? hipErrorNotSupported
-                                                                : scatter_via_tiles(b, c, m, n, 3, grad_bstride, grad_out, idx, weight, grad_points,
-                                                                        workspace, wsf, s, overwrite);
-        if (e != hipErrorNotSupported) return e;
-        e = scatter_via_csr<3, true>(b, c, m, n, grad_bstride, grad_out, idx, weight, grad_points, workspace,
-                                                wsf, s, overwrite);
-        if (e != hipErrorNotSupported) return e;
-    }
-    if (overwrite) {   // the channels-last scatter accumulates in the workspace and adds into grad_points
-        hipError_t e = zero_words(grad_points, (long long)b * c * m, s);
-        if (e == hipSuccess) e = zero_words(workspace, (long long)b * c * m, s);
-        if (e != hipSuccess) return e;
-    }
-    dim3 g1((n + SC_TILE - 1) / SC_TILE, (c + SC_TILE - 1) / SC_TILE, b);
-    hipLaunchKernelGGL((scatter_rows_cl_kernel<3, true>), g1, dim3(256), 0, s, c, n, m, grad_out, grad_bstride, idx, weight,
-                       workspace);
-    dim3 g2((m + SC_TILE - 1) / SC_TILE, (c + SC_TILE - 1) / SC_TILE, b);
-    hipLaunchKernelGGL(transpose_add_kernel, g2, dim3(256), 0, s, c, m, workspace, grad_points);
-    return hipGetLastError();
+    return scatter_grad_dispatch({b, c, m, n, 3, true, grad_bstride, grad_out, idx, weight, grad_points, workspace, overwrite,
+                                  FALLBACK_CL}, s);
 }
 
 GEOT_EXPORT int geot_three_interpolate_grad_ws(int b, int c, int n, int m, const float *grad_out,
@@ -2070,22 +2064,16 @@ GEOT_EXPORT int geot_rix_build(int b, int L, int m, int nt, const int *idx, cons
     if (ws_ints < r.ints || r.pairs > 0x7ffffff0LL || r.t > 0x7ffffff0LL || (long long)b * L > 0x7fffffffLL)
         return hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
-    int *off = ws + r.off;
-    hipError_t e = zero_words(off, r.t + 1, s);
-    if (e != hipSuccess || r.pairs == 0) return e;
-    int *rank_of = nullptr;
-    if (order) {
-        rank_of = ws + r.rank_of;
+    int *off = ws + r.off, *rank_of = order && r.pairs ? ws + r.rank_of : nullptr;
+    if (rank_of)
         hipLaunchKernelGGL(invert_order_kernel, dim3((unsigned)((r.t + 255) / 256)), dim3(256), 0, s, r.t, m, order, rank_of);
-    }
+    // pair ids into the lists first (any order), then every pair to its slot in ascending pair order, whatever
+    // GEOT_REPRODUCIBLE says: the index may outlive the setting
+    hipError_t e = rix_build_lists(b, L, m, nt, 1, L, idx, rank_of, off, ws + r.bsum, ws + r.rank, ws + r.tmp, s);
+    if (e != hipSuccess || r.pairs == 0) return e;
     const int pb = (int)((r.pairs + 255) / 256);
     const long long pbatch = (long long)L * nt;
-    hipLaunchKernelGGL(rix_count_kernel, dim3(pb), dim3(256), 0, s, r.pairs, pbatch, m, nt, 1, L, idx, off, ws + r.rank, rank_of);
-    exclusive_scan_i32((int)r.t, off, ws + r.bsum, nullptr, s);
     float *revw = (float *)(ws + r.revw);
-    // pair ids into the lists first (any order), then every pair to its slot in ascending pair order
-    hipLaunchKernelGGL((rix_fill_kernel<false>), dim3(pb), dim3(256), 0, s, r.pairs, pbatch, m, nt, 1, L, idx, nullptr, off,
-                       ws + r.rank, ws + r.rev, revw, ws + r.tmp, rank_of);
     if (weight)
         hipLaunchKernelGGL((rix_place_cl_kernel<true>), dim3(pb), dim3(256), 0, s, r.pairs, pbatch, m, nt, L, idx, weight, rank_of,
                            off, ws + r.rank, ws + r.tmp, ws + r.rev, revw, (unsigned *)(ws + r.rtgt));
@@ -2198,23 +2186,8 @@ GEOT_EXPORT int geot_group_points_grad_ws(int b, int c, int n, int npoints, int 
     long long npns = (long long)npoints * nsample;
     if (b == 0 || c == 0 || npns == 0 || n == 0) return hipSuccess;
     if (npns > 0x7fffffffLL || b > 65535) return hipErrorInvalidValue;
-    {
-        const long long wsf = geot_scatter_grad_ws_floats(b, c, n, npns, 1, 0);
-        hipError_t e = grad_form(b, c, n, npns, 1, false) != GRAD_TILES ? hipErrorNotSupported
-                                                                   : scatter_via_tiles(b, c, n, (int)npns, 1, (size_t)c * npns, grad_out, idx, nullptr,
-                                                                           grad_points, workspace, wsf, (hipStream_t)stream, false);
-        if (e != hipErrorNotSupported) return e;
-        e = scatter_via_csr<1, false>(b, c, n, (int)npns, (size_t)c * npns, grad_out, idx, nullptr, grad_points, workspace,
-                                                 wsf, (hipStream_t)stream);
-        if (e != hipErrorNotSupported) return e;
-    }
-    dim3 g1((unsigned)((npns + SC_TILE - 1) / SC_TILE), (c + SC_TILE - 1) / SC_TILE, b);
-    hipLaunchKernelGGL((scatter_rows_cl_kernel<1, false>), g1, dim3(256), 0, (hipStream_t)stream, c,
-                       (int)npns, n, grad_out, (size_t)c * npns, idx, nullptr, workspace);
-    dim3 g2((n + SC_TILE - 1) / SC_TILE, (c + SC_TILE - 1) / SC_TILE, b);
-    hipLaunchKernelGGL(transpose_add_kernel, g2, dim3(256), 0, (hipStream_t)stream, c, n, workspace,
-                       grad_points);
-    return hipGetLastError();
+    return scatter_grad_dispatch({b, c, n, (int)npns, 1, false, (size_t)c * npns, grad_out, idx, nullptr, grad_points,
+                                  workspace, false, FALLBACK_CL}, (hipStream_t)stream);
 }
 
 GEOT_EXPORT int geot_graph_feature(int b, int c, int nq, int nk, int k, const float *x_q, const float *x_k,
@@ -2249,22 +2222,8 @@ GEOT_EXPORT int geot_graph_feature_grad(int b, int c, int nq, int nk, int k, con
     else if (al && k == 16) hipLaunchKernelGGL(graph_feature_grad_q_kernel<4>, gq, dim3(GG_THREADS), 0, s, c, nq, k, grad_out, grad_xq);
     else hipLaunchKernelGGL(graph_feature_grad_q_kernel<0>, gq, dim3(GG_THREADS), 0, s, c, nq, k, grad_out, grad_xq);
     const int L = nq * k;
-    {
-        const long long wsf = geot_scatter_grad_ws_floats(b, c, nk, L, 1, 0);
-        hipError_t e = grad_form(b, c, nk, L, 1, false) != GRAD_TILES ? hipErrorNotSupported
-                                                                 : scatter_via_tiles(b, c, nk, L, 1, (size_t)2 * c * L, grad_out, idx, nullptr, grad_xk,
-                                                                         workspace, wsf, s, false);
-        if (e != hipErrorNotSupported) return e;
-        e = scatter_via_csr<1, false>(b, c, nk, L, (size_t)2 * c * L, grad_out, idx, nullptr, grad_xk,
-                                                 workspace, wsf, s);
-        if (e != hipErrorNotSupported) return e;
-    }
-    dim3 g1((L + SC_TILE - 1) / SC_TILE, (c + SC_TILE - 1) / SC_TILE, b);
-    hipLaunchKernelGGL((scatter_rows_cl_kernel<1, false>), g1, dim3(256), 0, s, c, L, nk, grad_out,
-                       (size_t)2 * c * L, idx, nullptr, workspace);
-    dim3 g2((nk + SC_TILE - 1) / SC_TILE, (c + SC_TILE - 1) / SC_TILE, b);
-    hipLaunchKernelGGL(transpose_add_kernel, g2, dim3(256), 0, s, c, nk, workspace, grad_xk);
-    return hipGetLastError();
+    return scatter_grad_dispatch({b, c, nk, L, 1, false, (size_t)2 * c * L, grad_out, idx, nullptr, grad_xk, workspace, false,
+                                  FALLBACK_CL}, s);
 }
 
 GEOT_EXPORT int geot_grouping_cl(int m, int nsample, int c, const float *input, const int *idx,

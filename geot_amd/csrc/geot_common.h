@@ -271,7 +271,7 @@ static inline hipError_t zero_words(void *dst, long long words, hipStream_t s)
 constexpr int RIX_SORT_MAX = 1 << 22;
 __device__ __forceinline__ int rix_sorted_position(const int *__restrict__ tmp, int a, int z, int mine, int fallback)
 {
-    if (z - a > RIX_SORT_MAX) return fallback;
+    if (!tmp || z - a > RIX_SORT_MAX) return fallback;       // (no pair ids: the caller keeps the arrival order)
     int r = 0;
     for (int q = a; q < z; ++q) r += tmp[q] < mine ? 1 : 0;
     return r;

@@ -106,11 +106,15 @@ long long geot_scatter_grad_ws_floats(int b, int c, int m_targets, long long n_s
 int geot_group_points_grad_ws(int b, int c, int n, int npoints, int nsample, const float *grad_out,
                               const int *idx, float *grad_points, float *workspace, void *stream);
 /* 0 when the *_grad_ws entry points only use their workspace as scratch for these sizes (gradient as a
- * gather over a reverse index), 1 when they accumulate in it and it must arrive zero-filled. */
+ * gather over a reverse index), 1 when they accumulate in it and it must arrive zero-filled.  The answer is the form
+ * the launch takes: query and launch share one planner that knows every limit of the two sorted forms.  A sorted form
+ * that is still refused at launch (a workspace that is not 8-byte aligned, an LDS grant the device denies) falls back
+ * to the accumulation, which then clears the workspace itself. */
 int geot_grad_ws_needs_zero(int b, int c, int m_targets, long long n_sources, int slots_per_source);
 /* Host-only (ABI 8): the form the *_grad_ws / _grad_out / _grad_from entry points take for these sizes -- 1 = the sorted
  * pair stream (tiles), 2 = the whole-row list walk (csr), 3 = the channels-last scatter with float atomics in the
- * workspace, 0 = nothing to launch -- under the same GEOT_GATHER_IMPL as the launches.  For 1, out receives the first
+ * workspace, 0 = nothing to launch -- under the same GEOT_GATHER_IMPL as the launches, and the form that is launched
+ * (one dispatcher switches on this answer).  For 1, out receives the first
  * n_out of: channels per workgroup, sources per tile, tiles, pairs per tile, entry slots per tile, LDS bytes of the
  * scatter, LDS bytes of the sort, workspace words.  out is a HOST array. */
 int geot_scatter_grad_plan(int b, int c, int m_targets, long long n_sources, int slots_per_source, int weighted,

@@ -18,6 +18,27 @@ def plan(lib, b, c, m, L, nt, weighted=None):
     return form, (dict(zip(PLAN_FIELDS, out)) if form == TILES else None)
 
 
+TLDS_FLOATS = 36864                               # the list walk holds whole rows of at most this many sources in LDS
+SCAN_CHUNK = 4096
+
+
+def whole_rows(c, m, L, nt):
+    """the shape half of the list walk's preference: whole rows in one part (fewer than 4 channels, or 4 rows fit the
+    LDS) and lists of 12 pairs or more on average"""
+    return 1 <= L <= TLDS_FLOATS and m >= 1 and nt >= 1 and (c < 4 or TLDS_FLOATS // L >= 4) and L * nt >= 12 * m
+
+
+def ws_floats_ref(b, c, m, L, nt, tile_ints):
+    """geot_scatter_grad_ws_floats restated: the largest of the channels-last accumulator, the tile plan's workspace
+    (tile_ints: its `ints`, 0 without a tile plan) and, where whole_rows holds, the one-part reverse index (offsets,
+    scan scratch, and rank / source / weight / pair id per pair)"""
+    if b < 1 or c < 1 or m < 1:
+        return 0
+    t, pairs = b * m, b * L * nt
+    rows = (t + 1) + (t + 1 + SCAN_CHUNK - 1) // SCAN_CHUNK + 4 * pairs + 8 if whole_rows(c, m, L, nt) else 0
+    return max(b * m * c, tile_ints, rows)
+
+
 def switch(pred, lo, hi):
     """x in [lo, hi) with pred(x) != pred(x + 1), by bisection; pred(lo) and pred(hi) must differ"""
     a, z = pred(lo), pred(hi)

@@ -286,3 +286,53 @@ def test_compiled_binding(lib, b, c, m, L, form):
     interp(lib, b, c, m, L, form, seed=20, binding=cpp)
     if plan(lib, b, c, m, L, 1)[0] in (TILES, CSR):
         gather(lib, b, c, m, L, plan(lib, b, c, m, L, 1)[0], seed=21, binding=cpp)
+
+
+# ---- the bare C ABI with a workspace the tile form refuses; the list order switch --------------------------------------
+
+@pytest.mark.parametrize("entry", ["geot_three_interpolate_grad_ws", "geot_group_points_grad_ws"])
+@pytest.mark.parametrize("misalign", [0, 4])
+def test_workspace_at_four_bytes(lib, entry, misalign):
+    """a workspace that is not 8-byte aligned (the tile form refuses it, the list walk does not apply): the call takes the
+    channels-last accumulator and clears it itself, although the plan had promised a form that needs no clearing"""
+    b, c, m, L = 2, 5, 300, 1000
+    nt = 3 if "interpolate" in entry else 1
+    assert plan(lib, b, c, m, L, nt)[0] == TILES and lib.geot_grad_ws_needs_zero(b, c, m, L, nt) == 0
+    assert L * c < 65536                                  # (the list walk's payload limit)
+    g, idx, w = make(b, c, L, nt, m, 22)
+    ws = torch.full((lib.geot_scatter_grad_ws_floats(b, c, m, L, nt, int(nt == 3)) + 2,), 1e30, device=DEV)
+    out = torch.zeros(b, c, m, device=DEV)
+    args = (b, c, L, m, g.data_ptr(), idx.data_ptr(), w.data_ptr()) if nt == 3 else (b, c, m, L, 1, g.data_ptr(), idx.data_ptr())
+    assert ws.data_ptr() % 8 == 0
+    err = getattr(lib, entry)(*args, out.data_ptr(), ws.data_ptr() + misalign, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert err == 0
+    assert rel(out, scatter64(g, idx, w if nt == 3 else None, m)) <= TOL
+
+
+def exact_case(b, c, L, nt, m, seed):
+    """small-integer gradients and power-of-two weights: every summation order gives the same fp32 sum"""
+    rng = np.random.default_rng(seed)
+    g = rng.integers(-8, 9, (b, c, L)).astype(np.float32)
+    idx = rng.integers(0, m, (b, L, nt)).astype(np.int32)
+    w = (2.0 ** rng.integers(-2, 2, (b, L, nt))).astype(np.float32)
+    return torch.from_numpy(g).to(DEV), torch.from_numpy(idx).to(DEV), torch.from_numpy(w).to(DEV)
+
+
+def test_arrival_order_lists(lib, monkeypatch):
+    """GEOT_REPRODUCIBLE=0 keeps the lists of the list walk in the order the pairs arrived: the same pairs, so sums that
+    do not depend on the order are exactly the fp64 ones -- one part per row, then three parts looped in the workgroup"""
+    from geot_amd.ext import pointnet2_ext as p2
+    monkeypatch.setenv("GEOT_REPRODUCIBLE", "0")
+    b, c, m, L = 2, 64, 64, 1024
+    assert plan(lib, b, c, m, L, 3)[0] == CSR
+    g, idx, w = exact_case(b, c, L, 3, m, 23)
+    assert torch.equal(p2.three_interpolate_grad(g, idx, w, m).double().cpu(), scatter64(g, idx, w, m))
+    monkeypatch.setenv("GEOT_GATHER_IMPL", "csr")
+    # L = 20000 sources are cut into 3 parts.  At c = 8 the workspace the size query grants (b m c floats: no tile plan under
+    # this switch) does not hold the index, so the plan is the channels-last form; c = 128 has the room and walks the parts
+    for c, form in ((8, CL), (128, CSR)):
+        b, m, L = 1, 700, 20000
+        assert plan(lib, b, c, m, L, 1)[0] == form and -(-4 * L // 36864) == 3
+        g, idx, _ = exact_case(b, c, L, 1, m, 24)
+        assert torch.equal(p2.gather_points_grad(g, idx.reshape(b, L), m).double().cpu(), scatter64(g, idx, None, m))

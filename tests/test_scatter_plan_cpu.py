@@ -11,7 +11,7 @@ import math
 import numpy as np
 import pytest
 
-from _scatter_ref import CL, CSR, NONE, TILES, plan, switch
+from _scatter_ref import CL, CSR, NONE, TILES, plan, switch, ws_floats_ref
 
 TS_LDS = 160 * 1024
 TS_BUILD_STATIC = 2048          # ts_build_kernel's static shared arrays fit in this much
@@ -87,7 +87,7 @@ def all_configs():
     return [(b, c, nt, w) for b in BS for c in CS for nt, w in NTS]
 
 
-def test_random_shapes(lib):
+def random_shapes():
     """200 k seeded (m, L), log-uniform over 1..40 000 targets and 1..5 M sources, each at both slot counts and a b, c
     drawn from the call sites' range"""
     rng = np.random.default_rng(20261016)
@@ -100,6 +100,11 @@ def test_random_shapes(lib):
     for m, L, b, c in zip(ms.tolist(), Ls.tolist(), bs.tolist(), cs.tolist()):
         for nt, w in NTS:
             shapes.append((b, c, m, L, nt, w))
+    return shapes
+
+
+def test_random_shapes(lib):
+    shapes = random_shapes()
     sweep(lib, shapes)
     forms = {plan(lib, b, c, m, L, nt, w)[0] for b, c, m, L, nt, w in shapes[:20000]}
     assert forms == {TILES, CSR, CL}          # the sweep reaches every form
@@ -191,3 +196,28 @@ def test_degenerate_and_forced(lib, monkeypatch):
     assert plan(lib, 8, 64, 24000, 6000 * 32, 1)[0] == CL
     monkeypatch.setenv("GEOT_GATHER_IMPL", "tiles")
     assert plan(lib, 8, 64, 512, 24000, 3)[0] == TILES
+
+
+def test_workspace_size_is_the_largest_of_its_three_users(lib, monkeypatch):
+    """geot_scatter_grad_ws_floats over the seeded shapes of test_random_shapes: the channels-last accumulator, the tile
+    plan's workspace, or the one-part reverse index where the list walk's shape condition holds (_scatter_ref)"""
+    shapes = random_shapes()
+    monkeypatch.setenv("GEOT_GATHER_IMPL", "tiles")      # the tile plan of every shape that has one, preferred or not
+    tiles = [(plan(lib, *s)[1] or {}).get("ints", 0) for s in shapes]
+    monkeypatch.delenv("GEOT_GATHER_IMPL")
+    bad = [(s, got, want) for s, t in zip(shapes, tiles)
+           for got, want in [(lib.geot_scatter_grad_ws_floats(*s[:5], int(s[5])), ws_floats_ref(*s[:5], t))] if got != want]
+    assert not bad, "%d sizes differ (shape, library, restated), e.g.\n%s" % (len(bad), "\n".join(map(str, bad[:20])))
+    assert any(t == 0 for t in tiles) and any(ws_floats_ref(*s[:5], 0) > s[0] * s[1] * s[2] for s in shapes)
+
+
+def test_list_walk_grid_limit_is_planned(lib, monkeypatch):
+    """the list walk's per-part launch puts b * Q on the grid's z axis (at most 65535): a shape beyond it is planned as
+    the channels-last form, whose workspace the caller clears, and not refused by the launch after the plan said csr"""
+    monkeypatch.setenv("GEOT_GATHER_IMPL", "csr")
+    assert plan(lib, 32768, 8, 16385, 18432, 1)[0] == CL             # Q = 2 parts, too many targets to loop them inside
+    assert lib.geot_grad_ws_needs_zero(32768, 8, 16385, 18432, 1) == 1
+    assert plan(lib, 32767, 8, 16385, 18432, 1)[0] == CSR
+    assert lib.geot_grad_ws_needs_zero(32767, 8, 16385, 18432, 1) == 0
+    assert plan(lib, 32768, 8, 16384, 18432, 1)[0] == CSR            # parts looped inside the workgroup: b on the z axis
+    assert lib.geot_grad_ws_needs_zero(32768, 8, 16384, 18432, 1) == 0
