@@ -1,11 +1,19 @@
-"""BatchNorm (+ ReLU) on channels-first (B, C, L) tensors over the streaming kernels of csrc/bnrelu.hip, and the
-PointnetFPModule front end whose output arrives with its BatchNorm sums.
+"""BatchNorm (+ ReLU) over the streaming kernels of csrc/bnrelu.hip (channels-first (B, C, L) tensors) and
+csrc/channels_last.hip (point-major (B, L, C) tensors), and the PointnetFPModule front end whose output arrives with its
+BatchNorm sums.
 
 ``bn_act(bn, x, relu)`` computes exactly what ``relu(bn(x))`` computes for an ``nn.BatchNorm1d/2d`` or
 ``nn.SyncBatchNorm`` module ``bn`` -- batch statistics, running-statistics update (momentum or cumulative average,
 unbiased variance), ``num_batches_tracked``, eval mode on the running statistics, SyncBatchNorm's all-reduce of the
 sums in both directions -- in 2 passes forward and 2 backward instead of 5 and 8 (csrc/bnrelu.hip).  The module is
 only a parameter / buffer container here; tensors the kernels do not cover (CPU, other dtypes) take ``bn(x)``.
+
+The BatchNorm functions are written once and take the layout as a parameter: a layout (``_CF``, ``_CL``) knows its
+kernels and the buffers they want, ``_module_statistics`` / ``_bwd_coef`` hold what happens between the passes, and
+``bn_act``, ``bn_act_cl`` and ``fp_stage_cl`` differ only in which tensors they cover and in the layout they hand on.
+``count`` throughout: the number of elements per channel over all ranks that the statistics were taken over -- a python
+float, a 1-element device double under SyncBatchNorm (the total never visits the host), 0.0 under running statistics,
+where the statistics do not depend on x.
 
 Further down: the small autograd ops that replace runs of torch launches around the dense layers (profiles/DESIGN_r01_r03.md 4.10) --
 ``max_last``, ``add_last_broadcast``, ``thin_mm``, ``linear`` (bias gradient as column sums), ``res_ln`` (residual add +
@@ -44,52 +52,130 @@ def _sync_group(bn):
     return group if dist.get_world_size(group) > 1 else None
 
 
-class _BnActFn(Function):
-    """out = act(x * scale + shift) with the full BatchNorm backward (the statistics' dependence on x included when
-    `count` > 0: training mode; `count` = number of elements per channel over all ranks)."""
+def _cl_stat_buffer(tiles, c, dev):
+    """Uninitialised statistics buffer of a point-major producer: (tiles, 3, c) records + tiles counts (flat)."""
+    return torch.empty(int(_lib.load().geot_cl_stat_floats(tiles, c)), dtype=torch.float32, device=dev)
 
-    @staticmethod
-    def forward(ctx, x, gamma, beta, mean, rstd, scale, shift, relu, count, group, pre_bias=None):
+
+class _ChannelsFirst:
+    """The BatchNorm passes over x (B, C, L): csrc/bnrelu.hip, every (batch, channel) row cut into slices.
+    The methods (the same in _PointMajor): stat_sums -> sums (C, 2) fp64 from the statistics records of x -- shifted sums
+    (s1, s2, pivot, count) per slice / tile, formed here unless they came with x, rebuilt and added in fp64; apply ->
+    act(x * scale + shift); bwd_sums -> this rank's (C, 2) fp64 sum g, sum g * xhat; bwd_apply -> scale (g - c1 - xhat c2)."""
+    channel_dim = 1
+
+    def stat_sums(self, x, partial, sums):
         b, c, l = x.shape
-        if scale is None:
-            scale = (gamma * rstd).contiguous()
-            shift = (beta - mean * scale).contiguous()
+        if partial is None:
+            partial = torch.empty((b, c, int(_lib.load().geot_bn_slices(b, c, l)), 4), dtype=torch.float32, device=x.device)
+            call("geot_bn_stats", x.device, b, c, l, ptr(x), ptr(partial))
+        # everything between the two passes in two launches (csrc/bnrelu.hip; ~13 torch launches per layer otherwise)
+        call("geot_bn_sums_shifted", x.device, b, c, partial.shape[2], ptr(partial), ptr(sums))
+
+    def apply(self, x, relu, scale, shift):
+        b, c, l = x.shape
         out = torch.empty_like(x)
         call("geot_bn_apply", x.device, b, c, l, int(relu), ptr(x), ptr(scale), ptr(shift), ptr(out))
-        ctx.save_for_backward(x, gamma, scale, shift, mean, rstd)
-        ctx.cfg = (bool(relu), count, group)      # count: python float, or a 1-element device double under SyncBatchNorm
-        ctx.has_pre_bias = pre_bias is not None
         return out
 
-    @staticmethod
-    def backward(ctx, dz):
-        x, gamma, scale, shift, mean, rstd = ctx.saved_tensors
-        relu, count, group = ctx.cfg
+    def bwd_sums(self, x, dz, relu, scale, shift, mean, rstd):
         b, c, l = x.shape
         dev = x.device
-        dz = dz.contiguous()
         slices = int(_lib.load().geot_bn_slices(b, c, l))
         partial = torch.empty((b, c, slices, 2), dtype=torch.float32, device=dev)
         call("geot_bn_bwd_reduce", dev, b, c, l, int(relu), ptr(x), ptr(dz), ptr(scale), ptr(shift), ptr(mean),
              ptr(rstd), ptr(partial))
-        local = torch.empty((c, 2), dtype=torch.float64, device=dev)         # sum g, sum g * xhat (this rank)
+        local = torch.empty((c, 2), dtype=torch.float64, device=dev)
         call("geot_bn_sums", dev, b, c, slices, ptr(partial), ptr(local))
-        sums = local
-        if group is not None:
-            import torch.distributed as dist
-            sums = local.clone()
-            dist.all_reduce(sums, group=group)                               # SyncBatchNorm: the means are over all ranks
-        coef = torch.empty((4, c), dtype=torch.float32, device=dev)          # g_gamma, g_beta, c1, c2
-        on_dev = torch.is_tensor(count)                                      # batch statistics: they depend on x (count > 0)
-        call("geot_bn_bwd_coef", dev, c, ptr(local), ptr(sums), 0.0 if on_dev else float(count), ptr(count) if on_dev else None,
-             ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(coef[3]))
+        return local
+
+    def bwd_apply(self, x, dz, relu, scale, shift, mean, rstd, c1, c2):
+        b, c, l = x.shape
         dx = torch.empty_like(x)
-        call("geot_bn_bwd_apply", dev, b, c, l, int(relu), ptr(x), ptr(dz), ptr(scale), ptr(shift), ptr(mean),
-             ptr(rstd), ptr(scale), ptr(coef[2]), ptr(coef[3]), ptr(dx))
-        g_pre = None
-        if ctx.has_pre_bias:    # d/d pre_bias = sum of dx over (b, l): exactly 0 under batch statistics, scale * sum g otherwise
-            g_pre = scale * coef[1] if (not on_dev and float(count) == 0.0) else torch.zeros_like(scale)
-        return dx, coef[0], coef[1], None, None, None, None, None, None, None, g_pre
+        call("geot_bn_bwd_apply", x.device, b, c, l, int(relu), ptr(x), ptr(dz), ptr(scale), ptr(shift), ptr(mean),
+             ptr(rstd), ptr(scale), ptr(c1), ptr(c2), ptr(dx))
+        return dx
+
+
+class _PointMajor:
+    """The same passes over x (B, L, C), C % 4 == 0: csrc/channels_last.hip, the b * l rows of c channels cut into tiles."""
+    channel_dim = 2
+
+    def stat_sums(self, x, partial, sums):
+        b, l, c = x.shape
+        if partial is None:
+            partial = _cl_stat_buffer(int(_lib.load().geot_cl_tiles(1, b * l, c)), c, x.device)
+            call("geot_bn_stats_cl", x.device, b * l, c, ptr(x), ptr(partial))
+        call("geot_bn_sums_shifted_cl", x.device, partial.numel() // (3 * c + 1), c, ptr(partial), ptr(sums))
+
+    def apply(self, x, relu, scale, shift):
+        b, l, c = x.shape
+        out = torch.empty_like(x)
+        call("geot_bn_apply_cl", x.device, b * l, c, int(relu), ptr(x), ptr(scale), ptr(shift), ptr(out))
+        return out
+
+    def bwd_sums(self, x, dz, relu, scale, shift, mean, rstd):
+        b, l, c = x.shape
+        dev = x.device
+        partial = torch.empty((int(_lib.load().geot_cl_tiles(1, b * l, c)), 2, c), dtype=torch.float32, device=dev)
+        call("geot_bn_bwd_reduce_cl", dev, b * l, c, int(relu), ptr(x), ptr(dz), ptr(scale), ptr(shift), ptr(mean), ptr(rstd),
+             ptr(partial))
+        local = torch.empty((c, 2), dtype=torch.float64, device=dev)
+        call("geot_bn_sums_cl", dev, partial.shape[0], c, ptr(partial), ptr(local))
+        return local
+
+    def bwd_apply(self, x, dz, relu, scale, shift, mean, rstd, c1, c2):
+        b, l, c = x.shape
+        dx = torch.empty_like(x)
+        call("geot_bn_bwd_apply_cl", x.device, b * l, c, int(relu), ptr(x), ptr(dz), ptr(scale), ptr(shift), ptr(mean), ptr(rstd),
+             ptr(scale), ptr(c1), ptr(c2), ptr(dx))
+        return dx
+
+
+_CF, _CL = _ChannelsFirst(), _PointMajor()
+
+
+def _bwd_coef(local, count, group):
+    """local (C, 2) fp64: this rank's sum g, sum g * xhat -> coef (4, C) = g_gamma, g_beta, c1, c2: the parameters'
+    gradients from this rank's sums, the means c1 / c2 that the input's gradient subtracts from those of all ranks."""
+    c, dev = local.shape[0], local.device
+    sums = local
+    if group is not None:
+        import torch.distributed as dist
+        sums = local.clone()
+        dist.all_reduce(sums, group=group)                                   # SyncBatchNorm: the means are over all ranks
+    coef = torch.empty((4, c), dtype=torch.float32, device=dev)
+    on_dev = torch.is_tensor(count)                                          # batch statistics: they depend on x (count > 0)
+    call("geot_bn_bwd_coef", dev, c, ptr(local), ptr(sums), 0.0 if on_dev else float(count), ptr(count) if on_dev else None,
+         ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(coef[3]))
+    return coef
+
+
+def _pre_bias_grad(scale, coef, count):
+    """d/d pre_bias = sum of dx over (b, l): exactly 0 under batch statistics, scale * sum g otherwise"""
+    return scale * coef[1] if (not torch.is_tensor(count) and float(count) == 0.0) else torch.zeros_like(scale)
+
+
+class _BnActFn(Function):
+    """out = act(x * scale + shift) in `layout`, with the full BatchNorm backward (the statistics' dependence on x
+    included when `count` > 0: training mode)."""
+
+    @staticmethod
+    def forward(ctx, layout, x, gamma, beta, mean, rstd, scale, shift, relu, count, group, pre_bias=None):
+        out = layout.apply(x, relu, scale, shift)
+        ctx.save_for_backward(x, scale, shift, mean, rstd)
+        ctx.cfg = (layout, bool(relu), count, group, pre_bias is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, scale, shift, mean, rstd = ctx.saved_tensors
+        layout, relu, count, group, has_pre_bias = ctx.cfg
+        dz = dz.contiguous()
+        coef = _bwd_coef(layout.bwd_sums(x, dz, relu, scale, shift, mean, rstd), count, group)
+        dx = layout.bwd_apply(x, dz, relu, scale, shift, mean, rstd, coef[2], coef[3])
+        g_pre = _pre_bias_grad(scale, coef, count) if has_pre_bias else None
+        return None, dx, coef[0], coef[1], None, None, None, None, None, None, None, g_pre
 
 
 def _covered(bn, x):
@@ -97,39 +183,17 @@ def _covered(bn, x):
             and x.dim() == 3 and x.shape[0] <= 65535 and x.shape[1] <= 65535 and x.numel() > 0)
 
 
-def _cl_stat_buffer(tiles, c, dev):
-    """Uninitialised statistics buffer of a point-major producer: (tiles, 3, c) records + tiles counts (flat)."""
-    return torch.empty(int(_lib.load().geot_cl_stat_floats(tiles, c)), dtype=torch.float32, device=dev)
-
-
-def _batch_statistics(bn, x, gamma, beta, partial, pre_bias, cl=False):
-    """Training-mode statistics of x (B, C, L) -- or, with cl, of the point-major x (B, L, C) -- for the module `bn`: the
-    stats pass (unless `partial` came with x), the all-reduce under SyncBatchNorm, mean / rstd / scale / shift and the
-    running-statistics update.
-    -> (stats (4, C) = mean, rstd, scale, shift; count (python float, or a 1-element device double); group)."""
-    if cl:
-        b, l, c = x.shape
-    else:
-        b, c, l = x.shape
+def _batch_statistics(bn, x, gamma, beta, partial, pre_bias, layout):
+    """Training-mode statistics of x in `layout` for the module `bn`: the stats pass (unless `partial` came with x), the
+    all-reduce under SyncBatchNorm, mean / rstd / scale / shift and the running-statistics update.
+    -> (stats (4, C) = mean, rstd, scale, shift; count; group)."""
+    c = x.shape[layout.channel_dim]
     dev = x.device
     group = _sync_group(bn)
     with torch.no_grad():
         sums = torch.empty((c, 2), dtype=torch.float64, device=dev)
-        # statistics records: shifted sums (s1, s2, pivot, count) per slice / tile, rebuilt and added in fp64
-        if cl:
-            if partial is None:
-                partial = _cl_stat_buffer(int(_lib.load().geot_cl_tiles(1, b * l, c)), c, dev)
-                call("geot_bn_stats_cl", dev, b * l, c, ptr(x), ptr(partial))
-            call("geot_bn_sums_shifted_cl", dev, partial.numel() // (3 * c + 1), c, ptr(partial), ptr(sums))
-        else:
-            if partial is None:
-                slices = int(_lib.load().geot_bn_slices(b, c, l))
-                partial = torch.empty((b, c, slices, 4), dtype=torch.float32, device=dev)
-                call("geot_bn_stats", dev, b, c, l, ptr(x), ptr(partial))
-            slices = partial.shape[2]
-            # everything between the two passes in two launches (csrc/bnrelu.hip; ~13 torch launches per layer otherwise)
-            call("geot_bn_sums_shifted", dev, b, c, slices, ptr(partial), ptr(sums))
-        count = float(b * l)
+        layout.stat_sums(x, partial, sums)
+        count = float(x.numel() // c)
         count_dev = None
         if group is not None:                  # SyncBatchNorm: sums and element counts of all ranks (counts may differ);
             import torch.distributed as dist   # the total stays on the device: no host synchronisation
@@ -165,6 +229,34 @@ def _batch_statistics(bn, x, gamma, beta, partial, pre_bias, cl=False):
     return stats, count, group
 
 
+def _affine(bn, c, dev):
+    """gamma, beta of the module (ones / zeros for one without affine parameters)"""
+    return (bn.weight if bn.weight is not None else torch.ones(c, device=dev),
+            bn.bias if bn.bias is not None else torch.zeros(c, device=dev))
+
+
+def _module_statistics(bn, x, gamma, beta, partial, pre_bias, layout):
+    """What the module `bn` normalises x with: batch statistics (_batch_statistics: training mode, or no running
+    buffers), else the running ones, `pre_bias` folded into the mean.
+    -> (stats; count; group), stats[0 .. 3] = mean, rstd, scale, shift: one (4, C) tensor under batch statistics."""
+    if bn.training or (bn.running_mean is None and bn.running_var is None):
+        return _batch_statistics(bn, x, gamma, beta, partial, pre_bias, layout)
+    with torch.no_grad():
+        mean = bn.running_mean.float() if pre_bias is None else bn.running_mean.float() - pre_bias.detach().float()
+        rstd = torch.rsqrt(bn.running_var.float() + bn.eps)
+        scale = (gamma.detach() * rstd).contiguous()
+        shift = (beta.detach() - mean * scale).contiguous()
+    return (mean, rstd, scale, shift), 0.0, None
+
+
+def _bn_act(layout, bn, x, relu, partial, pre_bias):
+    """bn_act / bn_act_cl on a tensor the kernels of `layout` cover"""
+    x = x.contiguous()
+    gamma, beta = _affine(bn, x.shape[layout.channel_dim], x.device)
+    stats, count, group = _module_statistics(bn, x, gamma, beta, partial, pre_bias, layout)
+    return _BnActFn.apply(layout, x, gamma, beta, *stats, relu, count, group, pre_bias)
+
+
 def bn_act(bn, x, relu=True, partial=None, pre_bias=None):
     """act(bn(x)) for x (B, C, L) float32 on the GPU; `partial` (B, C, S, 4): per-slice statistics records (shifted
     sums, pivot, count) when the producer of x already formed them (fp_front).  `pre_bias` (C,): act(bn(x + pre_bias[:, None])) without the add --
@@ -174,19 +266,13 @@ def bn_act(bn, x, relu=True, partial=None, pre_bias=None):
         from .pointnet2.pytorch_utils import batch_norm_nd
         y = batch_norm_nd(bn, x if pre_bias is None else x + pre_bias.view(1, -1, 1))
         return torch.relu(y) if relu else y
-    x = x.contiguous()
-    b, c, l = x.shape
-    dev = x.device
-    gamma = bn.weight if bn.weight is not None else torch.ones(c, device=dev)
-    beta = bn.bias if bn.bias is not None else torch.zeros(c, device=dev)
-    use_batch = bn.training or (bn.running_mean is None and bn.running_var is None)
-    if not use_batch:
-        with torch.no_grad():
-            mean = bn.running_mean.float() if pre_bias is None else bn.running_mean.float() - pre_bias.detach().float()
-            rstd = torch.rsqrt(bn.running_var.float() + bn.eps)
-        return _BnActFn.apply(x, gamma, beta, mean, rstd, None, None, relu, 0.0, None, pre_bias)
-    stats, count, group = _batch_statistics(bn, x, gamma, beta, partial, pre_bias)
-    return _BnActFn.apply(x, gamma, beta, stats[0], stats[1], stats[2], stats[3], relu, count, group, pre_bias)
+    return _bn_act(_CF, bn, x, relu, partial, pre_bias)
+
+
+def _skip_args(skip, wb):
+    """-> (cs, wbc) of an FP front end: the skip tensor's channels (0 without one) and its weight, contiguous (None then)"""
+    cs = 0 if skip is None else skip.shape[1]
+    return cs, (wb.contiguous() if cs else None)
 
 
 class _FpFrontFn(Function):
@@ -196,12 +282,10 @@ class _FpFrontFn(Function):
     def forward(ctx, a, idx, weight, skip, wb):
         b, c, m = a.shape
         n = idx.shape[1]
-        cs = 0 if skip is None else skip.shape[1]
-        lib = _lib.load()
-        slices = int(lib.geot_fp_front_slices(b, c, m, n))
+        cs, wbc = _skip_args(skip, wb)
+        slices = int(_lib.load().geot_fp_front_slices(b, c, m, n))
         y = torch.empty((b, c, n), dtype=torch.float32, device=a.device)
         partial = torch.empty((b, c, slices, 4), dtype=torch.float32, device=a.device)     # statistics records
-        wbc = wb.contiguous() if cs else None
         call("geot_fp_front", a.device, b, c, m, n, cs, ptr(a), ptr(idx), ptr(weight), ptr(skip), ptr(wbc), ptr(y), ptr(partial))
         ctx.save_for_backward(idx, weight, skip, wbc)
         ctx.m = m
@@ -327,22 +411,26 @@ class ReverseIndex:
         return out
 
 
+def _fp_front_cl_launch(a_cl, idx, weight, skip, wb, order):
+    """geot_fp_front_cl -> (y_cl (B, n, C), its statistics buffer, the skip weight as launched (None without skip channels))"""
+    b, m, c = a_cl.shape
+    n = idx.shape[1]
+    cs, wbc = _skip_args(skip, wb)
+    y = torch.empty((b, n, c), dtype=torch.float32, device=a_cl.device)
+    partial = _cl_stat_buffer(int(_lib.load().geot_fp_front_cl_tiles(b, c, n, cs)), c, a_cl.device)
+    call("geot_fp_front_cl", a_cl.device, b, c, m, n, cs, ptr(a_cl), ptr(idx), ptr(weight), ptr(skip), ptr(wbc), ptr(order),
+         ptr(y), ptr(partial))
+    return y, partial, wbc
+
+
 class _FpFrontClFn(Function):
     """y_cl = three_interpolate(A, idx, w) + skip^T Wb^T on point-major tensors, with the per-tile sums of y and y^2."""
 
     @staticmethod
     def forward(ctx, a_cl, idx, weight, skip, wb, order, rix):
-        b, m, c = a_cl.shape
-        n = idx.shape[1]
-        cs = 0 if skip is None else skip.shape[1]
-        tiles = int(_lib.load().geot_fp_front_cl_tiles(b, c, n, cs))
-        y = torch.empty((b, n, c), dtype=torch.float32, device=a_cl.device)
-        partial = _cl_stat_buffer(tiles, c, a_cl.device)
-        wbc = wb.contiguous() if cs else None
-        call("geot_fp_front_cl", a_cl.device, b, c, m, n, cs, ptr(a_cl), ptr(idx), ptr(weight), ptr(skip), ptr(wbc), ptr(order),
-             ptr(y), ptr(partial))
+        y, partial, wbc = _fp_front_cl_launch(a_cl, idx, weight, skip, wb, order)
         ctx.save_for_backward(idx, weight, skip, wbc)
-        ctx.m, ctx.rix = m, rix
+        ctx.m, ctx.rix = a_cl.shape[1], rix
         ctx.mark_non_differentiable(partial)
         return y, partial
 
@@ -370,52 +458,6 @@ def fp_front_cl(a_cl, idx, weight, skip, wb, order=None, rix=None):
                               None if skip is None else skip.contiguous().float(), wb, order, rix)
 
 
-class _BnActClFn(Function):
-    """_BnActFn on a point-major tensor (B, L, C)."""
-
-    @staticmethod
-    def forward(ctx, x, gamma, beta, mean, rstd, scale, shift, relu, count, group, pre_bias=None):
-        b, l, c = x.shape
-        if scale is None:
-            scale = (gamma * rstd).contiguous()
-            shift = (beta - mean * scale).contiguous()
-        out = torch.empty_like(x)
-        call("geot_bn_apply_cl", x.device, b * l, c, int(relu), ptr(x), ptr(scale), ptr(shift), ptr(out))
-        ctx.save_for_backward(x, gamma, scale, shift, mean, rstd)
-        ctx.cfg = (bool(relu), count, group)
-        ctx.has_pre_bias = pre_bias is not None
-        return out
-
-    @staticmethod
-    def backward(ctx, dz):
-        x, gamma, scale, shift, mean, rstd = ctx.saved_tensors
-        relu, count, group = ctx.cfg
-        b, l, c = x.shape
-        dev = x.device
-        dz = dz.contiguous()
-        partial = torch.empty((int(_lib.load().geot_cl_tiles(1, b * l, c)), 2, c), dtype=torch.float32, device=dev)
-        call("geot_bn_bwd_reduce_cl", dev, b * l, c, int(relu), ptr(x), ptr(dz), ptr(scale), ptr(shift), ptr(mean), ptr(rstd),
-             ptr(partial))
-        local = torch.empty((c, 2), dtype=torch.float64, device=dev)
-        call("geot_bn_sums_cl", dev, partial.shape[0], c, ptr(partial), ptr(local))
-        sums = local
-        if group is not None:
-            import torch.distributed as dist
-            sums = local.clone()
-            dist.all_reduce(sums, group=group)
-        coef = torch.empty((4, c), dtype=torch.float32, device=dev)
-        on_dev = torch.is_tensor(count)
-        call("geot_bn_bwd_coef", dev, c, ptr(local), ptr(sums), 0.0 if on_dev else float(count), ptr(count) if on_dev else None,
-             ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(coef[3]))
-        dx = torch.empty_like(x)
-        call("geot_bn_bwd_apply_cl", dev, b * l, c, int(relu), ptr(x), ptr(dz), ptr(scale), ptr(shift), ptr(mean), ptr(rstd),
-             ptr(scale), ptr(coef[2]), ptr(coef[3]), ptr(dx))
-        g_pre = None
-        if ctx.has_pre_bias:
-            g_pre = scale * coef[1] if (not on_dev and float(count) == 0.0) else torch.zeros_like(scale)
-        return dx, coef[0], coef[1], None, None, None, None, None, None, None, g_pre
-
-
 def bn_act_cl(bn, x, relu=True, partial=None, pre_bias=None):
     """bn_act for a point-major x (B, L, C) float32 on the GPU with C % 4 == 0 (geot_cl_tiles >= 0); `partial`: the
     statistics buffer fp_front_cl returned.  Same statistics, running buffers and SyncBatchNorm behaviour as bn_act."""
@@ -423,18 +465,7 @@ def bn_act_cl(bn, x, relu=True, partial=None, pre_bias=None):
     if not (isinstance(bn, nn.modules.batchnorm._BatchNorm) and x.is_cuda and x.dtype == torch.float32
             and _lib.load().geot_cl_tiles(1, b * l, c) > 0):
         return bn_act(bn, x.transpose(1, 2).contiguous(), relu, None, pre_bias).transpose(1, 2).contiguous()
-    x = x.contiguous()
-    dev = x.device
-    gamma = bn.weight if bn.weight is not None else torch.ones(c, device=dev)
-    beta = bn.bias if bn.bias is not None else torch.zeros(c, device=dev)
-    use_batch = bn.training or (bn.running_mean is None and bn.running_var is None)
-    if not use_batch:
-        with torch.no_grad():
-            mean = bn.running_mean.float() if pre_bias is None else bn.running_mean.float() - pre_bias.detach().float()
-            rstd = torch.rsqrt(bn.running_var.float() + bn.eps)
-        return _BnActClFn.apply(x, gamma, beta, mean, rstd, None, None, relu, 0.0, None, pre_bias)
-    stats, count, group = _batch_statistics(bn, x, gamma, beta, partial, pre_bias, cl=True)
-    return _BnActClFn.apply(x, gamma, beta, stats[0], stats[1], stats[2], stats[3], relu, count, group, pre_bias)
+    return _bn_act(_CL, bn, x, relu, partial, pre_bias)
 
 
 class _FpStageClFn(Function):
@@ -445,32 +476,14 @@ class _FpStageClFn(Function):
 
     @staticmethod
     def forward(ctx, a_cl, idx, weight, skip, wb, gamma, beta, bn, relu, order, rix):
-        b, m, c = a_cl.shape
-        n = idx.shape[1]
-        dev = a_cl.device
-        cs = 0 if skip is None else skip.shape[1]
-        tiles = int(_lib.load().geot_fp_front_cl_tiles(b, c, n, cs))
-        y = torch.empty((b, n, c), dtype=torch.float32, device=dev)
-        partial = _cl_stat_buffer(tiles, c, dev)
-        wbc = wb.contiguous() if cs else None
-        call("geot_fp_front_cl", dev, b, c, m, n, cs, ptr(a_cl), ptr(idx), ptr(weight), ptr(skip), ptr(wbc), ptr(order), ptr(y),
-             ptr(partial))
-        use_batch = bn.training or (bn.running_mean is None and bn.running_var is None)
-        if use_batch:
-            stats, count, group = _batch_statistics(bn, y, gamma, beta, partial, None, cl=True)
-            mean, rstd, scale, shift = stats[0], stats[1], stats[2], stats[3]
-        else:
-            mean = bn.running_mean.float()
-            rstd = torch.rsqrt(bn.running_var.float() + bn.eps)
-            scale = (gamma.detach() * rstd).contiguous()
-            shift = (beta.detach() - mean * scale).contiguous()
-            count, group = 0.0, None
-        z = torch.empty_like(y)
-        call("geot_bn_apply_cl", dev, b * n, c, int(relu), ptr(y), ptr(scale), ptr(shift), ptr(z))
+        y, partial, wbc = _fp_front_cl_launch(a_cl, idx, weight, skip, wb, order)
+        stats, count, group = _module_statistics(bn, y, gamma, beta, partial, None, _CL)
+        mean, rstd, scale, shift = stats
+        z = _CL.apply(y, relu, scale, shift)
         ctx.save_for_backward(y, idx, weight, skip, wbc, scale, shift, mean, rstd)
-        ctx.cfg = (bool(relu), count, group, m, order, rix)
+        ctx.cfg = (bool(relu), count, group, a_cl.shape[1], order, rix)
         # S2 of the skip-weight gradient (input data only); not under no_grad / for frozen weights
-        ctx.skip_sums = rowsum_f64(skip).sum(0) if (cs and ctx.needs_input_grad[4]) else None     # (B, cs) -> (cs,), fp64
+        ctx.skip_sums = rowsum_f64(skip).sum(0) if (wbc is not None and ctx.needs_input_grad[4]) else None   # (B, cs) -> (cs,), fp64
         return z
 
     @staticmethod
@@ -488,16 +501,7 @@ class _FpStageClFn(Function):
              ptr(skip), ptr(partial))
         sums_k = torch.empty((c, k), dtype=torch.float64, device=dev)
         call("geot_bn_sums_k_cl", dev, partial.shape[0], c, k, ptr(partial), ptr(sums_k))
-        local = sums_k[:, :2].contiguous()                                   # sum g, sum g xhat (this rank)
-        sums = local
-        if group is not None:
-            import torch.distributed as dist
-            sums = local.clone()
-            dist.all_reduce(sums, group=group)
-        coef = torch.empty((4, c), dtype=torch.float32, device=dev)          # g_gamma, g_beta, c1, c2
-        on_dev = torch.is_tensor(count)
-        call("geot_bn_bwd_coef", dev, c, ptr(local), ptr(sums), 0.0 if on_dev else float(count), ptr(count) if on_dev else None,
-             ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(coef[3]))
+        coef = _bwd_coef(sums_k[:, :2].contiguous(), count, group)            # from sum g, sum g xhat (this rank)
         ga = gskip = gwb = None
         if ctx.needs_input_grad[0]:
             if rix is None:
@@ -510,9 +514,7 @@ class _FpStageClFn(Function):
             gwb = torch.empty((c, cs), dtype=torch.float32, device=dev)
             call("geot_fp_skip_wgrad_cl", dev, c, cs, ptr(sums_k), ptr(scale), ptr(coef[2]), ptr(coef[3]), ptr(ctx.skip_sums), ptr(gwb))
         if cs and ctx.needs_input_grad[3]:                                   # (never in the model: the skip tensor is input data)
-            gy = torch.empty_like(y)
-            call("geot_bn_bwd_apply_cl", dev, b * n, c, int(relu), ptr(y), ptr(dz), ptr(scale), ptr(shift), ptr(mean), ptr(rstd),
-                 ptr(scale), ptr(coef[2]), ptr(coef[3]), ptr(gy))
+            gy = _CL.bwd_apply(y, dz, relu, scale, shift, mean, rstd, coef[2], coef[3])
             gskip = torch.matmul(gy, wb).transpose(1, 2)
         return ga, None, None, gskip, gwb, coef[0], coef[1], None, None, None, None
 
@@ -520,10 +522,7 @@ class _FpStageClFn(Function):
 def fp_stage_cl(bn, a_cl, idx, weight, skip, wb, relu=True, order=None, rix=None):
     """act(bn(fp_front_cl(...))) for a BatchNorm module `bn` (training or eval mode, SyncBatchNorm included) as one
     autograd node whose backward never materialises the gradient of the BatchNorm's input.  -> z_cl (B, n, C)."""
-    c = a_cl.shape[2]
-    dev = a_cl.device
-    gamma = bn.weight if bn.weight is not None else torch.ones(c, device=dev)
-    beta = bn.bias if bn.bias is not None else torch.zeros(c, device=dev)
+    gamma, beta = _affine(bn, a_cl.shape[2], a_cl.device)
     return _FpStageClFn.apply(a_cl.contiguous(), idx.contiguous(), weight.contiguous(),
                               None if skip is None else skip.contiguous().float(), wb, gamma, beta, bn, relu, order, rix)
 
@@ -869,5 +868,5 @@ def bn_relu_max(bn, y, n):
     y = y.contiguous()
     if not _aligned16(y):                                                   # (bn_pool reads y as float4)
         return max_last(bn_act(bn, y, relu=True).view(b, c, l // n, n))
-    stats, count, _ = _batch_statistics(bn, y, bn.weight, bn.bias, None, None)
+    stats, count, _ = _module_statistics(bn, y, bn.weight, bn.bias, None, None, _CF)         # (training mode: batch statistics)
     return _BnPoolFn.apply(y, bn.weight, bn.bias, stats, n, count)

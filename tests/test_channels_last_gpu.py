@@ -507,3 +507,57 @@ def test_bn_row_gather_against_fp64_in_both_target_orders(b, n, m, c, kind, relu
     assert rel(got.transpose(1, 2), want.transpose(1, 2)) <= 2e-5 * (30 if kind == "hub" else 1)
     if kind == "hub":
         assert float(got[:, 7].abs().max()) == 0.0 and float(got[:, m - 1].abs().max()) == 0.0
+
+
+def test_batchnorm_paths_launch_what_they_launched(monkeypatch):
+    """The C-ABI launches of bn_act, bn_act_cl and fp_stage_cl, in order, per mode: training / eval, statistics records
+    handed over by the FP front end, and the FP stage with / without skip channels, a ReverseIndex built ahead and a
+    skip tensor that wants its gradient."""
+    from _fused_ref import Launches
+    from geot_amd import fused_norm as fn
+    rec = Launches(monkeypatch)
+    torch.manual_seed(11)
+    b, c, l, m = 2, 8, 300, 40
+    pos = _cloud(b, l, 5)
+    idx, w = _nn3(pos, pos[:, :m].contiguous())
+
+    def run(out):
+        fwd = rec.take()
+        out.sum().backward()
+        return fwd, rec.take()
+
+    for sfx, act, front, shape in (("", fn.bn_act, fn.fp_front, (b, c, l)), ("_cl", fn.bn_act_cl, fn.fp_front_cl, (b, l, c))):
+        stats = ["geot_bn_stats" + sfx]
+        fwd = ["geot_bn_sums_shifted" + sfx, "geot_bn_finalize", "geot_bn_apply" + sfx]
+        bwd = ["geot_bn_bwd_reduce" + sfx, "geot_bn_sums" + sfx, "geot_bn_bwd_coef", "geot_bn_bwd_apply" + sfx]
+        bn = torch.nn.BatchNorm1d(c).to(DEV)
+        x = torch.randn(shape, device=DEV, requires_grad=True)
+        assert run(act(bn.train(), x)) == (stats + fwd, bwd), sfx
+        assert run(act(bn.eval(), x)) == (fwd[-1:], bwd), sfx
+        a = torch.randn((b, c, m) if not sfx else (b, m, c), device=DEV)
+        y, partial = front(a, idx, w, None, None)
+        assert rec.take() == ["geot_fp_front" + sfx]
+        assert run(act(bn.train(), y, partial=partial)) == (fwd, bwd), sfx
+
+    c = 256
+    front, tail = ["geot_fp_front_cl"], ["geot_bn_sums_shifted_cl", "geot_bn_finalize", "geot_bn_apply_cl"]
+    bwd = ["geot_bn_bwd_reduce_skip_cl", "geot_bn_sums_k_cl", "geot_bn_bwd_coef"]
+    gather = ["geot_gather_rows_csr_bn_cl"]
+    bn = torch.nn.BatchNorm1d(c).to(DEV)
+    a_cl = torch.randn(b, m, c, device=DEV, requires_grad=True)
+    skip = torch.randn(b, 3, l, device=DEV)
+    wb = torch.randn(c, 3, device=DEV, requires_grad=True)
+    stage = lambda skip, wb, **kw: fn.fp_stage_cl(bn, a_cl, idx, w, skip, wb, **kw)      # noqa: E731
+    bn.train()
+    assert run(stage(skip, wb)) == (front + tail + ["geot_rowsum_f64"],
+                                    bwd + ["geot_rix_build"] + gather + ["geot_fp_skip_wgrad_cl"])
+    rix = fn.ReverseIndex(idx, w, m)
+    assert rec.take() == ["geot_rix_build"]
+    assert run(stage(skip, wb, rix=rix)) == (front + tail + ["geot_rowsum_f64"], bwd + gather + ["geot_fp_skip_wgrad_cl"])
+    assert run(stage(None, None)) == (front + tail, bwd + ["geot_rix_build"] + gather)
+    assert run(stage(skip.clone().requires_grad_(True), wb)) == (
+        front + tail + ["geot_rowsum_f64"], bwd + ["geot_rix_build"] + gather + ["geot_fp_skip_wgrad_cl", "geot_bn_bwd_apply_cl"])
+    bn.eval()
+    assert run(stage(skip, wb))[0] == front + ["geot_bn_apply_cl", "geot_rowsum_f64"]
+    assert run(stage(skip, wb.detach()))[0] == front + ["geot_bn_apply_cl"]
+    assert run(stage(None, None))[0] == front + ["geot_bn_apply_cl"]
