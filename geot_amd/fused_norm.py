@@ -403,6 +403,11 @@ class ReverseIndex:
         self.ws = torch.empty(self.ws_ints, dtype=torch.int32, device=idx.device)
         call("geot_rix_build", idx.device, b, n, m, nt, ptr(idx), ptr(weight), ptr(order), ptr(self.ws), self.ws_ints)
 
+    def tree_fields(self):
+        """(attributes that hold buffers, attributes that hold identities): graph_step.py clones / refills the former; the
+        rest (the shape) must agree."""
+        return ("ws", "order"), ()
+
     def gather(self, g_cl):
         b, n, c = g_cl.shape
         assert (b, n) == (self.b, self.n)

@@ -42,35 +42,46 @@ import os
 import torch
 
 from . import streams
-from .fused_norm import ReverseIndex
-
-_IDENTITY_KEYS = ("pts", "version", "grouped", "src")     # of a geometry: tensor identities and events, never copied
 
 
-# ---- structure helpers: P's product is a tree of dicts / tuples of tensors, ReverseIndex objects and python scalars ------
+# ---- structure helpers: P's product is a tree of dicts / tuples (plain and named) of tensors, python scalars and objects
+# that say themselves which of their attributes are buffers and which identities (`tree_fields()`: Geometry, ReverseIndex) ----
+def _rebuilt(obj, items):
+    return type(obj)(*items) if hasattr(obj, "_fields") else type(obj)(items)      # (a namedtuple takes its items one by one)
+
+
 def tree_clone(obj):
-    """Fresh buffers with the same contents."""
+    """Fresh buffers with the same contents; identities (tensors matched by `is`, events) dropped."""
     if torch.is_tensor(obj):
         return obj.detach().clone()
     if isinstance(obj, dict):
-        return {k: (None if k in _IDENTITY_KEYS else tree_clone(v)) for k, v in obj.items()}
+        return {k: tree_clone(v) for k, v in obj.items()}
     if isinstance(obj, (list, tuple)):
-        return type(obj)(tree_clone(v) for v in obj)
-    if isinstance(obj, ReverseIndex):
+        return _rebuilt(obj, [tree_clone(v) for v in obj])
+    if hasattr(obj, "tree_fields"):
+        buffers, identities = obj.tree_fields()
         new = copy.copy(obj)
-        new.ws, new.order = tree_clone(obj.ws), tree_clone(obj.order)
+        for k in buffers:
+            setattr(new, k, tree_clone(getattr(obj, k)))
+        for k in identities:
+            setattr(new, k, None)
         return new
     return obj
 
 
 def tree_detach(obj):
-    """The same buffers without their autograd history (tensors only; containers rebuilt, everything else as it is)."""
+    """The same buffers without their autograd history (containers and tree_fields() objects rebuilt, everything else as it is)."""
     if torch.is_tensor(obj):
         return obj.detach()
     if isinstance(obj, dict):
         return {k: tree_detach(v) for k, v in obj.items()}
     if isinstance(obj, (list, tuple)):
-        return type(obj)(tree_detach(v) for v in obj)
+        return _rebuilt(obj, [tree_detach(v) for v in obj])
+    if hasattr(obj, "tree_fields"):
+        new = copy.copy(obj)
+        for k in obj.tree_fields()[0]:
+            setattr(new, k, tree_detach(getattr(obj, k)))
+        return new
     return obj
 
 
@@ -82,20 +93,22 @@ def tree_copy_(dst, src, path="pre"):
         dst.copy_(src)
     elif isinstance(dst, dict):
         for k, v in dst.items():
-            if k not in _IDENTITY_KEYS:
-                tree_copy_(v, src[k], "%s[%r]" % (path, k))
+            tree_copy_(v, src[k], "%s[%r]" % (path, k))
     elif isinstance(dst, (list, tuple)):
         if not isinstance(src, (list, tuple)) or len(dst) != len(src):
             raise RuntimeError("%s: structure changed" % path)
         for i, (d, s) in enumerate(zip(dst, src)):
             tree_copy_(d, s, "%s[%d]" % (path, i))
-    elif isinstance(dst, ReverseIndex):
-        if (dst.b, dst.n, dst.m, dst.nt, dst.ws_ints) != (src.b, src.n, src.m, src.nt, src.ws_ints):
-            raise RuntimeError("%s: reverse index of another shape" % path)
-        tree_copy_(dst.ws, src.ws, path + ".ws")
-        if dst.order is not None:
-            tree_copy_(dst.order, src.order, path + ".order")
-    elif dst != src:
+    elif hasattr(dst, "tree_fields"):
+        if type(src) is not type(dst):
+            raise RuntimeError("%s: structure changed" % path)
+        buffers, identities = dst.tree_fields()
+        for k in vars(dst):
+            if k in buffers:
+                tree_copy_(getattr(dst, k), getattr(src, k), "%s.%s" % (path, k))
+            elif k not in identities and getattr(dst, k) != getattr(src, k):
+                raise RuntimeError("%s.%s: %r became %r" % (path, k, getattr(dst, k), getattr(src, k)))
+    elif dst is not src and (torch.is_tensor(src) or dst != src):
         raise RuntimeError("%s: %r became %r" % (path, dst, src))
 
 

@@ -35,6 +35,7 @@ from ....pointnet2.pytorch_utils import PointwiseConv1d, PointwiseConv2d, pointw
 from ....knn_cuda import KNN, knn_sorted
 from .transformer_ops import (Group, fps, fps_downsample, graph_feature, get_graph_feature_unfused,  # noqa: F401
                               edgeconv_tail, edgeconv_tail_eligible, edgeconv_reverse_index)
+from .geometry import EdgeEntry, FpEntry, Geometry, IndexPlan
 from .... import streams
 from ....ntm import sig_t_mean  # noqa: F401  (transformer.py:1099-1131 lives in ntm.py)
 from ....fused_norm import bn_act, fp_front, fp_front_eligible, max_last, add_last_broadcast, thin_mm, add_channel_bias
@@ -331,11 +332,9 @@ class DGCNN_Propagation(nn.Module):
         """(B, 2C, Nq, k) = cat(x_k[nbr] - x_q, x_q), one fused kernel (transformer.py:343-364)."""
         return graph_feature(x_q, x_k, _knn_idx(coor_q, coor_k, self.k))
 
-    def _edge(self, layer, coor_q, x_q, coor_k, x_k, idx=None):
-        """idx: the kNN ids (B,Nq,k), or the pair (ids, reverse index of the ids) when the caller built both ahead."""
-        rix = None
-        if isinstance(idx, (tuple, list)):
-            idx, rix = idx
+    def _edge(self, layer, coor_q, x_q, coor_k, x_k, entry=None):
+        """entry: the EdgeEntry (kNN ids (B,Nq,k) and, optionally, their reverse index) the caller built ahead, or None."""
+        idx, rix = entry if entry is not None else (None, None)
         conv, norm, act = layer[0], layer[1], layer[2]
         if self.dense != "factored":
             y = conv(self.get_graph_feature(coor_q, x_q, coor_k, x_k))
@@ -354,8 +353,8 @@ class DGCNN_Propagation(nn.Module):
         return act(norm(y)).max(dim=-1, keepdim=False)[0]
 
     def forward(self, coor, f, coor_q, f_q, idx=None):
-        """coor, f: (B,3,G), (B,C,G) source; coor_q, f_q: (B,3,N), (B,C,N) target.  idx (optional): the two kNN id
-        tensors (queries among the sources, queries among themselves), when the caller has searched them already."""
+        """coor, f: (B,3,G), (B,C,G) source; coor_q, f_q: (B,3,N), (B,C,N) target.  idx (optional): the two EdgeEntry
+        records (queries among the sources, queries among themselves), when the caller has searched them already."""
         i1, i2 = idx if idx is not None else (None, None)
         f_q = self._edge(self.layer1, coor_q, f_q, coor, f, i1)
         return self._edge(self.layer2, coor_q, f_q, coor_q, f_q, i2)
@@ -364,8 +363,8 @@ class DGCNN_Propagation(nn.Module):
 def _fp_factored(fp, unknown, known, unknow_feats, known_feats, nn3=None, layout="cf"):
     """forward of a PointnetFPModule (pointnet2_modules.py:597-642) with the first 1x1 convolution moved in
     front of the interpolation (see the module docstring); the parameters are ``fp``'s own.  nn3 (optional): the
-    (idx, weight) pair of three_nn + the inverse-distance weights, when the caller has computed them already -- for the
-    point-major layout optionally followed by (order, rix): the Morton sequence of the unknown points
+    FpEntry of three_nn + the inverse-distance weights, when the caller has computed them already -- for the
+    point-major layout optionally with (order, rix): the Morton sequence of the unknown points
     (fused_norm.local_spatial_order) and the ReverseIndex of (idx, weight) for the gradient.
     layout "cl": the first stage runs on point-major (B, n, C) activations where the layer is wide enough."""
     layers = list(fp.mlp.children())
@@ -376,14 +375,11 @@ def _fp_factored(fp, unknown, known, unknow_feats, known_feats, nn3=None, layout
     # the two column blocks of the first convolution (known features | skip features) as ONE split: its backward is a single
     # concatenation, where two slices cost two zero-fills, two copies and an add per step
     w_known, w_skip = torch.split(w, [c, w.shape[1] - c], dim=1) if w.shape[1] > c else (w, None)
-    order = rix = None
     if nn3 is None:
         dist2, idx = pt_utils._ext.three_nn(unknown.contiguous(), known.contiguous())
-        weight = None
+        weight = order = rix = None
     else:
-        idx, weight = nn3[:2]
-        if len(nn3) > 2:
-            order, rix = nn3[2:]
+        idx, weight, order, rix = nn3
     has_bn = any(name == "bn" for name, _ in first.named_children())
     post_act = next(iter(first.named_children()))[0] == "conv"            # conv -> BatchNorm -> ReLU order
     if (layout == "cl" and conv.bias is None and has_bn and post_act and len(layers) > 1
@@ -533,7 +529,7 @@ class PointTransformer_seg_T(nn.Module):
             dist2, idx = pt_utils._ext.three_nn(unknown.contiguous(), known.contiguous())
             weight = pt_utils._ext.fp_weights(dist2)
             if self.fp_layout != "cl":
-                return idx, weight
+                return FpEntry(idx, weight)
             # point-major FP stages: in training the reverse index of the gradient; where the table of known points is
             # larger than an XCD's L2 (4 MB: m > 2048 rows at 384 channels in, 1536 out) also the Morton sequences in which
             # the forward takes its points and the gradient its targets -- a small table is L2-resident in any order
@@ -542,9 +538,8 @@ class PointTransformer_seg_T(nn.Module):
             big = known.shape[1] > 2048
             # the gradient's targets (= the known points) in Morton order for every stage: its workgroups are dealt consecutive
             # lists inside an XCD (gather_group.hip gr_deal), which only pays when consecutive lists share source rows
-            tgt_order = big or os.environ.get("GEOT_FP_RIX_ORDER", "all") == "all"
-            rix = ReverseIndex(idx, weight, known.shape[1], local_spatial_order(known) if tgt_order else None) if self.training else None
-            return idx, weight, local_spatial_order(unknown) if big else None, rix
+            rix = ReverseIndex(idx, weight, known.shape[1], local_spatial_order(known)) if self.training else None
+            return FpEntry(idx, weight, local_spatial_order(unknown) if big else None, rix)
         k2, k1 = self.dgcnn_pro_2.k, self.dgcnn_pro_1.k
 
         def graph(coor_q, coor_k, k):
@@ -552,59 +547,58 @@ class PointTransformer_seg_T(nn.Module):
             # per layer that would otherwise sit on the backward's critical path)
             idx = _knn_idx(coor_q, coor_k, k)
             if not (self.training and self.dgcnn_pro_1.fused_tail):
-                return idx
-            return idx, edgeconv_reverse_index(idx, coor_k.shape[2])
-        return {"center_pts": center_pts, "center_pts_trans": trans, "center_trans": center_trans,
-                "fp2": nn3(center_pts[1], center), "fp1": nn3(center_pts[0], center), "fp0": nn3(pts, center_pts[0]),
-                "dg2": (graph(trans[1], center_trans, k2), graph(trans[1], trans[1], k2)),
-                "dg1": (graph(trans[0], trans[1], k1), graph(trans[0], trans[0], k1))}
+                return EdgeEntry(idx)
+            return EdgeEntry(idx, edgeconv_reverse_index(idx, coor_k.shape[2]))
+        return IndexPlan(center_pts, trans, center_trans,
+                         fp2=nn3(center_pts[1], center), fp1=nn3(center_pts[0], center), fp0=nn3(pts, center_pts[0]),
+                         dg2=(graph(trans[1], center_trans, k2), graph(trans[1], trans[1], k2)),
+                         dg1=(graph(trans[0], trans[1], k1), graph(trans[0], trans[0], k1)))
 
     def forward(self, pts, x=None, cls_label=None, T=None, geometry=None):
         with pointops.fps_prefix_scope():       # the three pointops.fps targets are prefixes of one FPS run
             return self._forward(pts, x, cls_label, T, geometry)
 
+    def _coordinate_work(self, pts, after_group=None):
+        """The coordinate-only work of a batch on the CURRENT stream: Group, the 8192-sample FPS (largest target; the shorter
+        ones are prefixes) and the index plan -> (group, plan).  after_group(): called between Group and the rest."""
+        with pointops.fps_prefix_scope():
+            group = self.group_divider(pts)
+            if after_group is not None:
+                after_group()
+            pointops.fps_indices(pts, max(self.downsample_targets))
+            return group, self._index_plan(pts, group[1])
+
     @torch.no_grad()
-    def prefetch_geometry(self, pts, inline=False):
+    def prefetch_geometry(self, pts, inline=False, sources=None):
         """Queue everything forward() derives from the COORDINATES of a batch -- Group (512-sample FPS, kNN, the
         neighbourhoods), the 8192-sample FPS and the index plan -- on the side stream, for a batch that will be passed
         to forward(pts, ..., geometry=<the result>) later: a training loop calls this with batch k + 1 between the
         forward and the backward of batch k, so that ~6.5 ms of few-workgroup kernels run beside the GEMM-bound backward
-        instead of at the head of the next step and beside its (shorter) encoder.  GEOT_LOOKAHEAD=group queues Group only.  Same kernels on the same inputs: the
-        results are those forward() would compute itself.  None when the model cannot use it (CPU, overlap off)."""
+        instead of at the head of the next step and beside its (shorter) encoder.  Same kernels on the same inputs: the
+        results are those forward() would compute itself.  sources: the caller's tensors `pts` was assembled from (the
+        Geometry remembers them; default: pts).  None when the model cannot use it (CPU, overlap off)."""
         if inline:
             # the same work on the CURRENT stream, handed back as a geometry the caller vouches for ("static"): graph_step.py
             # captures it as a single-stream graph and replays that beside the training graph
             if not (pts.is_cuda and self.dense == "factored"):
                 return None
             pts = pts.contiguous()
-            with pointops.fps_prefix_scope():
-                group = self.group_divider(pts)
-                pointops.fps_indices(pts, max(self.downsample_targets))
-                plan = self._index_plan(pts, group[1])
-            return {"pts": pts, "version": None, "group": group, "grouped": None, "plan": plan, "training": self.training,
-                    "fp_layout": self.fp_layout, "static": True}
+            group, plan = self._coordinate_work(pts)
+            return Geometry(pts, group, plan, self.training, self.fp_layout, static=True)
         if not (pts.is_cuda and self.overlap and self.dense == "factored" and streams.may_fork(pts.device)):
             return None
         pts = pts.contiguous()
         dev = pts.device
         side, main = self._side_stream(dev), torch.cuda.current_stream(dev)
         side.wait_stream(main)            # pts is ready; every side-stream allocation starts behind main's earlier uses
-        with torch.cuda.stream(side), pointops.fps_prefix_scope():
-            group = self.group_divider(pts)
-            grouped = streams.event()
-            grouped.record(side)
-            plan = None
-            if os.environ.get("GEOT_LOOKAHEAD", "all") == "all":
-                # also the 8192-sample FPS and the index plan.  Beside the next batch's encoder + 12 blocks (~5 ms of main-stream
-                # work) those ~6 ms of side-stream work ARE the critical path: the decoder waits for them (measured: queueing
-                # only Group gains nothing, 33.94 vs 33.97 ms; queueing everything 33.64).  Beside the backward's GEMMs the
-                # FPS launch itself takes 5.6 instead of 4.7 ms, but nothing waits for it
-                pointops.fps_indices(pts, max(self.downsample_targets))
-                plan = self._index_plan(pts, group[1])
-            ready = streams.event()          # everything above is done: what a consumer OTHER than this model waits for
-            ready.record(side)               # (this model's own forward waits for its side stream; slice_geometry's user cannot)
-        return {"pts": pts, "version": pts._version, "group": group, "grouped": grouped, "plan": plan,
-                "training": self.training, "fp_layout": self.fp_layout, "ready": ready}
+        grouped, ready = streams.event(), streams.event()
+        with torch.cuda.stream(side):
+            # Beside the next batch's encoder + 12 blocks (~5 ms of main-stream work) the ~6 ms behind Group ARE the critical
+            # path: the decoder waits for them.  Beside the backward's GEMMs the FPS launch itself takes 5.6 instead of
+            # 4.7 ms, but nothing waits for it
+            group, plan = self._coordinate_work(pts, after_group=lambda: grouped.record(side))
+            ready.record(side)               # everything above is done: what a consumer OTHER than this model waits for
+        return Geometry(pts, group, plan, self.training, self.fp_layout, grouped=grouped, ready=ready, sources=sources)
 
     def _forward(self, pts, x, cls_label, T, geometry=None):
         B, N, _ = pts.shape
@@ -613,25 +607,17 @@ class PointTransformer_seg_T(nn.Module):
         top = max(self.downsample_targets)
         plan = ready = None
         forked = False                    # has this forward queued work on the side stream (and must wait for it)?
-        if (geometry is not None and geometry["training"] == self.training and geometry["fp_layout"] == self.fp_layout
-                and (geometry.get("static") or (side is not None and geometry["pts"] is pts and geometry["version"] == pts._version))):
-            # the coordinate-only work of this batch was queued on the side stream earlier (prefetch_geometry); "static": the
-            # caller holds the geometry in fixed buffers it refills itself and vouches for it (graph_step.py: a hipGraph replay
+        if geometry is not None and geometry.usable(pts, self.training, self.fp_layout, side is not None):
+            # the coordinate-only work of this batch was queued on the side stream earlier (prefetch_geometry), or is static:
+            # the caller holds it in fixed buffers it refills itself and vouches for it (graph_step.py: a hipGraph replay
             # has no tensor identities to check -- the wrapper checks them on the host before it replays)
             main = torch.cuda.current_stream(pts.device)
-            if geometry.get("grouped") is not None:
-                main.wait_event(geometry["grouped"])
-            ready = geometry.get("ready")
-            forked = not geometry.get("static")   # a queued geometry's plan is still on the side stream; a static one is memory
-            neighborhood, center, idx = geometry["group"]
-            plan = geometry["plan"]
-            if plan is None and side is not None:   # the long FPS and the index plan beside this batch's encoder, as without look-ahead
-                forked = True
-                side.wait_stream(main)
-                with torch.cuda.stream(side):
-                    pointops.fps_indices(pts, top)
-                    if os.environ.get("GEOT_INDEX_PLAN", "side") == "side":
-                        plan = self._index_plan(pts, center)
+            if geometry.grouped is not None:
+                main.wait_event(geometry.grouped)
+            ready = geometry.ready
+            forked = not geometry.static      # a queued geometry's plan is still on the side stream; a static one is memory
+            neighborhood, center, idx = geometry.group
+            plan = geometry.plan
         else:
             # the long FPS (largest target; the shorter ones are prefixes, pointops.fps_indices) beside the encoder
             if side is not None:
@@ -687,25 +673,19 @@ class PointTransformer_seg_T(nn.Module):
             "the length of the cardinality and the features should be the same"
         if forked:
             main.wait_stream(side)
-            if ready is not None:         # a geometry queued by ANOTHER model (slice_geometry): its producer's stream, not ours
+            if ready is not None:         # a geometry queued by ANOTHER model (Geometry.slice): its producer's stream, not ours
                 main.wait_event(ready)
-        if plan is not None:
-            center_pts, center_pts_trans = plan["center_pts"], plan["center_pts_trans"]
-        else:
-            plan = {}
+        if plan is None:                  # no entries: every module searches its own indices in line
             center_pts = [pointops.fps(pts, t) for t in self.downsample_targets]
-            center_pts_trans = [pt.transpose(-1, -2).contiguous() for pt in center_pts]
+            plan = IndexPlan(center_pts, [pt.transpose(-1, -2).contiguous() for pt in center_pts], center_trans)
+        center_pts, center_pts_trans = plan.center_pts, plan.center_pts_trans
 
         f_l3 = inter_feats[2]
-        f_l2 = self._fp(self.propogation_2, center_pts[1], center, center_pts_trans[1], inter_feats[1], plan.get("fp2"))
-        f_l1 = self._fp(self.propogation_1, center_pts[0], center, center_pts_trans[0], inter_feats[0], plan.get("fp1"))
-        if plan.get("dg2") is not None:
-            f_l2 = self.dgcnn_pro_2(center_trans, f_l3, center_pts_trans[1], f_l2, plan["dg2"])
-            f_l1 = self.dgcnn_pro_1(center_pts_trans[1], f_l2, center_pts_trans[0], f_l1, plan["dg1"])
-        else:
-            f_l2 = self.dgcnn_pro_2(center_trans, f_l3, center_pts_trans[1], f_l2)
-            f_l1 = self.dgcnn_pro_1(center_pts_trans[1], f_l2, center_pts_trans[0], f_l1)
-        f_l0 = self._fp(self.propogation_0, center_original, center_pts[0], f_l0, f_l1, plan.get("fp0"))
+        f_l2 = self._fp(self.propogation_2, center_pts[1], center, center_pts_trans[1], inter_feats[1], plan.fp2)
+        f_l1 = self._fp(self.propogation_1, center_pts[0], center, center_pts_trans[0], inter_feats[0], plan.fp1)
+        f_l2 = self.dgcnn_pro_2(center_trans, f_l3, center_pts_trans[1], f_l2, plan.dg2)
+        f_l1 = self.dgcnn_pro_1(center_pts_trans[1], f_l2, center_pts_trans[0], f_l1, plan.dg1)
+        f_l0 = self._fp(self.propogation_0, center_original, center_pts[0], f_l0, f_l1, plan.fp0)
 
         head = self.seg_head                     # conv -> BatchNorm1d -> Dropout -> conv; the BatchNorm as one fused op
         if self.dense != "reference" and isinstance(head[0], PointwiseConv1d):
@@ -715,40 +695,6 @@ class PointTransformer_seg_T(nn.Module):
             logit = head[3](head[2](bn_act(head[1], head[0](f_l0), relu=False)))
         correction = self.T_linear(T) if T is not None else None
         return logit, correction, self.sigma, f_l0
-
-
-def slice_geometry(geometry, lo, hi):
-    """The geometry (prefetch_geometry's result) of clouds [lo, hi) of the batch `geometry` describes, for a model in EVAL
-    mode: every entry is per cloud -- sample ids, neighbour ids and Morton orders are cloud-local -- so the slices are exactly
-    what prefetch_geometry(pts[lo:hi]) of an eval-mode model would compute; the training-only entries (the reverse indices of
-    the gradients) are dropped.  FixMatch's frozen teacher sees the weak view, which is also the last third of the student's
-    batch: its geometry -- an 8192-sample FPS, Group, the index plan -- need not be computed twice."""
-    if geometry is None or geometry.get("plan") is None:
-        return None
-    pts = geometry["pts"]
-    b, n = pts.shape[0], pts.shape[1]
-    neighborhood, center, idx = geometry["group"]
-    flat = None if idx is None else (idx.view(b, -1)[lo:hi] - lo * n).reshape(-1)
-    plan = geometry["plan"]
-
-    def cut(t):
-        return None if t is None else t[lo:hi]
-
-    def fp(entry):                   # (idx, weight) or (idx, weight, Morton order, reverse index)
-        return tuple(cut(t) for t in entry[:3]) + ((None,) if len(entry) > 3 else ())
-
-    def graph(entry):                # ids, or (ids, reverse index) in training
-        return cut(entry[0] if isinstance(entry, tuple) else entry)
-    new_plan = {"center_pts": [cut(t) for t in plan["center_pts"]], "center_pts_trans": [cut(t) for t in plan["center_pts_trans"]],
-                "center_trans": cut(plan["center_trans"]), "fp2": fp(plan["fp2"]), "fp1": fp(plan["fp1"]), "fp0": fp(plan["fp0"]),
-                "dg2": tuple(graph(e) for e in plan["dg2"]), "dg1": tuple(graph(e) for e in plan["dg1"])}
-    out = {"pts": pts[lo:hi], "version": geometry["version"], "group": (neighborhood[lo:hi], center[lo:hi], flat),
-           "grouped": geometry.get("grouped"), "plan": new_plan, "training": False, "fp_layout": geometry["fp_layout"]}
-    if geometry.get("static"):
-        out["static"] = True
-    if geometry.get("ready") is not None:
-        out["ready"] = geometry["ready"]
-    return out
 
 
 TOOTH_SEG_CFG = dict(trans_dim=384, depth=12, num_heads=4, group_size=32, num_group=512, encoder_dims=256,

@@ -50,39 +50,28 @@ class WholePartSeg(nn.Module):
     def prefetch_geometry(self, p0, u0=None, if_teacher=False, fixmatch=False, inline=False):
         """Queue the coordinate-only work of the batch a LATER forward(p0, ..., geometry=<result>) will see
         (PointTransformer_seg_T.prefetch_geometry); None when the segmentor has no such thing.  The result remembers WHICH
-        tensors it was computed from (`src`: the caller's coordinate tensors and their version counters): forward() takes it
-        only for exactly those tensors, unedited."""
+        tensors it was computed from (the caller's coordinate tensors and their version counters): forward() takes it only
+        for exactly those tensors, unedited.  inline: on the current stream, for a caller that vouches for it (graph_step.py)."""
         if not hasattr(self.segmentor, "prefetch_geometry"):
             return None
-        if inline:       # on the current stream, for a caller that vouches for it (graph_step.py)
-            return self.segmentor.prefetch_geometry(self.batch_positions(p0, u0, if_teacher, fixmatch), inline=True)
-        g = self.segmentor.prefetch_geometry(self.batch_positions(p0, u0, if_teacher, fixmatch))
-        if g is not None:
-            g["src"] = tuple((t, t._version) for t in self._position_views(p0, u0, if_teacher, fixmatch))
-        return g
+        return self.segmentor.prefetch_geometry(self.batch_positions(p0, u0, if_teacher, fixmatch), inline=inline,
+                                                sources=self._position_views(p0, u0, if_teacher, fixmatch))
 
     @classmethod
     def weak_view_geometry(cls, geometry, p0, u0):
         """From the geometry of a fixmatch=True batch (labelled + strong + weak views of p0 / u0) the geometry a frozen,
-        eval-mode teacher's forward(u0, if_teacher=True) takes: the weak view's slice (slice_geometry) -- the same sampling,
+        eval-mode teacher's forward(u0, if_teacher=True) takes: the weak view's slice (Geometry.slice) -- the same sampling,
         grouping and index work, not done twice.  None when there is nothing to slice."""
-        from ..backbone.transformer import slice_geometry
         if geometry is None:
             return None
         lo = p0["pos"].shape[0] + u0["pos_s"].shape[0]
-        g = slice_geometry(geometry, lo, lo + u0["pos_w"].shape[0])
-        if g is not None and not g.get("static"):
-            g["src"] = tuple((t, t._version) for t in cls._position_views(u0, if_teacher=True))
-        return g
+        return geometry.slice(lo, lo + u0["pos_w"].shape[0], sources=cls._position_views(u0, if_teacher=True))
 
     def forward(self, p0, f0=None, cls0=None, u0=None, if_teacher=False, fixmatch=False, geometry=None):
-        if geometry is not None and not geometry.get("static"):
+        if geometry is not None and not geometry.describes(self._position_views(p0, u0, if_teacher, fixmatch)):
             # a geometry describes the tensors it was computed from and nothing else: the same objects, not edited since
             # (a batch of the same SHAPE is not the same batch); anything else is computed in line
-            views = self._position_views(p0, u0, if_teacher, fixmatch)
-            src = geometry.get("src")
-            if src is None or len(src) != len(views) or not all(t is v and t._version == ver for v, (t, ver) in zip(views, src)):
-                geometry = None
+            geometry = None
         if if_teacher:
             p0, f0, cls0 = p0["pos_w"].detach(), p0["x_w"].detach(), p0["cls_w"].detach()
         elif hasattr(p0, "keys"):
@@ -95,10 +84,10 @@ class WholePartSeg(nn.Module):
                 p0, f0, cls0 = p0["pos"], p0["x"], p0["cls"]
         elif f0 is None:
             f0 = p0.transpose(1, 2).contiguous()
-        if geometry is not None and not geometry.get("static"):
+        if geometry is not None:
             # same coordinates (checked above): hand the segmentor the tensor the geometry was computed on, so that it
             # recognises it (the concatenation above made a new one)
-            p0 = geometry["pts"]
+            p0 = geometry.positions(p0)
         T = u0["T"] if (u0 is not None and "T" in u0.keys()) else None
         if geometry is not None:
             f, p, s, _ = self.segmentor(p0, f0, cls0, T, geometry=geometry)

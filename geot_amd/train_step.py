@@ -128,7 +128,7 @@ class GradSync:
 
     def __init__(self, modules, group=None, broadcast=True):
         import torch.distributed as dist
-        modules = [m.module if hasattr(m, "module") else m for m in modules]
+        modules = [_unwrapped(m) for m in modules]
         self.params = [p for m in modules for p in m.parameters() if p.requires_grad]
         self.group = group
         self.world = dist.get_world_size(group)
@@ -159,9 +159,26 @@ class GradSync:
         torch._foreach_copy_(flat_grads, self.views)
 
 
+def _unwrapped(module):
+    """The module inside a DistributedDataParallel wrapper (the module itself when it is not wrapped)."""
+    return module.module if hasattr(module, "module") else module
+
+
 def _inner(module, bypass):
     """The module a step calls: DDP's wrapped module when the step exchanges its gradients itself (GradSync)."""
-    return module.module if (bypass and hasattr(module, "module")) else module
+    return _unwrapped(module) if bypass else module
+
+
+def _update(grad_sync, clip, model, optimizers):
+    """The tail of an iteration behind its backward: the step's own gradient exchange (GradSync, if any), clipping of
+    `model`'s gradients, then every optimizer in order (train.py:656-660)."""
+    if grad_sync is not None:
+        grad_sync()
+    if clip is not None:
+        torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
+    for optimizer in optimizers:
+        optimizer.step()
+        optimizer.zero_grad(set_to_none=True)
 
 
 def parameter_groups(model, weight_decay=1e-4, skip_list=()):
@@ -170,7 +187,7 @@ def parameter_groups(model, weight_decay=1e-4, skip_list=()):
     train.py:169 / :225): every 1-D parameter (BatchNorm / LayerNorm / GroupNorm weights, `sigma`, ...), every
     `*.bias` and everything named in the model's no_weight_decay() goes WITHOUT weight decay, the rest with it.
     Group order and the `lr_scale` key are the factory's (first appearance; 1.0 without layer decay)."""
-    module = model.module if hasattr(model, "module") else model          # DDP wrapper: the factory looks inside (:190-193)
+    module = _unwrapped(model)                                            # DDP wrapper: the factory looks inside (:190-193)
     if not skip_list and hasattr(module, "no_weight_decay"):
         skip_list = module.no_weight_decay()
     groups = {}
@@ -226,14 +243,33 @@ def _mode(module, training):
         module.train(training)
 
 
-def _lookahead_at_blocks(segmentor, default):
-    """Where a step queues its look-ahead: inside the backward, when it reaches the transformer blocks ("blocks"; the model
-    must offer the hook), or right behind the forward ("forward").  GEOT_LOOKAHEAD_AT overrides the step's default --
-    measured (profiles/r03_ab_lookahead_at*.txt): the supervised step 33.27 ms at "blocks" against 33.61 at "forward" (behind
-    the forward the 8192-sample FPS shares the chip with the decoder's widest GEMMs and takes 5.5 instead of 4.8 ms); the
-    FixMatch iteration 32.1 ms at "forward" against 32.7 at "blocks" (behind its student forward come the NTM block and the
-    losses: a stretch of small kernels that leaves the FPS launches room)."""
-    return os.environ.get("GEOT_LOOKAHEAD_AT", default) == "blocks" and hasattr(segmentor, "at_blocks_backward")
+class _LookAhead:
+    """Where an iteration queues the next batch's geometry -- make() -> the geometry, or None: nothing to queue -- inside the
+    backward, when it reaches the transformer blocks ("blocks"; the segmentor must offer the hook), or right behind the
+    forward ("forward").  GEOT_LOOKAHEAD_AT overrides the step's default -- measured (profiles/r03_ab_lookahead_at*.txt): the
+    supervised step 33.27 ms at "blocks" against 33.61 at "forward" (behind the forward the 8192-sample FPS shares the chip
+    with the decoder's widest GEMMs and takes 5.5 instead of 4.8 ms); the FixMatch iteration 32.1 ms at "forward" against
+    32.7 at "blocks" (behind its student forward come the NTM block and the losses: a stretch of small kernels that leaves
+    the FPS launches room)."""
+
+    def __init__(self, segmentor, default, make):
+        self.segmentor, self.make, self.queued = segmentor, make, None
+        self.at_blocks = os.environ.get("GEOT_LOOKAHEAD_AT", default) == "blocks" and hasattr(segmentor, "at_blocks_backward")
+        if make is not None and self.at_blocks:
+            segmentor.at_blocks_backward = self._queue     # runs inside the backward, when it reaches the transformer blocks
+
+    def _queue(self):
+        self.queued = self.make()
+
+    def behind_forward(self):
+        if self.make is not None and not self.at_blocks:
+            self._queue()
+
+    def done(self):
+        """Behind the backward: clear the hook -> what was queued (None: nothing)."""
+        if self.at_blocks:
+            self.segmentor.at_blocks_backward = None
+        return self.queued
 
 
 class SupervisedStep:
@@ -270,7 +306,7 @@ class SupervisedStep:
         plan), on the CURRENT stream -> what iteration(geometry=...) takes.  graph_step.py replays this as a graph of its
         own beside the previous iteration's training graph."""
         _mode(self.model, True)
-        inner = self.model.module if hasattr(self.model, "module") else self.model
+        inner = _unwrapped(self.model)
         return inner.prefetch_geometry(pos, inline=True) if hasattr(inner, "prefetch_geometry") else None
 
     def forward_loss(self, pos, cls, target, geometry=None, class_weights=None):
@@ -285,19 +321,14 @@ class SupervisedStep:
     def backward_update(self, loss):
         """The second half: backward, clipping, the optimizer -> the detached loss."""
         loss.backward()
-        if self.grad_sync is not None:
-            self.grad_sync()
-        if self.clip is not None:
-            torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.clip)
-        self.optimizer.step()
-        self.optimizer.zero_grad(set_to_none=True)
+        _update(self.grad_sync, self.clip, self.model, self.optimizers())
         return loss.detach()
 
     def forward_backward_head(self, pos, cls, target, geometry=None, class_weights=None):
         """The iteration up to the point where the backward reaches the transformer blocks -- forward, loss, the backward of
         the head and the decoder -- for a model that can cut its autograd graph there (cut_at_blocks / take_cut: the
         segmentor); otherwise the whole backward.  -> (detached loss, what backward_rest_update needs)."""
-        inner = self.model.module if hasattr(self.model, "module") else self.model
+        inner = _unwrapped(self.model)
         can_cut = hasattr(inner, "take_cut")
         if can_cut:
             inner.cut_at_blocks = True
@@ -315,31 +346,20 @@ class SupervisedStep:
         """The rest of the backward (the blocks, the patch encoder), clipping, the optimizer."""
         if rest is not None:
             torch.autograd.backward(rest[0], rest[1])
-        if self.grad_sync is not None:
-            self.grad_sync()
-        if self.clip is not None:
-            torch.nn.utils.clip_grad_norm_(self.model.parameters(), self.clip)
-        self.optimizer.step()
-        self.optimizer.zero_grad(set_to_none=True)
+        _update(self.grad_sync, self.clip, self.model, self.optimizers())
 
     def iteration(self, pos, cls, target, geometry=None, next_pos=None, class_weights=None):
         """One iteration -> (detached loss, the geometry queued for next_pos or None)."""
-        inner = self.model.module if hasattr(self.model, "module") else self.model
-        queued = [None]
-        queue = None
+        inner = _unwrapped(self.model)
+        make = None
         if next_pos is not None and hasattr(inner, "prefetch_geometry"):
-            def queue():
-                queued[0] = inner.prefetch_geometry(next_pos)
-        at_blocks = _lookahead_at_blocks(inner, "blocks")
-        if queue is not None and at_blocks:
-            inner.at_blocks_backward = queue          # runs inside the backward, when it reaches the transformer blocks
+            def make():
+                return inner.prefetch_geometry(next_pos)
+        look = _LookAhead(inner, "blocks", make)
         loss = self.forward_loss(pos, cls, target, geometry, class_weights)
-        if queue is not None and not at_blocks:
-            queue()                                   # (GEOT_LOOKAHEAD_AT=forward: right behind the forward)
+        look.behind_forward()
         loss = self.backward_update(loss)
-        if at_blocks:
-            inner.at_blocks_backward = None
-        return loss, queued[0]
+        return loss, look.done()
 
 
 class FixMatchNTMStep:
@@ -372,7 +392,6 @@ class FixMatchNTMStep:
         self.group = group
         self._side = None
         self._geometry = (None, None)      # coordinate-only work of the next student / teacher batch (look-ahead)
-        self._geometry_src = None
         self._teacher_stream = None
         # the frozen teacher's forward on its own stream beside the student's (same results; GEOT_TEACHER_STREAM=0: in line)
         self.overlap_teacher = os.environ.get("GEOT_TEACHER_STREAM", "1") != "0"
@@ -420,16 +439,11 @@ class FixMatchNTMStep:
         next_batches = (data', data_u') of the NEXT iteration when the loop already holds them: the coordinate-only work of
         the next student and teacher batches is queued behind this iteration's student forward (SupervisedStep's look-ahead;
         the caller must then pass exactly those dicts next time -- the positions are matched by identity and version
-        counter, not trusted)."""
+        counter, not trusted: WholePartSeg.forward refuses a geometry of other tensors, for the student and for the teacher
+        alike, and the work is done in line)."""
         self.check_meter_batch(data_u)
-        geoms = self._geometry
-        self._geometry = (None, None)
-        if geoms[0] is not None and not _same_positions_impl(self._geometry_src, data, data_u):
-            geoms = (None, None)         # not the batches the look-ahead was given: do the work in line
+        geoms, self._geometry = self._geometry, (None, None)
         losses, self._geometry = self.iteration(data, data_u, geoms, next_batches)
-        if next_batches is not None:
-            src = (next_batches[0]["pos"], next_batches[1]["pos_s"], next_batches[1]["pos_w"])
-            self._geometry_src = src + (tuple(t._version for t in src),)
         return losses
 
     def _pseudo_labels(self, data_u, geom_t):
@@ -460,7 +474,7 @@ class FixMatchNTMStep:
         if self_labelling is None:
             self_labelling = self.self_labelling
         _mode(self.model, True)
-        inner = self.model.module if hasattr(self.model, "module") else self.model
+        inner = _unwrapped(self.model)
         with torch.no_grad():
             geom_s = inner.prefetch_geometry(data, data_u, fixmatch=True, inline=True)
             if not self_labelling:
@@ -506,20 +520,17 @@ class FixMatchNTMStep:
         if not self_labelling:
             with (torch.cuda.stream(t_stream) if t_stream is not None else contextlib.nullcontext()):
                 pseudo = self._pseudo_labels(data_u, geom_t)
-        inner = self.model.module if hasattr(self.model, "module") else self.model
-        queued = [(None, None)]
-        queue = None
+        inner = _unwrapped(self.model)
+        make = None
         if next_batches is not None:
             nd, nu = next_batches
 
-            def queue():
+            def make():
                 if not self_labelling:
                     _mode(self.model_t, False)
                 g_s = inner.prefetch_geometry(nd, nu, fixmatch=True)
-                queued[0] = (g_s, None if self_labelling else self._teacher_geometry(inner, g_s, nd, nu))
-        at_blocks = _lookahead_at_blocks(inner.segmentor, "forward")
-        if queue is not None and at_blocks:
-            inner.segmentor.at_blocks_backward = queue      # runs when the student's backward reaches the transformer blocks
+                return g_s, None if self_labelling else self._teacher_geometry(inner, g_s, nd, nu)
+        look = _LookAhead(inner.segmentor, "forward", make)
 
         def after_forward():
             # the teacher joins BEFORE the look-ahead is queued: the look-ahead's side streams (the student's and the
@@ -529,17 +540,14 @@ class FixMatchNTMStep:
             # teacher's decoder still reads them (the teacher is long done by the end of the student's forward: free)
             if t_stream is not None:
                 _join(dev, t_stream, *pseudo)
-            if queue is not None and not at_blocks:
-                queue()
+            look.behind_forward()
 
         def knn_graph():
             if nbr is not None:
                 _join(dev, self._side, nbr, order)
             return nbr, order
         losses = self.student_iteration(data, data_u, geom_s, pseudo, knn_graph, after_forward)
-        if at_blocks:
-            inner.segmentor.at_blocks_backward = None
-        return losses, queued[0]
+        return losses, look.done() or (None, None)
 
     def student_iteration(self, data, data_u, geom_s, pseudo, knn_graph, after_forward=None, ema_in_place=False,
                           defer_rest=False):
@@ -555,7 +563,7 @@ class FixMatchNTMStep:
         (losses, rest) -- rest() runs the backward of the blocks and the patch encoder, the EMA update and both optimisers
         (graph_step's split capture)."""
         cfg = self.cfg
-        seg = getattr(self.model.module if hasattr(self.model, "module") else self.model, "segmentor", None)
+        seg = getattr(_unwrapped(self.model), "segmentor", None)
         can_cut = defer_rest and hasattr(seg, "take_cut")
         bl, bu = data["pos"].shape[0], data_u["pos_w"].shape[0]
         n = data["pos"].shape[1]
@@ -643,14 +651,7 @@ class FixMatchNTMStep:
             if ema_in_place:
                 with torch.no_grad():
                     torch.mul(ema_next, 1.0, out=self.ema_t)   # behind everything that read the old one (a kernel, not a memcpy node)
-            if self.grad_sync is not None:
-                self.grad_sync()
-            if cfg["grad_norm_clip"] is not None:
-                torch.nn.utils.clip_grad_norm_(self.model.parameters(), cfg["grad_norm_clip"])
-            self.optimizer.step()
-            self.optimizer.zero_grad(set_to_none=True)
-            self.T_optimizer.step()
-            self.T_optimizer.zero_grad(set_to_none=True)
+            _update(self.grad_sync, cfg["grad_norm_clip"], self.model, self.optimizers())
         losses = {"loss": loss.detach(), "sup": sup_loss.detach(), "unsup": unsup_loss.detach(),
                   "threed": loss_3d.detach() if loss_3d is not None else torch.zeros((), device=loss.device)}
         if loss_feat is not None:
@@ -661,11 +662,6 @@ class FixMatchNTMStep:
             return losses, rest
         rest()
         return losses
-
-
-def _same_positions_impl(src, data, data_u):
-    return src is not None and src[0] is data["pos"] and src[1] is data_u["pos_s"] and src[2] is data_u["pos_w"] \
-        and all(t._version == v for t, v in zip(src, src[3]))
 
 
 def build_fixmatch(device, seg_cfg=None, cfg=None, use_ddp=True, group=None, graph_sync=False, min_world=2, meters=None):

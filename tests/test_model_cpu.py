@@ -198,3 +198,54 @@ def test_mode_guard_reasserts_a_child_toggled_on_its_own():
     assert m[2][0].training
     _mode(m, False)
     assert not m.training and not m[1].training and not m[2][0].training
+
+
+def test_geometry_answers_for_its_sources_and_round_trips_through_the_graph_buffers():
+    """Geometry (backbone/geometry.py) on host tensors: describes() takes exactly the tensors it was made from (or the tensor
+    the work was done on), unedited; usable() also wants the model's mode and layout and, unless static, a side stream;
+    slice() keeps the eval-mode entries and answers for the sources it is given; graph_step's tree helpers rebuild the
+    records by type, drop the identities, and refuse a changed scalar, tensor or structure."""
+    from geot_amd import graph_step as gs
+    from geot_amd.openpoints.models.backbone.geometry import EdgeEntry, FpEntry, Geometry, IndexPlan
+    pts = torch.randn(6, 10, 3)
+    a, b, c = pts[:2].clone(), pts[2:4].clone(), pts[4:].clone()
+
+    def fp(rix):
+        return FpEntry(torch.zeros(6, 10, 3, dtype=torch.int32), torch.ones(6, 10, 3), torch.arange(60).view(6, 10), rix)
+
+    def plan(rix):
+        pair = (EdgeEntry(torch.zeros(6, 3), rix), EdgeEntry(torch.zeros(6, 3)))
+        return IndexPlan([pts, pts], [pts, pts], pts, fp(rix), fp(rix), FpEntry(torch.zeros(6, 4), torch.zeros(6, 4)), pair, pair)
+    ids = torch.arange(6).view(6, 1) * 10 + torch.arange(4)      # Group's flat sample ids: cloud * n + point
+    group = (torch.zeros(6, 4, 3), torch.zeros(6, 4, 3), ids.reshape(-1))
+    g = Geometry(pts, group, plan(torch.zeros(5)), True, "cl", sources=[a, b, c])
+    assert g.describes([a, b, c]) and g.describes([pts]) and g.positions(a) is pts
+    assert not g.describes([a, b]) and not g.describes([a, b, c.clone()]) and not g.describes([pts.clone()])
+    assert g.usable(pts, True, "cl", True)
+    assert not g.usable(pts, False, "cl", True) and not g.usable(pts, True, "cf", True) and not g.usable(pts, True, "cl", False)
+    s = g.slice(4, 6, sources=[c])
+    assert s.describes([c]) and s.usable(s.pts, False, "cl", True) and s.training is False and s.pts.shape[0] == 2
+    assert s.plan.fp2.rix is None and s.plan.dg2[0].rix is None and s.plan.fp2.order.shape[0] == 2
+    assert torch.equal(s.group[2], ids[:2].reshape(-1))         # re-based to the slice's first cloud
+    c.add_(0)                                                   # version bump
+    assert not s.describes([c]) and not g.describes([a, b, c]) and g.describes([pts])
+    pts.add_(0)
+    assert not g.describes([pts]) and not s.describes([s.pts])
+    static = Geometry(pts, group, plan(None), True, "cl", static=True)
+    assert static.describes([a]) and static.usable(a, True, "cl", False) and static.positions(a) is a
+    pre = {"geom_s": static, "pseudo": None, "knn": (None, torch.zeros(3))}
+    held = gs.tree_clone(pre)
+    hg = held["geom_s"]
+    assert hg.pts is None and hg.static and type(hg.plan) is IndexPlan and type(hg.plan.fp2) is FpEntry
+    assert type(hg.plan.dg1[0]) is EdgeEntry and hg.plan.fp2.idx is not static.plan.fp2.idx
+    assert type(gs.tree_detach(static.plan).dg2[1]) is EdgeEntry
+    w = torch.ones(6, 4, requires_grad=True) * 2.0
+    det = gs.tree_detach(Geometry(pts, group, IndexPlan([pts], [pts], pts, fp0=FpEntry(torch.zeros(6, 4), w)), True, "cl"))
+    assert type(det) is Geometry and det.pts is pts and not det.plan.fp0.weight.requires_grad and w.requires_grad
+    assert not gs.tree_clone(Geometry(pts, group, plan(None), True, "cl")).describes([pts])      # identities dropped: nothing
+    gs.tree_copy_(held, pre)
+    for changed in (dict(pre, geom_s=Geometry(pts, group, plan(None), False, "cl", static=True)),     # a python scalar
+                    dict(pre, pseudo=torch.zeros(1)), dict(pre, knn=(None,)),                       # the structure
+                    dict(pre, knn=(None, torch.zeros(4)))):                                          # a shape
+        with pytest.raises(RuntimeError):
+            gs.tree_copy_(held, changed)

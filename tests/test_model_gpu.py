@@ -702,9 +702,9 @@ def test_fixmatch_look_ahead_changes_nothing_but_the_schedule():
                 a = step.model(d, u0=dict(u, T=step.ema_t), fixmatch=True, geometry=g_s)[0]
                 b = step.model(d, u0=dict(u, T=step.ema_t), fixmatch=True)[0]
                 step.model_t.eval()
-                # the teacher's geometry is the weak view's slice of the student's (slice_geometry), and the teacher takes it:
+                # the teacher's geometry is the weak view's slice of the student's (Geometry.slice), and the teacher takes it:
                 # no Group, no index plan of its own
-                assert g_t["pts"].data_ptr() == g_s["pts"][4:].data_ptr() and g_t["training"] is False
+                assert g_t.pts.data_ptr() == g_s.pts[4:].data_ptr() and g_t.training is False
                 seg_t, calls = step.model_t.segmentor, []
                 plan0, group0 = seg_t._index_plan, seg_t.group_divider.forward
                 seg_t._index_plan = lambda *a, **k: (calls.append("plan"), plan0(*a, **k))[1]
@@ -743,7 +743,7 @@ def test_wholepartseg_geometry_is_keyed_to_its_source_tensors():
     with torch.no_grad():
         want_b = model(pos_b, pos_b.transpose(1, 2).contiguous(), cls)[0]
         g_a = model.prefetch_geometry(pos_a)
-        assert g_a["src"][0][0] is pos_a
+        assert g_a.sources[0][0] is pos_a
         got = model(pos_b, pos_b.transpose(1, 2).contiguous(), cls, geometry=g_a)[0]      # same shape, another batch
         assert torch.equal(got, want_b)
         g_b = model.prefetch_geometry(pos_b)
@@ -752,3 +752,105 @@ def test_wholepartseg_geometry_is_keyed_to_its_source_tensors():
         g_e = model.prefetch_geometry(edited)
         edited.add_(0.0)                                  # version bump: the geometry no longer describes this tensor's history
         assert torch.equal(model(edited, edited.transpose(1, 2).contiguous(), cls, geometry=g_e)[0], want_b)
+
+
+def test_an_accepted_geometry_replaces_the_launches_a_refused_one_repeats(monkeypatch):
+    """What the bit-identity tests above cannot see -- a geometry that is wrongly ignored gives the same bits -- read off the
+    C-ABI launches (geot_amd.ext._common.trace sees every module's).  S = the launches of prefetch_geometry(x) itself.
+    Accepted (training segmentor): forward(x, geometry=g) launches none of the FPS / search entry points and, over ALL entry
+    points, S + launches(forward | g) == launches(forward | None) as multisets (the in-line forward runs the same index
+    plan, reverse indices included).  Refused -- a geometry of another tensor of the same shape, of a tensor edited since, of
+    the model in eval mode offered in training mode: launches(forward | g) == launches(forward | None).  WholePartSeg over
+    dict batches (2 + 2 + 2 clouds): accepted for the very dicts, refused when any one of the three position tensors is an
+    equal-valued clone.  The weak-view slice in an eval-mode teacher: no FPS / search launch.  An inline=True geometry is
+    taken for another tensor of the same values (the caller vouches for it).  FixMatchNTMStep: the call with the announced
+    batches launches fewer FPS / search entry points than the same call when other batches were announced, and that one as
+    many as the same call of a step that never looked ahead."""
+    from collections import Counter
+    from geot_amd.ext import _common
+    from geot_amd.openpoints.models.backbone.transformer import PointTransformer_seg_T
+    from geot_amd.openpoints.models.segmentation import WholePartSeg
+    from geot_amd import train_step as ts
+    from geot_amd.synth import make_batch, region_labels
+    dev = torch.device("cuda:0")
+    searches = ("geot_furthest_point_sampling", "geot_furthestsampling_offset", "geot_knn_sorted_ws", "geot_three_nn_ws")
+    names = []
+    monkeypatch.setattr(_common, "trace", lambda launch, name: (names.append(name), launch())[1])
+
+    def launches(fn):
+        del names[:]
+        out = fn()
+        torch.cuda.synchronize()
+        return Counter(names), out
+
+    def searched(counter):
+        return sum(counter[k] for k in searches)
+
+    def cloud(seed, b=2, n=6000):
+        return torch.from_numpy(make_batch(b, n, start_index=seed)[0]).to(dev)
+    torch.manual_seed(0)
+    m = PointTransformer_seg_T(**SMALL).to(dev).train()
+    x, other = cloud(0), cloud(40)
+    cls = torch.tensor([[0], [1]], device=dev)
+
+    def forward(pts, g=None, model=m):
+        with torch.no_grad():
+            return launches(lambda: model(pts, pts.transpose(1, 2).contiguous(), cls, geometry=g))[0]
+    plain = forward(x)
+    assert searched(plain) > 0
+    s_x, g = launches(lambda: m.prefetch_geometry(x))
+    taken = forward(x, g)
+    assert searched(taken) == 0, taken
+    assert s_x + taken == plain, (s_x, taken, plain)
+    # refused: another tensor of the same shape, a tensor edited since, a geometry of the other mode
+    assert forward(x, m.prefetch_geometry(other)) == plain
+    edited = x.clone()
+    g_e = m.prefetch_geometry(edited)
+    edited.mul_(1.0)
+    assert forward(edited, g_e) == plain
+    g_eval = m.eval().prefetch_geometry(x)
+    assert forward(x, g_eval, m.train()) == plain
+    # inline=True: on the current stream, vouched for by the caller -- taken for another tensor of the same values
+    assert searched(forward(x.clone(), m.prefetch_geometry(x, inline=True))) == 0
+
+    # WholePartSeg over dict batches: 2 labelled + 2 strong + 2 weak clouds
+    def batch(seed):
+        lab, unl = cloud(seed), cloud(seed + 50)
+        strong = unl * 1.04
+        z = torch.zeros(2, 1, dtype=torch.long, device=dev)
+        return ({"pos": lab, "x": lab.transpose(1, 2).contiguous(), "cls": z, "y": torch.from_numpy(region_labels(lab.cpu().numpy())).to(dev)},
+                {"pos_w": unl, "x_w": unl.transpose(1, 2).contiguous(), "cls_w": z, "pos_s": strong,
+                 "x_s": strong.transpose(1, 2).contiguous(), "cls_s": z, "raw_pos": unl})
+    student = WholePartSeg(segmentor_args=dict(NAME="PointTransformer_seg_T", **SMALL)).to(dev).train()
+    teacher = WholePartSeg(segmentor_args=dict(NAME="PointTransformer_seg_T", **SMALL)).to(dev).eval()
+    d, u = batch(3)
+
+    def whole(d, u, g=None):
+        with torch.no_grad():
+            return launches(lambda: student(d, u0=u, fixmatch=True, geometry=g))[0]
+    plain = whole(d, u)
+    assert searched(plain) > 0
+    s_du, g = launches(lambda: student.prefetch_geometry(d, u, fixmatch=True))
+    taken = whole(d, u, g)
+    assert searched(taken) == 0 and s_du + taken == plain, (s_du, taken, plain)
+    for which, key in ((0, "pos"), (1, "pos_s"), (1, "pos_w")):
+        pair = [dict(d), dict(u)]
+        pair[which][key] = pair[which][key].clone()
+        assert whole(pair[0], pair[1], g) == plain, key
+    # the weak view's slice in the frozen, eval-mode teacher
+    g_t = student.weak_view_geometry(g, d, u)
+    with torch.no_grad():
+        assert searched(launches(lambda: teacher(u, if_teacher=True))[0]) > 0
+        assert searched(launches(lambda: teacher(u, if_teacher=True, geometry=g_t))[0]) == 0
+
+    # FixMatchNTMStep: the same call step(b) -- announced, never looked ahead, other batches announced
+    torch.manual_seed(5)
+    step = ts.build_fixmatch(dev, seg_cfg=SMALL, cfg=dict(ts.NTM_CFG, threed_k=8), use_ddp=False)
+    a, b, c = batch(3), batch(400), batch(900)
+    step(a[0], a[1], next_batches=b)
+    announced = searched(launches(lambda: step(b[0], b[1]))[0])
+    never = searched(launches(lambda: step(b[0], b[1]))[0])
+    step(a[0], a[1], next_batches=c)
+    unannounced = searched(launches(lambda: step(b[0], b[1]))[0])
+    assert announced < unannounced == never, (announced, unannounced, never)
+

@@ -430,11 +430,11 @@ def test_batches_feed_the_supervised_step_and_its_look_ahead():
     forward = net._forward
 
     def spy(pts, x, cls_label, T, geometry=None):
-        offered.append(geometry is not None and geometry["pts"] is pts and geometry["version"] == pts._version)
+        offered.append(geometry is not None and geometry.pts is pts and geometry.version == pts._version)
         return forward(pts, x, cls_label, T, geometry)
     net._forward = spy
     l0 = step(first["pos"], first["cls"], first["y"], next_pos=second["pos"])
-    assert step._geometry is not None and step._geometry["pts"] is second["pos"]
+    assert step._geometry is not None and step._geometry.pts is second["pos"]
     assert len(grouped) == 2 and grouped[0] is first["pos"] and grouped[1] is second["pos"]
     l1 = step(second["pos"], second["cls"], second["y"])
     torch.cuda.synchronize()

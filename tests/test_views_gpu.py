@@ -377,7 +377,6 @@ def test_a_side_stream_batch_beside_a_running_step_equals_the_inline_batch():
 
 
 def test_batches_feed_the_step_and_its_look_ahead():
-    from geot_amd import train_step as ts
     from geot_amd.openpoints.dataset import FixMatchBatcher
     lab, unl = _synthetic_sets()
     batcher = FixMatchBatcher(lab, unl, M_STEP)
@@ -393,7 +392,7 @@ def test_batches_feed_the_step_and_its_look_ahead():
         return iteration(data, data_u, geoms, next_batches)
     step.iteration = spy
     l0 = step(first[0], first[1], next_batches=second)
-    assert step._geometry[0] is not None and ts._same_positions_impl(step._geometry_src, second[0], second[1])
+    assert step._geometry[0] is not None and step._geometry[0].describes([second[0]["pos"], second[1]["pos_s"], second[1]["pos_w"]])
     l1 = step(second[0], second[1])
     torch.cuda.synchronize()
     assert seen[0] == (None, None) and seen[1][0] is not None, "the look-ahead geometry was recomputed, not accepted"

@@ -11,6 +11,7 @@ from geot_amd.synth import make_batch  # noqa: E402
 from geot_amd.pointnet2.pointnet2_modules import PointnetFPModule  # noqa: E402
 from geot_amd.pointnet2 import pointnet2_utils as pu  # noqa: E402
 from geot_amd.openpoints.models.backbone.transformer import _fp_factored  # noqa: E402
+from geot_amd.openpoints.models.backbone.geometry import FpEntry  # noqa: E402
 from geot_amd import fused_norm as fn  # noqa: E402
 
 tuning.enable(path=os.environ.get("GEOT_TUNE_FILE"))
@@ -28,9 +29,9 @@ for name, n, m, cs in (("prop0", 24000, 8192, 5), ("prop1", 8192, 512, 3), ("pro
     weight = pu._ext.fp_weights(d2)
     for layout in ("cf", "cl"):
         def once():
-            nn3 = (idx, weight)
+            nn3 = FpEntry(idx, weight)
             if layout == "cl":      # the index plan's share (side stream in the model): timed separately below
-                nn3 = (idx, weight, order_u, fn.ReverseIndex(idx, weight, m, order_k) if PLAN_INSIDE else rix)
+                nn3 = FpEntry(idx, weight, order_u, fn.ReverseIndex(idx, weight, m, order_k) if PLAN_INSIDE else rix)
             y = _fp_factored(fp, unknown, known, sk, kf, nn3, layout=layout)
             y.backward(up)
             kf.grad = None
