@@ -14,6 +14,16 @@
 // evenly and the entry size decides how many waves a launch has (a wave is serial over its vertices).
 // Without a grid (fewer than SP_MIN_REF sampled points, GEOT_NN_IMPL=basic|wave) the wave scans all n sampled points, 64
 // per step, through the same insertion: the same (d2, index) order, the same bits.
+//
+// geot_scan_vote is the same kernel with one difference: the interpolated class values are not arg-maxed on the spot but
+// stored in (GEOT_VOTE_SET) or added to a caller-owned vertex-major accumulator acc (sum of the slots' vertices, c), and with
+// GEOT_VOTE_FINISH the arg-max is taken of the sum.  One writer per element, votes added in call order, no float atomics.
+// Two forms of the accumulator access (GEOT_VOTE_IMPL=row|tile, read at every call; profiles/scan_vote_timing.txt):
+//   row   the wave that finished vertex j adds its c values into the vertex's row: lanes < c, one 4 c-byte read (issued in
+//         front of the search, which hides it) and one write;
+//   tile  the values of the wave's 64 vertices go into a wave-private LDS tile [64][c | 1] (dynamic LDS, sized by c), then
+//         the 64 c contiguous floats are read, added and written coalesced; with FINISH lane j arg-maxes row j of the summed
+//         tile (the odd row stride keeps the 32 lanes of a half on 32 banks).
 #include "geot_common.h"
 #include "geot_hip.h"
 #include "knn_grid.h"
@@ -39,9 +49,9 @@ __device__ __forceinline__ void sp_brute(const float *__restrict__ K, int n, flo
     }
 }
 
-// sm_interp_argmax (seg_metrics.hip) with the classes spread over the lanes: the same statements per class, then
-// torch.argmax's rule -- the first NaN if there is one, else the first maximum.  Wave-uniform result.
-__device__ __forceinline__ int sp_class(const float *__restrict__ prob, int c, int n, const KgBest &B)
+// sm_interp_argmax (seg_metrics.hip) with the classes spread over the lanes, in two halves.  The interpolation: the same
+// statements per class; lane l < c returns class l's value, the others 0.
+__device__ __forceinline__ float sp_interp(const float *__restrict__ prob, int c, int n, const KgBest &B)
 {
     const int lane = lane_id();
     const int i0 = __builtin_amdgcn_readlane(B.li, 0), i1 = __builtin_amdgcn_readlane(B.li, 1), i2 = __builtin_amdgcn_readlane(B.li, 2);
@@ -49,28 +59,59 @@ __device__ __forceinline__ int sp_class(const float *__restrict__ prob, int c, i
     const float r0 = 1.0f / (sqrtf(d0) + 1e-8f), r1 = 1.0f / (sqrtf(d1) + 1e-8f), r2 = 1.0f / (sqrtf(d2) + 1e-8f);
     const float norm = (r0 + r2) + r1;
     const float w0 = r0 / norm, w1 = r1 / norm, w2 = r2 / norm;
-    const bool in = lane < c;
     float v = 0.f;
-    if (in) {
+    if (lane < c) {
         const float *P = prob + (size_t)lane * n;
         const float p0 = P[i0], p1 = P[i1], p2 = P[i2];
         v = p0 * w0 + p1 * w1 + p2 * w2;
     }
+    return v;
+}
+
+// torch.argmax's rule over the values of lanes < c -- the first NaN if there is one, else the first maximum.  Wave-uniform.
+__device__ __forceinline__ int sp_argmax(float v, int c)
+{
+    const bool in = lane_id() < c;
     const unsigned long long nan = __ballot(in && v != v);
     if (nan) return __builtin_ctzll(nan);
     const float mx = wave_max_f32(in ? v : -INFINITY);
     return __builtin_ctzll(__ballot(in && v == mx));     // c >= 1: lane 0 is in, so the ballot is not empty
 }
 
-template <bool GRID>
+// the same rule over one row of a summed tile, serially in one lane
+__device__ __forceinline__ int sp_argmax_row(const float *row, int c)
+{
+    float best = row[0];
+    int at = 0;
+    bool nan = best != best;
+    for (int k = 1; k < c; ++k) {
+        const float x = row[k];
+        if (!nan && (x != x || x > best)) { best = x; at = k; nan = x != x; }
+    }
+    return at;
+}
+
+// Between a wave's LDS writes and its other lanes' reads of them: the hardware keeps one wave's LDS accesses in order, this
+// keeps the compiler from moving them across.
+__device__ __forceinline__ void sp_wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+constexpr int SP_PREDICT = 0, SP_VOTE_ROW = 1, SP_VOTE_TILE = 2;     // what a kernel does with the interpolated values
+
+template <bool GRID, int FORM>
 __global__ __launch_bounds__(SP_THREADS) void scan_predict_kernel(
     int b, int c, int n, int gtarget, long long total, const float *__restrict__ points, const int *__restrict__ labels,
     const long long *__restrict__ offsets, int n_scans, const long long *__restrict__ scan_ids,
     const float *__restrict__ known, const float *__restrict__ prob, const int4 *__restrict__ work,
     const uint32_t *__restrict__ ws, size_t per_cloud, size_t off_rec, const long long *__restrict__ out_offsets,
-    long long *__restrict__ pred, unsigned long long *__restrict__ counts)
+    long long *__restrict__ pred, unsigned long long *__restrict__ counts, float *__restrict__ acc, int mode)
 {
     __shared__ unsigned h[SP_WAVES * SM_MAX_SLOTS];
+    extern __shared__ float tiles[];             // SP_VOTE_TILE: SP_WAVES tiles of 64 rows of c | 1 floats
     // everything up to the loop is uniform over the workgroup; an entry or a slot that cannot be used is skipped whole
     const int4 job = work[blockIdx.x];
     const int s = job.x;
@@ -104,7 +145,12 @@ __global__ __launch_bounds__(SP_THREADS) void scan_predict_kernel(
         start = reinterpret_cast<const int *>(W + KG_HDR);
         rec = reinterpret_cast<const float4 *>(W + off_rec);
     }
-    const long long out0 = pred ? out_offsets[s] : 0;
+    const long long out0 = (FORM != SP_PREDICT || pred) ? out_offsets[s] : 0;
+    // votes: SET stores where the others add; the arg-max is taken with FINISH, and only for someone who reads it
+    const bool set = (mode & GEOT_VOTE_SET) != 0;
+    const bool finish = (mode & GEOT_VOTE_FINISH) != 0 && (pred || counts);
+    const int cs = c | 1;
+    float *tile = tiles + (FORM == SP_VOTE_TILE ? wave * 64 * cs : 0);
 
     // the entry's vertices in SP_WAVES contiguous runs, one per wave; a wave takes its run 64 vertices at a time
     const long long per = ((long long)(end - first) + SP_WAVES - 1) / SP_WAVES;
@@ -120,6 +166,12 @@ __global__ __launch_bounds__(SP_THREADS) void scan_predict_kernel(
             const float qx = read_lane_f(vx, j), qy = read_lane_f(vy, j), qz = read_lane_f(vz, j);
             KgBest B;
             B.ld = INFINITY; B.li = 0; B.tau = INFINITY; B.taui = 0;
+            float *row = nullptr;
+            float old = 0.f;
+            if constexpr (FORM == SP_VOTE_ROW) {     // the vertex's row so far: read here, needed after the search
+                row = acc + (size_t)(out0 + base + j) * c;
+                if (!set && lane < c) old = row[lane];
+            }
             if constexpr (GRID) {
                 const int cx = kg_cell1(qx, g.lo[0], g.inv_h, g.dim[0]);
                 const int cy = kg_cell1(qy, g.lo[1], g.inv_h, g.dim[1]);
@@ -129,8 +181,34 @@ __global__ __launch_bounds__(SP_THREADS) void scan_predict_kernel(
             } else {
                 sp_brute(K, n, qx, qy, qz, B);
             }
-            const int a = sp_class(P, c, n, B);
-            if (lane == j) cls = a;
+            const float val = sp_interp(P, c, n, B);
+            if constexpr (FORM == SP_PREDICT) {
+                const int a = sp_argmax(val, c);
+                if (lane == j) cls = a;
+            } else if constexpr (FORM == SP_VOTE_ROW) {
+                const float sum = set ? val : old + val;
+                if (lane < c) row[lane] = sum;
+                if (finish) {
+                    const int a = sp_argmax(sum, c);
+                    if (lane == j) cls = a;
+                }
+            } else {
+                if (lane < c) tile[j * cs + lane] = val;
+            }
+        }
+        if constexpr (FORM == SP_VOTE_TILE) {       // the wave's cnt rows are contiguous in acc: one coalesced read-add-write
+            sp_wave_lds_sync();
+            float *A = acc + (size_t)(out0 + base) * c;
+            for (int i = lane; i < cnt * c; i += 64) {
+                const int r = i / c;
+                float *t = tile + r * cs + (i - r * c);
+                const float sum = set ? *t : A[i] + *t;
+                A[i] = sum;
+                *t = sum;
+            }
+            sp_wave_lds_sync();
+            if (finish && active) cls = sp_argmax_row(tile + lane * cs, c);
+            sp_wave_lds_sync();
         }
         if (pred && active) pred[out0 + v] = cls;
         if (counts) {
@@ -166,33 +244,71 @@ GEOT_EXPORT long long geot_scan_predict_ws_bytes(int b, int n)
     return geot_knn_grid_ws_bytes(b, n);
 }
 
-GEOT_EXPORT int geot_scan_predict(int b, int c, int n, int n_scans, long long total, const float *points, const int *labels,
-                                  const long long *offsets, const long long *scan_ids, const float *known, const float *prob,
-                                  int n_work, const int *work, const long long *out_offsets, long long *pred,
-                                  long long *counts, void *ws, long long ws_bytes, void *stream)
+// The argument checks and launches both entry points share.  form: what the kernel does with the interpolated values.
+static int sp_run(int form, int b, int c, int n, int n_scans, long long total, const float *points, const int *labels,
+                  const long long *offsets, const long long *scan_ids, const float *known, const float *prob, int n_work,
+                  const int *work, const long long *out_offsets, float *acc, int mode, long long *pred, long long *counts,
+                  void *ws, long long ws_bytes, void *stream)
 {
     if (b < 0 || b > 65535 || c < 1 || c > GEOT_NTM_MAX_C || n < 1 || n_scans < 1 || total < 1 || n_work < 0)
         return hipErrorInvalidValue;
-    if (!points || !offsets || !scan_ids || !known || !prob || (!pred && !counts) || (counts && !labels) ||
-        (pred && !out_offsets))
-        return hipErrorInvalidValue;
+    if (!points || !offsets || !scan_ids || !known || !prob || (counts && !labels)) return hipErrorInvalidValue;
+    if (form == SP_PREDICT) {
+        if ((!pred && !counts) || (pred && !out_offsets)) return hipErrorInvalidValue;
+    } else {
+        if (!acc || !out_offsets || (mode & ~(GEOT_VOTE_SET | GEOT_VOTE_FINISH)) != 0) return hipErrorInvalidValue;
+        if ((pred || counts) && !(mode & GEOT_VOTE_FINISH)) return hipErrorInvalidValue;
+    }
     if (b == 0 || n_work == 0) return hipSuccess;
     if (!work || ((uintptr_t)work & 15) != 0) return hipErrorInvalidValue;
     hipStream_t s = (hipStream_t)stream;
     unsigned long long *out = reinterpret_cast<unsigned long long *>(counts);
     const int4 *jobs = reinterpret_cast<const int4 *>(work);
-    if (sp_use_grid(n)) {
+    const bool grid = sp_use_grid(n);
+    const uint32_t *W = nullptr;
+    size_t per_cloud = 0, off_rec = 0;
+    int G = 0;
+    if (grid) {
         if (!ws || ((uintptr_t)ws & 15) != 0 || ws_bytes < geot_knn_grid_ws_bytes(b, n)) return hipErrorInvalidValue;
         const KgLayout L = kg_layout(n);
-        const int G = kg_target(n, 3);
+        G = kg_target(n, 3);
         kg_build(b, n, G, 0, 0.f, known, (uint32_t *)ws, s);
-        hipLaunchKernelGGL((scan_predict_kernel<true>), dim3(n_work), dim3(SP_THREADS), 0, s, b, c, n, G, total, points, labels,
-                           offsets, n_scans, scan_ids, known, prob, jobs, (const uint32_t *)ws, L.per_cloud_words, L.off_rec,
-                           out_offsets, pred, out);
-    } else {
-        hipLaunchKernelGGL((scan_predict_kernel<false>), dim3(n_work), dim3(SP_THREADS), 0, s, b, c, n, 0, total, points, labels,
-                           offsets, n_scans, scan_ids, known, prob, jobs, (const uint32_t *)nullptr, (size_t)0, (size_t)0,
-                           out_offsets, pred, out);
+        W = (const uint32_t *)ws;
+        per_cloud = L.per_cloud_words;
+        off_rec = L.off_rec;
     }
+    const size_t lds = form == SP_VOTE_TILE ? (size_t)SP_WAVES * 64 * (c | 1) * sizeof(float) : 0;
+#define SP_LAUNCH(GRID, FORM)                                                                                                  \
+    hipLaunchKernelGGL((scan_predict_kernel<GRID, FORM>), dim3(n_work), dim3(SP_THREADS), lds, s, b, c, n, G, total, points,    \
+                       labels, offsets, n_scans, scan_ids, known, prob, jobs, W, per_cloud, off_rec, out_offsets, pred, out, acc, \
+                       mode)
+    if (form == SP_PREDICT) {
+        if (grid) SP_LAUNCH(true, SP_PREDICT); else SP_LAUNCH(false, SP_PREDICT);
+    } else if (form == SP_VOTE_ROW) {
+        if (grid) SP_LAUNCH(true, SP_VOTE_ROW); else SP_LAUNCH(false, SP_VOTE_ROW);
+    } else {
+        if (grid) SP_LAUNCH(true, SP_VOTE_TILE); else SP_LAUNCH(false, SP_VOTE_TILE);
+    }
+#undef SP_LAUNCH
     return hipGetLastError();
+}
+
+GEOT_EXPORT int geot_scan_predict(int b, int c, int n, int n_scans, long long total, const float *points, const int *labels,
+                                  const long long *offsets, const long long *scan_ids, const float *known, const float *prob,
+                                  int n_work, const int *work, const long long *out_offsets, long long *pred,
+                                  long long *counts, void *ws, long long ws_bytes, void *stream)
+{
+    return sp_run(SP_PREDICT, b, c, n, n_scans, total, points, labels, offsets, scan_ids, known, prob, n_work, work, out_offsets,
+                  nullptr, 0, pred, counts, ws, ws_bytes, stream);
+}
+
+GEOT_EXPORT int geot_scan_vote(int b, int c, int n, int n_scans, long long total, const float *points, const int *labels,
+                               const long long *offsets, const long long *scan_ids, const float *known, const float *prob,
+                               int n_work, const int *work, const long long *out_offsets, float *acc, int mode, long long *pred,
+                               long long *counts, void *ws, long long ws_bytes, void *stream)
+{
+    const char *e = getenv("GEOT_VOTE_IMPL");      // read at every call; the default is the form that measured faster
+    const int form = e && e[0] == 't' ? SP_VOTE_TILE : SP_VOTE_ROW;
+    return sp_run(form, b, c, n, n_scans, total, points, labels, offsets, scan_ids, known, prob, n_work, work, out_offsets, acc,
+                  mode, pred, counts, ws, ws_bytes, stream);
 }

@@ -27,6 +27,14 @@ With the test split resident on the device (openpoints.dataset.DeviceScanSet) no
 
 geot_scan_predict (csrc/scan_predict.hip) reads the vertices and labels in place from the set, finds the three nearest
 sampled points, interpolates, arg-maxes and counts / writes in one pass: no per-scan loop, no idx / dist2 in memory.
+
+Test-time voting -- the config's `num_votes` and `datatransforms.vote`, which the reference carries and never uses: several
+samples of the same scans, optionally under the vote transform list, the class probabilities of all passes interpolated onto
+the whole scans and summed before the arg-max (geot_scan_vote: geot_scan_predict with a caller-owned accumulator):
+
+    out = validate_scans_voted(model, scans, cfg)            # validate_scans with cfg.num_votes passes per batch
+    preds = vote_scans(model, VoteBatcher(scans, n), idx, 10)    # the voted per-vertex labels of whole scans
+    votes = ScanVotes(batch, num_classes); votes.add(logits, batch); ...; votes.add(logits, batch, last=True, want_pred=True)
 """
 import logging
 
@@ -139,11 +147,12 @@ def scan_work_table(sizes, groups=SCAN_GROUPS, min_chunk=SCAN_CHUNK_MIN):
     return np.ascontiguousarray(table.astype(np.int32))
 
 
-def _scan_predict(logits, batch, num_classes, counts=None, want_pred=False, what="predict_scans"):
-    """One geot_scan_predict call for a ValBatcher batch: get_pred_whole's soft-max and de-normalisation as batched torch
-    statements (the same fp32 multiply and add per element as its per-scan `point * s + c`), then the kernel."""
-    need(isinstance(batch, dict) and all(k in batch for k in ("pos", "center", "scale", "scan_ids", "scans", "sizes")),
-         "%s: batch must come from ValBatcher.batch (pos, center, scale, scan_ids, scans, sizes)" % what)
+def _scan_inputs(logits, batch, num_classes, what, pos_key="pos"):
+    """The checks of one whole-scan call on a ValBatcher batch, then get_pred_whole's soft-max and de-normalisation as batched
+    torch statements (the same fp32 multiply and add per element as its per-scan `point * s + c`)
+    -> (b, n, scan_ids, prob (B, C, N), known (B, N, 3))."""
+    need(isinstance(batch, dict) and all(k in batch for k in (pos_key, "center", "scale", "scan_ids", "scans", "sizes")),
+         "%s: batch must come from ValBatcher.batch (%s, center, scale, scan_ids, scans, sizes)" % (what, pos_key))
     scans, sizes = batch["scans"], [int(m) for m in batch["sizes"]]
     dev = scans.device
     c = int(num_classes)
@@ -154,23 +163,37 @@ def _scan_predict(logits, batch, num_classes, counts=None, want_pred=False, what
     b, _, n = logits.shape
     need(b == len(sizes) and 1 <= b <= SCAN_MAX_SLOTS, "%s: %d logits rows for a batch of %d scans (1 .. %d)" %
          (what, b, len(sizes), SCAN_MAX_SLOTS))
-    need(all(torch.is_tensor(batch[k]) for k in ("pos", "center", "scale", "scan_ids")), "%s: batch pos, center, scale and scan_ids "
-         "must be tensors" % what)
-    need(n >= 1 and tuple(batch["pos"].shape) == (b, n, 3), "%s: logits (B, C, N) and batch pos (B, N, 3) must agree, N >= 1" % what)
+    need(all(torch.is_tensor(batch[k]) for k in (pos_key, "center", "scale", "scan_ids")), "%s: batch %s, center, scale and scan_ids "
+         "must be tensors" % (what, pos_key))
+    need(n >= 1 and tuple(batch[pos_key].shape) == (b, n, 3), "%s: logits (B, C, N) and batch %s (B, N, 3) must agree, N >= 1" %
+         (what, pos_key))
     need(tuple(batch["center"].shape) == (b, 3) and tuple(batch["scale"].shape) == (b,) and tuple(batch["scan_ids"].shape) == (b,),
          "%s: batch center (B, 3), scale (B,), scan_ids (B,)" % what)
-    for key, dt in (("pos", torch.float32), ("center", torch.float32), ("scale", torch.float32), ("scan_ids", torch.int64)):
+    for key, dt in ((pos_key, torch.float32), ("center", torch.float32), ("scale", torch.float32), ("scan_ids", torch.int64)):
         need(torch.is_tensor(batch[key]) and batch[key].device == dev and batch[key].dtype == dt,
              "%s: batch %s must be a %s tensor on %s" % (what, key, dt, dev))
     scan_ids = batch["scan_ids"].contiguous()
     prob = F.softmax(logits, dim=1).contiguous()
-    known = (batch["pos"] * batch["scale"].view(b, 1, 1) + batch["center"].view(b, 1, 3)).contiguous()
+    known = (batch[pos_key] * batch["scale"].view(b, 1, 1) + batch["center"].view(b, 1, 3)).contiguous()
+    return b, n, scan_ids, prob, known
+
+
+def _out_offsets(sizes, dev):
+    """Where every slot's vertices start in a per-vertex output laid out slot after slot: (b,) int64 on the device."""
+    ends = np.cumsum(sizes, dtype=np.int64)
+    return _to_device(np.concatenate([[0], ends[:-1]]).astype(np.int64), dev)
+
+
+def _scan_predict(logits, batch, num_classes, counts=None, want_pred=False, what="predict_scans"):
+    """One geot_scan_predict call for a ValBatcher batch: _scan_inputs, then the kernel."""
+    b, n, scan_ids, prob, known = _scan_inputs(logits, batch, num_classes, what)
+    scans, sizes = batch["scans"], [int(m) for m in batch["sizes"]]
+    dev, c = scans.device, int(num_classes)
     work = _to_device(scan_work_table(sizes), dev)
     pred = out_offs = None
-    ends = np.cumsum(sizes, dtype=np.int64)
     if want_pred:
-        pred = torch.empty(int(ends[-1]), dtype=torch.int64, device=dev)
-        out_offs = _to_device(np.concatenate([[0], ends[:-1]]).astype(np.int64), dev)
+        pred = torch.empty(sum(sizes), dtype=torch.int64, device=dev)
+        out_offs = _out_offsets(sizes, dev)
     nbytes = int(_lib.load().geot_scan_predict_ws_bytes(b, n))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     call("geot_scan_predict", dev, b, c, n, len(scans), int(scans.points.shape[0]), ptr(scans.points), ptr(scans.labels),
@@ -402,5 +425,125 @@ def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, n
         ahead = batcher.batch(parts[k + 1]) if k + 1 < len(parts) else None     # beside the forward pass when on a side stream
         logits, _, _ = model(data)
         metrics.update_from_scans(logits, data)
+        data = ahead
+    return _report(metrics.read(), cfg)
+
+
+class ScanVotes:
+    """The votes of one batch of scans: the accumulator -- fp32 (sum of the scans' vertices, C), vertex-major, slot after slot --
+    its out_offsets and the work table, made once; every add() is one geot_scan_vote call.  batch: a VoteBatcher (or
+    ValBatcher) batch of the scans voted on; every later batch must name the same scans in the same slots.  Nothing here
+    synchronises with the host."""
+
+    def __init__(self, batch, num_classes):
+        need(isinstance(batch, dict) and all(k in batch for k in ("scans", "sizes", "scan_ids")),
+             "ScanVotes: batch must come from VoteBatcher.batch or ValBatcher.batch")
+        c = int(num_classes)
+        need(1 <= c <= 32, "ScanVotes: 1..32 classes (include/geot_hip.h GEOT_NTM_MAX_C), got %d" % c)
+        self.scans, self.sizes, self.c = batch["scans"], [int(m) for m in batch["sizes"]], c
+        need(1 <= len(self.sizes) <= SCAN_MAX_SLOTS, "ScanVotes: 1 .. %d scans" % SCAN_MAX_SLOTS)
+        dev = self.device = self.scans.device
+        self.acc = torch.empty((sum(self.sizes), c), dtype=torch.float32, device=dev)      # the first add() stores
+        self.out_offsets = _out_offsets(self.sizes, dev)
+        self.work = _to_device(scan_work_table(self.sizes), dev)
+        self.votes, self.finished = 0, False
+
+    def add(self, logits, batch, last=False, counts=None, want_pred=False):
+        """One vote: the model's logits (B, C, N) on `batch`, a fresh sample of the same scans.  get_pred_whole's soft-max,
+        the de-normalisation of batch["pos_search"] (a plain ValBatcher batch: batch["pos"]) and one geot_scan_vote call that
+        adds the interpolated probabilities of every vertex.  last: the arg-max of the sums is taken; then counts (rows of a
+        SegMetrics buffer, ADDED to) and want_pred (-> list of (1, M_i) int64 labels, as predict_scans returns them) are
+        allowed."""
+        need(not self.finished, "ScanVotes.add: the last vote has been added")
+        need(last or (counts is None and not want_pred), "ScanVotes.add: counts and predictions come with the last vote (last=True)")
+        pos_key = "pos_search" if isinstance(batch, dict) and "pos_search" in batch else "pos"
+        b, n, scan_ids, prob, known = _scan_inputs(logits, batch, self.c, "ScanVotes.add", pos_key)
+        need(batch["scans"] is self.scans and [int(m) for m in batch["sizes"]] == self.sizes,
+             "ScanVotes.add: every vote's batch holds the same scans in the same slots")
+        dev, scans = self.device, self.scans
+        pred = torch.empty(sum(self.sizes), dtype=torch.int64, device=dev) if want_pred else None
+        mode = (_lib.VOTE_SET if self.votes == 0 else 0) | (_lib.VOTE_FINISH if last else 0)
+        nbytes = int(_lib.load().geot_scan_predict_ws_bytes(b, n))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        call("geot_scan_vote", dev, b, self.c, n, len(scans), int(scans.points.shape[0]), ptr(scans.points), ptr(scans.labels),
+             ptr(scans.offsets), ptr(scan_ids), ptr(known), ptr(prob), int(self.work.shape[0]), ptr(self.work),
+             ptr(self.out_offsets), ptr(self.acc), mode, ptr(pred), ptr(counts), ptr(ws), nbytes)
+        self.votes += 1
+        self.finished = bool(last)
+        if not want_pred:
+            return None
+        return [p.view(1, -1) for p in torch.split(pred, self.sizes)]
+
+    def probabilities(self):
+        """Per scan the (M_i, C) mean of the votes so far: the accumulator's rows times 1 / votes."""
+        need(self.votes >= 1, "ScanVotes.probabilities: no vote yet")
+        return list(torch.split(self.acc * (1.0 / self.votes), self.sizes))
+
+
+@torch.no_grad()
+def vote_scans(model, batcher, idx, num_votes, draws=None):
+    """The voted per-vertex labels of the scans `idx` of a VoteBatcher's set: list of (1, M_i) int64 tensors, as predict_scans
+    returns them.  num_votes model passes, each on a freshly drawn batch of the same scans (draws: a DeviceDraws for these
+    batches; default: the batcher's); the next batch is built beside the forward pass when the batcher has a side stream."""
+    need(int(num_votes) >= 1, "vote_scans: num_votes >= 1")
+    model.eval()
+    votes, preds = None, None
+    data = batcher.batch(idx, draws=draws)
+    for k in range(int(num_votes)):
+        last = k + 1 == int(num_votes)
+        batcher.join(data)
+        ahead = None if last else batcher.batch(idx, draws=draws)
+        logits, _, _ = model(data)
+        if votes is None:
+            votes = ScanVotes(data, logits.shape[1])
+        preds = votes.add(logits, data, last=last, want_pred=last)
+        data = ahead
+    return preds
+
+
+@torch.no_grad()
+def validate_scans_voted(model, scans, cfg, num_votes=None, vote=None, batch_size=2, indices=None, stream=None, draws=None):
+    """validate_scans with votes: every batch of scans runs through the model num_votes times, each time freshly sampled and
+    under the `vote` transform list, and is scored on the arg-max of the summed whole-scan probabilities.  scans: a
+    DeviceScanSet, or a VoteBatcher built on one.  num_votes defaults to cfg.num_votes, vote to cfg.datatransforms.vote when
+    present (else VoteBatcher's default, the yaml's [PointCloudScaling]); the lists' kwargs to cfg.datatransforms.kwargs.
+    num_votes < 1 raises ValueError: validate_scans is the un-voted call.  The next vote's batch is built on `stream` beside
+    the current forward pass.  Same log lines, return value and dtypes as validate()."""
+    from .openpoints.dataset.vote_batch import DEFAULT_VOTE, TOOTH_VIEW_KWARGS, VoteBatcher
+    num_votes = _cfg(cfg, "num_votes", 0) if num_votes is None else num_votes
+    if num_votes is None or int(num_votes) < 1:
+        raise ValueError("validate_scans_voted: num_votes must be >= 1, got %r (validate_scans is the un-voted call)" % (num_votes,))
+    num_votes = int(num_votes)
+    model.eval()
+    c = _cfg(cfg, "num_classes", 17)
+    if isinstance(scans, VoteBatcher):
+        batcher = scans
+        need(stream is None or stream is batcher.stream, "validate_scans_voted: the VoteBatcher was built for another stream")
+        need(vote is None or list(vote) == batcher.vote, "validate_scans_voted: the VoteBatcher was built for another vote list")
+    else:
+        need(_cfg(cfg, "num_points") is not None, "validate_scans_voted: cfg.num_points (the sample size) is missing")
+        transforms = _cfg(cfg, "datatransforms")
+        if vote is None:
+            vote = _cfg(transforms, "vote") if transforms is not None else None
+        kwargs = _cfg(transforms, "kwargs") if transforms is not None else None
+        batcher = VoteBatcher(scans, _cfg(cfg, "num_points"), c, vote=DEFAULT_VOTE if vote is None else vote,
+                              kwargs=TOOTH_VIEW_KWARGS if kwargs is None else kwargs, stream=stream, draws=draws)
+    need(int(batch_size) >= 1, "validate_scans_voted: batch_size >= 1")
+    order = list(range(len(batcher))) if indices is None else [int(i) for i in indices]
+    parts = [order[at:at + int(batch_size)] for at in range(0, len(order), int(batch_size))]
+    passes = [part for part in parts for _ in range(num_votes)]            # every batch of scans num_votes times
+    metrics = SegMetrics(c, batcher.device)
+    data = batcher.batch(passes[0], draws=draws) if passes else None
+    votes = None
+    for k in range(len(passes)):
+        batcher.join(data)
+        ahead = batcher.batch(passes[k + 1], draws=draws) if k + 1 < len(passes) else None     # beside the forward pass
+        logits, _, _ = model(data)
+        last = (k + 1) % num_votes == 0
+        if k % num_votes == 0:
+            votes = ScanVotes(data, c)
+        votes.add(logits, data, last=last, counts=metrics._rows(len(data["sizes"])) if last else None)
+        if last:
+            metrics.mandible += [bool(m) for m in data["mandible"]]
         data = ahead
     return _report(metrics.read(), cfg)

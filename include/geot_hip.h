@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 20
+#define GEOT_ABI_VERSION 21
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -802,6 +802,31 @@ int geot_scan_predict(int b, int c, int n, int n_scans, long long total, const f
                       const long long *offsets, const long long *scan_ids, const float *known, const float *prob,
                       int n_work, const int *work, const long long *out_offsets, long long *pred, long long *counts,
                       void *ws, long long ws_bytes, void *stream);
+
+/* ---- whole-scan predictions voted over several samples of the same scans (ABI 21) ------------------------------------------
+ * geot_scan_vote: geot_scan_predict with one difference -- a vertex's c interpolated class values are not arg-maxed on the
+ * spot but stored in, or added to, a caller-owned accumulator; after the last vote the arg-max is taken of the sum.  Every
+ * other argument, the work table, the search, the skip rules and the workspace (geot_scan_predict_ws_bytes(b, n)) are
+ * geot_scan_predict's; so is the number of launches.
+ * acc: fp32, vertex-major, (sum of the slots' vertex counts, c); vertex v of slot s owns row out_offsets[s] + v (out_offsets
+ * (b) int64 on the device).  Both are always required.  A skipped slot or work record leaves its rows untouched.
+ * mode: GEOT_VOTE_SET -- this is the first vote: the values are stored (acc may arrive uninitialised); without it they are
+ * added to what is there, value = acc + this vote's, one fp32 addition.  GEOT_VOTE_FINISH -- once this vote's values are in,
+ * pred and / or counts are written from the sums as geot_scan_predict writes them from one vote's values (first maximum, a NaN
+ * wins; counts ADDED to; counts needs labels).  pred and counts are legal only with GEOT_VOTE_FINISH.
+ * The per-class value is geot_scan_predict's statement for statement, so one call with GEOT_VOTE_SET | GEOT_VOTE_FINISH writes
+ * geot_scan_predict's pred and counts bit for bit and leaves the interpolated probabilities in acc.
+ * One writer per accumulator element and no float atomics: the votes are added in call order, and the same calls give the
+ * same bits.  GEOT_VOTE_IMPL=row|tile (read at every call) picks how acc is reached -- per vertex by the lanes that hold
+ * its values, or 64 vertices at a time through an LDS tile -- with the same results.
+ * geot_scan_predict's refusals, and: acc or out_offsets NULL, a mode bit other than the two, pred or counts without
+ * GEOT_VOTE_FINISH; all hipErrorInvalidValue before any launch. */
+#define GEOT_VOTE_SET 1
+#define GEOT_VOTE_FINISH 2
+int geot_scan_vote(int b, int c, int n, int n_scans, long long total, const float *points, const int *labels,
+                   const long long *offsets, const long long *scan_ids, const float *known, const float *prob,
+                   int n_work, const int *work, const long long *out_offsets, float *acc, int mode, long long *pred,
+                   long long *counts, void *ws, long long ws_bytes, void *stream);
 
 /* ---- transform lists as per-view programs (ABI 16) ---------------------------------------------------------------------------
  * geot_view_program: geot_fixmatch_views for ANY list of the reference's point transforms that keeps the point count
