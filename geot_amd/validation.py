@@ -35,6 +35,14 @@ the whole scans and summed before the arg-max (geot_scan_vote: geot_scan_predict
     out = validate_scans_voted(model, scans, cfg)            # validate_scans with cfg.num_votes passes per batch
     preds = vote_scans(model, VoteBatcher(scans, n), idx, 10)    # the voted per-vertex labels of whole scans
     votes = ScanVotes(batch, num_classes); votes.add(logits, batch); ...; votes.add(logits, batch, last=True, want_pred=True)
+
+Refinement -- the config's `refine` and the reference's part_seg_refinement (train.py:57-73), which it defines and never
+calls: the vertices of a class with fewer than n members in its scan, or of a class the jaw does not allow, take the majority
+label of their n + 1 nearest vertices (geot_scan_refine, csrc/scan_refine.hip: six launches per batch, no synchronisation):
+
+    preds = refine_scans(predict_scans(logits, batch), batch, n=10, parts=cls2parts)     # in place, the same views
+    preds = predict_scans(logits, batch, refine=10)          # also vote_scans, validate_scans, validate_scans_voted
+    pred = part_seg_refinement(pred, pos, cls, cls2parts, n=10)                         # the reference's dense (B, N) form
 """
 import logging
 
@@ -205,12 +213,138 @@ def _scan_predict(logits, batch, num_classes, counts=None, want_pred=False, what
 
 
 @torch.no_grad()
-def predict_scans(logits, batch):
+def predict_scans(logits, batch, refine=0, parts=None):
     """The per-vertex labels of the batch's whole scans: list of (1, M_i) int64 tensors (views of one buffer), equal to
     get_pred_whole(logits, batch["pos"], batch["points"], batch["center"], batch["scale"]).  logits (B, C, N) fp32 on the
-    scans' device, batch from ValBatcher.batch.  One geot_scan_predict call, no host synchronisation."""
+    scans' device, batch from ValBatcher.batch.  One geot_scan_predict call, no host synchronisation.  refine (0: off, True:
+    n = 10, an int: n) and parts: the labels then go through refine_scans."""
+    n_refine = _refine_n(refine, "predict_scans")
     need(torch.is_tensor(logits) and logits.dim() == 3, "predict_scans: logits must be a (B, C, N) tensor")
-    return _scan_predict(logits, batch, logits.shape[1], want_pred=True)
+    preds = _scan_predict(logits, batch, logits.shape[1], want_pred=True)
+    return refine_scans(preds, batch, n_refine, parts, num_classes=logits.shape[1]) if n_refine else preds
+
+
+REFINE_MAX_N = 63                   # include/geot_hip.h geot_scan_refine: n + 1 neighbours in one wave's list
+
+
+def _refine_n(refine, what):
+    """The `refine` keyword: 0 / False / None -> 0 (off), True -> 10 (the reference's default n), an int -> n."""
+    if refine is None or refine is False:
+        return 0
+    if refine is True:
+        return 10
+    need(isinstance(refine, (int, np.integer)), "%s: refine must be a bool or an int, got %r" % (what, refine))
+    need(0 <= int(refine) <= REFINE_MAX_N, "%s: refine n must be in 1..%d (0: off), got %d" % (what, REFINE_MAX_N, int(refine)))
+    return int(refine)
+
+
+def _allowed_masks(parts, jaws, c, what):
+    """parts (the reference's cls2parts: per jaw class the allowed labels) and the slots' jaw classes -> one bit mask per slot."""
+    masks = []
+    for row in parts:
+        labels = [int(l) for l in row]
+        need(all(0 <= l < c for l in labels), "%s: parts must hold labels in [0, %d)" % (what, c))
+        masks.append(sum(1 << l for l in set(labels)))
+    need(all(0 <= j < len(masks) for j in jaws), "%s: parts has %d rows, the jaw classes are %s" % (what, len(masks), sorted(set(jaws))))
+    return np.array([masks[j] for j in jaws], dtype=np.uint32)
+
+
+def _scan_refine(pred, n, c, points, offsets, scan_ids, n_scans, out_offs, allowed, b, want_stats):
+    """One geot_scan_refine call on the flat int64 label buffer `pred`."""
+    dev = pred.device
+    nbytes = int(_lib.load().geot_scan_refine_ws_bytes(b, int(pred.numel()), n))
+    need(nbytes >= 0, "geot_scan_refine: no workspace for b = %d, n = %d, %d labels" % (b, n, pred.numel()))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    stats = torch.empty((b, 4), dtype=torch.int32, device=dev) if want_stats else None
+    call("geot_scan_refine", dev, b, c, n, n_scans, int(points.shape[0]), ptr(points), ptr(offsets), ptr(scan_ids), ptr(out_offs),
+         ptr(allowed), ptr(pred), ptr(stats), ptr(ws), nbytes)
+    return stats
+
+
+@torch.no_grad()
+def refine_scans(preds, batch, n=10, parts=None, stats=False, num_classes=None):
+    """part_seg_refinement (train.py:57-73) on whole scans: preds as predict_scans / vote_scans return them -- per scan of the
+    batch a (1, M_i) int64 tensor -- refined IN PLACE when they are views of one buffer, slot after slot (a list that is not is
+    concatenated and split again); returns the list, with stats=True (list, (B, 4) int32 device tensor of steps, queries,
+    changed vertices, labels outside [0, C) per scan).  Per scan: a class with fewer than n vertices, or one that parts does
+    not allow for the scan's jaw, hands its vertices to the majority label of their n + 1 nearest vertices (the class itself
+    excluded, the lowest label among equals); classes in the order of their first vertex, every class's queries taken from the
+    labels as they came in.  parts: None (every class allowed) or, per jaw class (0 mandible, 1 maxillary, from
+    batch["mandible"]), the allowed labels -- the reference's cls2parts.  num_classes: default parts[-1][-1] + 1 as in the
+    reference, 32 without parts.  One geot_scan_refine call, no host synchronisation."""
+    need(isinstance(n, (int, np.integer)) and not isinstance(n, bool) and 1 <= int(n) <= REFINE_MAX_N,
+         "refine_scans: n must be an int in 1..%d, got %r" % (REFINE_MAX_N, n))
+    n = int(n)
+    need(isinstance(batch, dict) and all(k in batch for k in ("scan_ids", "scans", "sizes")),
+         "refine_scans: batch must come from ValBatcher.batch (scan_ids, scans, sizes)")
+    scans, sizes = batch["scans"], [int(m) for m in batch["sizes"]]
+    b = len(sizes)
+    need(isinstance(preds, (list, tuple)) and len(preds) == b and 1 <= b <= SCAN_MAX_SLOTS,
+         "refine_scans: one prediction tensor per scan of the batch (1 .. %d)" % SCAN_MAX_SLOTS)
+    for p, m in zip(preds, sizes):
+        need(torch.is_tensor(p) and p.dtype == torch.int64, "refine_scans: the predictions must be int64 tensors")
+        need(p.numel() == m, "refine_scans: %d predictions for a scan of %d vertices" % (p.numel(), m))
+        need(m >= n + 1, "refine_scans: a scan of %d vertices has no %d nearest vertices (n + 1)" % (m, n + 1))
+    if parts is not None:
+        c = int(parts[-1][-1]) + 1 if num_classes is None else int(num_classes)
+    else:
+        c = 32 if num_classes is None else int(num_classes)
+    need(1 <= c <= 32, "refine_scans: 1..32 classes (include/geot_hip.h GEOT_NTM_MAX_C), got %d" % c)
+    allowed = None
+    if parts is not None:
+        need("mandible" in batch and len(batch["mandible"]) == b, "refine_scans: parts needs the batch's jaw flags (mandible)")
+        allowed = _allowed_masks(parts, [0 if m else 1 for m in batch["mandible"]], c, "refine_scans")
+    dev = scans.device
+    need(all(p.is_cuda and p.device == dev for p in preds), "refine_scans: CPU not supported (the predictions must live on %s, "
+         "with the scans)" % dev)
+    need(torch.is_tensor(batch["scan_ids"]) and batch["scan_ids"].device == dev and batch["scan_ids"].dtype == torch.int64 and
+         tuple(batch["scan_ids"].shape) == (b,), "refine_scans: batch scan_ids must be (B,) int64 on %s" % dev)
+    at, views = preds[0].storage_offset(), True         # views of one buffer, slot after slot?
+    for p, m in zip(preds, sizes):
+        views = (views and p.is_contiguous() and p.untyped_storage().data_ptr() == preds[0].untyped_storage().data_ptr()
+                 and p.storage_offset() == at)
+        at += m
+    if views:
+        flat = torch.empty(0, dtype=torch.int64, device=dev).set_(preds[0].untyped_storage(), preds[0].storage_offset(), (sum(sizes),), (1,))
+        out = list(preds)
+    else:
+        flat = torch.cat([p.reshape(-1) for p in preds])
+        out = [f.view(p.shape) for f, p in zip(torch.split(flat, sizes), preds)]
+    allowed_dev = _to_device(allowed.view(np.int32), dev) if allowed is not None else None
+    st = _scan_refine(flat, n, c, scans.points, scans.offsets, batch["scan_ids"].contiguous(), len(scans), _out_offsets(sizes, dev),
+                      allowed_dev, b, stats)
+    return (out, st) if stats else out
+
+
+@torch.no_grad()
+def part_seg_refinement(pred, pos, cls, cls2parts, n=10):
+    """train.py:57-73 with the reference's signature: pred (B, N) int64 and pos (B, N, 3) fp32 on the GPU, cls the B shape
+    classes (rows of cls2parts), cls2parts per shape class the allowed labels; the class count is cls2parts[-1][-1] + 1.
+    pred is refined in place and returned.  The reference's rule for the CUDA tensors it is written for: the labels are
+    snapshotted before anything changes.  The same geot_scan_refine call as refine_scans, every row a scan of N vertices."""
+    need(isinstance(n, (int, np.integer)) and not isinstance(n, bool) and 1 <= int(n) <= REFINE_MAX_N,
+         "part_seg_refinement: n must be an int in 1..%d, got %r" % (REFINE_MAX_N, n))
+    n = int(n)
+    need(torch.is_tensor(pred) and torch.is_tensor(pos), "part_seg_refinement: pred and pos must be tensors")
+    need(pred.dtype == torch.int64 and pred.dim() == 2, "part_seg_refinement: pred must be (B, N) int64")
+    bsz, npts = pred.shape
+    need(pos.dtype == torch.float32 and tuple(pos.shape) == (bsz, npts, 3), "part_seg_refinement: pos must be (B, N, 3) fp32")
+    need(npts >= n + 1, "part_seg_refinement: %d points have no %d nearest points (n + 1)" % (npts, n + 1))
+    need(1 <= bsz <= SCAN_MAX_SLOTS, "part_seg_refinement: 1 .. %d shapes" % SCAN_MAX_SLOTS)
+    c = int(cls2parts[-1][-1]) + 1
+    need(1 <= c <= 32, "part_seg_refinement: 1..32 classes (include/geot_hip.h GEOT_NTM_MAX_C), got %d" % c)
+    jaws = [int(j) for j in (cls.detach().cpu().reshape(-1).tolist() if torch.is_tensor(cls) else np.asarray(cls).reshape(-1))]
+    need(len(jaws) == bsz, "part_seg_refinement: %d shape classes for %d shapes" % (len(jaws), bsz))
+    allowed = _allowed_masks(cls2parts, jaws, c, "part_seg_refinement")
+    need(pred.is_cuda and pos.is_cuda and pred.device == pos.device, "part_seg_refinement: CPU not supported (pred and pos must "
+         "live on one GPU)")
+    need(pred.is_contiguous(), "part_seg_refinement: pred must be contiguous (it is refined in place)")
+    dev = pred.device
+    offsets = _to_device(np.arange(bsz + 1, dtype=np.int64) * npts, dev)
+    ids = _to_device(np.arange(bsz, dtype=np.int64), dev)
+    _scan_refine(pred.view(-1), n, c, pos.contiguous().view(-1, 3), offsets, ids, bsz, offsets[:bsz], _to_device(allowed.view(np.int32), dev),
+                 bsz, False)
+    return pred
 
 
 def _mandible_flags(cls, b):
@@ -399,14 +533,17 @@ def _report(out, cfg):
 
 
 @torch.no_grad()
-def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, num_votes=0, data_transform=None):
+def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, num_votes=0, data_transform=None, refine=0,
+                   parts=None):
     """validate() without a loader: scans a DeviceScanSet (or a ValBatcher built on one, reused from epoch to epoch),
     batches of batch_size scans in the sequential sampler's order (the last, shorter batch is kept: drop_last is false for
     `val`), or of the scans `indices` names (a rank's shard).  cfg.num_points sizes the sample, cfg.num_classes (default
     17) the counts.  Same log lines, return value and dtypes as validate().  stream: the next batch is built on that side
     stream while the current one runs through the model.  num_votes and data_transform are accepted and unused, as in the
-    reference."""
+    reference.  refine (0: off -- cfg.refine is not read; True: n = 10; an int: n) and parts: the per-vertex labels are taken,
+    refined (refine_scans) and counted against the scans' labels with geot_seg_confusion."""
     from .openpoints.dataset.val_batch import ValBatcher
+    n_refine, cls2parts = _refine_n(refine, "validate_scans"), parts        # (`parts` below: the batches' scan numbers)
     model.eval()
     c = _cfg(cfg, "num_classes", 17)
     if isinstance(scans, ValBatcher):
@@ -424,9 +561,31 @@ def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, n
         batcher.join(data)
         ahead = batcher.batch(parts[k + 1]) if k + 1 < len(parts) else None     # beside the forward pass when on a side stream
         logits, _, _ = model(data)
-        metrics.update_from_scans(logits, data)
+        if n_refine:
+            preds = _scan_predict(logits, data, c, want_pred=True, what="validate_scans")
+            _count_refined(metrics, preds, data, n_refine, cls2parts)
+        else:
+            metrics.update_from_scans(logits, data)
         data = ahead
     return _report(metrics.read(), cfg)
+
+
+def _scan_labels(batch):
+    """The labels of the batch's scans, gathered from the set on the device: list of (M_i,) int64.  The sizes are the host's,
+    the scan ids stay on the device: no synchronisation."""
+    scans, sizes = batch["scans"], [int(m) for m in batch["sizes"]]
+    dev, b, total = scans.device, len(sizes), sum(sizes)
+    reps = _to_device(np.asarray(sizes, dtype=np.int64), dev)
+    slot = torch.repeat_interleave(torch.arange(b, device=dev), reps, output_size=total)
+    first = scans.offsets[batch["scan_ids"]] - _out_offsets(sizes, dev)
+    index = first[slot] + torch.arange(total, device=dev)
+    return list(torch.split(scans.labels[index].to(torch.int64), sizes))
+
+
+def _count_refined(metrics, preds, batch, n, parts):
+    """The validators' refine leg: refine the batch's per-vertex labels and count them against the scans' labels."""
+    preds = refine_scans(preds, batch, n, parts, num_classes=metrics.c)
+    metrics.update(preds, _scan_labels(batch), [0 if m else 1 for m in batch["mandible"]])
 
 
 class ScanVotes:
@@ -481,11 +640,13 @@ class ScanVotes:
 
 
 @torch.no_grad()
-def vote_scans(model, batcher, idx, num_votes, draws=None):
+def vote_scans(model, batcher, idx, num_votes, draws=None, refine=0, parts=None):
     """The voted per-vertex labels of the scans `idx` of a VoteBatcher's set: list of (1, M_i) int64 tensors, as predict_scans
     returns them.  num_votes model passes, each on a freshly drawn batch of the same scans (draws: a DeviceDraws for these
-    batches; default: the batcher's); the next batch is built beside the forward pass when the batcher has a side stream."""
+    batches; default: the batcher's); the next batch is built beside the forward pass when the batcher has a side stream.
+    refine (0: off, True: n = 10, an int: n) and parts: the voted labels then go through refine_scans."""
     need(int(num_votes) >= 1, "vote_scans: num_votes >= 1")
+    n_refine = _refine_n(refine, "vote_scans")
     model.eval()
     votes, preds = None, None
     data = batcher.batch(idx, draws=draws)
@@ -497,19 +658,24 @@ def vote_scans(model, batcher, idx, num_votes, draws=None):
         if votes is None:
             votes = ScanVotes(data, logits.shape[1])
         preds = votes.add(logits, data, last=last, want_pred=last)
+        if last and n_refine:
+            preds = refine_scans(preds, data, n_refine, parts, num_classes=votes.c)
         data = ahead
     return preds
 
 
 @torch.no_grad()
-def validate_scans_voted(model, scans, cfg, num_votes=None, vote=None, batch_size=2, indices=None, stream=None, draws=None):
+def validate_scans_voted(model, scans, cfg, num_votes=None, vote=None, batch_size=2, indices=None, stream=None, draws=None,
+                         refine=0, parts=None):
     """validate_scans with votes: every batch of scans runs through the model num_votes times, each time freshly sampled and
     under the `vote` transform list, and is scored on the arg-max of the summed whole-scan probabilities.  scans: a
     DeviceScanSet, or a VoteBatcher built on one.  num_votes defaults to cfg.num_votes, vote to cfg.datatransforms.vote when
     present (else VoteBatcher's default, the yaml's [PointCloudScaling]); the lists' kwargs to cfg.datatransforms.kwargs.
     num_votes < 1 raises ValueError: validate_scans is the un-voted call.  The next vote's batch is built on `stream` beside
-    the current forward pass.  Same log lines, return value and dtypes as validate()."""
+    the current forward pass.  Same log lines, return value and dtypes as validate().  refine, parts: as for validate_scans,
+    on the voted labels."""
     from .openpoints.dataset.vote_batch import DEFAULT_VOTE, TOOTH_VIEW_KWARGS, VoteBatcher
+    n_refine, cls2parts = _refine_n(refine, "validate_scans_voted"), parts      # (`parts` below: the batches' scan numbers)
     num_votes = _cfg(cfg, "num_votes", 0) if num_votes is None else num_votes
     if num_votes is None or int(num_votes) < 1:
         raise ValueError("validate_scans_voted: num_votes must be >= 1, got %r (validate_scans is the un-voted call)" % (num_votes,))
@@ -542,8 +708,11 @@ def validate_scans_voted(model, scans, cfg, num_votes=None, vote=None, batch_siz
         last = (k + 1) % num_votes == 0
         if k % num_votes == 0:
             votes = ScanVotes(data, c)
-        votes.add(logits, data, last=last, counts=metrics._rows(len(data["sizes"])) if last else None)
-        if last:
-            metrics.mandible += [bool(m) for m in data["mandible"]]
+        if last and n_refine:
+            _count_refined(metrics, votes.add(logits, data, last=True, want_pred=True), data, n_refine, cls2parts)
+        else:
+            votes.add(logits, data, last=last, counts=metrics._rows(len(data["sizes"])) if last else None)
+            if last:
+                metrics.mandible += [bool(m) for m in data["mandible"]]
         data = ahead
     return _report(metrics.read(), cfg)

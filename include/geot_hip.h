@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 21
+#define GEOT_ABI_VERSION 22
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -827,6 +827,41 @@ int geot_scan_vote(int b, int c, int n, int n_scans, long long total, const floa
                    const long long *offsets, const long long *scan_ids, const float *known, const float *prob,
                    int n_work, const int *work, const long long *out_offsets, float *acc, int mode, long long *pred,
                    long long *counts, void *ws, long long ws_bytes, void *stream);
+
+/* ---- whole-scan predictions refined by their neighbours' majority (ABI 22) ---------------------------------------------------
+ * geot_scan_refine: part_seg_refinement (train.py:57-73) for b batch slots, on per-vertex labels as geot_scan_predict /
+ * geot_scan_vote write them, in a number of launches (six) that depends neither on b, nor on the scans' sizes, nor on what the
+ * labels hold; no host synchronisation.  points, offsets, scan_ids, out_offsets: as for geot_scan_predict.  pred is refined
+ * in place: vertex v of slot s is pred[out_offsets[s] + v]; the slots' ranges must not overlap.  Per slot, with snap the
+ * slot's labels as they arrive:
+ *   count[i], first[i]: the members of class i in snap and the lowest vertex index among them.  With fewer than two classes
+ *   present the slot is left alone.  Otherwise every present class i with count[i] < n, or whose bit i of allowed[s] is clear
+ *   (allowed (b) 32-bit masks on the device; NULL: every class is allowed), is refined, the classes in ascending first[i]:
+ *     the queries are the vertices with snap == i (never a vertex that an earlier step relabelled to i);
+ *     each takes its n + 1 nearest vertices of the same scan, itself included, by (d2, vertex index), d2 = ((dx dx) +
+ *     (dy dy)) + (dz dz) as geot_three_nn forms it; an entry that was never filled (fewer than n + 1 finite distances) does
+ *     not vote;
+ *     it counts their CURRENT labels -- earlier steps' changes are seen, this step's are not: all queries of a step are
+ *     computed before one is written -- sets the count of class i to zero and takes the first maximum (the lowest class among
+ *     equals; all zero: class 0).
+ * A label outside [0, c) is never a query, never votes and is never written.  Integer atomics only, and no result depends
+ * on their order: the same call gives the same bits.
+ * stats (optional): (b, 4) int32, WRITTEN (a skipped slot: zeros) -- steps taken, queries, vertices whose label changed,
+ * labels outside [0, c).
+ * ws: geot_scan_refine_ws_bytes(b, total_out, n) bytes, 16-byte aligned, contents irrelevant; total_out = the length of pred
+ * (every out_offsets[s] + size of slot s <= total_out).  It holds the census, the plan, a query list of total_out ints and
+ * the neighbour table of total_out (n + 1) ints: the worst case, since the query count stays on the device.
+ * A slot whose scan_ids entry lies outside [0, n_scans), whose offsets pair is not 0 <= lo < hi <= total with hi - lo <=
+ * 2^31 - 1, or whose out_offsets entry does not leave room for it in a ws_bytes-sized workspace, is skipped: nothing of it is
+ * read or written.  That room is (ws_bytes - geot_scan_refine_ws_bytes(b, 0, n)) / (4 (n + 2)) vertices -- total_out exactly for a
+ * workspace of the size asked for, more for a larger one: the check guards the workspace, the length of pred is the caller's.  0 <= b <= 65535 (0: nothing to do), 1 <= c <= GEOT_NTM_MAX_C, 1 <= n <= 63 (the wave's best-k list holds
+ * one entry per lane: n + 1 <= 64), n_scans >= 1, total >= 1, no NULL among points, offsets, scan_ids, out_offsets, pred and ws,
+ * ws_bytes >= geot_scan_refine_ws_bytes(b, 0, n); anything else is hipErrorInvalidValue before any launch.
+ * geot_scan_refine_ws_bytes: -1 for arguments outside these ranges or total_out < 0. */
+long long geot_scan_refine_ws_bytes(int b, long long total_out, int n);
+int geot_scan_refine(int b, int c, int n, int n_scans, long long total, const float *points, const long long *offsets,
+                     const long long *scan_ids, const long long *out_offsets, const unsigned *allowed, long long *pred,
+                     int *stats, void *ws, long long ws_bytes, void *stream);
 
 /* ---- transform lists as per-view programs (ABI 16) ---------------------------------------------------------------------------
  * geot_view_program: geot_fixmatch_views for ANY list of the reference's point transforms that keeps the point count
