@@ -42,7 +42,42 @@ def draw_val_sel(sizes, num_points):
     return sel
 
 
-class ValBatcher(Batcher):
+class ScanBatcher(Batcher):
+    """What the batchers of whole scans (ValBatcher, vote_batch.VoteBatcher) share: the jaw classes, read from the device once,
+    here; the zero-copy views of every scan's vertices and labels; the idx checks; the keys of a batch that describe its scans;
+    `join` over the class's tensor keys."""
+
+    join_keys = ("pos", "x", "y", "cls", "center", "scale", "scan_ids")
+
+    def __init__(self, scans, num_points, num_classes, kwargs, stream, draws):
+        super().__init__(scans, num_points, num_classes, stream, draws)
+        self.kwargs = kwargs
+        self.cls_host = [int(v) for v in scans.cls.cpu().tolist()]       # the one copy: validate's `cls[ii] == 0` per scan
+        self._points = list(torch.split(scans.points, scans.sizes))      # views
+        self._labels = list(torch.split(scans.labels, scans.sizes))
+
+    def __len__(self):
+        return len(self.scans)
+
+    def _ids(self, idx):
+        ids, who = [int(i) for i in idx], type(self).__name__
+        need(len(ids) >= 1, "%s.batch: at least one scan" % who)
+        need(all(0 <= i < len(self.scans) for i in ids), "%s.batch: idx must lie in [0, %d)" % (who, len(self.scans)))
+        return ids
+
+    def _scan_keys(self, s, cls, ids):
+        """Every key of a batch but the views' (pos, x, ...)."""
+        return {"y": s["y"], "cls": cls, "center": s["center"], "scale": s["scale"],
+                "points": [self._points[i] for i in ids], "labels": [self._labels[i] for i in ids],
+                "scan_ids": s["scan_ids"], "scans": self.scans, "sizes": [self.scans.sizes[i] for i in ids],
+                "mandible": [self.cls_host[i] == 0 for i in ids]}
+
+    def join(self, batch):
+        """Hand a batch built on the side stream to the CURRENT stream (Batcher._join)."""
+        self._join(batch[key] for key in self.join_keys)
+
+
+class ValBatcher(ScanBatcher):
     """Replaces the reference's validation DataLoader: `batch(idx)` returns the dict described in the module text for the
     scans `idx` of the set (what the sequential sampler would yield), in freshly allocated tensors.
 
@@ -56,23 +91,14 @@ class ValBatcher(Batcher):
     DeviceDraws(seed, views=True) is accepted and changes nothing: the `val` list draws no view parameter."""
 
     def __init__(self, scans, num_points, num_classes=17, kwargs=TOOTH_VIEW_KWARGS, stream=None, draws=None):
-        super().__init__(scans, num_points, num_classes, stream, draws)
+        super().__init__(scans, num_points, num_classes, kwargs, stream, draws)
         need(int(_kw(kwargs, "gravity_dim")) in (0, 1, 2), "ValBatcher: gravity_dim must be 0, 1 or 2")
-        self.kwargs = kwargs
-        self.cls_host = [int(v) for v in scans.cls.cpu().tolist()]       # the one copy: validate's `cls[ii] == 0` per scan
-        self._points = list(torch.split(scans.points, scans.sizes))      # views
-        self._labels = list(torch.split(scans.labels, scans.sizes))
-
-    def __len__(self):
-        return len(self.scans)
 
     def batch(self, idx, sel=None, check=False, draws=None):
         """idx: scan numbers within the set; sel (B, m) vertex indices per scan, default the reference's draws
         (draw_val_sel's statements) or, with draws (a DeviceDraws; default: the constructor's), geot_sample_draw's.
         check=True reads the bad-index flags back (one host sync) and raises IndexError."""
-        ids = [int(i) for i in idx]
-        need(len(ids) >= 1, "ValBatcher.batch: at least one scan")
-        need(all(0 <= i < len(self.scans) for i in ids), "ValBatcher.batch: idx must lie in [0, %d)" % len(self.scans))
+        ids = self._ids(idx)
         weak = draw_view_params("train_w", self.kwargs)                   # the `val` list: nothing is drawn
         sel, params, ids_dev = self._draw(ids, (("sel", sel, len(ids)),), [weak] * len(ids), draws, None)
         return self._batch(ids, (len(ids),), sel, params, ids_dev, check)
@@ -84,11 +110,4 @@ class ValBatcher(Batcher):
         return fixmatch_views(raw, jobs, int(_kw(self.kwargs, "gravity_dim")), len(jobs))
 
     def _result(self, s, v, cls, ids, b):
-        return {"pos": v["pos"], "x": v["x"], "y": s["y"], "cls": cls, "center": s["center"], "scale": s["scale"],
-                "points": [self._points[i] for i in ids], "labels": [self._labels[i] for i in ids],
-                "scan_ids": s["scan_ids"], "scans": self.scans, "sizes": [self.scans.sizes[i] for i in ids],
-                "mandible": [self.cls_host[i] == 0 for i in ids]}
-
-    def join(self, batch):
-        """Hand a batch built on the side stream to the CURRENT stream (Batcher._join)."""
-        self._join(batch[key] for key in ("pos", "x", "y", "cls", "center", "scale", "scan_ids"))
+        return {"pos": v["pos"], "x": v["x"], **self._scan_keys(s, cls, ids)}

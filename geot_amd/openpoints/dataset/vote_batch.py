@@ -18,19 +18,17 @@ Host draws by default: per item np.random.choice, then the vote list's draws (Vi
 order.  draws=DeviceDraws(seed) draws the samples on the device, DeviceDraws(seed, views=True) the vote parameters too: a slot's
 two jobs draw under the slot's own draw id (views 0 and 1), as FixMatchBatcher's weak / strong pair does.
 """
-import torch
-
 from ...ext._common import need
-from .batcher import Batcher
 from .fixmatch_batch import TOOTH_VIEW_KWARGS
 from .sample_draw import ViewDrawHandle
+from .val_batch import ScanBatcher
 from .view_program import ViewProgram
 
 VAL_LIST = ["PointsToTensor", "PointCloudCenterAndNormalize"]       # the yaml's datatransforms.val
 DEFAULT_VOTE = ("PointCloudScaling",)                               # the yaml's datatransforms.vote
 
 
-class VoteBatcher(Batcher):
+class VoteBatcher(ScanBatcher):
     """`batch(idx)` returns the dict of the module text for the scans `idx` of the set, in freshly allocated tensors.  An
     empty `vote` list is allowed: pos_search then equals pos.  A list ViewProgram refuses (RandomDropout, ...) raises its
     NotImplementedError here, before any device call.
@@ -38,28 +36,21 @@ class VoteBatcher(Batcher):
     stream / draws: as ValBatcher's; with DeviceDraws(seed, views=True) the vote list's parameters are device draws too, and
     an explicit params= still wins.  Call `join(batch)` before the current stream reads a batch built on a side stream."""
 
+    join_keys = ScanBatcher.join_keys + ("pos_search",)
+
     def __init__(self, scans, num_points, num_classes=17, vote=DEFAULT_VOTE, kwargs=TOOTH_VIEW_KWARGS, stream=None, draws=None):
         need(not isinstance(vote, str), "VoteBatcher: vote is a list of transform class names")
         self.vote = list(vote)
         self.val_program = ViewProgram(VAL_LIST, kwargs)
         self.program = ViewProgram(VAL_LIST + self.vote, kwargs)       # NotImplementedError for what the kernel cannot do
-        super().__init__(scans, num_points, num_classes, stream, draws)
-        self.kwargs = kwargs
-        self.cls_host = [int(v) for v in scans.cls.cpu().tolist()]       # the one copy: validate's `cls[ii] == 0` per scan
-        self._points = list(torch.split(scans.points, scans.sizes))      # views
-        self._labels = list(torch.split(scans.labels, scans.sizes))
-
-    def __len__(self):
-        return len(self.scans)
+        super().__init__(scans, num_points, num_classes, kwargs, stream, draws)
 
     def batch(self, idx, sel=None, params=None, check=False, draws=None):
         """idx: scan numbers within the set; sel (B, m) vertex indices per scan and params (per scan one ViewProgram.draw
         result of the `val` + `vote` list, VoteBatcher.program) default to the reference's draws; draws: a DeviceDraws for
         this call (default: the constructor's).  check=True reads the bad-index flags back (one host sync) and raises
         IndexError."""
-        ids = [int(i) for i in idx]
-        need(len(ids) >= 1, "VoteBatcher.batch: at least one scan")
-        need(all(0 <= i < len(self.scans) for i in ids), "VoteBatcher.batch: idx must lie in [0, %d)" % len(self.scans))
+        ids = self._ids(idx)
         sel, params, ids_dev = self._draw(ids, (("sel", sel, len(ids)),), params, draws, lambda slot: self.program.draw(self.m))
         if not isinstance(params, ViewDrawHandle):          # per job: the `val` views (nothing is drawn), then the voted ones
             params = [self.val_program.draw(self.m)] * len(ids) + params
@@ -71,11 +62,4 @@ class VoteBatcher(Batcher):
         return jobs, b, 2 * b, [0] * b + [1] * b, 2 * list(range(b))
 
     def _result(self, s, v, cls, ids, b):
-        return {"pos": v["pos"][b:], "x": v["x"][b:], "pos_search": v["pos"][:b], "y": s["y"], "cls": cls, "center": s["center"],
-                "scale": s["scale"], "points": [self._points[i] for i in ids], "labels": [self._labels[i] for i in ids],
-                "scan_ids": s["scan_ids"], "scans": self.scans, "sizes": [self.scans.sizes[i] for i in ids],
-                "mandible": [self.cls_host[i] == 0 for i in ids]}
-
-    def join(self, batch):
-        """Hand a batch built on the side stream to the CURRENT stream (Batcher._join)."""
-        self._join(batch[key] for key in ("pos", "x", "pos_search", "y", "cls", "center", "scale", "scan_ids"))
+        return {"pos": v["pos"][b:], "x": v["x"][b:], "pos_search": v["pos"][:b], **self._scan_keys(s, cls, ids)}

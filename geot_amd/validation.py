@@ -35,6 +35,7 @@ the whole scans and summed before the arg-max (geot_scan_vote: geot_scan_predict
     out = validate_scans_voted(model, scans, cfg)            # validate_scans with cfg.num_votes passes per batch
     preds = vote_scans(model, VoteBatcher(scans, n), idx, 10)    # the voted per-vertex labels of whole scans
     votes = ScanVotes(batch, num_classes); votes.add(logits, batch); ...; votes.add(logits, batch, last=True, want_pred=True)
+    metrics.update_from_votes(votes, logits, batch)          # the last add(), counted into the epoch's rows
 
 Refinement -- the config's `refine` and the reference's part_seg_refinement (train.py:57-73), which it defines and never
 calls: the vertices of a class with fewer than n members in its scan, or of a class the jaw does not allow, take the majority
@@ -68,6 +69,33 @@ MAX_VERTICES = (1 << 31) - 1        # per scan (include/geot_hip.h geot_seg_conf
 SCAN_GROUPS = 4096
 SCAN_CHUNK_MIN = 64
 SCAN_MAX_SLOTS = 65535              # batch slots per call (include/geot_hip.h geot_scan_predict)
+REFINE_MAX_N = 63                   # include/geot_hip.h geot_scan_refine: n + 1 neighbours in one wave's list
+
+
+def _need_classes(num_classes, what):
+    c = int(num_classes)
+    need(1 <= c <= 32, "%s: 1..32 classes (include/geot_hip.h GEOT_NTM_MAX_C), got %d" % (what, c))
+    return c
+
+
+def _refine_n(n, what, keyword=True):
+    """Refine's n: an int, no bool, in 1 .. REFINE_MAX_N.  keyword: the `refine` keyword of predict_scans, vote_scans and the
+    validators, which is also 0 / False / None -> 0 (off) or True -> 10 (the reference's default n)."""
+    if keyword and (n is None or isinstance(n, bool)):
+        return 10 if n else 0
+    need(isinstance(n, (int, np.integer)) and not isinstance(n, bool) and (0 if keyword else 1) <= int(n) <= REFINE_MAX_N,
+         "%s: %s must be an int in 1..%d%s, got %r" % (what, "refine" if keyword else "n", REFINE_MAX_N, " (0: off)" if keyword else "", n))
+    return int(n)
+
+
+def _three_nn_inputs(points, points_whole, center, scale, index, dev):
+    """get_pred_whole's statements for scan `index` up to its three_nn call -> (unknown (1, M, 3), known (1, N, 3)), fp32."""
+    point = points[index].unsqueeze(0).contiguous()
+    s = torch.as_tensor(scale[index]).to(dev).unsqueeze(0).contiguous()
+    c = torch.as_tensor(center[index]).to(dev).unsqueeze(0).contiguous()
+    point_whole = torch.as_tensor(points_whole[index]).to(dev).unsqueeze(0).contiguous()
+    point = (point * s + c).contiguous()
+    return point_whole.float().contiguous(), point.float().contiguous()
 
 
 @torch.no_grad()
@@ -79,12 +107,7 @@ def get_pred_whole(logits, points, points_whole, center, scale):
     preds_whole = []
     for index in range(logits.shape[0]):
         logit = logits[index].unsqueeze(0).contiguous()
-        point = points[index].unsqueeze(0).contiguous()
-        s = torch.as_tensor(scale[index]).to(dev).unsqueeze(0).contiguous()
-        c = torch.as_tensor(center[index]).to(dev).unsqueeze(0).contiguous()
-        point_whole = torch.as_tensor(points_whole[index]).to(dev).unsqueeze(0).contiguous()
-        point = (point * s + c).contiguous()
-        dist, idx = pt_utils.three_nn(point_whole.float(), point.float())
+        dist, idx = pt_utils.three_nn(*_three_nn_inputs(points, points_whole, center, scale, index, dev))
         dist_recip = 1.0 / (dist + 1e-8)
         weight = dist_recip / torch.sum(dist_recip, dim=2, keepdim=True)
         logit_whole = pt_utils.three_interpolate(logit, idx, weight)
@@ -192,24 +215,28 @@ def _out_offsets(sizes, dev):
     return _to_device(np.concatenate([[0], ends[:-1]]).astype(np.int64), dev)
 
 
-def _scan_predict(logits, batch, num_classes, counts=None, want_pred=False, what="predict_scans"):
-    """One geot_scan_predict call for a ValBatcher batch: _scan_inputs, then the kernel."""
-    b, n, scan_ids, prob, known = _scan_inputs(logits, batch, num_classes, what)
+def _scan_launch(logits, batch, num_classes, what, counts=None, want_pred=False, votes=None, mode=0):
+    """One geot_scan_predict call for a ValBatcher batch -- for a ScanVotes, one geot_scan_vote call on its accumulator, work
+    table and out_offsets, searching batch["pos_search"] when the batch has one: _scan_inputs, the workspace, the kernel
+    -> the per-vertex labels as a list of (1, M_i) int64 views of one buffer, or None without want_pred."""
+    pos_key = "pos_search" if votes is not None and isinstance(batch, dict) and "pos_search" in batch else "pos"
+    b, n, scan_ids, prob, known = _scan_inputs(logits, batch, num_classes, what, pos_key)
     scans, sizes = batch["scans"], [int(m) for m in batch["sizes"]]
-    dev, c = scans.device, int(num_classes)
-    work = _to_device(scan_work_table(sizes), dev)
-    pred = out_offs = None
-    if want_pred:
-        pred = torch.empty(sum(sizes), dtype=torch.int64, device=dev)
-        out_offs = _out_offsets(sizes, dev)
+    dev = scans.device
+    if votes is not None:
+        need(scans is votes.scans and sizes == votes.sizes, "%s: every vote's batch holds the same scans in the same slots" % what)
+        work, out_offs = votes.work, votes.out_offsets
+    else:                               # the un-voted call builds its tables per call, out_offsets only for the labels
+        work = _to_device(scan_work_table(sizes), dev)
+        out_offs = _out_offsets(sizes, dev) if want_pred else None
+    pred = torch.empty(sum(sizes), dtype=torch.int64, device=dev) if want_pred else None
     nbytes = int(_lib.load().geot_scan_predict_ws_bytes(b, n))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    call("geot_scan_predict", dev, b, c, n, len(scans), int(scans.points.shape[0]), ptr(scans.points), ptr(scans.labels),
-         ptr(scans.offsets), ptr(scan_ids), ptr(known), ptr(prob), int(work.shape[0]), ptr(work), ptr(out_offs),
+    entry, acc = ("geot_scan_predict", ()) if votes is None else ("geot_scan_vote", (ptr(votes.acc), mode))
+    call(entry, dev, b, int(num_classes), n, len(scans), int(scans.points.shape[0]), ptr(scans.points), ptr(scans.labels),
+         ptr(scans.offsets), ptr(scan_ids), ptr(known), ptr(prob), int(work.shape[0]), ptr(work), ptr(out_offs), *acc,
          ptr(pred), ptr(counts), ptr(ws), nbytes)
-    if not want_pred:
-        return None
-    return [p.view(1, -1) for p in torch.split(pred, sizes)]
+    return [p.view(1, -1) for p in torch.split(pred, sizes)] if want_pred else None
 
 
 @torch.no_grad()
@@ -220,22 +247,8 @@ def predict_scans(logits, batch, refine=0, parts=None):
     n = 10, an int: n) and parts: the labels then go through refine_scans."""
     n_refine = _refine_n(refine, "predict_scans")
     need(torch.is_tensor(logits) and logits.dim() == 3, "predict_scans: logits must be a (B, C, N) tensor")
-    preds = _scan_predict(logits, batch, logits.shape[1], want_pred=True)
+    preds = _scan_launch(logits, batch, logits.shape[1], "predict_scans", want_pred=True)
     return refine_scans(preds, batch, n_refine, parts, num_classes=logits.shape[1]) if n_refine else preds
-
-
-REFINE_MAX_N = 63                   # include/geot_hip.h geot_scan_refine: n + 1 neighbours in one wave's list
-
-
-def _refine_n(refine, what):
-    """The `refine` keyword: 0 / False / None -> 0 (off), True -> 10 (the reference's default n), an int -> n."""
-    if refine is None or refine is False:
-        return 0
-    if refine is True:
-        return 10
-    need(isinstance(refine, (int, np.integer)), "%s: refine must be a bool or an int, got %r" % (what, refine))
-    need(0 <= int(refine) <= REFINE_MAX_N, "%s: refine n must be in 1..%d (0: off), got %d" % (what, REFINE_MAX_N, int(refine)))
-    return int(refine)
 
 
 def _allowed_masks(parts, jaws, c, what):
@@ -250,8 +263,9 @@ def _allowed_masks(parts, jaws, c, what):
 
 
 def _scan_refine(pred, n, c, points, offsets, scan_ids, n_scans, out_offs, allowed, b, want_stats):
-    """One geot_scan_refine call on the flat int64 label buffer `pred`."""
+    """One geot_scan_refine call on the flat int64 label buffer `pred`; allowed: _allowed_masks' host array, or None."""
     dev = pred.device
+    allowed = _to_device(allowed.view(np.int32), dev) if allowed is not None else None
     nbytes = int(_lib.load().geot_scan_refine_ws_bytes(b, int(pred.numel()), n))
     need(nbytes >= 0, "geot_scan_refine: no workspace for b = %d, n = %d, %d labels" % (b, n, pred.numel()))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -272,9 +286,7 @@ def refine_scans(preds, batch, n=10, parts=None, stats=False, num_classes=None):
     labels as they came in.  parts: None (every class allowed) or, per jaw class (0 mandible, 1 maxillary, from
     batch["mandible"]), the allowed labels -- the reference's cls2parts.  num_classes: default parts[-1][-1] + 1 as in the
     reference, 32 without parts.  One geot_scan_refine call, no host synchronisation."""
-    need(isinstance(n, (int, np.integer)) and not isinstance(n, bool) and 1 <= int(n) <= REFINE_MAX_N,
-         "refine_scans: n must be an int in 1..%d, got %r" % (REFINE_MAX_N, n))
-    n = int(n)
+    n = _refine_n(n, "refine_scans", keyword=False)
     need(isinstance(batch, dict) and all(k in batch for k in ("scan_ids", "scans", "sizes")),
          "refine_scans: batch must come from ValBatcher.batch (scan_ids, scans, sizes)")
     scans, sizes = batch["scans"], [int(m) for m in batch["sizes"]]
@@ -285,11 +297,9 @@ def refine_scans(preds, batch, n=10, parts=None, stats=False, num_classes=None):
         need(torch.is_tensor(p) and p.dtype == torch.int64, "refine_scans: the predictions must be int64 tensors")
         need(p.numel() == m, "refine_scans: %d predictions for a scan of %d vertices" % (p.numel(), m))
         need(m >= n + 1, "refine_scans: a scan of %d vertices has no %d nearest vertices (n + 1)" % (m, n + 1))
-    if parts is not None:
-        c = int(parts[-1][-1]) + 1 if num_classes is None else int(num_classes)
-    else:
-        c = 32 if num_classes is None else int(num_classes)
-    need(1 <= c <= 32, "refine_scans: 1..32 classes (include/geot_hip.h GEOT_NTM_MAX_C), got %d" % c)
+    if num_classes is None:
+        num_classes = 32 if parts is None else int(parts[-1][-1]) + 1
+    c = _need_classes(num_classes, "refine_scans")
     allowed = None
     if parts is not None:
         need("mandible" in batch and len(batch["mandible"]) == b, "refine_scans: parts needs the batch's jaw flags (mandible)")
@@ -310,9 +320,8 @@ def refine_scans(preds, batch, n=10, parts=None, stats=False, num_classes=None):
     else:
         flat = torch.cat([p.reshape(-1) for p in preds])
         out = [f.view(p.shape) for f, p in zip(torch.split(flat, sizes), preds)]
-    allowed_dev = _to_device(allowed.view(np.int32), dev) if allowed is not None else None
     st = _scan_refine(flat, n, c, scans.points, scans.offsets, batch["scan_ids"].contiguous(), len(scans), _out_offsets(sizes, dev),
-                      allowed_dev, b, stats)
+                      allowed, b, stats)
     return (out, st) if stats else out
 
 
@@ -322,17 +331,14 @@ def part_seg_refinement(pred, pos, cls, cls2parts, n=10):
     classes (rows of cls2parts), cls2parts per shape class the allowed labels; the class count is cls2parts[-1][-1] + 1.
     pred is refined in place and returned.  The reference's rule for the CUDA tensors it is written for: the labels are
     snapshotted before anything changes.  The same geot_scan_refine call as refine_scans, every row a scan of N vertices."""
-    need(isinstance(n, (int, np.integer)) and not isinstance(n, bool) and 1 <= int(n) <= REFINE_MAX_N,
-         "part_seg_refinement: n must be an int in 1..%d, got %r" % (REFINE_MAX_N, n))
-    n = int(n)
+    n = _refine_n(n, "part_seg_refinement", keyword=False)
     need(torch.is_tensor(pred) and torch.is_tensor(pos), "part_seg_refinement: pred and pos must be tensors")
     need(pred.dtype == torch.int64 and pred.dim() == 2, "part_seg_refinement: pred must be (B, N) int64")
     bsz, npts = pred.shape
     need(pos.dtype == torch.float32 and tuple(pos.shape) == (bsz, npts, 3), "part_seg_refinement: pos must be (B, N, 3) fp32")
     need(npts >= n + 1, "part_seg_refinement: %d points have no %d nearest points (n + 1)" % (npts, n + 1))
     need(1 <= bsz <= SCAN_MAX_SLOTS, "part_seg_refinement: 1 .. %d shapes" % SCAN_MAX_SLOTS)
-    c = int(cls2parts[-1][-1]) + 1
-    need(1 <= c <= 32, "part_seg_refinement: 1..32 classes (include/geot_hip.h GEOT_NTM_MAX_C), got %d" % c)
+    c = _need_classes(int(cls2parts[-1][-1]) + 1, "part_seg_refinement")
     jaws = [int(j) for j in (cls.detach().cpu().reshape(-1).tolist() if torch.is_tensor(cls) else np.asarray(cls).reshape(-1))]
     need(len(jaws) == bsz, "part_seg_refinement: %d shape classes for %d shapes" % (len(jaws), bsz))
     allowed = _allowed_masks(cls2parts, jaws, c, "part_seg_refinement")
@@ -342,8 +348,7 @@ def part_seg_refinement(pred, pos, cls, cls2parts, n=10):
     dev = pred.device
     offsets = _to_device(np.arange(bsz + 1, dtype=np.int64) * npts, dev)
     ids = _to_device(np.arange(bsz, dtype=np.int64), dev)
-    _scan_refine(pred.view(-1), n, c, pos.contiguous().view(-1, 3), offsets, ids, bsz, offsets[:bsz], _to_device(allowed.view(np.int32), dev),
-                 bsz, False)
+    _scan_refine(pred.view(-1), n, c, pos.contiguous().view(-1, 3), offsets, ids, bsz, offsets[:bsz], allowed, bsz, False)
     return pred
 
 
@@ -360,8 +365,7 @@ class SegMetrics:
     doubles as scans arrive) and each scan's jaw, kept on the host.  Neither update synchronises with the host."""
 
     def __init__(self, num_classes, device):
-        c = int(num_classes)
-        need(1 <= c <= 32, "SegMetrics: 1..32 classes (include/geot_hip.h GEOT_NTM_MAX_C), got %d" % c)
+        c = _need_classes(num_classes, "SegMetrics")
         dev = torch.device(device)
         need(dev.type == "cuda", "SegMetrics: the counts live on a GPU, got device %s" % dev)
         if dev.index is None:
@@ -443,16 +447,11 @@ class SegMetrics:
         at = 0
         for index in range(b):
             # get_pred_whole's three_nn inputs, statement for statement; its output goes into this scan's slice
-            point = points[index].unsqueeze(0).contiguous()
-            s = torch.as_tensor(scale[index]).to(dev).unsqueeze(0).contiguous()
-            c = torch.as_tensor(center[index]).to(dev).unsqueeze(0).contiguous()
-            point_whole = torch.as_tensor(points_whole[index]).to(dev).unsqueeze(0).contiguous()
-            point = (point * s + c).contiguous()
-            unknown, known = point_whole.float().contiguous(), point.float().contiguous()
+            unknown, known = _three_nn_inputs(points, points_whole, center, scale, index, dev)
             m = unknown.shape[1]
             need(unknown.dim() == 3 and unknown.shape[2] == 3 and m == sizes[index],
                  "SegMetrics.update_from_logits: scan %d has %d labels for %s vertices" % (index, sizes[index],
-                                                                                           tuple(point_whole.shape[1:])))
+                                                                                           tuple(unknown.shape[1:])))
             if m:
                 wp, wb, _keep = knn_workspace(dev, 1, m, n, 3)
                 call("geot_three_nn_ws", dev, 1, m, n, ptr(unknown), ptr(known), ptr(dist2) + 12 * at, ptr(idx) + 12 * at,
@@ -465,17 +464,30 @@ class SegMetrics:
                  ptr(rows))
         self.mandible += flags
 
+    def _scan_rows(self, batch, what):
+        """The jaw flags of a ValBatcher / VoteBatcher batch and the count rows of its scans."""
+        need(isinstance(batch, dict) and "mandible" in batch, "SegMetrics.%s: batch must come from ValBatcher.batch" % what)
+        need(batch["scans"].device == self.device, "SegMetrics.%s: the scans on %s, the counts on %s" %
+             (what, batch["scans"].device, self.device))
+        flags = [bool(m) for m in batch["mandible"]]
+        need(len(flags) == len(batch["sizes"]), "SegMetrics.%s: one jaw flag per scan" % what)
+        return flags, self._rows(len(flags))
+
     def update_from_scans(self, logits, batch):
         """Count one ValBatcher batch from the model's logits (B, C, N): update_from_logits' counts, from the scans where
         they lie -- one geot_scan_predict call whatever B and the scans' sizes, the jaws from the batch's host flags, no
         host synchronisation."""
-        need(isinstance(batch, dict) and "mandible" in batch, "SegMetrics.update_from_scans: batch must come from ValBatcher.batch")
-        need(batch["scans"].device == self.device, "SegMetrics.update_from_scans: the scans on %s, the counts on %s" %
-             (batch["scans"].device, self.device))
-        flags = [bool(m) for m in batch["mandible"]]
-        need(len(flags) == len(batch["sizes"]), "SegMetrics.update_from_scans: one jaw flag per scan")
-        rows = self._rows(len(flags))
-        _scan_predict(logits, batch, self.c, counts=rows, what="SegMetrics.update_from_scans")
+        flags, rows = self._scan_rows(batch, "update_from_scans")
+        _scan_launch(logits, batch, self.c, "SegMetrics.update_from_scans", counts=rows)
+        self.mandible += flags
+
+    def update_from_votes(self, votes, logits, batch):
+        """Count one batch of scans from its votes: `votes` (a ScanVotes of C classes) holds the earlier passes, the model's
+        logits on `batch` are the last one -- votes.add(logits, batch, last=True) with this epoch's next rows as counts, one
+        geot_scan_vote call; the jaws from the batch's host flags, no host synchronisation."""
+        need(votes.c == self.c, "SegMetrics.update_from_votes: the votes have %d classes, the counts %d" % (votes.c, self.c))
+        flags, rows = self._scan_rows(batch, "update_from_votes")
+        votes.add(logits, batch, last=True, counts=rows)
         self.mandible += flags
 
     def read(self):
@@ -532,6 +544,47 @@ def _report(out, cfg):
     return out["whole_macc"], out["whole_miou"], out["whole_mdsc"]
 
 
+def _passes(model, batcher, groups, repeats, draws):
+    """The look-ahead loop of every whole-scan pass: each list of scan numbers in `groups` runs through the model `repeats`
+    times, each time on a freshly drawn batch -> (batch, logits, first pass of its group, last pass of its group) per pass.
+    The next pass's batch is queued BEFORE the current forward pass -- beside it when the batcher has a side stream -- and
+    the host draws (np.random.choice) happen inside batch(): seeded runs are equal only while this order holds.  draws goes to
+    every batch() call as it is."""
+    passes = [(ids, k == 0, k + 1 == repeats) for ids in groups for k in range(repeats)]
+    data = batcher.batch(passes[0][0], draws=draws) if passes else None
+    for k, (_, first, last) in enumerate(passes):
+        batcher.join(data)
+        ahead = batcher.batch(passes[k + 1][0], draws=draws) if k + 1 < len(passes) else None
+        logits, _, _ = model(data)
+        yield data, logits, first, last
+        data = ahead
+
+
+def _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_refine, parts, what):
+    """The body of validate_scans (num_votes = 0: one pass per batch, scored by geot_scan_predict) and validate_scans_voted
+    (num_votes passes per batch, summed by geot_scan_vote and scored on the last): batches of batch_size scans in `indices`'
+    order through _passes, counted into one SegMetrics; with n_refine the labels are taken, refined and counted instead."""
+    need(int(batch_size) >= 1, "%s: batch_size >= 1" % what)
+    order = list(range(len(batcher))) if indices is None else [int(i) for i in indices]
+    groups = [order[at:at + int(batch_size)] for at in range(0, len(order), int(batch_size))]
+    metrics = SegMetrics(c, batcher.device)
+    votes = None
+    for data, logits, first, last in _passes(model, batcher, groups, max(num_votes, 1), draws):
+        if num_votes and first:
+            votes = ScanVotes(data, c)
+        if not last:
+            votes.add(logits, data)
+        elif n_refine:
+            preds = (votes.add(logits, data, last=True, want_pred=True) if num_votes else
+                     _scan_launch(logits, data, c, what, want_pred=True))
+            _count_refined(metrics, preds, data, n_refine, parts)
+        elif num_votes:
+            metrics.update_from_votes(votes, logits, data)
+        else:
+            metrics.update_from_scans(logits, data)
+    return _report(metrics.read(), cfg)
+
+
 @torch.no_grad()
 def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, num_votes=0, data_transform=None, refine=0,
                    parts=None):
@@ -543,7 +596,7 @@ def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, n
     reference.  refine (0: off -- cfg.refine is not read; True: n = 10; an int: n) and parts: the per-vertex labels are taken,
     refined (refine_scans) and counted against the scans' labels with geot_seg_confusion."""
     from .openpoints.dataset.val_batch import ValBatcher
-    n_refine, cls2parts = _refine_n(refine, "validate_scans"), parts        # (`parts` below: the batches' scan numbers)
+    n_refine = _refine_n(refine, "validate_scans")
     model.eval()
     c = _cfg(cfg, "num_classes", 17)
     if isinstance(scans, ValBatcher):
@@ -552,22 +605,7 @@ def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, n
     else:
         need(_cfg(cfg, "num_points") is not None, "validate_scans: cfg.num_points (the sample size) is missing")
         batcher = ValBatcher(scans, _cfg(cfg, "num_points"), c, stream=stream)
-    need(int(batch_size) >= 1, "validate_scans: batch_size >= 1")
-    order = list(range(len(batcher))) if indices is None else [int(i) for i in indices]
-    parts = [order[at:at + int(batch_size)] for at in range(0, len(order), int(batch_size))]
-    metrics = SegMetrics(c, batcher.device)
-    data = batcher.batch(parts[0]) if parts else None
-    for k in range(len(parts)):
-        batcher.join(data)
-        ahead = batcher.batch(parts[k + 1]) if k + 1 < len(parts) else None     # beside the forward pass when on a side stream
-        logits, _, _ = model(data)
-        if n_refine:
-            preds = _scan_predict(logits, data, c, want_pred=True, what="validate_scans")
-            _count_refined(metrics, preds, data, n_refine, cls2parts)
-        else:
-            metrics.update_from_scans(logits, data)
-        data = ahead
-    return _report(metrics.read(), cfg)
+    return _validate(model, batcher, cfg, c, batch_size, indices, 0, None, n_refine, parts, "validate_scans")
 
 
 def _scan_labels(batch):
@@ -597,8 +635,7 @@ class ScanVotes:
     def __init__(self, batch, num_classes):
         need(isinstance(batch, dict) and all(k in batch for k in ("scans", "sizes", "scan_ids")),
              "ScanVotes: batch must come from VoteBatcher.batch or ValBatcher.batch")
-        c = int(num_classes)
-        need(1 <= c <= 32, "ScanVotes: 1..32 classes (include/geot_hip.h GEOT_NTM_MAX_C), got %d" % c)
+        c = _need_classes(num_classes, "ScanVotes")
         self.scans, self.sizes, self.c = batch["scans"], [int(m) for m in batch["sizes"]], c
         need(1 <= len(self.sizes) <= SCAN_MAX_SLOTS, "ScanVotes: 1 .. %d scans" % SCAN_MAX_SLOTS)
         dev = self.device = self.scans.device
@@ -615,23 +652,11 @@ class ScanVotes:
         allowed."""
         need(not self.finished, "ScanVotes.add: the last vote has been added")
         need(last or (counts is None and not want_pred), "ScanVotes.add: counts and predictions come with the last vote (last=True)")
-        pos_key = "pos_search" if isinstance(batch, dict) and "pos_search" in batch else "pos"
-        b, n, scan_ids, prob, known = _scan_inputs(logits, batch, self.c, "ScanVotes.add", pos_key)
-        need(batch["scans"] is self.scans and [int(m) for m in batch["sizes"]] == self.sizes,
-             "ScanVotes.add: every vote's batch holds the same scans in the same slots")
-        dev, scans = self.device, self.scans
-        pred = torch.empty(sum(self.sizes), dtype=torch.int64, device=dev) if want_pred else None
         mode = (_lib.VOTE_SET if self.votes == 0 else 0) | (_lib.VOTE_FINISH if last else 0)
-        nbytes = int(_lib.load().geot_scan_predict_ws_bytes(b, n))
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        call("geot_scan_vote", dev, b, self.c, n, len(scans), int(scans.points.shape[0]), ptr(scans.points), ptr(scans.labels),
-             ptr(scans.offsets), ptr(scan_ids), ptr(known), ptr(prob), int(self.work.shape[0]), ptr(self.work),
-             ptr(self.out_offsets), ptr(self.acc), mode, ptr(pred), ptr(counts), ptr(ws), nbytes)
+        preds = _scan_launch(logits, batch, self.c, "ScanVotes.add", counts, want_pred, votes=self, mode=mode)
         self.votes += 1
         self.finished = bool(last)
-        if not want_pred:
-            return None
-        return [p.view(1, -1) for p in torch.split(pred, self.sizes)]
+        return preds
 
     def probabilities(self):
         """Per scan the (M_i, C) mean of the votes so far: the accumulator's rows times 1 / votes."""
@@ -648,20 +673,12 @@ def vote_scans(model, batcher, idx, num_votes, draws=None, refine=0, parts=None)
     need(int(num_votes) >= 1, "vote_scans: num_votes >= 1")
     n_refine = _refine_n(refine, "vote_scans")
     model.eval()
-    votes, preds = None, None
-    data = batcher.batch(idx, draws=draws)
-    for k in range(int(num_votes)):
-        last = k + 1 == int(num_votes)
-        batcher.join(data)
-        ahead = None if last else batcher.batch(idx, draws=draws)
-        logits, _, _ = model(data)
-        if votes is None:
+    votes = preds = None
+    for data, logits, first, last in _passes(model, batcher, [idx], int(num_votes), draws):
+        if first:
             votes = ScanVotes(data, logits.shape[1])
         preds = votes.add(logits, data, last=last, want_pred=last)
-        if last and n_refine:
-            preds = refine_scans(preds, data, n_refine, parts, num_classes=votes.c)
-        data = ahead
-    return preds
+    return refine_scans(preds, data, n_refine, parts, num_classes=votes.c) if n_refine else preds
 
 
 @torch.no_grad()
@@ -675,7 +692,7 @@ def validate_scans_voted(model, scans, cfg, num_votes=None, vote=None, batch_siz
     the current forward pass.  Same log lines, return value and dtypes as validate().  refine, parts: as for validate_scans,
     on the voted labels."""
     from .openpoints.dataset.vote_batch import DEFAULT_VOTE, TOOTH_VIEW_KWARGS, VoteBatcher
-    n_refine, cls2parts = _refine_n(refine, "validate_scans_voted"), parts      # (`parts` below: the batches' scan numbers)
+    n_refine = _refine_n(refine, "validate_scans_voted")
     num_votes = _cfg(cfg, "num_votes", 0) if num_votes is None else num_votes
     if num_votes is None or int(num_votes) < 1:
         raise ValueError("validate_scans_voted: num_votes must be >= 1, got %r (validate_scans is the un-voted call)" % (num_votes,))
@@ -694,25 +711,4 @@ def validate_scans_voted(model, scans, cfg, num_votes=None, vote=None, batch_siz
         kwargs = _cfg(transforms, "kwargs") if transforms is not None else None
         batcher = VoteBatcher(scans, _cfg(cfg, "num_points"), c, vote=DEFAULT_VOTE if vote is None else vote,
                               kwargs=TOOTH_VIEW_KWARGS if kwargs is None else kwargs, stream=stream, draws=draws)
-    need(int(batch_size) >= 1, "validate_scans_voted: batch_size >= 1")
-    order = list(range(len(batcher))) if indices is None else [int(i) for i in indices]
-    parts = [order[at:at + int(batch_size)] for at in range(0, len(order), int(batch_size))]
-    passes = [part for part in parts for _ in range(num_votes)]            # every batch of scans num_votes times
-    metrics = SegMetrics(c, batcher.device)
-    data = batcher.batch(passes[0], draws=draws) if passes else None
-    votes = None
-    for k in range(len(passes)):
-        batcher.join(data)
-        ahead = batcher.batch(passes[k + 1], draws=draws) if k + 1 < len(passes) else None     # beside the forward pass
-        logits, _, _ = model(data)
-        last = (k + 1) % num_votes == 0
-        if k % num_votes == 0:
-            votes = ScanVotes(data, c)
-        if last and n_refine:
-            _count_refined(metrics, votes.add(logits, data, last=True, want_pred=True), data, n_refine, cls2parts)
-        else:
-            votes.add(logits, data, last=last, counts=metrics._rows(len(data["sizes"])) if last else None)
-            if last:
-                metrics.mandible += [bool(m) for m in data["mandible"]]
-        data = ahead
-    return _report(metrics.read(), cfg)
+    return _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_refine, parts, "validate_scans_voted")

@@ -205,3 +205,78 @@ def test_nothing_synchronises_and_every_vote_is_one_call():
         _common.trace = None
         torch.cuda.set_sync_debug_mode(0)
     assert names[1] == names[4] == ["geot_scan_vote", "geot_scan_vote"], names
+
+
+def _logged(cls, events, *args, **kwargs):
+    """A ValBatcher / VoteBatcher that writes its batch() and join() calls into `events`, then does what it always does."""
+    class Logged(cls):
+        def batch(self, idx, *a, **kw):
+            events.append(("batch", [int(i) for i in idx]))
+            out = super().batch(idx, *a, **kw)
+            out["_ids"] = [int(i) for i in idx]
+            return out
+
+        def join(self, data):
+            events.append(("join", data["_ids"]))
+            return super().join(data)
+    return Logged(*args, **kwargs)
+
+
+class _LoggedRecorder(_Recorder):
+    def __init__(self, model, events):
+        super().__init__(model)
+        self.events = events
+
+    def __call__(self, data):
+        self.events.append(("model", data["_ids"]))
+        return super().__call__(data)
+
+
+def test_the_look_ahead_order_of_every_public_pass_loop():
+    """join, queue the next batch, run the model: the same sequence from validate_scans, validate_scans_voted and vote_scans,
+    with and without refine; the voted triple equals a replay of the recorded passes through ScanVotes and
+    SegMetrics.update_from_votes."""
+    from geot_amd.openpoints.dataset import ValBatcher, VoteBatcher
+    from geot_amd.validation import ScanVotes, SegMetrics, validate_scans, validate_scans_voted, vote_scans
+    from test_scan_refine_gpu import PARTS
+    from test_val_passes_cpu import look_ahead_events
+    dset = _set([3000, 777, 1500], 880, cls=[0, 1, 1])
+    cfg = type("Cfg", (), {"num_classes": 17, "num_points": 1024, "epoch": 3, "epochs": 100})()
+    groups = [[0, 1], [2]]
+
+    def run(kind, fn):
+        events = []
+        batcher = _logged(ValBatcher if kind == "val" else VoteBatcher, events, dset, 1024)
+        rec = _LoggedRecorder(_SeededLogits(), events)
+        np.random.seed(21)
+        torch.manual_seed(21)
+        with quiet():
+            out = fn(rec, batcher)
+        return events, out, rec
+
+    for refine in ({}, {"refine": 10, "parts": PARTS}):
+        events, out, _ = run("val", lambda rec, b: validate_scans(rec, b, cfg, batch_size=2, **refine))
+        assert events == look_ahead_events(groups, 1), (refine, events)
+        assert all(np.isfinite(float(v)) for v in out)
+        events, out, rec = run("vote", lambda rec, b: validate_scans_voted(rec, b, cfg, num_votes=2, batch_size=2, **refine))
+        assert events == look_ahead_events(groups, 2), (refine, events)
+        assert events[:6] == [("batch", [0, 1]), ("join", [0, 1]), ("batch", [0, 1]), ("model", [0, 1]), ("join", [0, 1]), ("batch", [2])]
+        assert all(np.isfinite(float(v)) for v in out)
+        if not refine:
+            voted, seen = out, rec.seen
+    events, preds, _ = run("vote", lambda rec, b: vote_scans(rec, b, [1, 2], 3))
+    assert events == look_ahead_events([[1, 2]], 3), events
+    assert [tuple(p.shape) for p in preds] == [(1, 777), (1, 1500)]
+    # the voted scores, replayed from the passes the model saw
+    metrics = SegMetrics(17, DEV)
+    assert len(seen) == 4
+    for k in (0, 2):
+        votes = ScanVotes(seen[k][0], 17)
+        votes.add(seen[k][1], seen[k][0])
+        metrics.update_from_votes(votes, seen[k + 1][1], seen[k + 1][0])
+    assert metrics.scans == 3 and metrics.mandible == [True, False, False]
+    with quiet():
+        want = metrics.read()
+    for g, key in zip(voted, ("whole_macc", "whole_miou", "whole_mdsc")):
+        print("validate_scans_voted %s: %r (replayed %r)" % (key, g, want[key]))
+        assert np.asarray(g).dtype == np.asarray(want[key]).dtype and ref.same_value(g, want[key]), (key, g, want[key])
