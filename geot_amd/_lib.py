@@ -148,6 +148,9 @@ PROTOTYPES["geot_scan_predict"] = ([_c_int] * 4 + [ctypes.c_longlong] + [_P] * 6
 PROTOTYPES["geot_scan_vote"] = ([_c_int] * 4 + [ctypes.c_longlong] + [_P] * 6 + [_c_int] + [_P] * 3 + [_c_int] + [_P] * 3 +
                                 [ctypes.c_longlong, _c_void_p])
 PROTOTYPES["geot_scan_refine"] = [_c_int] * 4 + [ctypes.c_longlong] + [_P] * 8 + [ctypes.c_longlong, _c_void_p]
+PROTOTYPES["geot_pseudo_refine"] = [_c_int] * 6 + [_c_float] * 2 + [_P] * 5 + [_c_void_p]
+PSEUDO_MODES = {"max": 0, "margin": 1, "margin_v1": 2}    # GEOT_PSEUDO_MAX / _MARGIN / _MARGIN_V1
+PSEUDO_REFINE_MAX_N = 32                                  # GEOT_PSEUDO_REFINE_MAX_N
 VOTE_SET, VOTE_FINISH = 1, 2    # GEOT_VOTE_SET / GEOT_VOTE_FINISH: geot_scan_vote's mode bits
 PROTOTYPES["geot_view_program"] = [_c_int] * 6 + [_P] * 10 + [_c_void_p]
 PROTOTYPES["geot_view_draw"] = [_c_int] * 4 + [_P] * 4 + [ctypes.c_ulonglong] * 2 + [_P, _P, _P, _c_void_p]
@@ -199,7 +202,7 @@ VIEW_MAX_OPS = 16        # GEOT_VIEW_MAX_OPS: ops of one geot_view_program job
 VIEW_PROGRAM_JOB_WORDS = 8 + 14 * VIEW_MAX_OPS     # GEOT_VIEW_PROGRAM_JOB_WORDS
 VIEW_DRAW_MAX_STEPS = 24                           # GEOT_VIEW_DRAW_MAX_STEPS: drawn quantities of one geot_view_draw job
 VIEW_DRAW_PLAN_WORDS = 8 + 12 * VIEW_DRAW_MAX_STEPS     # GEOT_VIEW_DRAW_PLAN_WORDS
-ABI_VERSION = 22    # include/geot_hip.h GEOT_ABI_VERSION this binding was written against
+ABI_VERSION = 23    # include/geot_hip.h GEOT_ABI_VERSION this binding was written against
 KNN_KMAX_HEAP = 1024      # GEOT_KNN_KMAX_HEAP: largest nsample of the heap-ordered kNN (knnquery_cuda, pointops.knn)
 KNN_KMAX_SORTED = 4096    # GEOT_KNN_KMAX_SORTED: largest k of the sorted kNN (knn_cuda.KNN, knn_point in 3-D)
 

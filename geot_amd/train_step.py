@@ -30,9 +30,14 @@ NTM_CFG = dict(threshold=0.0, unsupervised_loss_weight=1.0, ema_t_decay=0.999, l
                threed_loss_weight=0.1, threed_k=32, threed_sigma=1.0, filter_outlier=False, lr=1e-3,
                weight_decay=1e-4, grad_norm_clip=None, batch_size_l=2, batch_size_u=2, num_classes=17, switch_ep=50,
                criterion="Poly1FocalLoss", criterion_u="Poly1FocalLoss_U_corr", use_3d_loss=True, use_feat_loss=False,
-               feat_loss_weight=10.0, feat_k=16, feat_sigma=1.0, use_identity_loss=False, identity_loss_weight=1.0)
+               feat_loss_weight=10.0, feat_k=16, feat_sigma=1.0, use_identity_loss=False, identity_loss_weight=1.0,
+               pseudo_refine=False, pseudo_refine_size=4, pseudo_refine_neighbors=1)
 # cfgs/tooth_semi/transformer_finetune_fixmatch_ntm.yaml:45-96 (+ default.yaml); criterion / criterion_u are its
-# criterion_args.NAME / criterion_u_args.NAME (a {"NAME": ..., **constructor arguments} dict is taken too)
+# criterion_args.NAME / criterion_u_args.NAME (a {"NAME": ..., **constructor arguments} dict is taken too).
+# pseudo_refine (yaml:75, which the reference never reads): False, True (= "max") or one of utils/pseudo_mask.py's three
+# refinements, "max" / "margin" / "margin_v1"; pseudo_refine_size / pseudo_refine_neighbors are their neigborhood_size / n_neigbors
+PSEUDO_REFINE_MODES = ("max", "margin", "margin_v1")
+PSEUDO_REFINE_MAX_SIZE = 32      # include/geot_hip.h GEOT_PSEUDO_REFINE_MAX_N
 
 
 def _criterion(spec, allowed, what):
@@ -54,8 +59,39 @@ def check_cfg(cfg):
     if cfg["use_feat_loss"] and not (isinstance(cfg["feat_k"], int) and cfg["feat_k"] >= 1 and cfg["feat_sigma"] > 0):
         raise ValueError("cfg use_feat_loss: feat_k must be a positive int and feat_sigma positive, got %r / %r"
                          % (cfg["feat_k"], cfg["feat_sigma"]))
-    return (_criterion(cfg["criterion"], SUPERVISED_CRITERIA, "criterion")
-            + _criterion(cfg["criterion_u"], UNSUPERVISED_CRITERIA, "criterion_u"))
+    out = (_criterion(cfg["criterion"], SUPERVISED_CRITERIA, "criterion")
+           + _criterion(cfg["criterion_u"], UNSUPERVISED_CRITERIA, "criterion_u"))
+    mode = pseudo_refine_mode(cfg)
+    size, k = cfg["pseudo_refine_size"], cfg["pseudo_refine_neighbors"]
+    for key, v in (("pseudo_refine_size", size), ("pseudo_refine_neighbors", k)):
+        if not isinstance(v, int) or isinstance(v, bool):
+            raise TypeError("cfg %s must be an int, got %r" % (key, v))
+    if not 1 <= k <= size <= PSEUDO_REFINE_MAX_SIZE:
+        raise ValueError("cfg pseudo_refine: 1 <= pseudo_refine_neighbors <= pseudo_refine_size <= %d, got %r / %r"
+                         % (PSEUDO_REFINE_MAX_SIZE, k, size))
+    if mode is not None:
+        if out[2] == "Weight_CELoss_U":      # train.py:586-587: its call has no mask
+            raise ValueError("cfg pseudo_refine=%r: criterion_u='Weight_CELoss_U' takes no mask (train.py:586-587)"
+                             % (cfg["pseudo_refine"],))
+        c = cfg["num_classes"]
+        if (mode != "max" and c < 2) or (mode == "margin_v1" and c > 17):
+            raise ValueError("cfg pseudo_refine=%r: the margin needs 2 classes, margin_v1's E_joint has 17; num_classes is %r"
+                             % (mode, c))
+    return out
+
+
+def pseudo_refine_mode(cfg):
+    """cfg pseudo_refine -> None (off) or "max" / "margin" / "margin_v1" (True = "max")."""
+    v = cfg["pseudo_refine"]
+    if v is False:
+        return None
+    if v is True:
+        return "max"
+    if not isinstance(v, str):
+        raise TypeError("cfg pseudo_refine must be False, True or one of %s, got %r" % (", ".join(PSEUDO_REFINE_MODES), v))
+    if v not in PSEUDO_REFINE_MODES:
+        raise ValueError("cfg pseudo_refine must be False, True or one of %s, got %r" % (", ".join(PSEUDO_REFINE_MODES), v))
+    return v
 
 
 def unused_parameters(cfg=None):
@@ -385,6 +421,10 @@ class FixMatchNTMStep:
         self.Identity_t = torch.eye(c, device=dev) if self.cfg["use_identity_loss"] else None              # train.py:430
         # the corrected strong logits have a reader only under these two (train.py:591-596)
         self.needs_correction = self.criterion_u_name not in _IGNORES_CORRECTION
+        self.refine_mode = pseudo_refine_mode(self.cfg)      # None: off -- nothing below runs
+        if self.refine_mode == "margin_v1" and dev.type == "cuda":
+            from .utils.pseudo_mask import _e_joint
+            _e_joint(dev, c)          # uploaded here: a first use under graph capture would be a memcpy node
         self.optimizer = make_optimizer(student, self.cfg["lr"], self.cfg["weight_decay"])
         self.T_optimizer = make_optimizer(t_predictor, self.cfg["lr"], self.cfg["weight_decay"])
         self.ema_t = torch.eye(c, device=dev)                                          # train.py:274
@@ -463,6 +503,11 @@ class FixMatchNTMStep:
             g = inner.weak_view_geometry(geom_s, data, data_u)
         return g if g is not None else self.model_t.prefetch_geometry(data_u, if_teacher=True, inline=inline)
 
+    def _refine_neighbours(self, data_u):
+        """The neighbour table cfg pseudo_refine reads: the weak view's nearest neighbours (batch-only work)."""
+        from .utils.pseudo_mask import neighbours
+        return neighbours(data_u["pos_w"].contiguous(), self.cfg["pseudo_refine_size"])
+
     def lookahead_work(self, data, data_u, self_labelling=None):
         """Everything of an iteration that depends on its batches and on FROZEN state alone, on the CURRENT stream: the
         student's and the teacher's geometry, the teacher's forward -> pseudo labels (the teacher is never updated:
@@ -470,7 +515,8 @@ class FixMatchNTMStep:
         order of the 3-D loss.  -> the `pre` dict student_iteration() takes.  graph_step.py replays this as a graph of its own
         on a second stream beside the PREVIOUS iteration's training graph; the eager iteration() below spreads the same work
         over side streams inside the iteration instead.  After switch_ep (self_labelling; default: the step's epoch) the
-        teacher does not run: the student's geometry and the 3-D loss's graph only, "pseudo" is None."""
+        teacher does not run: the student's geometry and the 3-D loss's graph only, "pseudo" is None.  With cfg pseudo_refine
+        the weak view's neighbour table is one more entry, "refine_nbr"."""
         if self_labelling is None:
             self_labelling = self.self_labelling
         _mode(self.model, True)
@@ -485,8 +531,12 @@ class FixMatchNTMStep:
                 raw = data_u["raw_pos"].contiguous()
                 nbr = self.threed_loss.neighbours(raw)
                 order = ntm_mod.spatial_order(raw)
+            refine_nbr = self._refine_neighbours(data_u) if self.refine_mode is not None else None
         pseudo = None if self_labelling else self._pseudo_labels(data_u, geom_t)
-        return {"geom_s": geom_s, "pseudo": pseudo, "knn": (nbr, order)}
+        pre = {"geom_s": geom_s, "pseudo": pseudo, "knn": (nbr, order)}
+        if refine_nbr is not None:
+            pre["refine_nbr"] = refine_nbr
+        return pre
 
     def iteration(self, data, data_u, geoms=(None, None), next_batches=None):
         """One iteration, eagerly, its batch-only work spread over side streams -> (dict of detached losses, (student,
@@ -495,16 +545,20 @@ class FixMatchNTMStep:
         self_labelling = self.self_labelling
         # the kNN graph of the 3-D loss needs raw_pos only: build it beside the teacher / student forwards
         dev = data["pos"].device
-        nbr = order = None
-        if dev.type == "cuda" and self.cfg["use_3d_loss"]:
+        nbr = order = refine_nbr = None
+        if dev.type == "cuda" and (self.cfg["use_3d_loss"] or self.refine_mode is not None):
             if self._side is None:
                 self._side = torch.cuda.Stream(device=dev)
             main = torch.cuda.current_stream(dev)
             self._side.wait_stream(main)
             with torch.cuda.stream(self._side):
-                raw = data_u["raw_pos"].contiguous()
-                nbr = self.threed_loss.neighbours(raw)
-                order = ntm_mod.spatial_order(raw)
+                if self.cfg["use_3d_loss"]:
+                    raw = data_u["raw_pos"].contiguous()
+                    nbr = self.threed_loss.neighbours(raw)
+                    order = ntm_mod.spatial_order(raw)
+                if self.refine_mode is not None:      # the weak view's neighbour table: batch-only work, like the graph above
+                    with torch.no_grad():
+                        refine_nbr = self._refine_neighbours(data_u)
         # 1. pseudo labels from the frozen teacher on the weak view (train.py:462-475).  The teacher's 2-cloud forward
         #    is short and mostly waits for its own 8192-sample FPS (4.7 ms on 2 CUs); nothing in the student's forward
         #    depends on it, so it is queued on a stream of its own and the student's kernels fill the gap (the eval-mode
@@ -546,11 +600,16 @@ class FixMatchNTMStep:
             if nbr is not None:
                 _join(dev, self._side, nbr, order)
             return nbr, order
-        losses = self.student_iteration(data, data_u, geom_s, pseudo, knn_graph, after_forward)
+
+        def refine_table():
+            _join(dev, self._side, refine_nbr)
+            return refine_nbr
+        losses = self.student_iteration(data, data_u, geom_s, pseudo, knn_graph, after_forward,
+                                        refine_nbr=refine_table if refine_nbr is not None else None)
         return losses, look.done() or (None, None)
 
     def student_iteration(self, data, data_u, geom_s, pseudo, knn_graph, after_forward=None, ema_in_place=False,
-                          defer_rest=False):
+                          defer_rest=False, refine_nbr=None):
         """Steps 2-5 of the iteration (train.py:478-602, 646-660): the student on labelled + strong + weak views, the class
         transition, the per-point matrices, the corrected logits, the losses, backward, both optimisers (and the meters).
         pseudo = (pred_u, logits_u_aug, label_u_aug) of the teacher, or None after switch_ep: then they are the soft-max of
@@ -561,7 +620,10 @@ class FixMatchNTMStep:
         update ema_t IN its buffer (a captured graph holds the buffer, not the attribute); defer_rest: stop where the
         backward reaches the student's transformer blocks (the segmentor cuts its autograd graph there) and return
         (losses, rest) -- rest() runs the backward of the blocks and the patch encoder, the EMA update and both optimisers
-        (graph_step's split capture)."""
+        (graph_step's split capture); refine_nbr: with cfg pseudo_refine, the weak view's neighbour table
+        (utils/pseudo_mask.py neighbours) or a callable that returns it; None: computed in line.  The refined mask is taken
+        from the pred_u the class transition reads and goes to the unsupervised criterion as its mask= (train.py:500,
+        588-596); scale_factor keeps the unrefined threshold mask (:599-602); the losses gain "kept", the mask's sum."""
         cfg = self.cfg
         seg = getattr(_unwrapped(self.model), "segmentor", None)
         can_cut = defer_rest and hasattr(seg, "take_cut")
@@ -617,15 +679,21 @@ class FixMatchNTMStep:
         else:
             sup_loss = self.criterion(pred_l, data["y"])
         conf, thresh = logits_u_aug.detach(), cfg["threshold"]
+        mask = None                                             # train.py:500
+        if self.refine_mode is not None:
+            from .utils.pseudo_mask import pseudo_refine_mask
+            table = refine_nbr() if callable(refine_nbr) else refine_nbr
+            mask = pseudo_refine_mask(pred_u, thresh, data_u["pos_w"], cfg["pseudo_refine_size"], cfg["pseudo_refine_neighbors"],
+                                      mode=self.refine_mode, nbr=table)
         if self.criterion_u_name == "Weight_CELoss_U":          # (the labelled batch's weights: train.py:585-587)
             unsup_loss = self.criterion_u(pred_u_strong, label_u_aug.detach(), data["class_weights"], conf, thresh=thresh)
         elif self.criterion_u_name == "Poly1FocalLoss_U":
-            unsup_loss = self.criterion_u(pred_u_strong, label_u_aug.detach(), conf, thresh=thresh)
+            unsup_loss = self.criterion_u(pred_u_strong, label_u_aug.detach(), conf, thresh=thresh, mask=mask)
         elif self.criterion_u_name == "Poly1FocalLoss_U_corr":
-            unsup_loss = self.criterion_u(pred_u_strong_corr, label_u_aug.detach(), conf, thresh=thresh)
+            unsup_loss = self.criterion_u(pred_u_strong_corr, label_u_aug.detach(), conf, thresh=thresh, mask=mask)
         else:                                                   # Poly1FocalLoss_U_T
             unsup_loss = self.criterion_u(pred_u_strong, label_u_aug.detach(), conf, self.ema_t, pred_u_strong_corr,
-                                          thresh=thresh)
+                                          thresh=thresh, mask=mask)
         thresh_mask = logits_u_aug.ge(cfg["threshold"])
         unsup_loss = unsup_loss * (cfg["unsupervised_loss_weight"] * (bu * n) / thresh_mask.sum())
         loss = sup_loss + unsup_loss                            # train.py:646-655, in its order
@@ -658,6 +726,8 @@ class FixMatchNTMStep:
             losses["feat"] = loss_feat.detach()
         if loss_ident is not None:
             losses["identity"] = loss_ident.detach()
+        if mask is not None:
+            losses["kept"] = mask.sum()
         if defer_rest:
             return losses, rest
         rest()

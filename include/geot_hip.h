@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 22
+#define GEOT_ABI_VERSION 23
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -986,6 +986,41 @@ int geot_sample_draw(int s, int m, int n_scans, long long total, const long long
 int geot_view_draw(int j, int m, int n_noise, int n_mask, const void *tmpl_host, const void *plans_host, const void *tmpl,
                    const void *plans, unsigned long long seed, unsigned long long draw_base, void *jobs, float *noise,
                    float *mask, void *stream);
+
+/* ---- FixMatch pseudo-label masks refined by the neighbours' probabilities (ABI 23) -------------------------------------------
+ * geot_pseudo_refine: utils/pseudo_mask.py's pseudo_label_refine (mode GEOT_PSEUDO_MAX, :38-53), pseudo_label_refine_margin
+ * (GEOT_PSEUDO_MARGIN, :55-90) and pseudo_label_refine_margin_v1 (GEOT_PSEUDO_MARGIN_V1, :92-170) behind their neighbour
+ * search, for the b * npts points of a batch in ONE launch: no workspace, no atomics, no host synchronisation, safe to
+ * capture.  prob (b, c, npts) fp32, the reference's channel-first layout; nbr (b, npts, n) int32 ids LOCAL to the point's
+ * cloud -- slots 1 .. n of pointops.knn(pos, pos, n + 1): slot 0 is dropped as pseudo_mask.py:19-21 drops it, whatever it
+ * holds; n the neighbourhood size, k the reference's n_neigbors.  Per point i and class cl, every statement ONE correctly
+ * rounded fp32 operation in the order written (the library is built with -ffp-contract=off):
+ *   1. of the n values prob[cl][nbr[i][j]] the k largest, in descending order (equal values are equal: their order cannot
+ *      matter); a NaN ranks above every number, as in torch.topk;
+ *   2. p = prob[cl][i], then once per taken value v, largest first:
+ *        GEOT_PSEUDO_MAX, GEOT_PSEUDO_MARGIN   p = (p + beta * v) - ((p * v) * beta)                      (:48, :82)
+ *        GEOT_PSEUDO_MARGIN_V1                 ub = (e_joint[cl] * p) / v;  p = (p + v) - (p * ub)         (:156-160)
+ *   3. over the classes: value = the largest p (GEOT_PSEUDO_MAX), or the largest minus the second largest (the margin
+ *      modes; two equal largest values give 0); NaN above every number again, as in torch.max / torch.topk;
+ *   4. keep = value >= th ? 1 : 0 (a NaN value: 0).
+ * beta: the reference's torch.exp(torch.tensor(-1/2)), computed by the caller in fp32.  e_joint: c fp32 entries on the
+ * device (E_joint, :93-98), read in GEOT_PSEUDO_MARGIN_V1 only.  keep (b, npts) uint8, what the fused criteria take as
+ * their hard mask; value (b, npts) fp32, optional (NULL: not written).  The result is the reference's bit for bit given the
+ * same neighbour ids.
+ * A neighbour id outside [0, npts) is never followed -- nothing is read through it: the point's keep is 0 and its value a
+ * quiet NaN, every other point is unaffected; there is no flag output, and the id is not clamped into a neighbour.
+ * GEOT_PSEUDO_REFINE_IMPL=point|split (read at every call) picks how a workgroup of 64 points shares the classes out -- a
+ * lane per point over all classes, or four waves that take every fourth class each and merge their top two through LDS --
+ * with the same bits.
+ * 1 <= b <= 65535, 1 <= c <= GEOT_NTM_MAX_C (c >= 2 for the margin modes), 1 <= k <= n <= GEOT_PSEUDO_REFINE_MAX_N,
+ * npts >= n + 1, a mode of the three, no NULL among prob, nbr and keep (nor e_joint in GEOT_PSEUDO_MARGIN_V1); anything else
+ * is hipErrorInvalidValue before the launch. */
+#define GEOT_PSEUDO_MAX 0
+#define GEOT_PSEUDO_MARGIN 1
+#define GEOT_PSEUDO_MARGIN_V1 2
+#define GEOT_PSEUDO_REFINE_MAX_N 32
+int geot_pseudo_refine(int b, int c, int npts, int n, int k, int mode, float th, float beta, const float *prob, const int *nbr,
+                       const float *e_joint, unsigned char *keep, float *value, void *stream);
 
 #ifdef __cplusplus
 }
