@@ -42,12 +42,13 @@ def out_path(name):
 
 
 def _generate():
-    header = os.path.join(ROOT, "include", "geot_hip.h")
-    gen = os.path.join(CSRC, "gen_dispatch.py")
-    if (not os.path.exists(GENERATED)
-            or os.path.getmtime(GENERATED) < max(os.path.getmtime(header), os.path.getmtime(gen))):
+    from . import _header
+    from .csrc_torch import gen_dispatch
+    sources = [_header.HEADER, _header.__file__, gen_dispatch.__file__]
+    if not os.path.exists(GENERATED) or os.path.getmtime(GENERATED) < max(os.path.getmtime(p) for p in sources):
         tmp = "%s.%d.tmp" % (GENERATED, os.getpid())
-        subprocess.check_call([sys.executable, gen, header, tmp], stdout=subprocess.DEVNULL)
+        with open(tmp, "w") as f:
+            f.write(gen_dispatch.emit(_header.parse()[0])[0])
         os.replace(tmp, GENERATED)
 
 

@@ -17,6 +17,7 @@ import warnings
 
 import torch
 
+from . import _lib
 from .ext._common import call, need, ptr
 
 # train_one_epoch's return order (train.py:710-715)
@@ -37,7 +38,7 @@ class FixMatchMeters:
         (C, C) transition buffer, reported by read() (it is updated in place, never rebound; FixMatchNTMStep fills it in
         when it is None)."""
         c = int(num_classes)
-        need(1 <= c <= 32, "FixMatchMeters: 1..32 classes (include/geot_hip.h GEOT_NTM_MAX_C), got %d" % c)
+        need(1 <= c <= _lib.NTM_MAX_C, "FixMatchMeters: 1..%d classes (include/geot_hip.h GEOT_NTM_MAX_C), got %d" % (_lib.NTM_MAX_C, c))
         self.c = c
         self.n_l, self.n_u = int(batch_size_l), int(batch_size_u)
         self.threshold = float(threshold)

@@ -25,8 +25,8 @@ from .ext._common import f32, i32, same_device, need, call, ptr, check_index
 from .knn_cuda import knn_sorted
 
 LABEL_PROJ = [0, 8, 7, 6, 5, 4, 3, 2, 1, 9, 10, 11, 12, 13, 14, 15, 16]  # train.py:48
-NTM_CLASSES = len(LABEL_PROJ)   # = GEOT_NTM_C in include/geot_hip.h: the class count the specialised kernels are built for
-NTM_MAX_CLASSES = 32            # any other count up to here runs the run-time-C kernels (csrc/ntm_generic.hip)
+NTM_CLASSES = len(LABEL_PROJ)   # = GEOT_NTM_C of csrc/ntm.hip: the class count the specialised kernels are built for
+NTM_MAX_CLASSES = _lib.NTM_MAX_C    # any other count up to here runs the run-time-C kernels (csrc/ntm_generic.hip)
 
 
 def _need_ntm_classes(c, what):

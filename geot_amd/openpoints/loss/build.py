@@ -12,13 +12,14 @@ import torch
 import torch.nn.functional as F
 from torch.autograd import Function
 
+from ... import _lib
+
 
 class _Poly1FocalFn(Function):
     """csrc/loss.hip: the loss from integer labels in two launches, its gradient in one."""
 
     @staticmethod
     def forward(ctx, logits, labels, keep, alpha, gamma, epsilon):
-        from ... import _lib
         from ...ext._common import call, ptr
         b, c, n = logits.shape
         ws = torch.empty(int(_lib.load().geot_poly1_focal_ws_doubles(b, c, n)), dtype=torch.float64, device=logits.device)
@@ -125,7 +126,6 @@ class _Poly1FocalBetaFn(Function):
 
     @staticmethod
     def forward(ctx, logits, labels, keep, conf, t, alpha, gamma, epsilon):
-        from ... import _lib
         from ...ext._common import call, ptr
         b, c, n = logits.shape
         ws = torch.empty(int(_lib.load().geot_poly1_focal_ws_doubles(b, c, n)), dtype=torch.float64, device=logits.device)
@@ -177,7 +177,7 @@ class Poly1FocalLoss_U_T(Poly1FocalLoss):
         return torch.sum(poly1 * keep) / (keep.sum() * poly1.shape[1] + 0.001)
 
 
-MAX_FUSED_CLASSES = 32      # include/geot_hip.h GEOT_NTM_MAX_C: the class cap of the library's per-point kernels
+MAX_FUSED_CLASSES = _lib.NTM_MAX_C      # include/geot_hip.h GEOT_NTM_MAX_C: the class cap of the library's per-point kernels
 
 
 def _plain_f32(t, shape, device):
@@ -194,7 +194,6 @@ class _WeightedCEFn(Function):
 
     @staticmethod
     def forward(ctx, logits, labels, class_weights, conf, thresh):
-        from ... import _lib
         from ...ext._common import call, ptr
         b, c, n = logits.shape
         bw = class_weights.shape[0]

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ntm as ntm_mod
+from . import _lib, ntm as ntm_mod
 from .openpoints.loss.build import SUPERVISED_CRITERIA, UNSUPERVISED_CRITERIA, criterion_class
 from .openpoints.models.segmentation import WholePartSeg
 
@@ -37,7 +37,7 @@ NTM_CFG = dict(threshold=0.0, unsupervised_loss_weight=1.0, ema_t_decay=0.999, l
 # pseudo_refine (yaml:75, which the reference never reads): False, True (= "max") or one of utils/pseudo_mask.py's three
 # refinements, "max" / "margin" / "margin_v1"; pseudo_refine_size / pseudo_refine_neighbors are their neigborhood_size / n_neigbors
 PSEUDO_REFINE_MODES = ("max", "margin", "margin_v1")
-PSEUDO_REFINE_MAX_SIZE = 32      # include/geot_hip.h GEOT_PSEUDO_REFINE_MAX_N
+PSEUDO_REFINE_MAX_SIZE = _lib.PSEUDO_REFINE_MAX_N      # include/geot_hip.h GEOT_PSEUDO_REFINE_MAX_N
 
 
 def _criterion(spec, allowed, what):

@@ -74,7 +74,7 @@ REFINE_MAX_N = 63                   # include/geot_hip.h geot_scan_refine: n + 1
 
 def _need_classes(num_classes, what):
     c = int(num_classes)
-    need(1 <= c <= 32, "%s: 1..32 classes (include/geot_hip.h GEOT_NTM_MAX_C), got %d" % (what, c))
+    need(1 <= c <= _lib.NTM_MAX_C, "%s: 1..%d classes (include/geot_hip.h GEOT_NTM_MAX_C), got %d" % (what, _lib.NTM_MAX_C, c))
     return c
 
 
