@@ -52,6 +52,9 @@ VOTE_SET, VOTE_FINISH = CONSTANTS["GEOT_VOTE_SET"], CONSTANTS["GEOT_VOTE_FINISH"
 PSEUDO_MODES = {"max": CONSTANTS["GEOT_PSEUDO_MAX"], "margin": CONSTANTS["GEOT_PSEUDO_MARGIN"],
                 "margin_v1": CONSTANTS["GEOT_PSEUDO_MARGIN_V1"]}
 PSEUDO_REFINE_MAX_N = CONSTANTS["GEOT_PSEUDO_REFINE_MAX_N"]
+CONTRAST_MAX_B = CONSTANTS["GEOT_CONTRAST_MAX_B"]     # the geot_contrast_* entry points: clouds, channels, sample_nums
+CONTRAST_MAX_D = CONSTANTS["GEOT_CONTRAST_MAX_D"]
+CONTRAST_MAX_S = CONSTANTS["GEOT_CONTRAST_MAX_S"]
 
 _lib = None
 

@@ -403,13 +403,13 @@ class GraphedFixMatchStep(_Graphed):
         def train():
             pre = self.pre
             return step.student_iteration(self.data, self.data_u, pre["geom_s"], pre["pseudo"], pre["knn"], ema_in_place=True,
-                                          refine_nbr=pre.get("refine_nbr"))
+                                          refine_nbr=pre.get("refine_nbr"), feat_t=pre.get("feat_t"))
         if self.split:
             def head():
                 pre = self.pre
                 self._losses, rest = step.student_iteration(self.data, self.data_u, pre["geom_s"], pre["pseudo"], pre["knn"],
                                                             ema_in_place=True, defer_rest=True,
-                                                            refine_nbr=pre.get("refine_nbr"))
+                                                            refine_nbr=pre.get("refine_nbr"), feat_t=pre.get("feat_t"))
                 return rest
 
             def rest_update(rest):

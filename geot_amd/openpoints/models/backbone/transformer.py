@@ -452,6 +452,8 @@ class PointTransformer_seg_T(nn.Module):
         self._side = {}
         self.at_blocks_backward = None    # one-shot callback of the training step (set before forward, see _forward)
         self.cut_at_blocks = False        # detach the decoder from the blocks for a two-phase backward (see _forward, take_cut)
+        self.keep_head_feature = False    # keep seg_head[1]'s output of every forward as self.head_feature (see _forward)
+        self.head_feature = None
         self._cut = None
 
         self.group_divider = Group(num_group=self.num_group, group_size=self.group_size)
@@ -690,9 +692,14 @@ class PointTransformer_seg_T(nn.Module):
         head = self.seg_head                     # conv -> BatchNorm1d -> Dropout -> conv; the BatchNorm as one fused op
         if self.dense != "reference" and isinstance(head[0], PointwiseConv1d):
             y = pointwise(head[0].weight.view(head[0].out_channels, -1), f_l0)       # the bias goes through bn_act
-            logit = head[3](head[2](bn_act(head[1], y, relu=False, pre_bias=head[0].bias)))
+            feat = bn_act(head[1], y, relu=False, pre_bias=head[0].bias)
         else:
-            logit = head[3](head[2](bn_act(head[1], head[0](f_l0), relu=False)))
+            feat = bn_act(head[1], head[0](f_l0), relu=False)
+        if self.keep_head_feature:
+            # the 128-wide per-point feature the contrastive loss reads (train_step cfg use_contrastive): the BatchNorm's
+            # output in front of the Dropout, (B, 128, N) channel-first, still attached to the graph
+            self.head_feature = feat
+        logit = head[3](head[2](feat))
         correction = self.T_linear(T) if T is not None else None
         return logit, correction, self.sigma, f_l0
 

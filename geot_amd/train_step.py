@@ -31,11 +31,15 @@ NTM_CFG = dict(threshold=0.0, unsupervised_loss_weight=1.0, ema_t_decay=0.999, l
                weight_decay=1e-4, grad_norm_clip=None, batch_size_l=2, batch_size_u=2, num_classes=17, switch_ep=50,
                criterion="Poly1FocalLoss", criterion_u="Poly1FocalLoss_U_corr", use_3d_loss=True, use_feat_loss=False,
                feat_loss_weight=10.0, feat_k=16, feat_sigma=1.0, use_identity_loss=False, identity_loss_weight=1.0,
-               pseudo_refine=False, pseudo_refine_size=4, pseudo_refine_neighbors=1)
+               pseudo_refine=False, pseudo_refine_size=4, pseudo_refine_neighbors=1,
+               use_contrastive=False, contrastive_loss_weight=1.0, cur_threshold=0.9, contrast_samples=1024, contrast_seed=0)
 # cfgs/tooth_semi/transformer_finetune_fixmatch_ntm.yaml:45-96 (+ default.yaml); criterion / criterion_u are its
 # criterion_args.NAME / criterion_u_args.NAME (a {"NAME": ..., **constructor arguments} dict is taken too).
 # pseudo_refine (yaml:75, which the reference never reads): False, True (= "max") or one of utils/pseudo_mask.py's three
 # refinements, "max" / "margin" / "margin_v1"; pseudo_refine_size / pseudo_refine_neighbors are their neigborhood_size / n_neigbors
+# use_contrastive / contrastive_loss_weight / cur_threshold (yaml:70, 71, 68, which the reference never reads either): the
+# teacher-student contrastive loss of utils/cluster_contrastloss.py on the 128-wide head feature, its weight in the total and
+# its selection threshold; contrast_samples is the class's sample_nums, contrast_seed the key of its device draws
 PSEUDO_REFINE_MODES = ("max", "margin", "margin_v1")
 PSEUDO_REFINE_MAX_SIZE = _lib.PSEUDO_REFINE_MAX_N      # include/geot_hip.h GEOT_PSEUDO_REFINE_MAX_N
 
@@ -77,7 +81,30 @@ def check_cfg(cfg):
         if (mode != "max" and c < 2) or (mode == "margin_v1" and c > 17):
             raise ValueError("cfg pseudo_refine=%r: the margin needs 2 classes, margin_v1's E_joint has 17; num_classes is %r"
                              % (mode, c))
+    check_contrast_cfg(cfg)
     return out
+
+
+def check_contrast_cfg(cfg):
+    """The contrastive loss's keys (a cfg without them is one with the switch off)."""
+    if "use_contrastive" not in cfg:
+        return
+    if not isinstance(cfg["use_contrastive"], bool):
+        raise TypeError("cfg use_contrastive must be a bool, got %r" % (cfg["use_contrastive"],))
+    full = dict(NTM_CFG, **cfg)
+    for key in ("contrast_samples", "contrast_seed"):
+        if not isinstance(full[key], int) or isinstance(full[key], bool):
+            raise TypeError("cfg %s must be an int, got %r" % (key, full[key]))
+    for key in ("contrastive_loss_weight", "cur_threshold"):
+        if isinstance(full[key], bool) or not isinstance(full[key], (int, float)):
+            raise TypeError("cfg %s must be a number, got %r" % (key, full[key]))
+    w, th, s = float(full["contrastive_loss_weight"]), float(full["cur_threshold"]), full["contrast_samples"]
+    if not (0.0 < w < float("inf")):
+        raise ValueError("cfg contrastive_loss_weight must be positive and finite, got %r" % (full["contrastive_loss_weight"],))
+    if not 0.0 < th <= 1.0:
+        raise ValueError("cfg cur_threshold must be in (0, 1], got %r" % (full["cur_threshold"],))
+    if not 1 <= s <= _lib.CONTRAST_MAX_S:
+        raise ValueError("cfg contrast_samples must be in 1..%d, got %r" % (_lib.CONTRAST_MAX_S, s))
 
 
 def pseudo_refine_mode(cfg):
@@ -422,6 +449,20 @@ class FixMatchNTMStep:
         # the corrected strong logits have a reader only under these two (train.py:591-596)
         self.needs_correction = self.criterion_u_name not in _IGNORES_CORRECTION
         self.refine_mode = pseudo_refine_mode(self.cfg)      # None: off -- nothing below runs
+        # cfg use_contrastive: the teacher-student contrastive loss on the 128-wide head feature (the output of seg_head[1]);
+        # off (the default): nothing is allocated and no launch is added.  Bank, pointer and draw counter are allocated
+        # here, per rank like every other buffer of the step: a first use under graph capture would be a memcpy node
+        self.contrast = None
+        if self.cfg["use_contrastive"]:
+            from .utils.cluster_contrastloss import nativeContrastLoss_t
+            from .openpoints.dataset.sample_draw import DeviceDraws
+            segs = [getattr(_unwrapped(m), "segmentor", None) for m in (student, teacher)]
+            if not all(hasattr(sg, "keep_head_feature") for sg in segs):
+                raise RuntimeError("cfg use_contrastive: the segmentor has no head feature to tap (PointTransformer_seg_T has)")
+            self.contrast = nativeContrastLoss_t(self.cfg["contrast_samples"], segs[0].seg_head[1].num_features,
+                                                 self.cfg["cur_threshold"], dev, DeviceDraws(self.cfg["contrast_seed"]))
+            for sg in segs:
+                sg.keep_head_feature = True
         if self.refine_mode == "margin_v1" and dev.type == "cuda":
             from .utils.pseudo_mask import _e_joint
             _e_joint(dev, c)          # uploaded here: a first use under graph capture would be a memcpy node
@@ -494,6 +535,14 @@ class FixMatchNTMStep:
             logits_u_aug, label_u_aug = torch.max(pred_u, dim=1)
         return pred_u, logits_u_aug, label_u_aug
 
+    def _teacher_feature(self):
+        """cfg use_contrastive: the head feature of the teacher's last forward (no_grad: a constant), taken off the module."""
+        if self.contrast is None:
+            return None
+        seg = _unwrapped(self.model_t).segmentor
+        feat, seg.head_feature = seg.head_feature, None
+        return feat
+
     def _teacher_geometry(self, inner, geom_s, data, data_u, inline=False):
         """The teacher's geometry: the weak view is the last third of the student's batch, so its sampling / grouping / index
         work is a slice of the student's (WholePartSeg.weak_view_geometry; the teacher's own 8192-sample FPS was 4.7 ms on two
@@ -516,7 +565,8 @@ class FixMatchNTMStep:
         on a second stream beside the PREVIOUS iteration's training graph; the eager iteration() below spreads the same work
         over side streams inside the iteration instead.  After switch_ep (self_labelling; default: the step's epoch) the
         teacher does not run: the student's geometry and the 3-D loss's graph only, "pseudo" is None.  With cfg pseudo_refine
-        the weak view's neighbour table is one more entry, "refine_nbr"."""
+        the weak view's neighbour table is one more entry, "refine_nbr"; with cfg use_contrastive, while the teacher runs, its
+        head feature is "feat_t"."""
         if self_labelling is None:
             self_labelling = self.self_labelling
         _mode(self.model, True)
@@ -534,6 +584,9 @@ class FixMatchNTMStep:
             refine_nbr = self._refine_neighbours(data_u) if self.refine_mode is not None else None
         pseudo = None if self_labelling else self._pseudo_labels(data_u, geom_t)
         pre = {"geom_s": geom_s, "pseudo": pseudo, "knn": (nbr, order)}
+        feat_t = None if self_labelling else self._teacher_feature()
+        if feat_t is not None:
+            pre["feat_t"] = feat_t
         if refine_nbr is not None:
             pre["refine_nbr"] = refine_nbr
         return pre
@@ -565,7 +618,7 @@ class FixMatchNTMStep:
         #    teacher draws no random numbers: identical results).  Its outputs are first used at step 3, after the join;
         #    next iteration's entry wait keeps the stream's allocations ordered behind this iteration's readers.
         #    After switch_ep there is no teacher: student_iteration takes the pseudo labels from the student's weak view.
-        t_stream = pseudo = None
+        t_stream = pseudo = feat_t = None
         if dev.type == "cuda" and self.overlap_teacher and not self_labelling:
             if self._teacher_stream is None:
                 self._teacher_stream = torch.cuda.Stream(device=dev)
@@ -574,6 +627,7 @@ class FixMatchNTMStep:
         if not self_labelling:
             with (torch.cuda.stream(t_stream) if t_stream is not None else contextlib.nullcontext()):
                 pseudo = self._pseudo_labels(data_u, geom_t)
+                feat_t = self._teacher_feature()
         inner = _unwrapped(self.model)
         make = None
         if next_batches is not None:
@@ -593,7 +647,7 @@ class FixMatchNTMStep:
             # forward returns -- behind this join those blocks cannot be handed to the look-ahead's kernels while the
             # teacher's decoder still reads them (the teacher is long done by the end of the student's forward: free)
             if t_stream is not None:
-                _join(dev, t_stream, *pseudo)
+                _join(dev, t_stream, *pseudo, feat_t)
             look.behind_forward()
 
         def knn_graph():
@@ -605,11 +659,11 @@ class FixMatchNTMStep:
             _join(dev, self._side, refine_nbr)
             return refine_nbr
         losses = self.student_iteration(data, data_u, geom_s, pseudo, knn_graph, after_forward,
-                                        refine_nbr=refine_table if refine_nbr is not None else None)
+                                        refine_nbr=refine_table if refine_nbr is not None else None, feat_t=feat_t)
         return losses, look.done() or (None, None)
 
     def student_iteration(self, data, data_u, geom_s, pseudo, knn_graph, after_forward=None, ema_in_place=False,
-                          defer_rest=False, refine_nbr=None):
+                          defer_rest=False, refine_nbr=None, feat_t=None):
         """Steps 2-5 of the iteration (train.py:478-602, 646-660): the student on labelled + strong + weak views, the class
         transition, the per-point matrices, the corrected logits, the losses, backward, both optimisers (and the meters).
         pseudo = (pred_u, logits_u_aug, label_u_aug) of the teacher, or None after switch_ep: then they are the soft-max of
@@ -623,7 +677,12 @@ class FixMatchNTMStep:
         (graph_step's split capture); refine_nbr: with cfg pseudo_refine, the weak view's neighbour table
         (utils/pseudo_mask.py neighbours) or a callable that returns it; None: computed in line.  The refined mask is taken
         from the pred_u the class transition reads and goes to the unsupervised criterion as its mask= (train.py:500,
-        588-596); scale_factor keeps the unrefined threshold mask (:599-602); the losses gain "kept", the mask's sum."""
+        588-596); scale_factor keeps the unrefined threshold mask (:599-602); the losses gain "kept", the mask's sum.
+        feat_t: with cfg use_contrastive, the teacher's head feature (B_u, 128, N) of its weak-view forward; None (after
+        switch_ep): the student's own weak-view slice, detached.  The contrastive loss (utils/cluster_contrastloss.py) reads
+        the student's strong-view slice against it, both channel-first and in place, selects by logits_u_aug >= cfg
+        cur_threshold with draws made on the device, and is added LAST, times cfg contrastive_loss_weight; the losses gain
+        "contrast" and "anchors" (the number of anchors, a device tensor)."""
         cfg = self.cfg
         seg = getattr(_unwrapped(self.model), "segmentor", None)
         can_cut = defer_rest and hasattr(seg, "take_cut")
@@ -641,6 +700,9 @@ class FixMatchNTMStep:
             if can_cut:
                 seg.cut_at_blocks = False
         cut = seg.take_cut() if can_cut else None
+        feat_all = None
+        if self.contrast is not None:
+            feat_all, seg.head_feature = seg.head_feature, None
         # (split, not two slices: its backward is one concatenation kernel; a slice's backward copies the gradient into a zero
         # tensor with a device-to-device memcpy -- a memcpy node when the iteration is captured)
         pred_l, pred_u_strong, pred_u_weak = torch.split(pred_all, [bl, bu, pred_all.shape[0] - bl - bu])
@@ -703,6 +765,14 @@ class FixMatchNTMStep:
             loss = loss + loss_ident
         if loss_3d is not None:
             loss = loss + loss_3d
+        loss_contrast = None
+        if self.contrast is not None:
+            # (split, as above: all three pieces, so that the backward is one concatenation kernel)
+            _, feat_strong, feat_weak = torch.split(feat_all, [bl, bu, feat_all.shape[0] - bl - bu])
+            if feat_t is None:
+                feat_t = feat_weak.detach()
+            loss_contrast = self.contrast(feat_strong, logits_u_aug.detach(), feat_t, channels_first=True)[0]
+            loss = loss + cfg["contrastive_loss_weight"] * loss_contrast
         if self.meters is not None:
             if "y" not in data_u:
                 raise RuntimeError("FixMatchNTMStep(meters=...): the unlabelled batch carries no ground truth data_u['y']")
@@ -728,6 +798,8 @@ class FixMatchNTMStep:
             losses["identity"] = loss_ident.detach()
         if mask is not None:
             losses["kept"] = mask.sum()
+        if loss_contrast is not None:
+            losses["contrast"], losses["anchors"] = loss_contrast.detach(), self.contrast.anchors
         if defer_rest:
             return losses, rest
         rest()

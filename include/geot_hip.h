@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 23
+#define GEOT_ABI_VERSION 24
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -1021,6 +1021,71 @@ int geot_view_draw(int j, int m, int n_noise, int n_mask, const void *tmpl_host,
 #define GEOT_PSEUDO_REFINE_MAX_N 32
 int geot_pseudo_refine(int b, int c, int npts, int n, int k, int mode, float th, float beta, const float *prob, const int *nbr,
                        const float *e_joint, unsigned char *keep, float *value, void *stream);
+
+/* ---- the teacher-student point contrastive loss (ABI 24) ------------------------------------------------------------------------
+ * utils/cluster_contrastloss.py's nativeContrastLoss_t (:1188-1408) with fixed shapes, counts kept on the device and no host
+ * round trip: kernel launches only, no workspace cleared by memset, no float atomics, no dependence on arrival order --
+ * bit-identical from run to run and safe to capture.  b clouds of p points, d channels, s = sample_nums; cap = b * s anchor
+ * slots, of which the first A (read on the device) are in use; grids are sized by cap and slots beyond A idle: what they
+ * would write stays as it arrived.  Features are read in place, point-major (b, p, d) or channel-first (b, d, p)
+ * (channels_first != 0); point ids are global, cloud * p + point.
+ *
+ * geot_contrast_select (:1233-1264 and the draw of :1210): per cloud the candidates are the points with score >= th in
+ * ascending order (a NaN score is none), K of them, m = min(K, s) anchors cand[perm[j]], j < m, packed cloud after cloud.
+ *   score (b, p) fp32.  perm (b, s) int64: row c holds the first m entries of a permutation of [0, K_c); perm_q (s) int64: the
+ *   first min(A, s) entries of a permutation of [0, A); both given (the host mode) or both NULL.  An entry outside its range
+ *   is never followed: the anchor id / the bank row is -1, which the entry points below read as a row of zeros / skip.
+ *   Both NULL: the keyed bijection of geot_sample_draw in its n >= m construction (Philox4x32-10, key = seed), n = K_c read
+ *   on the device: entry j of cloud c is pi_d(j) walked back into [0, K_c) with the draw id d = *counter + c, the bank rows
+ *   use n = A and d = *counter + b; the second kernel stores *counter + b + 1 to counter (every block draws from a copy the
+ *   first kernel took).  counter: one unsigned long long on the device, required in this mode, not read with perm given.
+ *   ws: geot_contrast_select_ws_ints(b, p) = b * p + b + 2 int32 of scratch.  anchors (cap) int32: ids of slots 0 .. A - 1,
+ *   -1 beyond; count (b + 1) int32: m per cloud, then A; enqueue_rows (s) int32: anchor slots, -1 from min(A, s) on;
+ *   inv (b * p) int32: the slot of a point that is an anchor, -1 otherwise.  Two launches.
+ *
+ * geot_contrast_loss (:1385-1388, _ppc_contrastive_andbank :1337-1377): slot a < A holds x = the row of feat_s and t = the
+ * row of feat_t at anchors[a]; x^ = x / max(|x|, 1e-12), |x| = sqrt of the sum of squares (fma, channels lane, lane + 64,
+ * .. per lane, then a butterfly over the wave), t^ likewise; only these A rows are normalised.  u_aj = (x^_a . t^_j) / tau
+ * over the A slots, v_aq = (x^_a . bank_q) / tau over the 4 s bank rows, dot products by fma in ascending channel order, the
+ * quotient a division; mu_a = max_j u_aj, nu_a = max_q v_aq, Z_a = sum_j exp(u_aj - mu_a) + sum_q exp(v_aq - nu_a),
+ * W_a = sum_j exp(u_aj - mu_a) t^_j + sum_q exp(v_aq - nu_a) bank_q -- ONE streaming pass: keys in chunks of 1024, each
+ * chunk in tiles of at least 16 keys with a running maximum (sum and W rescaled by exp(old - new)), the chunks merged in
+ * ascending order; expf /
+ * logf of the device library.  ell[a] = -(tau / tau_b) ((u_aa - mu_a) - log Z_a), u_aa by its own wave-wide dot product;
+ * grad_dir[a] = t^_a - W_a / Z_a; loss = (sum of ell in a fixed tree) / A, exactly 0 when A = 0.
+ *   bank (4 s, d) fp32.  Outputs xhat, that (cap, d), norm (cap) = |x|, ell (cap), grad_dir (cap, d), loss (1);
+ *   ws: geot_contrast_ws_floats(b, s, d) fp32 of scratch.  Four launches.
+ *
+ * geot_contrast_loss_grad: upstream (1) fp32 on the device, g.  dy_a = -(g / (A tau_b)) grad_dir[a]; through the
+ * normalisation as autograd of F.normalize does: |x| >= 1e-12: (dy - x^ (dy . x^)) / |x|, otherwise dy / 1e-12 (a row of norm
+ * 0 included).  rows (cap, d) scratch; grad: the dense gradient in the layout of feat_s, EVERY element written (zero where
+ * inv is -1) by a kernel.  Two launches.
+ *
+ * geot_contrast_enqueue (_queue_operations :1207-1220): cnt = min(A, s); row r < cnt of the block is
+ * t^[enqueue_rows[r]] normalised once more; the block is rows [4 s - cnt, 4 s) and *ptr becomes 0 when *ptr + cnt > 4 s,
+ * otherwise rows [*ptr, *ptr + cnt) and *ptr becomes (*ptr + cnt) mod 4 s.  ptr: one int64 on the device; a value outside
+ * [0, 4 s) writes nothing.  A = 0 leaves bank and ptr untouched.  Call it after geot_contrast_loss has read the bank.
+ * Two launches.
+ *
+ * 1 <= b <= GEOT_CONTRAST_MAX_B, 1 <= d <= GEOT_CONTRAST_MAX_D, 1 <= s <= GEOT_CONTRAST_MAX_S, p >= 1, b * p <= 2^31 - 1,
+ * tau > 0, tau_b > 0, no NULL pointer but perm / perm_q (and counter with them); anything else is hipErrorInvalidValue before
+ * any launch. */
+#define GEOT_CONTRAST_MAX_B 64
+#define GEOT_CONTRAST_MAX_D 256
+#define GEOT_CONTRAST_MAX_S 1024
+long long geot_contrast_select_ws_ints(int b, int p);
+long long geot_contrast_ws_floats(int b, int s, int d);
+int geot_contrast_select(int b, int p, int s, float th, const float *score, const long long *perm, const long long *perm_q,
+                         unsigned long long seed, unsigned long long *counter, int *ws, int *anchors, int *count,
+                         int *enqueue_rows, int *inv, void *stream);
+int geot_contrast_loss(int b, int p, int d, int s, int channels_first, const float *feat_s, const float *feat_t,
+                       const int *anchors, const int *count, const float *bank, float tau, float tau_b, float *xhat, float *that,
+                       float *norm, float *ws, float *ell, float *grad_dir, float *loss, void *stream);
+int geot_contrast_loss_grad(int b, int p, int d, int s, int channels_first, const int *count, const int *inv, const float *xhat,
+                            const float *norm, const float *grad_dir, const float *upstream, float tau_b, float *rows,
+                            float *grad, void *stream);
+int geot_contrast_enqueue(int b, int d, int s, const int *count, const int *enqueue_rows, const float *that, float *bank,
+                          long long *ptr, void *stream);
 
 #ifdef __cplusplus
 }
