@@ -55,6 +55,14 @@ PSEUDO_REFINE_MAX_N = CONSTANTS["GEOT_PSEUDO_REFINE_MAX_N"]
 CONTRAST_MAX_B = CONSTANTS["GEOT_CONTRAST_MAX_B"]     # the geot_contrast_* entry points: clouds, channels, sample_nums
 CONTRAST_MAX_D = CONSTANTS["GEOT_CONTRAST_MAX_D"]
 CONTRAST_MAX_S = CONSTANTS["GEOT_CONTRAST_MAX_S"]
+OPTIM_TAIL_CAP = CONSTANTS["GEOT_OPTIM_TAIL_CAP"]     # the geot_optim_tail_* entry points: records per launch,
+OPTIM_TAIL_BLOCK_ELEMS = CONSTANTS["GEOT_OPTIM_TAIL_BLOCK_ELEMS"]     # elements per workgroup,
+OPTIM_TAIL_STEP_CAP = CONSTANTS["GEOT_OPTIM_TAIL_STEP_CAP"]           # step counters per finish launch,
+OPTIM_TAIL_REC_WORDS = CONSTANTS["GEOT_OPTIM_TAIL_REC_WORDS"]         # 32-bit words of a record / of a group,
+OPTIM_TAIL_GROUP_WORDS = CONSTANTS["GEOT_OPTIM_TAIL_GROUP_WORDS"]
+OPTIM_TAIL_MAX_GROUPS = CONSTANTS["GEOT_OPTIM_TAIL_MAX_GROUPS"]
+OPTIM_TAIL_CLIPPED, OPTIM_TAIL_VECTOR = CONSTANTS["GEOT_OPTIM_TAIL_CLIPPED"], CONSTANTS["GEOT_OPTIM_TAIL_VECTOR"]     # record flags
+OPTIM_TAIL_EMA_ONLY, OPTIM_TAIL_INT64 = CONSTANTS["GEOT_OPTIM_TAIL_EMA_ONLY"], CONSTANTS["GEOT_OPTIM_TAIL_INT64"]
 
 _lib = None
 

@@ -14,7 +14,11 @@ An iteration is two SINGLE-STREAM graphs (geot_amd/streams.py: on ROCm 7.0 a gra
   geometry, the frozen teacher's forward -> pseudo labels, the kNN graph and Morton order of the 3-D loss; after the
   step's switch_ep (FixMatchNTMStep.set_epoch) the student's geometry and the kNN graph / order only -- each phase has a
   P and an M of its own ("P" / "M" and "P@2" / "M@2"), captured on first use, and a look-ahead made under one phase is
-  never handed to the other's M (P then runs in line, same results).
+  never handed to the other's M (P then runs in line, same results).  With cfg ema_teacher the teacher moves with every
+  update, so its forward cannot run beside the update before it: before switch_ep that step has a third phase ("P@e" /
+  "M@e") whose P holds the student's and the teacher's geometry, the kNN graph / order and the refine table -- no pseudo
+  labels, no teacher feature -- and whose M starts with the teacher's forward and ends with the tail that moves it; after
+  switch_ep the teacher no longer runs and "P@2" / "M@2" are what they were, M@2 with the tail at its end.
 * **M** -- the training iteration proper over P's product: forward, losses, backward, AdamW (capturable=True; under
   fused=True the step counters live on the device either way: the same kernel), the EMA transition matrix updated in
   its buffer.
@@ -383,7 +387,9 @@ class GraphedFixMatchStep(_Graphed):
                 _fits(v, src[k], "%s[%r]" % (what, k))
         self._check_lr()
         self_labelling = step.self_labelling
-        tag, p_keys = ("@2" if self_labelling else ""), _p_keys(self_labelling, step.cfg.get("use_3d_loss", True))
+        moving = bool(step.cfg.get("ema_teacher")) and not self_labelling      # the teacher's forward belongs to M: phase "@e"
+        tag = "@2" if self_labelling else "@e" if moving else ""
+        p_keys = _p_keys(self_labelling, step.cfg.get("use_3d_loss", True))
         announced_now = self._is_announced([b[k] for b, keys in zip((data, data_u), p_keys) for k in keys])
         self._join_pending()
         for dst, src in ((self.data, data), (self.data_u, data_u)):
@@ -400,16 +406,25 @@ class GraphedFixMatchStep(_Graphed):
         def lookahead():
             return step.lookahead_work(self.next[0], self.next[1], self_labelling=self_labelling)
 
+        def pseudo_of(pre):
+            """(pseudo labels, teacher feature) of M: P's product, or -- a moving teacher -- its forward, here."""
+            if not moving:
+                return pre["pseudo"], pre.get("feat_t")
+            pseudo = step._pseudo_labels(self.data_u, pre["geom_t"])
+            return pseudo, step._teacher_feature()
+
         def train():
             pre = self.pre
-            return step.student_iteration(self.data, self.data_u, pre["geom_s"], pre["pseudo"], pre["knn"], ema_in_place=True,
-                                          refine_nbr=pre.get("refine_nbr"), feat_t=pre.get("feat_t"))
+            pseudo, feat_t = pseudo_of(pre)
+            return step.student_iteration(self.data, self.data_u, pre["geom_s"], pseudo, pre["knn"], ema_in_place=True,
+                                          refine_nbr=pre.get("refine_nbr"), feat_t=feat_t)
         if self.split:
             def head():
                 pre = self.pre
-                self._losses, rest = step.student_iteration(self.data, self.data_u, pre["geom_s"], pre["pseudo"], pre["knn"],
+                pseudo, feat_t = pseudo_of(pre)
+                self._losses, rest = step.student_iteration(self.data, self.data_u, pre["geom_s"], pseudo, pre["knn"],
                                                             ema_in_place=True, defer_rest=True,
-                                                            refine_nbr=pre.get("refine_nbr"), feat_t=pre.get("feat_t"))
+                                                            refine_nbr=pre.get("refine_nbr"), feat_t=feat_t)
                 return rest
 
             def rest_update(rest):

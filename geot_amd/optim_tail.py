@@ -1,0 +1,294 @@
+"""The tail of a training iteration behind its backward -- gradient clipping, AdamW, and the exponential moving average that
+makes a mean teacher follow its student -- as one multi-tensor HIP pass (csrc/optim_tail.hip, include/geot_hip.h "ABI 25").
+
+    tail = OptimTail([optimizer, t_optimizer], clip_params=student.parameters(), max_norm=1.0,
+                     teacher=teacher, student=student, ema_decay=0.99)
+    loss.backward()
+    tail.step()                     # norm sweep, finish, update sweep; tail.total_norm is a device scalar
+    optimizer.zero_grad(set_to_none=True)
+
+The reference clips and steps with torch ops (examples/segmentation/train.py:656-660, cfgs/tooth_semi/default.yaml:83) and
+names an `ema_decay` (cfgs/tooth_semi/transformer_finetune_fixmatch_ntm.yaml:66) that it never applies: its teacher is loaded,
+frozen (train.py:218-222) and left alone.
+
+The torch optimizers stay the owners of the state: step() is another way of executing their step().  exp_avg / exp_avg_sq /
+step are created in optimizer.state[p] in the form fused, capturable torch.optim.AdamW creates them (zeros like the parameter,
+a 0-dim float32 step on the parameter's device) for the parameters that have a gradient when they first get one, and existing
+state is adopted; the only difference is that every `step` is a 0-dim VIEW of one flat float32 tensor, which lets one
+workgroup raise all of them.  optimizer.state_dict() therefore loads into a fresh torch.optim.AdamW and continues there, and a
+state loaded into the optimizer is adopted by the next step().
+
+composite() runs the same semantics in torch ops -- clip_grad_norm_, optimizer.step(), torch._foreach_lerp_ and a kernel copy
+for integer buffers: the second oracle of the tests and the baseline tools/time_optim_tail.py measures against.
+
+There is no fallback: a missing library or kernel raises.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from .ext._common import call, need
+
+CAP = _lib.OPTIM_TAIL_CAP
+BLOCK_ELEMS = _lib.OPTIM_TAIL_BLOCK_ELEMS
+MAX_GROUPS = _lib.OPTIM_TAIL_MAX_GROUPS
+CLIPPED, VECTOR = _lib.OPTIM_TAIL_CLIPPED, _lib.OPTIM_TAIL_VECTOR
+EMA_ONLY, INT64 = _lib.OPTIM_TAIL_EMA_ONLY, _lib.OPTIM_TAIL_INT64
+
+# the host records of include/geot_hip.h (GEOT_OPTIM_TAIL_REC_WORDS / GEOT_OPTIM_TAIL_GROUP_WORDS 32-bit words)
+RECORD = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("t", "<u8"), ("n", "<i8"),
+                   ("first_block", "<i4"), ("group", "<i4"), ("flags", "<i4"), ("step", "<i4")])
+GROUP = np.dtype([("beta1", "<f8"), ("beta2", "<f8"), ("eps", "<f4"), ("weight_decay", "<f4"), ("lr", "<f4"),
+                  ("pad", "<i4"), ("lr_ptr", "<u8")])
+assert RECORD.itemsize == 4 * _lib.OPTIM_TAIL_REC_WORDS
+assert GROUP.itemsize == 4 * _lib.OPTIM_TAIL_GROUP_WORDS
+
+
+def plan(counts, aligned, flags):
+    """geot_optim_tail_plan: -> dict update_launches, norm_launches, update_blocks, slots, blocks (T,), vector (T,)."""
+    t = len(counts)
+    counts = np.ascontiguousarray(counts, dtype=np.int64)
+    aligned = np.ascontiguousarray(aligned, dtype=np.int32)
+    flags = np.ascontiguousarray(flags, dtype=np.int32)
+    need(len(aligned) == t and len(flags) == t, "optim_tail.plan: counts, aligned and flags must have one entry per record")
+    out = np.zeros(4 + 2 * t, dtype=np.int64)
+    ok = _lib.load().geot_optim_tail_plan(t, counts.ctypes.data, aligned.ctypes.data, flags.ctypes.data, out.ctypes.data, len(out))
+    need(ok == 1, "geot_optim_tail_plan refused the records (a negative count)")
+    return {"update_launches": int(out[0]), "norm_launches": int(out[1]), "update_blocks": int(out[2]), "slots": int(out[3]),
+            "blocks": out[4:4 + t].copy(), "vector": out[4 + t:].copy()}
+
+
+def _unwrapped(module):
+    return module.module if hasattr(module, "module") else module
+
+
+def teacher_pairs(student, teacher):
+    """The (student tensor, teacher tensor, name) of every state_dict() entry of the unwrapped modules, paired by name.
+    A mismatch of names, shapes or dtypes, or a dtype that is neither float32 nor int64, is a RuntimeError."""
+    s_sd, t_sd = _unwrapped(student).state_dict(keep_vars=True), _unwrapped(teacher).state_dict(keep_vars=True)
+    if list(s_sd) != list(t_sd):
+        odd = sorted(set(s_sd) ^ set(t_sd))
+        raise RuntimeError("OptimTail: student and teacher do not hold the same entries (%s)" % (", ".join(odd[:6]) or "order differs"))
+    pairs = []
+    for name, s in s_sd.items():
+        t = t_sd[name]
+        if s.shape != t.shape or s.dtype != t.dtype or s.device != t.device:
+            raise RuntimeError("OptimTail: %s is %s %s on %s in the student, %s %s on %s in the teacher"
+                               % (name, tuple(s.shape), s.dtype, s.device, tuple(t.shape), t.dtype, t.device))
+        if s.dtype not in (torch.float32, torch.int64):
+            raise RuntimeError("OptimTail: %s is %s; the EMA takes float32 entries and copies int64 ones" % (name, s.dtype))
+        if not (s.is_contiguous() and t.is_contiguous()):
+            raise RuntimeError("OptimTail: %s is not contiguous" % name)
+        if s.data_ptr() == t.data_ptr() and s.numel():
+            raise RuntimeError("OptimTail: %s is the same tensor in student and teacher" % name)
+        pairs.append((s, t, name))
+    return pairs
+
+
+class OptimTail:
+    def __init__(self, optimizers, clip_params=None, max_norm=None, teacher=None, student=None, ema_decay=None):
+        """optimizers: torch.optim.AdamW objects, stepped in order, at most 4 parameter groups together (amsgrad / maximize
+        groups are refused).  clip_params + max_norm: the parameters whose gradients clip_grad_norm_ would see, and its
+        max_norm; max_norm None: no clipping, no norm sweep.  teacher + student + ema_decay: the teacher's state_dict() entries
+        follow the student's -- float32 entries (parameters, BatchNorm running statistics) by t = d t + (1 - d) s with the
+        constant d = ema_decay, int64 entries (num_batches_tracked) by copy."""
+        self.optimizers = list(optimizers)
+        need(self.optimizers, "OptimTail: no optimizer")
+        self.groups = []                      # (optimizer, its group dict)
+        for opt in self.optimizers:
+            if not isinstance(opt, torch.optim.AdamW):
+                raise RuntimeError("OptimTail: %s is not a torch.optim.AdamW" % type(opt).__name__)
+            for group in opt.param_groups:
+                if group.get("amsgrad") or group.get("maximize"):
+                    raise RuntimeError("OptimTail: amsgrad / maximize are not supported")
+                self.groups.append((opt, group))
+        if len(self.groups) > MAX_GROUPS:
+            raise RuntimeError("OptimTail: %d parameter groups, the kernels take %d" % (len(self.groups), MAX_GROUPS))
+        self.params = []                      # (parameter, optimizer, group index), in stepping order
+        for gi, (opt, group) in enumerate(self.groups):
+            for p in group["params"]:
+                if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+                    raise RuntimeError("OptimTail: parameters must be contiguous float32 tensors on the GPU")
+                self.params.append((p, opt, gi))
+        need(self.params, "OptimTail: the optimizers hold no parameter")
+        self.device = self.params[0][0].device
+        need(all(p.device == self.device for p, _, _ in self.params), "OptimTail: all parameters must live on one device")
+        if len({id(p) for p, _, _ in self.params}) != len(self.params):
+            raise RuntimeError("OptimTail: a parameter appears in two groups")
+        self.max_norm = None if max_norm is None else float(max_norm)
+        self.clip_params = list(clip_params) if clip_params is not None else []
+        if self.max_norm is not None and not self.clip_params:
+            raise RuntimeError("OptimTail: max_norm without clip_params")
+        clipped = {id(p) for p in self.clip_params} if self.max_norm is not None else set()
+        self._clipped = [id(p) in clipped for p, _, _ in self.params]
+        owned = {id(p) for p, _, _ in self.params}
+        if any(p.requires_grad and id(p) not in owned for p in self.clip_params):
+            raise RuntimeError("OptimTail: a clipped parameter that takes a gradient belongs to none of the optimizers")
+        self.pairs = []
+        self.ema_decay = None
+        if teacher is not None or student is not None or ema_decay is not None:
+            if teacher is None or student is None or ema_decay is None:
+                raise RuntimeError("OptimTail: teacher, student and ema_decay go together")
+            if isinstance(ema_decay, bool) or not isinstance(ema_decay, (int, float)) or not 0.0 <= float(ema_decay) < 1.0:
+                raise RuntimeError("OptimTail: 0 <= ema_decay < 1, got %r" % (ema_decay,))
+            self.ema_decay = float(ema_decay)
+            self.pairs = teacher_pairs(student, teacher)
+            need(all(s.device == self.device for s, _, _ in self.pairs), "OptimTail: the teacher must live on the parameters' device")
+        self._teacher_of = {id(s): t for s, t, _ in self.pairs}
+        self.steps = torch.zeros(len(self.params), dtype=torch.float32, device=self.device)      # every step counter
+        self._step_views = [None] * len(self.params)
+        self._bound = None                    # the active set whose state is known to be bound
+        self._states = [None] * len(self.optimizers)       # the optimizers' state dicts the views were bound into
+        self.scalars = torch.zeros(2, dtype=torch.float32, device=self.device)
+        self.scalars[1] = 1.0
+        self.total_norm = self.scalars[0]     # device scalars, rewritten by every step()
+        self.clip_coef = self.scalars[1]
+        self._active = None                   # indices into self.params of the cached table
+        self._table = None
+        self._slots = None
+        self._plan = None
+        self._group_table = np.zeros(len(self.groups), dtype=GROUP)
+        self.launches = 0                     # kernel launches of the last step()
+
+    # ---- state ------------------------------------------------------------------------------------------------------------
+    def _bind_state(self, active):
+        """exp_avg / exp_avg_sq / step of the active parameters: created as torch.optim.AdamW would, or adopted; every step
+        a view of self.steps.  Creating or adopting issues fills and copies: not under graph capture."""
+        rebound = [opt.state is not self._states[k] for k, opt in enumerate(self.optimizers)]
+        if not any(rebound) and self._bound == tuple(active):
+            return False
+        todo = []
+        for i in active:
+            p, opt, _ = self.params[i]
+            k = self.optimizers.index(opt)
+            st = opt.state.get(p)
+            if st is None or "step" not in st or "exp_avg" not in st or rebound[k] or st["step"] is not self._step_views[i]:
+                todo.append(i)
+        self._bound = tuple(active)
+        if not todo:
+            return False
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("OptimTail: optimizer state has to be created or adopted under graph capture -- run the step "
+                               "eagerly once before capturing it")
+        for i in todo:
+            p, opt, _ = self.params[i]
+            st = opt.state[p]
+            view = self.steps[i]
+            if "step" in st and "exp_avg" in st and "exp_avg_sq" in st:
+                old = st["step"]
+                if torch.is_tensor(old):
+                    if old.data_ptr() != view.data_ptr():
+                        view.copy_(old.to(device=self.device, dtype=torch.float32))
+                else:
+                    view.fill_(float(old))
+                for key in ("exp_avg", "exp_avg_sq"):
+                    t = st[key]
+                    if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == p.shape):
+                        raise RuntimeError("OptimTail: the optimizer's %s is not a contiguous float32 tensor like its parameter" % key)
+            else:
+                view.zero_()
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["step"] = view
+            self._step_views[i] = view
+        self._states = [opt.state for opt in self.optimizers]
+        return True
+
+    # ---- the table ----------------------------------------------------------------------------------------------------------
+    def _build(self, active, grads):
+        """The record table for these active parameters (pointers of p, m, v, t cached; g filled per call)."""
+        recs = []
+        has_grad = set()
+        for i in active:
+            p, opt, gi = self.params[i]
+            st = opt.state[p]
+            t = self._teacher_of.get(id(p))
+            recs.append((p.data_ptr(), 0, st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                         0 if t is None else t.data_ptr(), p.numel(), 0, gi, CLIPPED if self._clipped[i] else 0, i))
+            has_grad.add(id(p))
+        for s, t, _ in self.pairs:
+            if id(s) in has_grad:
+                continue
+            recs.append((s.data_ptr(), 0, 0, 0, t.data_ptr(), s.numel(), 0, 0, INT64 if s.dtype == torch.int64 else EMA_ONLY, 0))
+        table = np.array(recs, dtype=RECORD)
+        self._n_active = len(active)
+        self._table, self._active = table, tuple(active)
+        self._plan = None
+
+    def _plan_for(self, table):
+        aligned = np.ones(len(table), dtype=np.int32)
+        for key in ("p", "g", "m", "v", "t"):
+            aligned &= (table[key] % 16 == 0)
+        return plan(table["n"], aligned, table["flags"])
+
+    def _groups_now(self):
+        gt = self._group_table
+        for k, (_, group) in enumerate(self.groups):
+            lr = group["lr"]
+            if torch.is_tensor(lr):
+                if not (lr.is_cuda and lr.dtype == torch.float32 and lr.numel() == 1 and lr.device == self.device):
+                    raise RuntimeError("OptimTail: a tensor lr must be one float32 on the parameters' device")
+                gt[k]["lr"], gt[k]["lr_ptr"] = 0.0, lr.data_ptr()
+            else:
+                gt[k]["lr"], gt[k]["lr_ptr"] = float(lr), 0
+            gt[k]["beta1"], gt[k]["beta2"] = group["betas"]
+            gt[k]["eps"], gt[k]["weight_decay"] = group["eps"], group["weight_decay"]
+        return gt
+
+    def step(self):
+        """clip + AdamW + EMA on the current stream.  The gradients are read, not scaled in place: drop them afterwards."""
+        active, grads = [], []
+        for i, (p, _, _) in enumerate(self.params):
+            g = p.grad
+            if g is not None:
+                active.append(i)
+                grads.append(g)
+        rebuilt = self._bind_state(active)
+        if rebuilt or self._active != tuple(active):
+            self._build(active, grads)
+        table = self._table
+        ptrs = []
+        for g, i in zip(grads, active):
+            p = self.params[i][0]
+            if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape or g.device != self.device or g.is_sparse:
+                raise RuntimeError("OptimTail: gradients must be dense contiguous float32 tensors like their parameters")
+            ptrs.append(g.data_ptr())
+        table["g"][:len(ptrs)] = ptrs
+        pl = self._plan_for(table)
+        clip = self.max_norm is not None
+        if clip and (self._slots is None or self._slots.numel() < max(pl["slots"], 1)):
+            self._slots = torch.empty(max(pl["slots"], 1), dtype=torch.float32, device=self.device)
+        dev, t, host = self.device, len(table), table.ctypes.data
+        if clip:
+            call("geot_optim_tail_norm", dev, t, host, self._slots.data_ptr(), self._slots.numel())
+        call("geot_optim_tail_finish", dev, t, host, int(clip), pl["slots"] if clip else 0,
+             self._slots.data_ptr() if clip else None, self.max_norm if clip else 0.0, self.steps.data_ptr(),
+             self.steps.numel(), self.scalars.data_ptr())
+        groups = self._groups_now()
+        call("geot_optim_tail_update", dev, t, host, len(groups), groups.ctypes.data, self.scalars.data_ptr(),
+             self.steps.data_ptr(), self.steps.numel(), self.ema_decay if self.ema_decay is not None else 0.0)
+        n_adamw = self._n_active
+        steps_cap = _lib.OPTIM_TAIL_STEP_CAP
+        self.launches = (pl["norm_launches"] if clip else 0) + max(1, -(-n_adamw // steps_cap)) + pl["update_launches"]
+        self.last_plan = pl
+        return self.total_norm
+
+    # ---- the same semantics in torch ops ----------------------------------------------------------------------------------------
+    def composite(self):
+        """clip_grad_norm_ + optimizer.step() + torch._foreach_lerp_ (+ a kernel copy for integer buffers) -> total_norm
+        (None without a clip).  The optimizers keep whatever state they have (a state the fused step bound stays bound)."""
+        total = None
+        if self.max_norm is not None:
+            total = torch.nn.utils.clip_grad_norm_(self.clip_params, self.max_norm)
+        for opt in self.optimizers:
+            opt.step()
+        if self.pairs:
+            with torch.no_grad():
+                fs = [s.detach() for s, t, _ in self.pairs if s.dtype == torch.float32]
+                ft = [t.detach() for s, t, _ in self.pairs if s.dtype == torch.float32]
+                if ft:
+                    torch._foreach_lerp_(ft, fs, 1.0 - self.ema_decay)
+                for s, t, _ in self.pairs:
+                    if s.dtype == torch.int64:
+                        torch.add(s.detach(), 0, out=t.detach())       # (a kernel: copy_ would be a memcpy node under capture)
+        return total

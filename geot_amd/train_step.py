@@ -32,7 +32,8 @@ NTM_CFG = dict(threshold=0.0, unsupervised_loss_weight=1.0, ema_t_decay=0.999, l
                criterion="Poly1FocalLoss", criterion_u="Poly1FocalLoss_U_corr", use_3d_loss=True, use_feat_loss=False,
                feat_loss_weight=10.0, feat_k=16, feat_sigma=1.0, use_identity_loss=False, identity_loss_weight=1.0,
                pseudo_refine=False, pseudo_refine_size=4, pseudo_refine_neighbors=1,
-               use_contrastive=False, contrastive_loss_weight=1.0, cur_threshold=0.9, contrast_samples=1024, contrast_seed=0)
+               use_contrastive=False, contrastive_loss_weight=1.0, cur_threshold=0.9, contrast_samples=1024, contrast_seed=0,
+               ema_teacher=False, ema_decay=0.99, fused_tail=False)
 # cfgs/tooth_semi/transformer_finetune_fixmatch_ntm.yaml:45-96 (+ default.yaml); criterion / criterion_u are its
 # criterion_args.NAME / criterion_u_args.NAME (a {"NAME": ..., **constructor arguments} dict is taken too).
 # pseudo_refine (yaml:75, which the reference never reads): False, True (= "max") or one of utils/pseudo_mask.py's three
@@ -40,6 +41,10 @@ NTM_CFG = dict(threshold=0.0, unsupervised_loss_weight=1.0, ema_t_decay=0.999, l
 # use_contrastive / contrastive_loss_weight / cur_threshold (yaml:70, 71, 68, which the reference never reads either): the
 # teacher-student contrastive loss of utils/cluster_contrastloss.py on the 128-wide head feature, its weight in the total and
 # its selection threshold; contrast_samples is the class's sample_nums, contrast_seed the key of its device draws
+# ema_teacher / ema_decay (yaml:66 names the decay; the reference freezes its teacher, train.py:218-222, and never applies it):
+# after every update the teacher's state_dict() entries follow the student's, t = ema_decay t + (1 - ema_decay) s (integer
+# buffers are copied); fused_tail: clip + AdamW (+ that EMA) in one multi-tensor HIP pass (geot_amd/optim_tail.py) instead of
+# clip_grad_norm_ + optimizer.step() -- ema_teacher without it runs the same semantics in torch ops
 PSEUDO_REFINE_MODES = ("max", "margin", "margin_v1")
 PSEUDO_REFINE_MAX_SIZE = _lib.PSEUDO_REFINE_MAX_N      # include/geot_hip.h GEOT_PSEUDO_REFINE_MAX_N
 
@@ -82,7 +87,21 @@ def check_cfg(cfg):
             raise ValueError("cfg pseudo_refine=%r: the margin needs 2 classes, margin_v1's E_joint has 17; num_classes is %r"
                              % (mode, c))
     check_contrast_cfg(cfg)
+    check_tail_cfg(cfg)
     return out
+
+
+def check_tail_cfg(cfg):
+    """The keys of the moving teacher and the fused tail (a cfg without them is one with the switches off)."""
+    for key in ("ema_teacher", "fused_tail"):
+        if key in cfg and not isinstance(cfg[key], bool):
+            raise TypeError("cfg %s must be a bool, got %r" % (key, cfg[key]))
+    if "ema_decay" in cfg:
+        d = cfg["ema_decay"]
+        if isinstance(d, bool) or not isinstance(d, (int, float)):
+            raise TypeError("cfg ema_decay must be a number, got %r" % (d,))
+        if not 0.0 <= float(d) < 1.0:
+            raise ValueError("cfg ema_decay must be in [0, 1), got %r" % (d,))
 
 
 def check_contrast_cfg(cfg):
@@ -232,11 +251,21 @@ def _inner(module, bypass):
     return _unwrapped(module) if bypass else module
 
 
-def _update(grad_sync, clip, model, optimizers):
+def _update(grad_sync, clip, model, optimizers, tail=None, fused=False):
     """The tail of an iteration behind its backward: the step's own gradient exchange (GradSync, if any), clipping of
-    `model`'s gradients, then every optimizer in order (train.py:656-660)."""
+    `model`'s gradients, then every optimizer in order (train.py:656-660).  tail: the step's OptimTail (geot_amd/optim_tail.py),
+    which holds the same clip and optimizers (and the teacher's EMA, if any): its fused pass when `fused`, else the same
+    semantics in torch ops."""
     if grad_sync is not None:
         grad_sync()
+    if tail is not None:
+        if fused:
+            tail.step()
+        else:
+            tail.composite()
+        for optimizer in optimizers:
+            optimizer.zero_grad(set_to_none=True)
+        return
     if clip is not None:
         torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
     for optimizer in optimizers:
@@ -336,15 +365,24 @@ class _LookAhead:
 
 
 class SupervisedStep:
-    def __init__(self, model, lr=1e-3, weight_decay=1e-4, grad_norm_clip=None, grad_sync=None, criterion="Poly1FocalLoss"):
+    def __init__(self, model, lr=1e-3, weight_decay=1e-4, grad_norm_clip=None, grad_sync=None, criterion="Poly1FocalLoss",
+                 fused_tail=False):
         """criterion: cfg criterion_args -- "Poly1FocalLoss" or "Weight_CELoss" (or {"NAME": ..., **kwargs}); the latter takes
-        the batch's class_weights (train.py:449-450)."""
+        the batch's class_weights (train.py:449-450).  fused_tail: clip + AdamW as one multi-tensor HIP pass
+        (geot_amd/optim_tail.py; with a clip, self.tail.total_norm is the gradient norm on the device)."""
+        if not isinstance(fused_tail, bool):
+            raise TypeError("SupervisedStep: fused_tail must be a bool, got %r" % (fused_tail,))
         self.criterion_name, self.criterion = _criterion(criterion, SUPERVISED_CRITERIA, "criterion")
         self.model = model
         self.optimizer = make_optimizer(model, lr, weight_decay)
         self.clip = grad_norm_clip
         self._geometry = None          # coordinate-only work of the next batch, queued by the previous call
         self.grad_sync = grad_sync     # a GradSync: the step exchanges its gradients itself (bare modules: sync_only)
+        self.tail = None
+        if fused_tail:
+            from .optim_tail import OptimTail
+            self.tail = OptimTail([self.optimizer], max_norm=grad_norm_clip,
+                                  clip_params=list(model.parameters()) if grad_norm_clip is not None else None)
 
     def optimizers(self):
         return [self.optimizer]
@@ -384,7 +422,7 @@ class SupervisedStep:
     def backward_update(self, loss):
         """The second half: backward, clipping, the optimizer -> the detached loss."""
         loss.backward()
-        _update(self.grad_sync, self.clip, self.model, self.optimizers())
+        _update(self.grad_sync, self.clip, self.model, self.optimizers(), self.tail, self.tail is not None)
         return loss.detach()
 
     def forward_backward_head(self, pos, cls, target, geometry=None, class_weights=None):
@@ -409,7 +447,7 @@ class SupervisedStep:
         """The rest of the backward (the blocks, the patch encoder), clipping, the optimizer."""
         if rest is not None:
             torch.autograd.backward(rest[0], rest[1])
-        _update(self.grad_sync, self.clip, self.model, self.optimizers())
+        _update(self.grad_sync, self.clip, self.model, self.optimizers(), self.tail, self.tail is not None)
 
     def iteration(self, pos, cls, target, geometry=None, next_pos=None, class_weights=None):
         """One iteration -> (detached loss, the geometry queued for next_pos or None)."""
@@ -468,6 +506,15 @@ class FixMatchNTMStep:
             _e_joint(dev, c)          # uploaded here: a first use under graph capture would be a memcpy node
         self.optimizer = make_optimizer(student, self.cfg["lr"], self.cfg["weight_decay"])
         self.T_optimizer = make_optimizer(t_predictor, self.cfg["lr"], self.cfg["weight_decay"])
+        # cfg ema_teacher / fused_tail (both off: no tail object, _update is the torch code it always was).  The teacher's
+        # parameters keep requires_grad=False: the EMA writes their memory, autograd never sees them
+        self.tail = None
+        if self.cfg["ema_teacher"] or self.cfg["fused_tail"]:
+            from .optim_tail import OptimTail
+            clip, ema = self.cfg["grad_norm_clip"], self.cfg["ema_teacher"]
+            self.tail = OptimTail(self.optimizers(), clip_params=list(student.parameters()) if clip is not None else None,
+                                  max_norm=clip, teacher=teacher if ema else None, student=student if ema else None,
+                                  ema_decay=self.cfg["ema_decay"] if ema else None)
         self.ema_t = torch.eye(c, device=dev)                                          # train.py:274
         self.cm = cm if cm is not None else torch.full((c, c), 1.0 / c, device=dev)    # cal_mean_feature's output
         self.group = group
@@ -566,7 +613,8 @@ class FixMatchNTMStep:
         over side streams inside the iteration instead.  After switch_ep (self_labelling; default: the step's epoch) the
         teacher does not run: the student's geometry and the 3-D loss's graph only, "pseudo" is None.  With cfg pseudo_refine
         the weak view's neighbour table is one more entry, "refine_nbr"; with cfg use_contrastive, while the teacher runs, its
-        head feature is "feat_t"."""
+        head feature is "feat_t".  With cfg ema_teacher the teacher is no frozen state: before switch_ep the product holds its
+        geometry, "geom_t", and neither "pseudo" nor "feat_t" -- its forward runs inside the iteration."""
         if self_labelling is None:
             self_labelling = self.self_labelling
         _mode(self.model, True)
@@ -582,6 +630,13 @@ class FixMatchNTMStep:
                 nbr = self.threed_loss.neighbours(raw)
                 order = ntm_mod.spatial_order(raw)
             refine_nbr = self._refine_neighbours(data_u) if self.refine_mode is not None else None
+        if self.cfg["ema_teacher"] and not self_labelling:
+            # a teacher that moves with every update cannot run ahead of the update before it: its forward belongs to the
+            # iteration itself (graph_step runs it at the head of M); what depends on the batch alone is its geometry
+            pre = {"geom_s": geom_s, "geom_t": geom_t, "knn": (nbr, order)}
+            if refine_nbr is not None:
+                pre["refine_nbr"] = refine_nbr
+            return pre
         pseudo = None if self_labelling else self._pseudo_labels(data_u, geom_t)
         pre = {"geom_s": geom_s, "pseudo": pseudo, "knn": (nbr, order)}
         feat_t = None if self_labelling else self._teacher_feature()
@@ -623,6 +678,9 @@ class FixMatchNTMStep:
             if self._teacher_stream is None:
                 self._teacher_stream = torch.cuda.Stream(device=dev)
             t_stream = self._teacher_stream
+            # (cfg ema_teacher: this wait also puts the teacher's forward behind the previous iteration's update, which
+            # wrote the teacher's weights on the current stream; the join behind the student's forward puts this
+            # iteration's update behind the teacher's reads)
             t_stream.wait_stream(torch.cuda.current_stream(dev))
         if not self_labelling:
             with (torch.cuda.stream(t_stream) if t_stream is not None else contextlib.nullcontext()):
@@ -789,7 +847,7 @@ class FixMatchNTMStep:
             if ema_in_place:
                 with torch.no_grad():
                     torch.mul(ema_next, 1.0, out=self.ema_t)   # behind everything that read the old one (a kernel, not a memcpy node)
-            _update(self.grad_sync, cfg["grad_norm_clip"], self.model, self.optimizers())
+            _update(self.grad_sync, cfg["grad_norm_clip"], self.model, self.optimizers(), self.tail, cfg["fused_tail"])
         losses = {"loss": loss.detach(), "sup": sup_loss.detach(), "unsup": unsup_loss.detach(),
                   "threed": loss_3d.detach() if loss_3d is not None else torch.zeros((), device=loss.device)}
         if loss_feat is not None:
@@ -800,6 +858,8 @@ class FixMatchNTMStep:
             losses["kept"] = mask.sum()
         if loss_contrast is not None:
             losses["contrast"], losses["anchors"] = loss_contrast.detach(), self.contrast.anchors
+        if cfg["fused_tail"] and cfg["grad_norm_clip"] is not None:
+            losses["grad_norm"] = self.tail.total_norm       # (a device scalar the tail rewrites: read it behind the update)
         if defer_rest:
             return losses, rest
         rest()

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 24
+#define GEOT_ABI_VERSION 25
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -1086,6 +1086,62 @@ int geot_contrast_loss_grad(int b, int p, int d, int s, int channels_first, cons
                             float *grad, void *stream);
 int geot_contrast_enqueue(int b, int d, int s, const int *count, const int *enqueue_rows, const float *that, float *bank,
                           long long *ptr, void *stream);
+
+/* ---- the fused tail of an iteration: gradient clip + AdamW + the teacher's EMA (ABI 25) -------------------------------------
+ * torch.nn.utils.clip_grad_norm_(norm_type=2, error_if_nonfinite=False), torch.optim.AdamW's step (decoupled weight decay,
+ * both bias corrections; no amsgrad, no maximize) and t = d t + (1 - d) p for a mean teacher, over a list of T tensor
+ * records, in two sweeps that read every parameter once.  The reference clips and steps in torch ops (examples/segmentation/
+ * train.py:656-660, cfgs/tooth_semi/default.yaml:83) and names an ema_decay it never applies (cfgs/tooth_semi/
+ * transformer_finetune_fixmatch_ntm.yaml:66).
+ *
+ * A record is GEOT_OPTIM_TAIL_REC_WORDS 32-bit words in a HOST array: five 64-bit device addresses p, g, exp_avg,
+ * exp_avg_sq, t (t = 0: no teacher), the element count (int64), then four int32: first block (ignored on input: the
+ * launcher's), group id, flags, index of the record's step counter.  Flags: GEOT_OPTIM_TAIL_CLIPPED (g is part of the norm and
+ * is scaled by coef), GEOT_OPTIM_TAIL_VECTOR (ignored on input: set by the launcher when EVERY address of the record is 16-byte
+ * aligned -- dwordx4 accesses; otherwise one element per access), GEOT_OPTIM_TAIL_EMA_ONLY (a buffer, or a parameter without a
+ * gradient: only p and t are read, t = d t + (1 - d) p), GEOT_OPTIM_TAIL_INT64 (count int64 elements are copied from p to t).
+ * A group is GEOT_OPTIM_TAIL_GROUP_WORDS words: beta1, beta2 (double), eps, weight_decay, lr (float), one word of padding and
+ * a 64-bit device address of a float32 learning rate (0: use lr); at most GEOT_OPTIM_TAIL_MAX_GROUPS groups.
+ *
+ * The records reach the kernels BY VALUE in the kernel arguments, GEOT_OPTIM_TAIL_CAP per launch: nothing is uploaded, so the
+ * calls capture into kernel nodes alone although gradient addresses change every iteration.  A workgroup of 256 threads owns
+ * GEOT_OPTIM_TAIL_BLOCK_ELEMS consecutive elements of one record.
+ *
+ * geot_optim_tail_plan (host only): for T records with these counts, alignments (1: every address 16-byte aligned) and flags
+ *   -> out[0] launches of the update sweep, out[1] launches of the norm sweep, out[2] workgroups of the update sweep, out[3]
+ *   partial slots, out[4 + i] workgroups of record i, out[4 + T + i] its path (1 vector, 0 scalar).  Launch l of a sweep
+ *   holds the sweep's records [l CAP, (l + 1) CAP) and is not issued when they hold no element; the norm sweep's records are
+ *   the clipped ones that are neither EMA-only nor integer.  Returns 1, or 0 (n_out < 4 + 2 T, a negative count).  The
+ *   launchers below call the same function.
+ * geot_optim_tail_norm: slot k (fp32) = the sum of the squares of the k-th workgroup's gradient elements, workgroups counted
+ *   through the clipped records in table order.  Every one of the plan's slots is written; no atomics.  n_slots: the room.
+ * geot_optim_tail_finish: ONE workgroup.  clip != 0: the first n_slots slots are summed in a fixed order in double;
+ *   scalars[0] = total_norm = (float)sqrt(sum), scalars[1] = coef = min(1, max_norm / (total_norm + 1e-6)) in fp32 (a NaN
+ *   stays a NaN, an infinite norm gives 0, as torch.clamp does).  clip == 0: scalars = (0, 1).  Then steps[k] += 1 for the
+ *   step index k of every record that is neither EMA-only nor integer (they must differ).  More than
+ *   GEOT_OPTIM_TAIL_STEP_CAP such records take further launches of the same kernel.
+ * geot_optim_tail_update: per element in fp32, un-contracted, in this order:
+ *     g' = coef g (clipped records);  p1 = p - (lr wd) p;  m' = m + (1 - b1)(g' - m);  v' = b2 v + ((1 - b2) g') g';
+ *     p' = p1 - ((lr / bc1) m') / (sqrt(v') / sqrt(bc2) + eps);  t' = d t + (1 - d) p'   (t given)
+ *   with bc1 = 1 - b1^step, bc2 = 1 - b2^step from the counter geot_optim_tail_finish has just raised, formed in double.
+ *   g is NOT written back (a caller drops its gradients right after: zero_grad(set_to_none=True)).  0 <= ema_decay < 1.
+ * A malformed record, group or size is hipErrorInvalidValue before any launch. */
+#define GEOT_OPTIM_TAIL_CAP 48             /* records per launch */
+#define GEOT_OPTIM_TAIL_BLOCK_ELEMS 4096   /* elements per workgroup */
+#define GEOT_OPTIM_TAIL_STEP_CAP 896       /* step counters per geot_optim_tail_finish launch */
+#define GEOT_OPTIM_TAIL_REC_WORDS 16
+#define GEOT_OPTIM_TAIL_GROUP_WORDS 10
+#define GEOT_OPTIM_TAIL_MAX_GROUPS 4
+#define GEOT_OPTIM_TAIL_CLIPPED 1
+#define GEOT_OPTIM_TAIL_VECTOR 2
+#define GEOT_OPTIM_TAIL_EMA_ONLY 4
+#define GEOT_OPTIM_TAIL_INT64 8
+int geot_optim_tail_plan(int t, const long long *counts, const int *aligned, const int *flags, long long *out, int n_out);
+int geot_optim_tail_norm(int t, const void *records_host, float *slots, long long n_slots, void *stream);
+int geot_optim_tail_finish(int t, const void *records_host, int clip, long long n_slots, const float *slots, float max_norm,
+                           float *steps, int n_steps, float *scalars, void *stream);
+int geot_optim_tail_update(int t, const void *records_host, int n_groups, const void *groups_host, const float *scalars,
+                           const float *steps, int n_steps, double ema_decay, void *stream);
 
 #ifdef __cplusplus
 }
