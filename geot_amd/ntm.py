@@ -11,7 +11,9 @@ Mirrors the reference pieces that make up the FixMatch+NTM step (SURVEY.md secti
 Same constructor arguments / call signatures / returned tensors as the reference.  The
 per-point (B*N, C, C) work runs in fused HIP kernels (geot_amd/csrc/ntm.hip); the C x C
 bookkeeping of class_transition() is vectorised torch (no Python loop over classes, no
-host round trips -- the reference does 289 scalar device ops per step there).
+host round trips -- the reference does 289 scalar device ops per step there).  With
+filter_outlier the class anchors are an exact radix select per class and a filtered
+arg-max scan (filtered_anchors, geot_amd/csrc/ntm_outlier.hip).
 """
 import math
 import os
@@ -206,6 +208,25 @@ def _filtered_anchor_rows(eta, q):
     return torch.where(done, rows_f, rows_u), rows_f[cols, cols]
 
 
+FILTER_MAX_POINTS = 1 << 24     # B * N of geot_ntm_filtered_anchors (32-bit flat indices; fl32(B * N - 1) exact)
+
+
+def filtered_anchors(eta, q=0.97):
+    """_filtered_anchor_rows in two launches (csrc/ntm_outlier.hip): an exact radix select per class instead of
+    torch.quantile's full sort of a transposed copy, then the arg-max scan over the filtered values and the anchor rows.
+    eta (B, C, N) CUDA fp32, C <= 32, 1 <= B * N <= 2^24, 0 <= q <= 1.  Returns (class_T (C,C), v_star (C,), thresh (C,));
+    the contract is spelled out at geot_ntm_filtered_anchors in include/geot_hip.h: thresh is torch.quantile's linear
+    interpolation restated in un-contracted fp32, so it may differ from torch's own in the last bit of the last step."""
+    eta = f32(eta.detach().contiguous(), "filtered_anchors: eta", 3)      # (CPU tensors take _filtered_anchor_rows)
+    B, C, N = eta.shape
+    need(1 <= C <= 32 and 1 <= B * N <= FILTER_MAX_POINTS and 0.0 <= q <= 1.0,
+         "filtered_anchors: takes 1..32 classes, 1..2^24 points and 0 <= q <= 1, got C = %d, B * N = %d, q = %r" % (C, B * N, q))
+    class_T, v_star, thresh = torch.empty((C + 2, C), dtype=torch.float32, device=eta.device).split([C, 1, 1])
+    v_star, thresh = v_star.view(C), thresh.view(C)
+    call("geot_ntm_filtered_anchors", eta.device, B, N, C, float(q), ptr(eta), ptr(class_T), ptr(v_star), ptr(thresh))
+    return class_T, v_star, thresh
+
+
 def class_transition(eta, sigma, ema_t, geo_lambda=0.999, ema_decay=0.999, group=None, filter_outlier=False,
                      outlier_q=0.97):
     """The class-level transition estimate of train.py:505-545 + EMA update :556-557.
@@ -231,6 +252,8 @@ def class_transition(eta, sigma, ema_t, geo_lambda=0.999, ema_decay=0.999, group
     if fused:      # anchors in one launch (+ the transition block in another) instead of ~6 + ~40 torch launches
         if empty:
             class_T, v_star = class_T_e, v_star_e
+        elif filter_outlier and B * N <= FILTER_MAX_POINTS:
+            class_T, v_star, _ = filtered_anchors(eta, outlier_q)
         elif filter_outlier:
             class_T, v_star = _filtered_anchor_rows(eta, outlier_q)
         else:

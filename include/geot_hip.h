@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 25
+#define GEOT_ABI_VERSION 26
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -568,6 +568,23 @@ int geot_ntm_correct_grad(int b, int n, int c, float lam, const float *logits, c
  * eta[b, cc, n] (eta (b,c,n) fp32: the weak view's soft-max), the first maximum in flattened (b, n) order as
  * torch.argmax picks it; v_star (c, nullable) receives the maxima (the multi-rank exchange compares them). */
 int geot_ntm_class_anchors(int b, int n, int c, const float *eta, float *class_T, float *v_star, void *stream);
+/* The same anchors behind cfg.filter_outlier, train.py:510-526 (ABI 26; csrc/ntm_outlier.hip): before the arg-max of class cc
+ * every probability of that class at or above its q-quantile over the batch counts as 0.  1 <= c <= 32, 1 <= b*n <= 2^24,
+ * 0 <= q <= 1; anything else is hipErrorInvalidValue before any launch.  Two launches, no workspace: thresh (c) is a result
+ * and the only scratch; v_star (c) may be NULL.  Exactly:
+ *   thresh[cc] = torch.quantile(eta[:, cc, :].flatten(), q), linear interpolation, in fp32 as torch computes it: with M = b*n
+ *     and s the ascending order of the class's values, rank = fl32(q) * fl32(M-1) (one fp32 product), lo = floor(rank),
+ *     hi = ceil(rank), w = rank - lo, d = s[hi] - s[lo]; s[lo] + w*d when w < 0.5, else s[hi] - d*(1 - w), un-contracted
+ *     (a numpy float32 restatement reproduces the bits; torch's own lerp may be contracted: one ulp in the last step).
+ *     s[lo] and s[hi] come from an exact radix select on order-preserving keys of the bit patterns, so any finite float
+ *     orders correctly, negatives included (-0 and +0 in either order).
+ *   f(b, cc, n) = eta >= thresh[cc] ? 0 : eta    (0, not skipped: a class filtered everywhere has anchor 0, v_star 0)
+ *   anchor of cc = the first maximum of f(., cc, .) in flattened (b, n) order; v_star[cc] = that filtered maximum
+ *   class_T[cc][k] = f(b*, k, n*) for k <= cc, eta[b*, k, n*] for k > cc: the reference filters eta IN PLACE class after
+ *     class (robust_eta is a view, :511-513), so the row read at :526 sees columns 0..cc filtered and the later ones not.
+ * NaN is outside the contract, as for geot_ntm_class_anchors: results are then unspecified, accesses stay in bounds. */
+int geot_ntm_filtered_anchors(int b, int n, int c, double q, const float *eta, float *class_T, float *v_star, float *thresh,
+                              void *stream);
 /* Class-level transition block, train.py:505-557 once the anchor rows class_T (c,c) are gathered: Gaussian
  * tooth-adjacency prior from sigma (c) over the label projection proj (c) (train.py:48), blend, the three
  * `X / X.sum(1)` normalisations exactly as written there (column k divided by row-sum k), EMA.  c <= 32.
