@@ -8,6 +8,16 @@
 //                           of the records it is handed go up by one
 //   geot_optim_tail_update  sweep 2: g' = coef g, AdamW, t = d t + (1 - d) p_new, every parameter read once
 //
+// With step_per_update = k > 1 (ABI 27) the gradients of k calls are summed before one update, gated on a counter in device
+// memory, so that every call issues the same launches and one captured graph serves every call of a window:
+//
+//   geot_optim_tail_accumulate  sweep 1': acc = acc + g in a flat fp32 accumulator (one writer per element), and the sum of the
+//                               squares of the NEW accumulator values per workgroup, partitioned and ordered as sweep 1 does
+//   geot_optim_tail_acc_finish  one workgroup: raises the window counter; on call k of a window it does what
+//                               geot_optim_tail_finish does and resets the counter, otherwise nothing else
+//   geot_optim_tail_acc_update  sweep 2 with the accumulated value in the place of g, which it then zeroes; its workgroups
+//                               return at once on a call that is no update
+//
 // The records travel BY VALUE in the kernel arguments, OT_CAP per launch (gradient addresses are new every iteration, and
 // under graph capture an upload would be a memcpy node): the entry points read a host table and issue ceil(T / OT_CAP)
 // launches per sweep.  A workgroup finds its record by a scan of the launch's first-block indices (uniform, scalar loads).
@@ -185,6 +195,124 @@ __global__ __launch_bounds__(OT_THREADS) void ot_finish_kernel(const OtSteps st,
     }
 }
 
+// ---- step_per_update > 1: the gated window ------------------------------------------------------------------------------------
+struct OtSlotBase { int s[OT_CAP]; };                    // a record's first norm slot; -1: it is not part of the norm
+static_assert(sizeof(OtTable) + sizeof(OtSlotBase) + 64 <= 4096, "kernel arguments fit 4 KB");
+
+// acc = acc + g over the launch's records (g null: the record got no gradient in this call, its sum stands), and per workgroup
+// of a clipped record the sum of the squares of the new values: ot_norm_kernel's partition, its order within a thread and
+// within the workgroup, so that the slots hold what ot_norm_kernel gives for the summed gradient.
+__global__ __launch_bounds__(OT_THREADS) void ot_acc_kernel(const OtTable tab, const OtSlotBase sb, int count,
+                                                             float *__restrict__ acc, const long long *__restrict__ offs,
+                                                             long long n_acc, float *__restrict__ slots)
+{
+    __shared__ float lds[OT_THREADS / GEOT_WAVE];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int at = ot_find(tab, count, b);
+    const OtRec &r = tab.r[at];
+    const long long n = r.n, base = (long long)(b - r.first_block) * OT_BLOCK;
+    const long long off = offs[r.step];
+    if (off < 0 || (off & 3) || off + n > n_acc) return;   // (uniform; the host builds the table: never taken)
+    float *__restrict__ a = acc + off;
+    const float *__restrict__ g = r.g;
+    const bool add = g != nullptr;
+    float sum = 0.f;
+    if (r.flags & GEOT_OPTIM_TAIL_VECTOR) {
+#pragma unroll
+        for (int it = 0; it < OT_PER_THREAD / 4; ++it) {
+            const long long e = base + ((long long)it * OT_THREADS + tid) * 4;
+            if (e + 3 < n) {
+                float4 q = *reinterpret_cast<float4 *>(a + e);
+                if (add) {
+                    const float4 gq = *reinterpret_cast<const float4 *>(g + e);
+                    q.x = q.x + gq.x;
+                    q.y = q.y + gq.y;
+                    q.z = q.z + gq.z;
+                    q.w = q.w + gq.w;
+                    *reinterpret_cast<float4 *>(a + e) = q;
+                }
+                sum += q.x * q.x;
+                sum += q.y * q.y;
+                sum += q.z * q.z;
+                sum += q.w * q.w;
+            } else {
+                for (int k = 0; k < 4; ++k) {
+                    if (e + k < n) {
+                        float x = a[e + k];
+                        if (add) {
+                            x = x + g[e + k];
+                            a[e + k] = x;
+                        }
+                        sum += x * x;
+                    }
+                }
+            }
+        }
+    } else {
+#pragma unroll 4
+        for (int it = 0; it < OT_PER_THREAD; ++it) {
+            const long long e = base + (long long)it * OT_THREADS + tid;
+            if (e < n) {
+                float x = a[e];
+                if (add) {
+                    x = x + g[e];
+                    a[e] = x;
+                }
+                sum += x * x;
+            }
+        }
+    }
+    const int s0 = sb.s[at];
+    if (s0 < 0) return;                                  // (uniform)
+    const float total = ot_block_sum(sum, lds);
+    if (tid == 0) slots[s0 + (b - r.first_block)] = total;
+}
+
+// ot_finish_kernel behind the window counter.  gate[0]: calls of the open window, gate[1]: 1 when this call updates.  mode 1 / 2
+// (the first launch of a call): the counter goes up; at k it returns to 0 and the flag is set, otherwise the flag is cleared
+// and nothing else is written.  mode 0 (a further launch of step counters) follows the flag.
+__global__ __launch_bounds__(OT_THREADS) void ot_acc_finish_kernel(const OtSteps st, int n_steps, int mode, long long n_slots,
+                                                                    const float *__restrict__ slots, float max_norm,
+                                                                    float *__restrict__ steps, float *__restrict__ scalars,
+                                                                    int *__restrict__ gate, int k)
+{
+    __shared__ double lds[OT_THREADS];
+    __shared__ int update;
+    const int tid = threadIdx.x;
+    if (tid == 0) {                                      // (the only thread that touches the gate)
+        if (mode == 0) {
+            update = gate[1];
+        } else {
+            const int w = gate[0] + 1;
+            update = w >= k ? 1 : 0;
+            gate[0] = update ? 0 : w;
+            gate[1] = update;
+        }
+    }
+    __syncthreads();
+    if (!update) return;
+    for (int i = tid; i < n_steps; i += OT_THREADS) steps[st.idx[i]] += 1.0f;
+    if (mode == 2 && tid == 0) {
+        scalars[0] = 0.f;
+        scalars[1] = 1.f;
+    }
+    if (mode != 1) return;
+    double acc = 0.0;
+    for (long long i = tid; i < n_slots; i += OT_THREADS) acc += (double)slots[i];
+    lds[tid] = acc;
+    __syncthreads();
+    for (int half = OT_THREADS / 2; half > 0; half >>= 1) {
+        if (tid < half) lds[tid] += lds[tid + half];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const float total = (float)sqrt(lds[0]);
+        const float x = max_norm / (total + 1e-6f);
+        scalars[0] = total;
+        scalars[1] = x < 1.0f ? x : (x != x ? x : 1.0f);
+    }
+}
+
 struct OtConst {                     // what a record's elements share
     float coef, lrwd, omb1, b2, omb2, bc2_sqrt, eps, step_size, d, omd;
     bool teacher;
@@ -209,11 +337,23 @@ __device__ inline void ot_adamw(float &p, float g, float &m, float &v, float &t,
     if (c.teacher) t = c.d * t + c.omd * p;
 }
 
-__global__ __launch_bounds__(OT_THREADS) void ot_update_kernel(const OtTable tab, const OtGroups groups, int count,
-                                                                const float *__restrict__ scalars,
-                                                                const float *__restrict__ steps, double decay)
+// The accumulator of a gated tail: a flat buffer, the record with step index s at acc[offs[s]...]; gate[0] is the window
+// counter, gate[1] the flag "this call updates" the finish stage has just written.
+struct OtAcc {
+    float *acc;
+    const long long *offs;
+    long long n_acc;
+    const int *gate;
+};
+
+// ACC: the gradient is the record's stretch of the accumulator, zeroed once it is read; nothing happens unless gate[1] is set.
+template <bool ACC>
+__device__ __forceinline__ void ot_update_body(const OtTable &tab, const OtGroups &groups, int count,
+                                               const float *__restrict__ scalars, const float *__restrict__ steps,
+                                               double decay, const OtAcc &ac)
 {
     __shared__ float shared[2];
+    if (ACC && ac.gate[1] == 0) return;                  // (uniform: a call inside a window)
     const int b = blockIdx.x, tid = threadIdx.x;
     const OtRec &r = tab.r[ot_find(tab, count, b)];
     const long long n = r.n, base = (long long)(b - r.first_block) * OT_BLOCK;
@@ -279,7 +419,14 @@ __global__ __launch_bounds__(OT_THREADS) void ot_update_kernel(const OtTable tab
     c.step_size = shared[0];
     c.bc2_sqrt = shared[1];
     float *__restrict__ p = r.p;
-    const float *__restrict__ g = r.g;                   // read only: gradients are dropped right after the tail
+    // k = 1: read only (gradients are dropped right after the tail); ACC: the accumulator, read and zeroed by this thread
+    float *ga = nullptr;
+    if (ACC) {
+        const long long off = ac.offs[r.step];
+        if (off < 0 || (off & 3) || off + n > ac.n_acc) return;      // (uniform; the host builds the table: never taken)
+        ga = ac.acc + off;
+    }
+    const float *__restrict__ g = ACC ? nullptr : r.g;
     float *__restrict__ m = r.m;
     float *__restrict__ v = r.v;
     float *t = r.t;
@@ -289,7 +436,7 @@ __global__ __launch_bounds__(OT_THREADS) void ot_update_kernel(const OtTable tab
             const long long e = base + ((long long)it * OT_THREADS + tid) * 4;
             if (e + 3 < n) {
                 float4 pq = *reinterpret_cast<float4 *>(p + e);
-                const float4 gq = *reinterpret_cast<const float4 *>(g + e);
+                const float4 gq = *reinterpret_cast<const float4 *>((ACC ? ga : g) + e);
                 float4 mq = *reinterpret_cast<float4 *>(m + e);
                 float4 vq = *reinterpret_cast<float4 *>(v + e);
                 float4 tq = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -302,12 +449,14 @@ __global__ __launch_bounds__(OT_THREADS) void ot_update_kernel(const OtTable tab
                 *reinterpret_cast<float4 *>(m + e) = mq;
                 *reinterpret_cast<float4 *>(v + e) = vq;
                 if (c.teacher) *reinterpret_cast<float4 *>(t + e) = tq;
+                if (ACC) *reinterpret_cast<float4 *>(ga + e) = make_float4(0.f, 0.f, 0.f, 0.f);
             } else {
                 for (int k = 0; k < 4; ++k) {
                     if (e + k < n) {
                         float tt = c.teacher ? t[e + k] : 0.f;
-                        ot_adamw(p[e + k], g[e + k], m[e + k], v[e + k], tt, c, clipped);
+                        ot_adamw(p[e + k], ACC ? ga[e + k] : g[e + k], m[e + k], v[e + k], tt, c, clipped);
                         if (c.teacher) t[e + k] = tt;
+                        if (ACC) ga[e + k] = 0.f;
                     }
                 }
             }
@@ -317,18 +466,34 @@ __global__ __launch_bounds__(OT_THREADS) void ot_update_kernel(const OtTable tab
             const long long e = base + (long long)it * OT_THREADS + tid;
             if (e < n) {
                 float tt = c.teacher ? t[e] : 0.f;
-                ot_adamw(p[e], g[e], m[e], v[e], tt, c, clipped);
+                ot_adamw(p[e], ACC ? ga[e] : g[e], m[e], v[e], tt, c, clipped);
                 if (c.teacher) t[e] = tt;
+                if (ACC) ga[e] = 0.f;
             }
         }
     }
+}
+
+__global__ __launch_bounds__(OT_THREADS) void ot_update_kernel(const OtTable tab, const OtGroups groups, int count,
+                                                                const float *__restrict__ scalars,
+                                                                const float *__restrict__ steps, double decay)
+{
+    ot_update_body<false>(tab, groups, count, scalars, steps, decay, OtAcc{});
+}
+
+__global__ __launch_bounds__(OT_THREADS) void ot_acc_update_kernel(const OtTable tab, const OtGroups groups, int count,
+                                                                    const float *__restrict__ scalars,
+                                                                    const float *__restrict__ steps, double decay, const OtAcc ac)
+{
+    ot_update_body<true>(tab, groups, count, scalars, steps, decay, ac);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
 static inline bool ot_aligned16(const void *q) { return q == nullptr || (reinterpret_cast<uintptr_t>(q) & 15u) == 0; }
 
 // The table as the launches take it: checked, with the plan's paths set.  false: a record is malformed.
-static bool ot_prepare(int t, const void *records_host, int n_groups, int n_steps, std::vector<OtRec> &recs, OtPlan &plan)
+static bool ot_prepare(int t, const void *records_host, int n_groups, int n_steps, std::vector<OtRec> &recs, OtPlan &plan,
+                       bool need_g = true)
 {
     if (t < 0 || (t > 0 && !records_host)) return false;
     const OtRec *host = static_cast<const OtRec *>(records_host);
@@ -341,7 +506,7 @@ static bool ot_prepare(int t, const void *records_host, int n_groups, int n_step
         const bool held = r.n > 0;                       // (an empty tensor has no address)
         if (r.flags & (GEOT_OPTIM_TAIL_EMA_ONLY | GEOT_OPTIM_TAIL_INT64)) {
             if (held && (!r.p || !r.t)) return false;
-        } else if ((held && (!r.p || !r.g || !r.m || !r.v)) || r.group < 0 || r.group >= n_groups || r.step < 0 ||
+        } else if ((held && (!r.p || (need_g && !r.g) || !r.m || !r.v)) || r.group < 0 || r.group >= n_groups || r.step < 0 ||
                    r.step >= n_steps) {
             return false;
         }
@@ -463,6 +628,151 @@ GEOT_EXPORT int geot_optim_tail_update(int t, const void *records_host, int n_gr
     hipStream_t s = (hipStream_t)stream;
     const int err = ot_sweep(recs, plan, false, [&](const OtTable &tab, int count, int blocks, long long) {
         hipLaunchKernelGGL(ot_update_kernel, dim3(blocks), dim3(OT_THREADS), 0, s, tab, groups, count, scalars, steps, ema_decay);
+    });
+    return err ? err : hipGetLastError();
+}
+
+// ---- step_per_update > 1 ---------------------------------------------------------------------------------------------------
+namespace geot {
+
+// The launches of the gated tail for these records.  The accumulate sweep takes the records that are neither EMA-only nor
+// integer, OT_CAP per launch in table order (a launch without an element is not issued); the gated update sweep is ot_plan's
+// update sweep; the finish stage takes one launch per OT_STEP_CAP of the accumulate sweep's records, and at least one.
+struct OtAccPlan {
+    long long acc_launches = 0, acc_blocks = 0, finish_launches = 1;
+};
+
+static void ot_acc_plan(int t, const int *flags, const OtPlan &plan, OtAccPlan &ap)
+{
+    long long in_launch = 0, records = 0;
+    for (int i = 0; i < t; ++i) {
+        if (!ot_adamw_record(flags[i])) continue;
+        ap.acc_blocks += plan.blocks[(size_t)i];
+        in_launch += plan.blocks[(size_t)i];
+        if (++records % OT_CAP == 0) {
+            ap.acc_launches += in_launch > 0;
+            in_launch = 0;
+        }
+    }
+    ap.acc_launches += in_launch > 0;
+    ap.finish_launches = records > OT_STEP_CAP ? (records + OT_STEP_CAP - 1) / OT_STEP_CAP : 1;
+}
+
+} // namespace geot
+
+GEOT_EXPORT int geot_optim_tail_acc_plan(int t, const long long *counts, const int *aligned, const int *flags, long long *out,
+                                         int n_out)
+{
+    if (t < 0 || !out || n_out < 6 || (t > 0 && (!counts || !aligned || !flags))) return 0;
+    OtPlan plan;
+    if (!ot_plan(t, counts, aligned, flags, plan)) return 0;
+    OtAccPlan ap;
+    ot_acc_plan(t, flags, plan, ap);
+    out[0] = ap.acc_launches;
+    out[1] = ap.finish_launches;
+    out[2] = plan.update_launches;
+    out[3] = ap.acc_blocks;
+    out[4] = plan.update_blocks;
+    out[5] = plan.slots;
+    return 1;
+}
+
+GEOT_EXPORT int geot_optim_tail_accumulate(int t, const void *records_host, float *acc, const long long *acc_offsets,
+                                           long long n_acc, int n_steps, float *slots, long long n_slots, void *stream)
+{
+    if (!acc || !acc_offsets || n_acc < 0 || n_steps < 0 || n_slots < 0) return hipErrorInvalidValue;
+    if (reinterpret_cast<uintptr_t>(acc) & 15u) return hipErrorInvalidValue;
+    std::vector<OtRec> recs;
+    OtPlan plan;
+    if (!ot_prepare(t, records_host, GEOT_OPTIM_TAIL_MAX_GROUPS, n_steps, recs, plan, false)) return hipErrorInvalidValue;
+    if (plan.slots > n_slots || (plan.slots > 0 && !slots) || plan.slots > 0x7fffffffLL) return hipErrorInvalidValue;
+    std::vector<int> flags((size_t)t);
+    for (int i = 0; i < t; ++i) {
+        flags[(size_t)i] = recs[(size_t)i].flags;
+        if (ot_adamw_record(recs[(size_t)i].flags) && recs[(size_t)i].n > n_acc) return hipErrorInvalidValue;
+    }
+    OtAccPlan ap;
+    ot_acc_plan(t, flags.data(), plan, ap);
+    if (ap.acc_blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+    hipStream_t s = (hipStream_t)stream;
+    OtTable tab;
+    OtSlotBase sb;
+    int count = 0;
+    long long blocks = 0, slot = 0, issued = 0;
+    auto flush = [&]() {
+        if (blocks > 0) {
+            hipLaunchKernelGGL(ot_acc_kernel, dim3((unsigned)blocks), dim3(OT_THREADS), 0, s, tab, sb, count, acc, acc_offsets,
+                               n_acc, slots);
+            ++issued;
+        }
+        count = 0;
+        blocks = 0;
+    };
+    for (int i = 0; i < t; ++i) {
+        const OtRec &r = recs[(size_t)i];
+        if (!ot_adamw_record(r.flags)) continue;
+        tab.r[count] = r;
+        tab.r[count].first_block = (int)blocks;
+        sb.s[count] = ot_in_norm(r.flags) ? (int)slot : -1;
+        if (ot_in_norm(r.flags)) slot += plan.blocks[(size_t)i];
+        blocks += plan.blocks[(size_t)i];
+        if (++count == OT_CAP) flush();
+    }
+    flush();
+    if (issued != ap.acc_launches) return hipErrorUnknown;      // (the plan and the sweep are one rule)
+    return hipGetLastError();
+}
+
+GEOT_EXPORT int geot_optim_tail_acc_finish(int t, const void *records_host, int clip, long long n_slots, const float *slots,
+                                           float max_norm, float *steps, int n_steps, float *scalars, int *gate, int k,
+                                           void *stream)
+{
+    if (t < 0 || (t > 0 && !records_host) || !scalars || !gate || k < 1 || n_steps < 0 || n_slots < 0) return hipErrorInvalidValue;
+    if (clip && n_slots > 0 && !slots) return hipErrorInvalidValue;
+    const OtRec *host = static_cast<const OtRec *>(records_host);
+    std::vector<int> idx;
+    std::vector<bool> seen((size_t)n_steps, false);
+    for (int i = 0; i < t; ++i) {
+        if (!ot_adamw_record(host[i].flags)) continue;
+        const int c = host[i].step;
+        if (!steps || c < 0 || c >= n_steps || seen[(size_t)c]) return hipErrorInvalidValue;      // one writer per counter
+        seen[(size_t)c] = true;
+        idx.push_back(c);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    size_t at = 0;
+    int mode = clip ? 1 : 2;
+    do {
+        OtSteps st;
+        const int cnt = (int)((idx.size() - at < (size_t)OT_STEP_CAP) ? idx.size() - at : (size_t)OT_STEP_CAP);
+        for (int i = 0; i < cnt; ++i) st.idx[i] = idx[at + (size_t)i];
+        hipLaunchKernelGGL(ot_acc_finish_kernel, dim3(1), dim3(OT_THREADS), 0, s, st, cnt, mode, n_slots, slots, max_norm,
+                           steps, scalars, gate, k);
+        at += (size_t)cnt;
+        mode = 0;
+    } while (at < idx.size());
+    return hipGetLastError();
+}
+
+GEOT_EXPORT int geot_optim_tail_acc_update(int t, const void *records_host, int n_groups, const void *groups_host,
+                                           const float *scalars, const float *steps, int n_steps, double ema_decay, float *acc,
+                                           const long long *acc_offsets, long long n_acc, const int *gate, void *stream)
+{
+    if (n_groups < 0 || n_groups > GEOT_OPTIM_TAIL_MAX_GROUPS || (n_groups > 0 && !groups_host) || !scalars) return hipErrorInvalidValue;
+    if (!(ema_decay >= 0.0 && ema_decay < 1.0)) return hipErrorInvalidValue;
+    if (!acc || !acc_offsets || n_acc < 0 || !gate || (reinterpret_cast<uintptr_t>(acc) & 15u)) return hipErrorInvalidValue;
+    std::vector<OtRec> recs;
+    OtPlan plan;
+    if (!ot_prepare(t, records_host, n_groups, n_steps, recs, plan, false)) return hipErrorInvalidValue;
+    for (const OtRec &r : recs)
+        if (ot_adamw_record(r.flags) && (!steps || r.n > n_acc)) return hipErrorInvalidValue;
+    OtGroups groups = {};
+    for (int i = 0; i < n_groups; ++i) groups.g[i] = static_cast<const OtGroup *>(groups_host)[i];
+    const OtAcc ac = {acc, acc_offsets, n_acc, gate};
+    hipStream_t s = (hipStream_t)stream;
+    const int err = ot_sweep(recs, plan, false, [&](const OtTable &tab, int count, int blocks, long long) {
+        hipLaunchKernelGGL(ot_acc_update_kernel, dim3(blocks), dim3(OT_THREADS), 0, s, tab, groups, count, scalars, steps,
+                           ema_decay, ac);
     });
     return err ? err : hipGetLastError();
 }

@@ -38,6 +38,11 @@ SyncBatchNorm-converted modules with a gradient exchange of its own (train_step.
 all-reduce between backward and optimizer, a kernel node) replays like the single-GPU one -- SyncBatchNorm's statistic
 all-reduces and the anchor all-gather of the class transition are captured where they stand.
 
+cfg step_per_update = k > 1 (train.py:435, 440, 463, 657-669) with the fused tail replays the graphs of k = 1: the tail gates its
+update on a counter in device memory, every call issues the same launches, and the warm-up calls are calls of the window like
+the replays.  Without fused_tail the schedule is host logic and the wrappers refuse the step; with a GradSync (N > 1) they
+raise NotImplementedError -- the exchange belongs to update calls alone and a captured collective cannot be gated.
+
 Mirrors the loop body of examples/segmentation/train.py:410-669; the reference never leaves eager mode.
 """
 import copy
@@ -131,6 +136,19 @@ class _Graphed:
         them at the same point of the collective sequence -- the ranks fall back to the eager step together instead of
         meeting each other with different collectives."""
         self.agree = agree
+        # step_per_update = k > 1: the fused tail gates its update on a counter in device memory, so the graphs captured for
+        # k = 1 serve every call of a window (the warm-up calls are calls of the window like any other).  The torch form
+        # decides "update or not" in python, which a capture would bake in; a captured collective cannot be gated either.
+        if getattr(step, "step_per_update", 1) > 1:
+            tail = getattr(step, "tail", None)
+            if tail is None or tail.accumulate != step.step_per_update:
+                raise RuntimeError("graph_step: step_per_update=%d without fused_tail updates on a count kept in python, which "
+                                   "a captured graph would fix at one answer -- build the step with fused_tail=True (its tail "
+                                   "gates the update on a device counter)" % step.step_per_update)
+            if getattr(step, "grad_sync", None) is not None:
+                raise NotImplementedError("graph_step: step_per_update=%d with a gradient exchange of the step's own -- the "
+                                          "exchange belongs to update calls alone, and a captured collective cannot be "
+                                          "gated; run N > 1 with accumulation eagerly" % step.step_per_update)
         for net in (getattr(step, n, None) for n in ("model", "model_t", "T_predictor")):
             if isinstance(net, torch.nn.parallel.DistributedDataParallel):
                 raise RuntimeError(

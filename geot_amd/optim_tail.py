@@ -21,6 +21,18 @@ state loaded into the optimizer is adopted by the next step().
 composite() runs the same semantics in torch ops -- clip_grad_norm_, optimizer.step(), torch._foreach_lerp_ and a kernel copy
 for integer buffers: the second oracle of the tests and the baseline tools/time_optim_tail.py measures against.
 
+accumulate=k > 1 (cfg step_per_update, examples/segmentation/train.py:435, 440, 463, 657-669: the reference updates its
+optimizers every step_per_update-th iteration, and every backward in between adds into .grad): step() adds the gradients
+into one flat float32 accumulator, in call order, and call k of a window clips, steps and moves the teacher with the
+sum -- gated on a counter in device memory (`tail.window`), so that every call issues the same launches and one captured
+graph serves every call of a window.  The gradients are still dropped after every call.  total_norm / clip_coef are written
+by update calls only: between two updates they hold the norm of the last window's sum.  A window that an epoch cuts off is
+not lost: restart() returns the counter to 0 and keeps the sum, which joins the next window, as the reference's num_iter = 0
+(train.py:435) against its zero_grad() (train.py:664) has it.  `tail.window` and `tail.accumulator` are public: a checkpoint
+in the middle of a window saves both and hands them back with accumulator.copy_() and restart(window=n).  Which parameters
+an open window holds is followed on the host, by the eager calls (a replayed graph has its set fixed); a caller that changes the
+set of parameters with gradients between a replay and an eager call of one window starts that window with restart(drop=True).
+
 There is no fallback: a missing library or kernel raises.
 """
 import numpy as np
@@ -58,6 +70,29 @@ def plan(counts, aligned, flags):
             "blocks": out[4:4 + t].copy(), "vector": out[4 + t:].copy()}
 
 
+def acc_plan(counts, aligned, flags):
+    """geot_optim_tail_acc_plan: -> dict acc_launches, finish_launches, update_launches, acc_blocks, update_blocks, slots."""
+    t = len(counts)
+    counts = np.ascontiguousarray(counts, dtype=np.int64)
+    aligned = np.ascontiguousarray(aligned, dtype=np.int32)
+    flags = np.ascontiguousarray(flags, dtype=np.int32)
+    need(len(aligned) == t and len(flags) == t, "optim_tail.acc_plan: counts, aligned and flags must have one entry per record")
+    out = np.zeros(6, dtype=np.int64)
+    ok = _lib.load().geot_optim_tail_acc_plan(t, counts.ctypes.data, aligned.ctypes.data, flags.ctypes.data, out.ctypes.data, len(out))
+    need(ok == 1, "geot_optim_tail_acc_plan refused the records (a negative count)")
+    return dict(zip(("acc_launches", "finish_launches", "update_launches", "acc_blocks", "update_blocks", "slots"),
+                    (int(v) for v in out)))
+
+
+def check_accumulate(k, what="accumulate"):
+    """step_per_update: an int >= 1 (a bool is none)."""
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise TypeError("%s must be an int, got %r" % (what, k))
+    if k < 1:
+        raise ValueError("%s must be at least 1, got %r" % (what, k))
+    return k
+
+
 def _unwrapped(module):
     return module.module if hasattr(module, "module") else module
 
@@ -86,12 +121,14 @@ def teacher_pairs(student, teacher):
 
 
 class OptimTail:
-    def __init__(self, optimizers, clip_params=None, max_norm=None, teacher=None, student=None, ema_decay=None):
+    def __init__(self, optimizers, clip_params=None, max_norm=None, teacher=None, student=None, ema_decay=None, accumulate=1):
         """optimizers: torch.optim.AdamW objects, stepped in order, at most 4 parameter groups together (amsgrad / maximize
         groups are refused).  clip_params + max_norm: the parameters whose gradients clip_grad_norm_ would see, and its
         max_norm; max_norm None: no clipping, no norm sweep.  teacher + student + ema_decay: the teacher's state_dict() entries
         follow the student's -- float32 entries (parameters, BatchNorm running statistics) by t = d t + (1 - d) s with the
-        constant d = ema_decay, int64 entries (num_batches_tracked) by copy."""
+        constant d = ema_decay, int64 entries (num_batches_tracked) by copy.  accumulate = k: every k-th step() updates, with
+        the sum of the gradients of the k calls (module docstring); 1: every call, nothing is allocated for it."""
+        self.accumulate = check_accumulate(accumulate, "OptimTail: accumulate")
         self.optimizers = list(optimizers)
         need(self.optimizers, "OptimTail: no optimizer")
         self.groups = []                      # (optimizer, its group dict)
@@ -149,6 +186,19 @@ class OptimTail:
         self._plan = None
         self._group_table = np.zeros(len(self.groups), dtype=GROUP)
         self.launches = 0                     # kernel launches of the last step()
+        self.accumulator = self.window = None
+        self._kept = {}                       # composite(): parameter index -> the gradient summed so far
+        self._calls = self._composite_calls = 0       # the host's view of the window (which records an update holds)
+        self._pending = set()                 # parameter indices with a gradient in the open window
+        if self.accumulate > 1:
+            offsets, at = [], 0
+            for p, _, _ in self.params:       # every stretch starts on 16 bytes: the dwordx4 path
+                offsets.append(at)
+                at += -(-p.numel() // 4) * 4
+            self.accumulator = torch.zeros(max(at, 4), dtype=torch.float32, device=self.device)
+            self._acc_offsets = torch.tensor(offsets, dtype=torch.int64, device=self.device)       # written once, here
+            self._gate = torch.zeros(2, dtype=torch.int32, device=self.device)
+            self.window = self._gate[0]       # calls of the open window, a device int
 
     # ---- state ------------------------------------------------------------------------------------------------------------
     def _bind_state(self, active):
@@ -235,8 +285,86 @@ class OptimTail:
             gt[k]["eps"], gt[k]["weight_decay"] = group["eps"], group["weight_decay"]
         return gt
 
-    def step(self):
-        """clip + AdamW + EMA on the current stream.  The gradients are read, not scaled in place: drop them afterwards."""
+    def restart(self, drop=False, window=0):
+        """accumulate > 1: the window counter returns to `window` (0) and the sum accumulated so far STAYS -- the reference
+        restarts num_iter at every epoch (train.py:435) but zeroes its gradients only behind an update (train.py:664), so a
+        window that the end of an epoch cuts off joins the next epoch's first update.  drop=True also clears the sum.
+        accumulate == 1: nothing is issued."""
+        if self.accumulate == 1:
+            return
+        window = int(window)
+        need(0 <= window < self.accumulate, "OptimTail.restart: 0 <= window < accumulate")
+        self.window.fill_(window)
+        self._calls = self._composite_calls = window
+        if drop:
+            self.accumulator.zero_()
+            self._pending = set()
+            self._kept = {}
+
+    def _grad_ptr(self, g, p):
+        if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape or g.device != self.device or g.is_sparse:
+            raise RuntimeError("OptimTail: gradients must be dense contiguous float32 tensors like their parameters")
+        return g.data_ptr()
+
+    def _step_window(self, sync=None):
+        """step() with accumulate > 1: accumulate sweep, gated finish, gated update sweep -- the same launches every call."""
+        k = self.accumulate
+        capturing = torch.cuda.is_current_stream_capturing()
+        grads = {i: p.grad for i, (p, _, _) in enumerate(self.params) if p.grad is not None}
+        union = sorted(set(grads) | self._pending)
+        if capturing and union != sorted(grads):
+            raise RuntimeError("OptimTail: a captured call fixes the parameters of its window's update, and the open window "
+                               "holds the gradient of one that has none in this call -- capture behind an update, or restart(drop=True)")
+        rebuilt = self._bind_state(union)
+        if rebuilt or self._active != tuple(union):
+            self._build(union, None)
+        table = self._table
+        table["g"][:len(union)] = [self._grad_ptr(grads[i], self.params[i][0]) if i in grads else 0 for i in union]
+        aligned = np.ones(len(table), dtype=np.int32)
+        for key in ("p", "g", "m", "v", "t"):
+            aligned &= (table[key] % 16 == 0)
+        pl = acc_plan(table["n"], aligned, table["flags"])
+        clip = self.max_norm is not None
+        if clip and (self._slots is None or self._slots.numel() < max(pl["slots"], 1)):
+            self._slots = torch.empty(max(pl["slots"], 1), dtype=torch.float32, device=self.device)
+        dev, t, host = self.device, len(table), table.ctypes.data
+        acc, offs, gate = self.accumulator, self._acc_offsets, self._gate
+
+        def accumulate():
+            call("geot_optim_tail_accumulate", dev, t, host, acc.data_ptr(), offs.data_ptr(), acc.numel(), offs.numel(),
+                 self._slots.data_ptr() if clip else None, self._slots.numel() if clip else 0)
+        accumulate()
+        sweeps = 1
+        update_call = self._calls + 1 >= k
+        if sync is not None and update_call:
+            if capturing:
+                raise NotImplementedError("OptimTail: the gradient exchange of an accumulated window cannot be gated inside a graph")
+            sync.exchange(acc)
+            if clip:                          # the norm of the exchanged sum: the same sweep with nothing to add
+                table["g"][:len(union)] = 0
+                accumulate()
+                sweeps = 2
+        call("geot_optim_tail_acc_finish", dev, t, host, int(clip), pl["slots"] if clip else 0,
+             self._slots.data_ptr() if clip else None, self.max_norm if clip else 0.0, self.steps.data_ptr(),
+             self.steps.numel(), self.scalars.data_ptr(), gate.data_ptr(), k)
+        groups = self._groups_now()
+        call("geot_optim_tail_acc_update", dev, t, host, len(groups), groups.ctypes.data, self.scalars.data_ptr(),
+             self.steps.data_ptr(), self.steps.numel(), self.ema_decay if self.ema_decay is not None else 0.0,
+             acc.data_ptr(), offs.data_ptr(), acc.numel(), gate.data_ptr())
+        self._calls = 0 if update_call else self._calls + 1
+        self._pending = set() if update_call else set(union)
+        self.launches = sweeps * pl["acc_launches"] + pl["finish_launches"] + pl["update_launches"]
+        self.last_plan = pl
+        return self.total_norm
+
+    def step(self, sync=None):
+        """clip + AdamW + EMA on the current stream.  The gradients are read, not scaled in place: drop them afterwards.
+        accumulate > 1: the gradients join the window's sum, and call k of the window updates with it; total_norm is the norm
+        of the sum of the last COMPLETED window (update calls write it, the calls in between leave it).  The records of an
+        update are those of every parameter that had a gradient in any call of its window.  sync: an object whose
+        exchange(flat tensor) averages the accumulator over the ranks (train_step.GradSync), called on update calls only."""
+        if self.accumulate > 1:
+            return self._step_window(sync)
         active, grads = [], []
         for i, (p, _, _) in enumerate(self.params):
             g = p.grad
@@ -276,8 +404,25 @@ class OptimTail:
     # ---- the same semantics in torch ops ----------------------------------------------------------------------------------------
     def composite(self):
         """clip_grad_norm_ + optimizer.step() + torch._foreach_lerp_ (+ a kernel copy for integer buffers) -> total_norm
-        (None without a clip).  The optimizers keep whatever state they have (a state the fused step bound stays bound)."""
+        (None without a clip).  The optimizers keep whatever state they have (a state the fused step bound stays bound).
+        accumulate > 1: the gradients are added in place into kept ones (torch._foreach_add_); call k of a window hands
+        the sums back as .grad and runs the above, the calls before it return None and leave every state alone."""
         total = None
+        if self.accumulate > 1:
+            with torch.no_grad():
+                have = [(i, p.grad) for i, (p, _, _) in enumerate(self.params) if p.grad is not None]
+                for i, g in have:
+                    if i not in self._kept:
+                        self._kept[i] = torch.zeros_like(g)
+                if have:
+                    torch._foreach_add_([self._kept[i] for i, _ in have], [g for _, g in have])
+            self._composite_calls += 1
+            if self._composite_calls < self.accumulate:
+                return None
+            self._composite_calls = 0
+            for i, (p, _, _) in enumerate(self.params):
+                p.grad = self._kept.get(i)
+            self._kept = {}
         if self.max_norm is not None:
             total = torch.nn.utils.clip_grad_norm_(self.clip_params, self.max_norm)
         for opt in self.optimizers:

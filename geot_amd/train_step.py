@@ -33,7 +33,7 @@ NTM_CFG = dict(threshold=0.0, unsupervised_loss_weight=1.0, ema_t_decay=0.999, l
                feat_loss_weight=10.0, feat_k=16, feat_sigma=1.0, use_identity_loss=False, identity_loss_weight=1.0,
                pseudo_refine=False, pseudo_refine_size=4, pseudo_refine_neighbors=1,
                use_contrastive=False, contrastive_loss_weight=1.0, cur_threshold=0.9, contrast_samples=1024, contrast_seed=0,
-               ema_teacher=False, ema_decay=0.99, fused_tail=False)
+               ema_teacher=False, ema_decay=0.99, fused_tail=False, step_per_update=1)
 # cfgs/tooth_semi/transformer_finetune_fixmatch_ntm.yaml:45-96 (+ default.yaml); criterion / criterion_u are its
 # criterion_args.NAME / criterion_u_args.NAME (a {"NAME": ..., **constructor arguments} dict is taken too).
 # pseudo_refine (yaml:75, which the reference never reads): False, True (= "max") or one of utils/pseudo_mask.py's three
@@ -45,6 +45,10 @@ NTM_CFG = dict(threshold=0.0, unsupervised_loss_weight=1.0, ema_t_decay=0.999, l
 # after every update the teacher's state_dict() entries follow the student's, t = ema_decay t + (1 - ema_decay) s (integer
 # buffers are copied); fused_tail: clip + AdamW (+ that EMA) in one multi-tensor HIP pass (geot_amd/optim_tail.py) instead of
 # clip_grad_norm_ + optimizer.step() -- ema_teacher without it runs the same semantics in torch ops
+# step_per_update (train.py:435, 440, 463, 657-669): clipping, both optimizers, the EMA and zero_grad run on every
+# step_per_update-th call only, with the gradients of the calls in between summed; set_epoch() with another epoch restarts the
+# count and keeps the sum, as train.py:435 against :664 does.  With fused_tail the sum is the tail's flat accumulator and the
+# count a device int, so a replayed step needs no further graph; without it .grad accumulates in place (eager only)
 PSEUDO_REFINE_MODES = ("max", "margin", "margin_v1")
 PSEUDO_REFINE_MAX_SIZE = _lib.PSEUDO_REFINE_MAX_N      # include/geot_hip.h GEOT_PSEUDO_REFINE_MAX_N
 
@@ -96,12 +100,23 @@ def check_tail_cfg(cfg):
     for key in ("ema_teacher", "fused_tail"):
         if key in cfg and not isinstance(cfg[key], bool):
             raise TypeError("cfg %s must be a bool, got %r" % (key, cfg[key]))
+    if "step_per_update" in cfg:
+        check_step_per_update(cfg["step_per_update"], "cfg step_per_update")
     if "ema_decay" in cfg:
         d = cfg["ema_decay"]
         if isinstance(d, bool) or not isinstance(d, (int, float)):
             raise TypeError("cfg ema_decay must be a number, got %r" % (d,))
         if not 0.0 <= float(d) < 1.0:
             raise ValueError("cfg ema_decay must be in [0, 1), got %r" % (d,))
+
+
+def check_step_per_update(k, what="step_per_update"):
+    """An int >= 1 (a bool is none), checked on the host."""
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise TypeError("%s must be an int, got %r" % (what, k))
+    if k < 1:
+        raise ValueError("%s must be at least 1, got %r" % (what, k))
+    return k
 
 
 def check_contrast_cfg(cfg):
@@ -240,6 +255,15 @@ class GradSync:
         self.collectives += 1
         torch._foreach_copy_(flat_grads, self.views)
 
+    def exchange(self, flat):
+        """The same exchange for gradients that already lie in one flat buffer (OptimTail's accumulator under
+        step_per_update): divided by the world size, summed over the ranks, in place -- one collective."""
+        import torch.distributed as dist
+        if self.world > 1:
+            flat.mul_(1.0 / self.world)
+        dist.all_reduce(flat, group=self.group)
+        self.collectives += 1
+
 
 def _unwrapped(module):
     """The module inside a DistributedDataParallel wrapper (the module itself when it is not wrapped)."""
@@ -271,6 +295,38 @@ def _update(grad_sync, clip, model, optimizers, tail=None, fused=False):
     for optimizer in optimizers:
         optimizer.step()
         optimizer.zero_grad(set_to_none=True)
+
+
+def _window_update(step, clip, model, fused):
+    """_update under the step's step_per_update = k.  1: _update, call for call.  With the fused tail every call runs it: the
+    tail sums the gradients, gates the update on its device counter and exchanges its accumulator on update calls; the
+    gradients are dropped every time.  Otherwise the reference's form: nothing runs before call k of a window, and .grad
+    accumulates in place (host logic: eager only)."""
+    k = step.step_per_update
+    if k == 1:
+        return _update(step.grad_sync, clip, model, step.optimizers(), step.tail, fused)
+    if fused:
+        step.tail.step(sync=step.grad_sync)
+        for optimizer in step.optimizers():
+            optimizer.zero_grad(set_to_none=True)
+        return
+    step._window_calls += 1
+    if step._window_calls < k:
+        return
+    step._window_calls = 0
+    _update(step.grad_sync, clip, model, step.optimizers(), step.tail, False)
+
+
+def _accumulating(step, fused):
+    """The context of a call's forward and backward: with step_per_update > 1 in the torch form, a DistributedDataParallel
+    module runs the calls that do not update under its no_sync() -- its reducer exchanges the accumulated .grad on the update
+    call alone.  (With the fused tail the gradients are dropped after every call, so each call's exchange is needed.)"""
+    stack = contextlib.ExitStack()
+    if step.step_per_update > 1 and not fused and step._window_calls + 1 < step.step_per_update:
+        for m in step.sync_modules():
+            if isinstance(m, nn.parallel.DistributedDataParallel):
+                stack.enter_context(m.no_sync())
+    return stack
 
 
 def parameter_groups(model, weight_decay=1e-4, skip_list=()):
@@ -366,12 +422,16 @@ class _LookAhead:
 
 class SupervisedStep:
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, grad_norm_clip=None, grad_sync=None, criterion="Poly1FocalLoss",
-                 fused_tail=False):
+                 fused_tail=False, step_per_update=1):
         """criterion: cfg criterion_args -- "Poly1FocalLoss" or "Weight_CELoss" (or {"NAME": ..., **kwargs}); the latter takes
         the batch's class_weights (train.py:449-450).  fused_tail: clip + AdamW as one multi-tensor HIP pass
-        (geot_amd/optim_tail.py; with a clip, self.tail.total_norm is the gradient norm on the device)."""
+        (geot_amd/optim_tail.py; with a clip, self.tail.total_norm is the gradient norm on the device).  step_per_update = k:
+        clipping, the optimizer and zero_grad run on every k-th call with the gradients summed since (cfg step_per_update,
+        train.py:657-669) -- in the fused tail's accumulator, or without it in .grad (eager only); new_epoch() restarts the count."""
         if not isinstance(fused_tail, bool):
             raise TypeError("SupervisedStep: fused_tail must be a bool, got %r" % (fused_tail,))
+        self.step_per_update = check_step_per_update(step_per_update, "SupervisedStep: step_per_update")
+        self._window_calls = 0         # calls of the open window (the torch form's count; the fused tail keeps its own)
         self.criterion_name, self.criterion = _criterion(criterion, SUPERVISED_CRITERIA, "criterion")
         self.model = model
         self.optimizer = make_optimizer(model, lr, weight_decay)
@@ -382,10 +442,19 @@ class SupervisedStep:
         if fused_tail:
             from .optim_tail import OptimTail
             self.tail = OptimTail([self.optimizer], max_norm=grad_norm_clip,
-                                  clip_params=list(model.parameters()) if grad_norm_clip is not None else None)
+                                  clip_params=list(model.parameters()) if grad_norm_clip is not None else None,
+                                  accumulate=self.step_per_update)
 
     def optimizers(self):
         return [self.optimizer]
+
+    def new_epoch(self):
+        """step_per_update > 1: the count of the open window returns to 0 and the gradients summed so far stay, joining the
+        next epoch's first update (train.py:435 against :664).  With step_per_update = 1 nothing is issued."""
+        if self.step_per_update > 1:
+            self._window_calls = 0
+            if self.tail is not None:
+                self.tail.restart()
 
     def sync_modules(self):
         return [self.model]
@@ -399,7 +468,8 @@ class SupervisedStep:
         The queued work is used only if the next call passes that very tensor, unedited (the model checks the tensor, its
         version counter and, for WholePartSeg, the tensors it was assembled from); anything else is computed in line."""
         geometry, self._geometry = self._geometry, None
-        loss, self._geometry = self.iteration(pos, cls, target, geometry, next_pos, class_weights)
+        with _accumulating(self, self.tail is not None):
+            loss, self._geometry = self.iteration(pos, cls, target, geometry, next_pos, class_weights)
         return loss
 
     def lookahead_work(self, pos):
@@ -422,7 +492,7 @@ class SupervisedStep:
     def backward_update(self, loss):
         """The second half: backward, clipping, the optimizer -> the detached loss."""
         loss.backward()
-        _update(self.grad_sync, self.clip, self.model, self.optimizers(), self.tail, self.tail is not None)
+        _window_update(self, self.clip, self.model, self.tail is not None)
         return loss.detach()
 
     def forward_backward_head(self, pos, cls, target, geometry=None, class_weights=None):
@@ -447,7 +517,7 @@ class SupervisedStep:
         """The rest of the backward (the blocks, the patch encoder), clipping, the optimizer."""
         if rest is not None:
             torch.autograd.backward(rest[0], rest[1])
-        _update(self.grad_sync, self.clip, self.model, self.optimizers(), self.tail, self.tail is not None)
+        _window_update(self, self.clip, self.model, self.tail is not None)
 
     def iteration(self, pos, cls, target, geometry=None, next_pos=None, class_weights=None):
         """One iteration -> (detached loss, the geometry queued for next_pos or None)."""
@@ -509,12 +579,15 @@ class FixMatchNTMStep:
         # cfg ema_teacher / fused_tail (both off: no tail object, _update is the torch code it always was).  The teacher's
         # parameters keep requires_grad=False: the EMA writes their memory, autograd never sees them
         self.tail = None
+        self.step_per_update = self.cfg["step_per_update"]
+        self._window_calls = 0         # calls of the open window (the torch form's count; the fused tail keeps its own)
         if self.cfg["ema_teacher"] or self.cfg["fused_tail"]:
             from .optim_tail import OptimTail
             clip, ema = self.cfg["grad_norm_clip"], self.cfg["ema_teacher"]
             self.tail = OptimTail(self.optimizers(), clip_params=list(student.parameters()) if clip is not None else None,
                                   max_norm=clip, teacher=teacher if ema else None, student=student if ema else None,
-                                  ema_decay=self.cfg["ema_decay"] if ema else None)
+                                  ema_decay=self.cfg["ema_decay"] if ema else None,
+                                  accumulate=self.step_per_update if self.cfg["fused_tail"] else 1)
         self.ema_t = torch.eye(c, device=dev)                                          # train.py:274
         self.cm = cm if cm is not None else torch.full((c, c), 1.0 / c, device=dev)    # cal_mean_feature's output
         self.group = group
@@ -541,8 +614,15 @@ class FixMatchNTMStep:
 
     def set_epoch(self, epoch):
         """The epoch of the iterations that follow (train.py's loop variable): above cfg switch_ep the pseudo labels come
-        from the student's own weak view and the teacher no longer runs (train.py:469-475, 494-498)."""
-        self.epoch = None if epoch is None else int(epoch)
+        from the student's own weak view and the teacher no longer runs (train.py:469-475, 494-498).  cfg step_per_update
+        > 1: another epoch than the last restarts the count of the open window and keeps the gradients summed so far, which
+        join the new epoch's first update (train.py:435 against :664); with step_per_update = 1 nothing is issued."""
+        epoch = None if epoch is None else int(epoch)
+        if self.step_per_update > 1 and epoch != self.epoch:
+            self._window_calls = 0
+            if self.tail is not None:
+                self.tail.restart()
+        self.epoch = epoch
 
     @property
     def self_labelling(self):
@@ -571,7 +651,8 @@ class FixMatchNTMStep:
         alike, and the work is done in line)."""
         self.check_meter_batch(data_u)
         geoms, self._geometry = self._geometry, (None, None)
-        losses, self._geometry = self.iteration(data, data_u, geoms, next_batches)
+        with _accumulating(self, self.cfg["fused_tail"]):
+            losses, self._geometry = self.iteration(data, data_u, geoms, next_batches)
         return losses
 
     def _pseudo_labels(self, data_u, geom_t):
@@ -847,7 +928,7 @@ class FixMatchNTMStep:
             if ema_in_place:
                 with torch.no_grad():
                     torch.mul(ema_next, 1.0, out=self.ema_t)   # behind everything that read the old one (a kernel, not a memcpy node)
-            _update(self.grad_sync, cfg["grad_norm_clip"], self.model, self.optimizers(), self.tail, cfg["fused_tail"])
+            _window_update(self, cfg["grad_norm_clip"], self.model, cfg["fused_tail"])
         losses = {"loss": loss.detach(), "sup": sup_loss.detach(), "unsup": unsup_loss.detach(),
                   "threed": loss_3d.detach() if loss_3d is not None else torch.zeros((), device=loss.device)}
         if loss_feat is not None:

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 26
+#define GEOT_ABI_VERSION 27
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -1159,6 +1159,41 @@ int geot_optim_tail_finish(int t, const void *records_host, int clip, long long 
                            float *steps, int n_steps, float *scalars, void *stream);
 int geot_optim_tail_update(int t, const void *records_host, int n_groups, const void *groups_host, const float *scalars,
                            const float *steps, int n_steps, double ema_decay, void *stream);
+
+/* ---- the same tail with the gradients of k calls summed before one update (ABI 27; cfg step_per_update) ------------------------
+ * The reference updates its optimizers every cfg.step_per_update-th iteration only (examples/segmentation/train.py:435, 440,
+ * 463, 657-669): every backward adds into .grad, and clip_grad_norm_, both step() and both zero_grad() run when the count
+ * reaches step_per_update.  Here the sum lives in ONE flat float32 accumulator per tail, the count in device memory, and every
+ * call issues the same launches with the same arguments -- a captured graph of kernel nodes serves every call of a window.
+ * The record and the group are the ones above, unchanged; g may be 0 (the parameter got no gradient in this call).
+ *
+ * acc / acc_offsets / n_acc: the accumulator (16-byte aligned, n_acc floats) and a DEVICE table of n_steps int64 offsets into
+ *   it, indexed by a record's step-counter index; every offset a multiple of 4, offset + count <= n_acc (a record whose
+ *   offset breaks that is passed over by the kernels).  Written once by the caller; nothing is uploaded per call.
+ * gate: two DEVICE int32 -- gate[0] the calls of the open window (0 .. k-1 between calls), gate[1] whether the last
+ *   geot_optim_tail_acc_finish was an update.
+ * geot_optim_tail_acc_plan (host only): -> out[0] launches of the accumulate sweep, out[1] of the finish stage, out[2] of the
+ *   update sweep, out[3] workgroups of the accumulate sweep, out[4] of the update sweep, out[5] partial slots.  The
+ *   accumulate sweep holds the records that are neither EMA-only nor integer, GEOT_OPTIM_TAIL_CAP per launch in table order;
+ *   the update sweep is geot_optim_tail_plan's; paths and workgroups per record are geot_optim_tail_plan's too.  Returns 1,
+ *   or 0 (n_out < 6, a negative count).  The launchers below call the same function.
+ * geot_optim_tail_accumulate: acc[e] = acc[e] + g[e] in fp32 for every such record with g != 0, one writer per element, and
+ *   slot k (fp32) = the sum of the squares of the NEW accumulator values of the k-th workgroup of the clipped records, in
+ *   geot_optim_tail_norm's partition and order: the slots are what geot_optim_tail_norm gives for the summed gradient.
+ * geot_optim_tail_acc_finish: ONE workgroup.  gate[0] + 1 < k: gate = (gate[0] + 1, 0) and nothing else is written.
+ *   Otherwise gate = (0, 1) and the stage is geot_optim_tail_finish: total_norm and coef from the slots, the step counters.
+ * geot_optim_tail_acc_update: gate[1] == 0: every workgroup returns.  Otherwise geot_optim_tail_update with the accumulated
+ *   value in the place of g; the accumulator's elements are zeroed as they are read.  EMA-only and integer records are
+ *   applied under the same gate.
+ * A malformed record, group or size is hipErrorInvalidValue before any launch. */
+int geot_optim_tail_acc_plan(int t, const long long *counts, const int *aligned, const int *flags, long long *out, int n_out);
+int geot_optim_tail_accumulate(int t, const void *records_host, float *acc, const long long *acc_offsets, long long n_acc,
+                               int n_steps, float *slots, long long n_slots, void *stream);
+int geot_optim_tail_acc_finish(int t, const void *records_host, int clip, long long n_slots, const float *slots, float max_norm,
+                               float *steps, int n_steps, float *scalars, int *gate, int k, void *stream);
+int geot_optim_tail_acc_update(int t, const void *records_host, int n_groups, const void *groups_host, const float *scalars,
+                               const float *steps, int n_steps, double ema_decay, float *acc, const long long *acc_offsets,
+                               long long n_acc, const int *gate, void *stream);
 
 #ifdef __cplusplus
 }
