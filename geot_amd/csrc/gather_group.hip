@@ -1923,6 +1923,22 @@ static int three_interpolate_launch(int b, int c, int m, int n, const float *poi
     return hipGetLastError();
 }
 
+// host-only: the form geot_gather_points / geot_group_points / geot_three_interpolate[_into] launch for a table of m_table
+// floats per (batch, channel) row and n_out_elems output elements per row, and the table-in-LDS geometry (tlds_plan: the
+// same decision the four launchers take)
+GEOT_EXPORT int geot_gather_plan(int b, int c, int m_table, long long n_out_elems, long long *out, int n_out)
+{
+    if (b < 1 || c < 1 || m_table < 0 || n_out_elems < 1 || n_out_elems > 0x7fffffffLL) return 0;
+    const TldsPlan p = tlds_plan(b, c, m_table, n_out_elems, 1);
+    if (!p.ch) return 1;
+    if (out) {
+        const long long chunks = (c + p.ch - 1) / p.ch;
+        const long long v[5] = {p.ch, chunks, p.slices, (n_out_elems + p.slices - 1) / p.slices, (long long)p.lds};
+        for (int i = 0; i < n_out && i < 5; ++i) out[i] = v[i];
+    }
+    return 2;
+}
+
 GEOT_EXPORT int geot_three_interpolate(int b, int c, int m, int n, const float *points, const int *idx,
                                        const float *weight, float *out, void *stream)
 {

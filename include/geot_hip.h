@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 27
+#define GEOT_ABI_VERSION 28
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -73,6 +73,13 @@ int geot_gather_points_grad(int b, int c, int n, int m, const float *grad_out, c
  * workspace: geot_scatter_grad_ws_floats(b, c, n, m, 1, 0) floats of scratch. */
 int geot_gather_points_grad_ws(int b, int c, int n, int m, const float *grad_out, const int *idx,
                                float *grad_points, float *workspace, void *stream);
+/* Host-only (ABI 28): the form geot_gather_points, geot_group_points, geot_three_interpolate and
+ * geot_three_interpolate_into launch for a table of m_table floats per (batch, channel) row and n_out_elems output
+ * elements per row (m; npoints * nsample; n) -- 0 = nothing to launch, 1 = the plain register gather, 2 = the
+ * table-in-LDS gather -- under the same GEOT_GATHER_IMPL as the launches and from the planner the four launchers call.
+ * For 2, out receives the first n_out of: channels per workgroup, channel chunks, slices, elements per slice, LDS
+ * bytes.  out is a HOST array. */
+int geot_gather_plan(int b, int c, int m_table, long long n_out_elems, long long *out, int n_out);
 
 /* ---- ball query -------------------------------------------------------------
  * pointnet2/_ext_src/src/ball_query_gpu.cu:49-57 query_ball_point_kernel_wrapper

@@ -151,6 +151,17 @@ def test_host_only_planning_entry_points(monkeypatch):
                  (1, 6000, 32, 3, 3, (ctypes.c_int * 3)(64, 257, 128)), (-1, 6000, 32, 3, 3, w3)):
         untouched = (ctypes.c_longlong * 27)(*([-7] * 27))
         assert lib.geot_sa_plan(*args, 256, 1, untouched, 27) == 0 and list(untouched) == [-7] * 27
+    # forward gathers (ABI 28): 2 and the table-in-LDS geometry, a prefix on request, 1 / 0 and nothing written otherwise
+    gp = (ctypes.c_longlong * 5)(*([-7] * 5))
+    assert lib.geot_gather_plan(8, 384, 8192, 24000, gp, 5) == 2 and list(gp) == [4, 96, 1, 24000, 131072]
+    short = (ctypes.c_longlong * 5)(*([-7] * 5))
+    assert lib.geot_gather_plan(16, 8, 18432, 36864, short, 3) == 2 and list(short) == [2, 4, 8, -7, -7]
+    for args, form in (((1, 16, 64, 4095), 1), ((1, 2, 36865, 32768), 1), ((0, 16, 64, 4096), 0), ((1, 16, 64, 0), 0)):
+        untouched = (ctypes.c_longlong * 5)(*([-7] * 5))
+        assert lib.geot_gather_plan(*args, untouched, 5) == form and list(untouched) == [-7] * 5
+    monkeypatch.setenv("GEOT_GATHER_IMPL", "plain")             # the environment switch moves the plan with the dispatch
+    assert lib.geot_gather_plan(8, 384, 8192, 24000, gp, 5) == 1
+    monkeypatch.delenv("GEOT_GATHER_IMPL")
 
 
 def test_grid_search_plan_entry_points(monkeypatch):

@@ -605,6 +605,9 @@ def test_fps_multi_commit_soak_against_unpruned_kernel(ext, monkeypatch):
 def test_lds_table_paths_match_plain_kernels(ext, b, c, m, L, monkeypatch):
     """table-in-LDS gather (forward) and reverse-index gather (backward) against the register-gather / atomic
     kernels on odd shapes: forward bit for bit, backward to summation order."""
+    from geot_amd import _lib
+    for n_out in (L, L // 4 * 4):                 # three_interpolate / gather_points, group_points: all plan the LDS form
+        assert _lib.load().geot_gather_plan(b, c, m, n_out, None, 0) == 2, (b, c, m, n_out)
     rng = np.random.default_rng(b * 1000 + c)
     feat = dev(rng.standard_normal((b, c, m)).astype(np.float32))
     idx3 = dev(rng.integers(0, m, (b, L, 3)).astype(np.int32))
