@@ -18,7 +18,8 @@ An iteration is two SINGLE-STREAM graphs (geot_amd/streams.py: on ROCm 7.0 a gra
   update, so its forward cannot run beside the update before it: before switch_ep that step has a third phase ("P@e" /
   "M@e") whose P holds the student's and the teacher's geometry, the kNN graph / order and the refine table -- no pseudo
   labels, no teacher feature -- and whose M starts with the teacher's forward and ends with the tail that moves it; after
-  switch_ep the teacher no longer runs and "P@2" / "M@2" are what they were, M@2 with the tail at its end.
+  switch_ep the teacher no longer runs and "P@2" / "M@2" are what they were, M@2 with the tail at its end.  The step says
+  which phase it is in and which batch keys its look-ahead reads there; its product (train_step.BatchWork) is only handed on.
 * **M** -- the training iteration proper over P's product: forward, losses, backward, AdamW (capturable=True; under
   fused=True the step counters live on the device either way: the same kernel), the EMA transition matrix updated in
   its buffer.
@@ -54,44 +55,38 @@ from . import streams
 
 
 # ---- structure helpers: P's product is a tree of dicts / tuples (plain and named) of tensors, python scalars and objects
-# that say themselves which of their attributes are buffers and which identities (`tree_fields()`: Geometry, ReverseIndex) ----
+# that say themselves which of their attributes are buffers and which identities (`tree_fields()`: Geometry, ReverseIndex, the FixMatch step's BatchWork) ----
 def _rebuilt(obj, items):
     return type(obj)(*items) if hasattr(obj, "_fields") else type(obj)(items)      # (a namedtuple takes its items one by one)
 
 
-def tree_clone(obj):
-    """Fresh buffers with the same contents; identities (tensors matched by `is`, events) dropped."""
+def _tree_map(obj, leaf, keep_identities):
+    """The tree rebuilt (containers and tree_fields() objects) with leaf(tensor) for every tensor, everything else as it is."""
     if torch.is_tensor(obj):
-        return obj.detach().clone()
+        return leaf(obj)
     if isinstance(obj, dict):
-        return {k: tree_clone(v) for k, v in obj.items()}
+        return {k: _tree_map(v, leaf, keep_identities) for k, v in obj.items()}
     if isinstance(obj, (list, tuple)):
-        return _rebuilt(obj, [tree_clone(v) for v in obj])
+        return _rebuilt(obj, [_tree_map(v, leaf, keep_identities) for v in obj])
     if hasattr(obj, "tree_fields"):
         buffers, identities = obj.tree_fields()
         new = copy.copy(obj)
         for k in buffers:
-            setattr(new, k, tree_clone(getattr(obj, k)))
-        for k in identities:
+            setattr(new, k, _tree_map(getattr(obj, k), leaf, keep_identities))
+        for k in () if keep_identities else identities:
             setattr(new, k, None)
         return new
     return obj
 
 
+def tree_clone(obj):
+    """Fresh buffers with the same contents; identities (tensors matched by `is`, events) dropped."""
+    return _tree_map(obj, lambda t: t.detach().clone(), False)
+
+
 def tree_detach(obj):
-    """The same buffers without their autograd history (containers and tree_fields() objects rebuilt, everything else as it is)."""
-    if torch.is_tensor(obj):
-        return obj.detach()
-    if isinstance(obj, dict):
-        return {k: tree_detach(v) for k, v in obj.items()}
-    if isinstance(obj, (list, tuple)):
-        return _rebuilt(obj, [tree_detach(v) for v in obj])
-    if hasattr(obj, "tree_fields"):
-        new = copy.copy(obj)
-        for k in obj.tree_fields()[0]:
-            setattr(new, k, tree_detach(getattr(obj, k)))
-        return new
-    return obj
+    """The same buffers without their autograd history."""
+    return _tree_map(obj, torch.Tensor.detach, True)
 
 
 def tree_copy_(dst, src, path="pre"):
@@ -299,6 +294,18 @@ class _Graphed:
         self.calls += 1
         return out
 
+    def _split(self, args):
+        """The pair _iterate takes for a split capture: the step's forward_backward_head(*args()) / backward_rest_update.  M1's
+        product is what is left of the backward, as data (tree_detach releases it); the step's result waits here for M2."""
+        def head():
+            self._result, rest = self.step.forward_backward_head(*args())
+            return rest
+
+        def rest_update(rest):
+            self.step.backward_rest_update(rest)
+            return self._result
+        return head, rest_update
+
     def _is_announced(self, tensors):
         a = self._announced
         return a is not None and len(a) == len(tensors) and all(t is s and t._version == v for t, (s, v) in zip(tensors, a))
@@ -355,25 +362,8 @@ class GraphedSupervisedStep(_Graphed):
         def train():
             return self.step.iteration(self.x[0], self.x[1], self.x[2], self.pre, None, cw)[0]
         if self.split:
-            def head():
-                self._loss, rest = self.step.forward_backward_head(self.x[0], self.x[1], self.x[2], self.pre, cw)
-                return rest
-
-            def rest_update(rest):
-                self.step.backward_rest_update(rest)
-                return self._loss
-            train = (head, rest_update)
+            train = self._split(lambda: (self.x[0], self.x[1], self.x[2], self.pre, cw))
         return self._iterate(announced_now, None if next_pos is None else (next_pos,), load_next, lookahead, train)
-
-
-_P_KEYS = (("pos",), ("pos_s", "pos_w", "x_w", "cls_w", "raw_pos"))      # what FixMatchNTMStep.lookahead_work reads
-_P_KEYS_2 = (("pos",), ("pos_s", "pos_w", "raw_pos"))                     # ... after switch_ep (no teacher forward)
-
-
-def _p_keys(self_labelling, use_3d_loss=True):
-    """... and without raw_pos when cfg use_3d_loss is off: the look-ahead then builds no kNN graph and no Morton order."""
-    keys = _P_KEYS_2 if self_labelling else _P_KEYS
-    return keys if use_3d_loss else (keys[0], tuple(k for k in keys[1] if k != "raw_pos"))
 
 
 class GraphedFixMatchStep(_Graphed):
@@ -399,15 +389,12 @@ class GraphedFixMatchStep(_Graphed):
             self.data = {k: v.detach().clone().contiguous() for k, v in data.items() if torch.is_tensor(v)}
             self.data_u = {k: v.detach().clone().contiguous() for k, v in data_u.items() if torch.is_tensor(v) and k != "T"}
             self.next = tuple({k: torch.empty_like(d[k]) for k in keys}
-                              for d, keys in zip((self.data, self.data_u), _p_keys(False, step.cfg.get("use_3d_loss", True))))
+                              for d, keys in zip((self.data, self.data_u), step.lookahead_keys("")))      # (the widest phase's)
         for dst, src, what in ((self.data, data, "data"), (self.data_u, data_u, "data_u")):
             for k, v in dst.items():
                 _fits(v, src[k], "%s[%r]" % (what, k))
         self._check_lr()
-        self_labelling = step.self_labelling
-        moving = bool(step.cfg.get("ema_teacher")) and not self_labelling      # the teacher's forward belongs to M: phase "@e"
-        tag = "@2" if self_labelling else "@e" if moving else ""
-        p_keys = _p_keys(self_labelling, step.cfg.get("use_3d_loss", True))
+        p_keys = step.lookahead_keys()
         announced_now = self._is_announced([b[k] for b, keys in zip((data, data_u), p_keys) for k in keys])
         self._join_pending()
         for dst, src in ((self.data, data), (self.data_u, data_u)):
@@ -422,35 +409,14 @@ class GraphedFixMatchStep(_Graphed):
                     dst[k].copy_(src[k])
 
         def lookahead():
-            return step.lookahead_work(self.next[0], self.next[1], self_labelling=self_labelling)
-
-        def pseudo_of(pre):
-            """(pseudo labels, teacher feature) of M: P's product, or -- a moving teacher -- its forward, here."""
-            if not moving:
-                return pre["pseudo"], pre.get("feat_t")
-            pseudo = step._pseudo_labels(self.data_u, pre["geom_t"])
-            return pseudo, step._teacher_feature()
+            return step.lookahead_work(self.next[0], self.next[1])
 
         def train():
-            pre = self.pre
-            pseudo, feat_t = pseudo_of(pre)
-            return step.student_iteration(self.data, self.data_u, pre["geom_s"], pseudo, pre["knn"], ema_in_place=True,
-                                          refine_nbr=pre.get("refine_nbr"), feat_t=feat_t)
+            return step.student_iteration(self.data, self.data_u, self.pre)
         if self.split:
-            def head():
-                pre = self.pre
-                pseudo, feat_t = pseudo_of(pre)
-                self._losses, rest = step.student_iteration(self.data, self.data_u, pre["geom_s"], pseudo, pre["knn"],
-                                                            ema_in_place=True, defer_rest=True,
-                                                            refine_nbr=pre.get("refine_nbr"), feat_t=feat_t)
-                return rest
-
-            def rest_update(rest):
-                rest()
-                return self._losses
-            train = (head, rest_update)
+            train = self._split(lambda: (self.data, self.data_u, self.pre))
         next_src = None if next_batches is None else [b[k] for b, keys in zip(next_batches, p_keys) for k in keys]
-        return self._iterate(announced_now, next_src, load_next, lookahead, train, tag)
+        return self._iterate(announced_now, next_src, load_next, lookahead, train, step.phase)
 
     def set_epoch(self, epoch):
         """The wrapped step's set_epoch."""

@@ -329,6 +329,52 @@ def _accumulating(step, fused):
     return stack
 
 
+class _UpdateWindow:
+    """What both steps keep of the open update window (cfg step_per_update): the calls counted so far in the torch form, the
+    clip value and whether the tail is its fused pass -- the arguments of _window_update / _accumulating, held once."""
+
+    def open_window(self, step_per_update, clip, fused):
+        self.step_per_update, self.clip, self.fused = step_per_update, clip, fused
+        self._window_calls = 0         # calls of the open window (the torch form's count; the fused tail keeps its own)
+
+    def restart_window(self):
+        """step_per_update > 1: the count of the open window returns to 0 and the gradients summed so far stay, joining the
+        next window's first update (train.py:435 against :664).  With step_per_update = 1 nothing is issued."""
+        if self.step_per_update > 1:
+            self._window_calls = 0
+            if self.tail is not None:
+                self.tail.restart()
+
+
+class _Cut:
+    """A forward with the segmentor cutting its autograd graph at the transformer blocks (cut_at_blocks / take_cut), for a
+    two-phase backward:  with _Cut(seg) as cut: <forward>;  loss.backward() then stops at the blocks and cut.rest() hands
+    back the second phase as data -- (the blocks' outputs, their gradients), what backward_rest() takes; None for a model
+    that cannot cut (or on=False): loss.backward() was the whole backward."""
+
+    def __init__(self, seg, on=True):
+        self.seg, self.cut = seg if on and hasattr(seg, "take_cut") else None, None
+
+    def __enter__(self):
+        if self.seg is not None:
+            self.seg.cut_at_blocks = True
+        return self
+
+    def __exit__(self, kind, *_):
+        if self.seg is not None:
+            self.seg.cut_at_blocks = False
+            self.cut = self.seg.take_cut() if kind is None else None
+
+    def rest(self):
+        return None if self.cut is None else (self.cut[0], [d.grad for d in self.cut[1]])
+
+
+def backward_rest(rest):
+    """The rest of a backward that _Cut stopped at the blocks (the blocks, the patch encoder); None: nothing is left."""
+    if rest is not None:
+        torch.autograd.backward(rest[0], rest[1])
+
+
 def parameter_groups(model, weight_decay=1e-4, skip_list=()):
     """The two AdamW parameter groups of the reference's optimizer factory (openpoints/optim/optim_factory.py:66-119
     get_parameter_groups, reached through build_optimizer_from_cfg :190-198 with its default filter_bias_and_bn=True,
@@ -362,6 +408,49 @@ def _join(dev, side, *tensors):
         for t in tensors:
             if t is not None and t.is_cuda:
                 t.record_stream(cur)
+
+
+class BatchWork:
+    """Everything of a FixMatch iteration that depends on its batches (and on frozen state) alone -- what
+    FixMatchNTMStep.lookahead_work() returns and student_iteration() consumes.  None: not part of this phase / switch off.
+    geom_s / geom_t: the student's / the teacher's Geometry (geom_t only while a MOVING teacher's forward is still to run:
+    a frozen teacher's forward has consumed it); pseudo: (pred_u, logits_u_aug, label_u_aug) of the teacher, feat_t: its
+    head feature (cfg use_contrastive); knn: (nbr, order), the 3-D loss's kNN graph and Morton order of raw_pos (cfg
+    use_3d_loss); refine_nbr: the weak view's neighbour table (cfg pseudo_refine, utils/pseudo_mask.py neighbours).
+    The object alone knows which fields were made on a side stream (made_on) and still need joining: the first read of
+    such a field hands it -- and the fields made with it -- to the current stream (_join); a product made in line has
+    nothing to join.  made() asks whether a field is there without joining it."""
+    FIELDS = ("geom_s", "geom_t", "pseudo", "feat_t", "knn", "refine_nbr")
+
+    def __init__(self, geom_s=None, geom_t=None, pseudo=None, feat_t=None, knn=None, refine_nbr=None):
+        self.__dict__.update(geom_s=geom_s, geom_t=geom_t, pseudo=pseudo, feat_t=feat_t, knn=knn, refine_nbr=refine_nbr)
+        self._sides = {}               # field -> (side stream, the fields made there together), until joined
+
+    def tree_fields(self):
+        """(buffers, identities) for graph_step.py, as Geometry.tree_fields: a clone has nothing left to join."""
+        return self.FIELDS, ("_sides",)
+
+    def made_on(self, side, *names):
+        """These fields were queued on `side` together (None: in line, nothing to join)."""
+        for n in names if side is not None else ():
+            self._sides[n] = (side, names)
+
+    def made(self, name):
+        return self.__dict__[name] is not None
+
+    def _read(self, name):
+        pending = self._sides.pop(name, None) if self._sides else None
+        if pending is not None:
+            side, names = pending
+            for n in names:
+                self._sides.pop(n, None)
+            values = [self.__dict__[n] for n in names]
+            _join(side.device, side, *(t for v in values for t in (v if isinstance(v, tuple) else (v,))))
+        return self.__dict__[name]
+
+
+for _name in BatchWork.FIELDS:      # plain attributes to write; reading one joins it first
+    setattr(BatchWork, _name, property(lambda self, n=_name: self._read(n), lambda self, v, n=_name: self.__dict__.__setitem__(n, v)))
 
 
 def make_optimizer(model, lr=1e-3, weight_decay=1e-4):
@@ -420,7 +509,7 @@ class _LookAhead:
         return self.queued
 
 
-class SupervisedStep:
+class SupervisedStep(_UpdateWindow):
     def __init__(self, model, lr=1e-3, weight_decay=1e-4, grad_norm_clip=None, grad_sync=None, criterion="Poly1FocalLoss",
                  fused_tail=False, step_per_update=1):
         """criterion: cfg criterion_args -- "Poly1FocalLoss" or "Weight_CELoss" (or {"NAME": ..., **kwargs}); the latter takes
@@ -430,12 +519,10 @@ class SupervisedStep:
         train.py:657-669) -- in the fused tail's accumulator, or without it in .grad (eager only); new_epoch() restarts the count."""
         if not isinstance(fused_tail, bool):
             raise TypeError("SupervisedStep: fused_tail must be a bool, got %r" % (fused_tail,))
-        self.step_per_update = check_step_per_update(step_per_update, "SupervisedStep: step_per_update")
-        self._window_calls = 0         # calls of the open window (the torch form's count; the fused tail keeps its own)
+        self.open_window(check_step_per_update(step_per_update, "SupervisedStep: step_per_update"), grad_norm_clip, fused_tail)
         self.criterion_name, self.criterion = _criterion(criterion, SUPERVISED_CRITERIA, "criterion")
         self.model = model
         self.optimizer = make_optimizer(model, lr, weight_decay)
-        self.clip = grad_norm_clip
         self._geometry = None          # coordinate-only work of the next batch, queued by the previous call
         self.grad_sync = grad_sync     # a GradSync: the step exchanges its gradients itself (bare modules: sync_only)
         self.tail = None
@@ -448,13 +535,7 @@ class SupervisedStep:
     def optimizers(self):
         return [self.optimizer]
 
-    def new_epoch(self):
-        """step_per_update > 1: the count of the open window returns to 0 and the gradients summed so far stay, joining the
-        next epoch's first update (train.py:435 against :664).  With step_per_update = 1 nothing is issued."""
-        if self.step_per_update > 1:
-            self._window_calls = 0
-            if self.tail is not None:
-                self.tail.restart()
+    new_epoch = _UpdateWindow.restart_window       # (the next call opens an epoch)
 
     def sync_modules(self):
         return [self.model]
@@ -468,7 +549,7 @@ class SupervisedStep:
         The queued work is used only if the next call passes that very tensor, unedited (the model checks the tensor, its
         version counter and, for WholePartSeg, the tensors it was assembled from); anything else is computed in line."""
         geometry, self._geometry = self._geometry, None
-        with _accumulating(self, self.tail is not None):
+        with _accumulating(self, self.fused):
             loss, self._geometry = self.iteration(pos, cls, target, geometry, next_pos, class_weights)
         return loss
 
@@ -492,32 +573,22 @@ class SupervisedStep:
     def backward_update(self, loss):
         """The second half: backward, clipping, the optimizer -> the detached loss."""
         loss.backward()
-        _window_update(self, self.clip, self.model, self.tail is not None)
+        _window_update(self, self.clip, self.model, self.fused)
         return loss.detach()
 
     def forward_backward_head(self, pos, cls, target, geometry=None, class_weights=None):
         """The iteration up to the point where the backward reaches the transformer blocks -- forward, loss, the backward of
         the head and the decoder -- for a model that can cut its autograd graph there (cut_at_blocks / take_cut: the
         segmentor); otherwise the whole backward.  -> (detached loss, what backward_rest_update needs)."""
-        inner = _unwrapped(self.model)
-        can_cut = hasattr(inner, "take_cut")
-        if can_cut:
-            inner.cut_at_blocks = True
-        try:
+        with _Cut(_unwrapped(self.model)) as cut:
             loss = self.forward_loss(pos, cls, target, geometry, class_weights)
-        finally:
-            if can_cut:
-                inner.cut_at_blocks = False
-        cut = inner.take_cut() if can_cut else None
         loss.backward()
-        rest = None if cut is None else (cut[0], [d.grad for d in cut[1]])
-        return loss.detach(), rest
+        return loss.detach(), cut.rest()
 
     def backward_rest_update(self, rest):
         """The rest of the backward (the blocks, the patch encoder), clipping, the optimizer."""
-        if rest is not None:
-            torch.autograd.backward(rest[0], rest[1])
-        _window_update(self, self.clip, self.model, self.tail is not None)
+        backward_rest(rest)
+        _window_update(self, self.clip, self.model, self.fused)
 
     def iteration(self, pos, cls, target, geometry=None, next_pos=None, class_weights=None):
         """One iteration -> (detached loss, the geometry queued for next_pos or None)."""
@@ -533,7 +604,17 @@ class SupervisedStep:
         return loss, look.done()
 
 
-class FixMatchNTMStep:
+PHASES = ("", "@e", "@2")      # frozen teacher; moving teacher (cfg ema_teacher), up to switch_ep; self-labelling, after it
+
+
+def lookahead_keys(phase, cfg):
+    """The keys of (data, data_u) FixMatchNTMStep.lookahead_work reads in `phase`: after switch_ep no teacher forward, and
+    without cfg use_3d_loss no raw_pos -- the look-ahead then builds no kNN graph and no Morton order."""
+    keys_u = ("pos_s", "pos_w", "raw_pos") if phase == "@2" else ("pos_s", "pos_w", "x_w", "cls_w", "raw_pos")
+    return ("pos",), keys_u if cfg.get("use_3d_loss", True) else tuple(k for k in keys_u if k != "raw_pos")
+
+
+class FixMatchNTMStep(_UpdateWindow):
     """State of train_one_epoch that survives an iteration: ema_t (C,C), cm (C,C), both optimisers (and the epoch meters,
     when asked for).  The epoch set by set_epoch() picks the pseudo labels' source, as train.py:469-498 does: the frozen
     teacher up to cfg switch_ep (and when no epoch was ever set), the student's own weak view after it."""
@@ -579,8 +660,7 @@ class FixMatchNTMStep:
         # cfg ema_teacher / fused_tail (both off: no tail object, _update is the torch code it always was).  The teacher's
         # parameters keep requires_grad=False: the EMA writes their memory, autograd never sees them
         self.tail = None
-        self.step_per_update = self.cfg["step_per_update"]
-        self._window_calls = 0         # calls of the open window (the torch form's count; the fused tail keeps its own)
+        self.open_window(self.cfg["step_per_update"], self.cfg["grad_norm_clip"], self.cfg["fused_tail"])
         if self.cfg["ema_teacher"] or self.cfg["fused_tail"]:
             from .optim_tail import OptimTail
             clip, ema = self.cfg["grad_norm_clip"], self.cfg["ema_teacher"]
@@ -614,20 +694,26 @@ class FixMatchNTMStep:
 
     def set_epoch(self, epoch):
         """The epoch of the iterations that follow (train.py's loop variable): above cfg switch_ep the pseudo labels come
-        from the student's own weak view and the teacher no longer runs (train.py:469-475, 494-498).  cfg step_per_update
-        > 1: another epoch than the last restarts the count of the open window and keeps the gradients summed so far, which
-        join the new epoch's first update (train.py:435 against :664); with step_per_update = 1 nothing is issued."""
+        from the student's own weak view and the teacher no longer runs (train.py:469-475, 494-498).  Another epoch than the
+        last: restart_window()."""
         epoch = None if epoch is None else int(epoch)
-        if self.step_per_update > 1 and epoch != self.epoch:
-            self._window_calls = 0
-            if self.tail is not None:
-                self.tail.restart()
+        if epoch != self.epoch:
+            self.restart_window()
         self.epoch = epoch
 
     @property
     def self_labelling(self):
         """True after switch_ep: the phase in which the student labels its own weak view."""
         return self.epoch is not None and self.epoch > self.cfg["switch_ep"]
+
+    @property
+    def phase(self):
+        """One of PHASES: who makes the pseudo labels now, and can that forward run ahead of the update before it."""
+        return "@2" if self.self_labelling else "@e" if self.cfg["ema_teacher"] else ""
+
+    def lookahead_keys(self, phase=None):
+        """lookahead_keys() of a phase (default: the current one) under the step's cfg."""
+        return lookahead_keys(self.phase if phase is None else phase, self.cfg)
 
     def check_meter_batch(self, data_u):
         """With the meters on, the unlabelled batch must carry its ground truth data_u["y"] on the meters' GPU: checked
@@ -651,25 +737,22 @@ class FixMatchNTMStep:
         alike, and the work is done in line)."""
         self.check_meter_batch(data_u)
         geoms, self._geometry = self._geometry, (None, None)
-        with _accumulating(self, self.cfg["fused_tail"]):
+        with _accumulating(self, self.fused):
             losses, self._geometry = self.iteration(data, data_u, geoms, next_batches)
         return losses
 
-    def _pseudo_labels(self, data_u, geom_t):
-        """train.py:462-475: the frozen teacher on the weak view -> (softmax, its maximum, its arg-max)."""
+    def _teacher_forward(self, data_u, geom_t):
+        """train.py:462-475: the teacher on the weak view -> ((softmax, its maximum, its arg-max), with cfg use_contrastive
+        the head feature of that forward (no_grad: a constant), taken off the module -- else None)."""
         with torch.no_grad():
             _mode(self.model_t, False)
             pred_u = F.softmax(self.model_t(data_u, if_teacher=True, geometry=geom_t)[0], dim=1)
             logits_u_aug, label_u_aug = torch.max(pred_u, dim=1)
-        return pred_u, logits_u_aug, label_u_aug
-
-    def _teacher_feature(self):
-        """cfg use_contrastive: the head feature of the teacher's last forward (no_grad: a constant), taken off the module."""
-        if self.contrast is None:
-            return None
-        seg = _unwrapped(self.model_t).segmentor
-        feat, seg.head_feature = seg.head_feature, None
-        return feat
+        feat = None
+        if self.contrast is not None:
+            seg = _unwrapped(self.model_t).segmentor
+            feat, seg.head_feature = seg.head_feature, None
+        return (pred_u, logits_u_aug, label_u_aug), feat
 
     def _teacher_geometry(self, inner, geom_s, data, data_u, inline=False):
         """The teacher's geometry: the weak view is the last third of the student's batch, so its sampling / grouping / index
@@ -689,84 +772,76 @@ class FixMatchNTMStep:
         """Everything of an iteration that depends on its batches and on FROZEN state alone, on the CURRENT stream: the
         student's and the teacher's geometry, the teacher's forward -> pseudo labels (the teacher is never updated:
         train.py:218-222 loads and freezes it; it is in eval mode and draws no random numbers), the kNN graph and Morton
-        order of the 3-D loss.  -> the `pre` dict student_iteration() takes.  graph_step.py replays this as a graph of its own
-        on a second stream beside the PREVIOUS iteration's training graph; the eager iteration() below spreads the same work
-        over side streams inside the iteration instead.  After switch_ep (self_labelling; default: the step's epoch) the
-        teacher does not run: the student's geometry and the 3-D loss's graph only, "pseudo" is None.  With cfg pseudo_refine
-        the weak view's neighbour table is one more entry, "refine_nbr"; with cfg use_contrastive, while the teacher runs, its
-        head feature is "feat_t".  With cfg ema_teacher the teacher is no frozen state: before switch_ep the product holds its
-        geometry, "geom_t", and neither "pseudo" nor "feat_t" -- its forward runs inside the iteration."""
-        if self_labelling is None:
-            self_labelling = self.self_labelling
-        _mode(self.model, True)
-        inner = _unwrapped(self.model)
-        with torch.no_grad():
-            geom_s = inner.prefetch_geometry(data, data_u, fixmatch=True, inline=True)
-            if not self_labelling:
-                _mode(self.model_t, False)
-                geom_t = self._teacher_geometry(inner, geom_s, data, data_u, inline=True)
-            nbr = order = None
-            if self.cfg["use_3d_loss"]:                   # (off: nobody reads the 3-D loss's graph)
-                raw = data_u["raw_pos"].contiguous()
-                nbr = self.threed_loss.neighbours(raw)
-                order = ntm_mod.spatial_order(raw)
-            refine_nbr = self._refine_neighbours(data_u) if self.refine_mode is not None else None
-        if self.cfg["ema_teacher"] and not self_labelling:
-            # a teacher that moves with every update cannot run ahead of the update before it: its forward belongs to the
-            # iteration itself (graph_step runs it at the head of M); what depends on the batch alone is its geometry
-            pre = {"geom_s": geom_s, "geom_t": geom_t, "knn": (nbr, order)}
-            if refine_nbr is not None:
-                pre["refine_nbr"] = refine_nbr
-            return pre
-        pseudo = None if self_labelling else self._pseudo_labels(data_u, geom_t)
-        pre = {"geom_s": geom_s, "pseudo": pseudo, "knn": (nbr, order)}
-        feat_t = None if self_labelling else self._teacher_feature()
-        if feat_t is not None:
-            pre["feat_t"] = feat_t
-        if refine_nbr is not None:
-            pre["refine_nbr"] = refine_nbr
-        return pre
+        order of the 3-D loss (and what the switches add: BatchWork).  -> the BatchWork student_iteration() takes.
+        graph_step.py replays this as a graph of its own on a second stream beside the PREVIOUS iteration's training graph;
+        the eager iteration() below spreads the same work over side streams inside the iteration instead.  After switch_ep
+        (self_labelling; default: the step's epoch) the teacher does not run.  With cfg ema_teacher the teacher is no frozen
+        state: before switch_ep the product holds its geometry and its forward runs inside the iteration."""
+        return self._batch_work(data, data_u, self.self_labelling if self_labelling is None else self_labelling)
 
-    def iteration(self, data, data_u, geoms=(None, None), next_batches=None):
-        """One iteration, eagerly, its batch-only work spread over side streams -> (dict of detached losses, (student,
-        teacher) geometries queued for next_batches; no teacher geometry after switch_ep)."""
-        geom_s, geom_t = geoms
-        self_labelling = self.self_labelling
-        # the kNN graph of the 3-D loss needs raw_pos only: build it beside the teacher / student forwards
+    def _forked(self, name, dev):
+        """The step's side stream `name` (created on first use), put behind the current stream."""
+        side = getattr(self, name) or torch.cuda.Stream(device=dev)
+        setattr(self, name, side)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        return side
+
+    def _batch_work(self, data, data_u, self_labelling, geoms=None):
+        """The batch-only work, listed once.  geoms None: in line -- everything on the current stream, the geometry included.
+        geoms = (student, teacher) geometries the previous call queued, or Nones: the eager iteration -- the kNN graph and
+        the refine table on self._side, the teacher's forward on self._teacher_stream (GEOT_TEACHER_STREAM=0: in line),
+        to be joined by the product's first reader."""
+        inline = geoms is None
         dev = data["pos"].device
-        nbr = order = refine_nbr = None
-        if dev.type == "cuda" and (self.cfg["use_3d_loss"] or self.refine_mode is not None):
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=dev)
-            main = torch.cuda.current_stream(dev)
-            self._side.wait_stream(main)
-            with torch.cuda.stream(self._side):
-                if self.cfg["use_3d_loss"]:
-                    raw = data_u["raw_pos"].contiguous()
-                    nbr = self.threed_loss.neighbours(raw)
-                    order = ntm_mod.spatial_order(raw)
-                if self.refine_mode is not None:      # the weak view's neighbour table: batch-only work, like the graph above
-                    with torch.no_grad():
-                        refine_nbr = self._refine_neighbours(data_u)
+        with torch.no_grad():
+            if inline:
+                _mode(self.model, True)
+                inner = _unwrapped(self.model)
+                geom_s, geom_t = inner.prefetch_geometry(data, data_u, fixmatch=True, inline=True), None
+                if not self_labelling:
+                    _mode(self.model_t, False)
+                    geom_t = self._teacher_geometry(inner, geom_s, data, data_u, inline=True)
+            else:
+                geom_s, geom_t = geoms
+            pre = BatchWork(geom_s)
+            # the kNN graph of the 3-D loss needs raw_pos only: build it beside the teacher / student forwards
+            if self.cfg["use_3d_loss"] or self.refine_mode is not None:
+                side = None if inline else self._forked("_side", dev)
+                with torch.cuda.stream(side):
+                    if self.cfg["use_3d_loss"]:                   # (off: nobody reads the 3-D loss's graph)
+                        raw = data_u["raw_pos"].contiguous()
+                        pre.knn = (self.threed_loss.neighbours(raw), ntm_mod.spatial_order(raw))
+                        pre.made_on(side, "knn")
+                    if self.refine_mode is not None:      # the weak view's neighbour table: batch-only work, like the graph above
+                        pre.refine_nbr = self._refine_neighbours(data_u)
+                        pre.made_on(side, "refine_nbr")
         # 1. pseudo labels from the frozen teacher on the weak view (train.py:462-475).  The teacher's 2-cloud forward
         #    is short and mostly waits for its own 8192-sample FPS (4.7 ms on 2 CUs); nothing in the student's forward
         #    depends on it, so it is queued on a stream of its own and the student's kernels fill the gap (the eval-mode
         #    teacher draws no random numbers: identical results).  Its outputs are first used at step 3, after the join;
         #    next iteration's entry wait keeps the stream's allocations ordered behind this iteration's readers.
         #    After switch_ep there is no teacher: student_iteration takes the pseudo labels from the student's weak view.
-        t_stream = pseudo = feat_t = None
-        if dev.type == "cuda" and self.overlap_teacher and not self_labelling:
-            if self._teacher_stream is None:
-                self._teacher_stream = torch.cuda.Stream(device=dev)
-            t_stream = self._teacher_stream
-            # (cfg ema_teacher: this wait also puts the teacher's forward behind the previous iteration's update, which
-            # wrote the teacher's weights on the current stream; the join behind the student's forward puts this
+        if self_labelling:
+            return pre
+        if self.cfg["ema_teacher"] and inline:
+            # a teacher that moves with every update cannot run ahead of the update before it: its forward belongs to the
+            # iteration itself (student_iteration runs it at its head); what depends on the batch alone is its geometry
+            pre.geom_t = geom_t
+        else:
+            # (cfg ema_teacher: the fork's wait also puts the teacher's forward behind the previous iteration's update,
+            # which wrote the teacher's weights on the current stream; the join behind the student's forward puts this
             # iteration's update behind the teacher's reads)
-            t_stream.wait_stream(torch.cuda.current_stream(dev))
-        if not self_labelling:
-            with (torch.cuda.stream(t_stream) if t_stream is not None else contextlib.nullcontext()):
-                pseudo = self._pseudo_labels(data_u, geom_t)
-                feat_t = self._teacher_feature()
+            t_stream = self._forked("_teacher_stream", dev) if self.overlap_teacher and not inline else None
+            with torch.cuda.stream(t_stream):
+                pre.pseudo, pre.feat_t = self._teacher_forward(data_u, geom_t)
+            pre.made_on(t_stream, "pseudo", "feat_t")
+        return pre
+
+    def iteration(self, data, data_u, geoms=(None, None), next_batches=None):
+        """One iteration, eagerly, its batch-only work spread over side streams -> (dict of detached losses, (student,
+        teacher) geometries queued for next_batches; no teacher geometry after switch_ep)."""
+        self_labelling = self.self_labelling
+        pre = self._batch_work(data, data_u, self_labelling, geoms)
         inner = _unwrapped(self.model)
         make = None
         if next_batches is not None:
@@ -778,73 +853,53 @@ class FixMatchNTMStep:
                 g_s = inner.prefetch_geometry(nd, nu, fixmatch=True)
                 return g_s, None if self_labelling else self._teacher_geometry(inner, g_s, nd, nu)
         look = _LookAhead(inner.segmentor, "forward", make)
-
-        def after_forward():
-            # the teacher joins BEFORE the look-ahead is queued: the look-ahead's side streams (the student's and the
-            # teacher's segmentor streams) start behind the current stream only, and a teacher forward without a prefetched
-            # geometry allocates its in-line index plan on the teacher segmentor's side stream and frees it when the no_grad
-            # forward returns -- behind this join those blocks cannot be handed to the look-ahead's kernels while the
-            # teacher's decoder still reads them (the teacher is long done by the end of the student's forward: free)
-            if t_stream is not None:
-                _join(dev, t_stream, *pseudo, feat_t)
-            look.behind_forward()
-
-        def knn_graph():
-            if nbr is not None:
-                _join(dev, self._side, nbr, order)
-            return nbr, order
-
-        def refine_table():
-            _join(dev, self._side, refine_nbr)
-            return refine_nbr
-        losses = self.student_iteration(data, data_u, geom_s, pseudo, knn_graph, after_forward,
-                                        refine_nbr=refine_table if refine_nbr is not None else None, feat_t=feat_t)
+        losses = self.student_iteration(data, data_u, pre, look.behind_forward)
         return losses, look.done() or (None, None)
 
-    def student_iteration(self, data, data_u, geom_s, pseudo, knn_graph, after_forward=None, ema_in_place=False,
-                          defer_rest=False, refine_nbr=None, feat_t=None):
-        """Steps 2-5 of the iteration (train.py:478-602, 646-660): the student on labelled + strong + weak views, the class
-        transition, the per-point matrices, the corrected logits, the losses, backward, both optimisers (and the meters).
-        pseudo = (pred_u, logits_u_aug, label_u_aug) of the teacher, or None after switch_ep: then they are the soft-max of
-        the student's weak-view slice and its maximum (train.py:494-498) -- from the DETACHED slice: the reference only
-        ever uses detached copies of that pred_u (:498, :507), so autograd stays out of it; knn_graph = (nbr, order) of
-        raw_pos or a callable that returns them (called where they are first needed); after_forward(): called behind the
-        student's forward (the eager iteration joins its teacher stream and queues its look-ahead there); ema_in_place:
-        update ema_t IN its buffer (a captured graph holds the buffer, not the attribute); defer_rest: stop where the
-        backward reaches the student's transformer blocks (the segmentor cuts its autograd graph there) and return
-        (losses, rest) -- rest() runs the backward of the blocks and the patch encoder, the EMA update and both optimisers
-        (graph_step's split capture); refine_nbr: with cfg pseudo_refine, the weak view's neighbour table
-        (utils/pseudo_mask.py neighbours) or a callable that returns it; None: computed in line.  The refined mask is taken
-        from the pred_u the class transition reads and goes to the unsupervised criterion as its mask= (train.py:500,
-        588-596); scale_factor keeps the unrefined threshold mask (:599-602); the losses gain "kept", the mask's sum.
-        feat_t: with cfg use_contrastive, the teacher's head feature (B_u, 128, N) of its weak-view forward; None (after
-        switch_ep): the student's own weak-view slice, detached.  The contrastive loss (utils/cluster_contrastloss.py) reads
-        the student's strong-view slice against it, both channel-first and in place, selects by logits_u_aug >= cfg
-        cur_threshold with draws made on the device, and is added LAST, times cfg contrastive_loss_weight; the losses gain
-        "contrast" and "anchors" (the number of anchors, a device tensor)."""
+    def student_iteration(self, data, data_u, pre, after_forward=None, defer_rest=False):
+        """Steps 2-5 of the iteration (train.py:478-602, 646-660) over its batch-only work `pre` (a BatchWork): the student on
+        labelled + strong + weak views, the class transition, the per-point matrices, the corrected logits, the losses,
+        backward, both optimisers (and the meters).  pre.pseudo None before switch_ep (a moving teacher under replay): the
+        teacher's forward runs here, at the head, in line, over pre.geom_t.  None after switch_ep: the labels are the soft-max
+        of the student's weak-view slice and its maximum (train.py:494-498) -- from the DETACHED slice: the reference only
+        ever uses detached copies of that pred_u (:498, :507), so autograd stays out of it.  after_forward(): called behind
+        the student's forward and behind the read of pre.pseudo (the eager iteration queues its look-ahead there).
+        defer_rest: stop where the backward reaches the student's transformer blocks (_Cut) and return (losses, rest) --
+        backward_rest_update(rest) runs the rest of the backward, the EMA update and both optimisers (graph_step's split).
+        cfg pseudo_refine: the refined mask is taken from the pred_u the class transition reads and goes to the unsupervised
+        criterion as its mask= (train.py:500, 588-596); scale_factor keeps the unrefined threshold mask (:599-602); the losses
+        gain "kept", the mask's sum.  cfg use_contrastive: the loss (utils/cluster_contrastloss.py) reads the student's
+        strong-view slice against pre.feat_t (B_u, 128, N) -- None (after switch_ep): the student's own weak-view slice,
+        detached -- both channel-first and in place, selects by logits_u_aug >= cfg cur_threshold with draws made on the
+        device, and is added LAST, times cfg contrastive_loss_weight; the losses gain "contrast" and "anchors" (the number
+        of anchors, a device tensor)."""
         cfg = self.cfg
         seg = getattr(_unwrapped(self.model), "segmentor", None)
-        can_cut = defer_rest and hasattr(seg, "take_cut")
         bl, bu = data["pos"].shape[0], data_u["pos_w"].shape[0]
         n = data["pos"].shape[1]
+        pseudo = feat_t = None
+        if not pre.made("pseudo") and not self.self_labelling:
+            pseudo, feat_t = self._teacher_forward(data_u, pre.geom_t)
         # 2. student on labelled + strong + weak (train.py:478-492)
         _mode(self.model, True)
         _mode(self.T_predictor, True)
         data_u = dict(data_u, T=self.ema_t)
-        if can_cut:
-            seg.cut_at_blocks = True
-        try:
-            pred_all, _, sigma = _inner(self.model, self.grad_sync is not None)(data, u0=data_u, fixmatch=True, geometry=geom_s)
-        finally:
-            if can_cut:
-                seg.cut_at_blocks = False
-        cut = seg.take_cut() if can_cut else None
+        with _Cut(seg, defer_rest) as cut:
+            pred_all, _, sigma = _inner(self.model, self.grad_sync is not None)(data, u0=data_u, fixmatch=True, geometry=pre.geom_s)
         feat_all = None
         if self.contrast is not None:
             feat_all, seg.head_feature = seg.head_feature, None
         # (split, not two slices: its backward is one concatenation kernel; a slice's backward copies the gradient into a zero
         # tensor with a device-to-device memcpy -- a memcpy node when the iteration is captured)
         pred_l, pred_u_strong, pred_u_weak = torch.split(pred_all, [bl, bu, pred_all.shape[0] - bl - bu])
+        # the teacher joins (the read of pre.pseudo) BEFORE the look-ahead is queued (after_forward): the look-ahead's side
+        # streams (the student's and the teacher's segmentor streams) start behind the current stream only, and a teacher
+        # forward without a prefetched geometry allocates its in-line index plan on the teacher segmentor's side stream and
+        # frees it when the no_grad forward returns -- behind this join those blocks cannot be handed to the look-ahead's
+        # kernels while the teacher's decoder still reads them (the teacher is long done by the end of the student's
+        # forward: free)
+        if pseudo is None:
+            pseudo, feat_t = pre.pseudo, pre.feat_t
         if pseudo is None:
             with torch.no_grad():
                 pred_u = F.softmax(pred_u_weak.detach(), dim=1)
@@ -863,9 +918,6 @@ class FixMatchNTMStep:
         # (Poly1FocalLoss_U / Weight_CELoss_U read the uncorrected logits: the correction would have no reader)
         pred_u_strong_corr = ntm_mod.correct_logits(pred_u_strong, ins_t, ema_t_corr, cfg["lambma"]) \
             if self.needs_correction else None
-        if not ema_in_place:
-            with torch.no_grad():      # in its buffer, never rebound: a captured replay (graph_step) holds this very tensor
-                self.ema_t.copy_(ema_next)
         # 5. losses (train.py:560-602)
         loss_feat = loss_ident = loss_3d = None
         if cfg["use_feat_loss"]:
@@ -873,7 +925,7 @@ class FixMatchNTMStep:
         if cfg["use_identity_loss"]:
             loss_ident = self.identity_loss(ins_t, self.Identity_t) * cfg["identity_loss_weight"]
         if cfg["use_3d_loss"]:
-            nbr, order = knn_graph() if callable(knn_graph) else knn_graph
+            nbr, order = pre.knn
             loss_3d = self.threed_loss(data_u["raw_pos"], label_u_aug, ins_t, nbr=nbr, order=order) * cfg["threed_loss_weight"]
         if self.criterion_name == "Weight_CELoss":
             sup_loss = self.criterion(pred_l, data["y"], data["class_weights"])
@@ -883,9 +935,8 @@ class FixMatchNTMStep:
         mask = None                                             # train.py:500
         if self.refine_mode is not None:
             from .utils.pseudo_mask import pseudo_refine_mask
-            table = refine_nbr() if callable(refine_nbr) else refine_nbr
             mask = pseudo_refine_mask(pred_u, thresh, data_u["pos_w"], cfg["pseudo_refine_size"], cfg["pseudo_refine_neighbors"],
-                                      mode=self.refine_mode, nbr=table)
+                                      mode=self.refine_mode, nbr=pre.refine_nbr)
         if self.criterion_u_name == "Weight_CELoss_U":          # (the labelled batch's weights: train.py:585-587)
             unsup_loss = self.criterion_u(pred_u_strong, label_u_aug.detach(), data["class_weights"], conf, thresh=thresh)
         elif self.criterion_u_name == "Poly1FocalLoss_U":
@@ -920,15 +971,7 @@ class FixMatchNTMStep:
                                loss_3d if loss_3d is not None else torch.zeros((), device=loss.device), ema_t_corr,
                                feat=loss_feat, identity=loss_ident)
         loss.backward()
-        rest_in = None if cut is None else (cut[0], [d.grad for d in cut[1]])
-
-        def rest():
-            if rest_in is not None:
-                torch.autograd.backward(rest_in[0], rest_in[1])
-            if ema_in_place:
-                with torch.no_grad():
-                    torch.mul(ema_next, 1.0, out=self.ema_t)   # behind everything that read the old one (a kernel, not a memcpy node)
-            _window_update(self, cfg["grad_norm_clip"], self.model, cfg["fused_tail"])
+        rest = (cut.rest(), ema_next)
         losses = {"loss": loss.detach(), "sup": sup_loss.detach(), "unsup": unsup_loss.detach(),
                   "threed": loss_3d.detach() if loss_3d is not None else torch.zeros((), device=loss.device)}
         if loss_feat is not None:
@@ -943,8 +986,22 @@ class FixMatchNTMStep:
             losses["grad_norm"] = self.tail.total_norm       # (a device scalar the tail rewrites: read it behind the update)
         if defer_rest:
             return losses, rest
-        rest()
+        self.backward_rest_update(rest)
         return losses
+
+    def forward_backward_head(self, data, data_u, pre):
+        """As SupervisedStep's: up to where the backward reaches the student's blocks -> (losses, what backward_rest_update needs)."""
+        return self.student_iteration(data, data_u, pre, defer_rest=True)
+
+    def backward_rest_update(self, rest):
+        """The rest of the backward (the blocks, the patch encoder), the EMA transition matrix, clipping, both optimisers.
+        rest = (what _Cut left or None, the next ema_t)."""
+        backward_rest(rest[0])
+        with torch.no_grad():
+            # in its buffer, never rebound (a captured replay holds this very tensor, and so do the meters), behind everything
+            # that read the old one; a kernel, not a memcpy node (x 1.0 is exact)
+            torch.mul(rest[1], 1.0, out=self.ema_t)
+        _window_update(self, self.clip, self.model, self.fused)
 
 
 def build_fixmatch(device, seg_cfg=None, cfg=None, use_ddp=True, group=None, graph_sync=False, min_world=2, meters=None):

@@ -157,7 +157,7 @@ def test_graphed_step_equals_eager_and_holds_kernel_nodes_only(epoch):
         torch.cuda.synchronize()
         if mode == "graph":
             assert call.captured and all(set(call.node_types[k]) == {"kernel"} for k in call.graphs), call.node_types
-            assert ("feat_t" in call.pre) == (epoch <= 50)
+            assert (call.pre.feat_t is not None) == (epoch <= 50)
         runs[mode] = (out, dict(_state(step), **_contrast_state(step)))
     for i, (a, b) in enumerate(zip(runs["eager"][0], runs["graph"][0])):
         assert "contrast" in a and set(a) == set(b) and 0 < int(a["anchors"]) < 2 * S
@@ -176,6 +176,7 @@ def test_refusals():
     step = _new_step(_on())
     d, u = _batches()[0]
     pre = step.lookahead_work(d, u)
-    assert tuple(pre["feat_t"].shape) == (2, 128, 4096) and not pre["feat_t"].requires_grad
+    assert tuple(pre.feat_t.shape) == (2, 128, 4096) and not pre.feat_t.requires_grad
+    pre.feat_t = pre.feat_t.clone().requires_grad_(True)
     with pytest.raises(ValueError, match="feat_t"):
-        step.student_iteration(d, u, pre["geom_s"], pre["pseudo"], pre["knn"], feat_t=pre["feat_t"].clone().requires_grad_(True))
+        step.student_iteration(d, u, pre)

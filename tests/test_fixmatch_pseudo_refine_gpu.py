@@ -161,7 +161,7 @@ def test_off_adds_no_launch(monkeypatch):
     out = step(d, u)
     pre = step.lookahead_work(d, u)
     torch.cuda.synchronize()
-    assert not calls and "kept" not in out and "refine_nbr" not in pre
+    assert not calls and "kept" not in out and pre.refine_nbr is None
 
 
 def test_graphed_step_equals_eager_and_holds_kernel_nodes_only():
@@ -181,7 +181,7 @@ def test_graphed_step_equals_eager_and_holds_kernel_nodes_only():
         if mode == "graph":
             assert {"P", "M"} <= set(call.graphs) and call.captured, sorted(call.graphs)
             assert all(set(call.node_types[k]) == {"kernel"} for k in call.graphs), call.node_types
-            assert "refine_nbr" in call.pre and call.pre["refine_nbr"].dtype == torch.int32
+            assert call.pre.refine_nbr is not None and call.pre.refine_nbr.dtype == torch.int32
         runs[mode] = (out, _state(step))
     for i, (a, b) in enumerate(zip(runs["eager"][0], runs["graph"][0])):
         assert "kept" in a and set(a) == set(b)

@@ -158,6 +158,46 @@ def test_fixmatch_iteration_from_a_graph_equals_eager(look, split):
     _same(runs["eager"][1], runs["graph"][1])
 
 
+@pytest.mark.parametrize("epoch", [1, 51])
+def test_fixmatch_every_field_at_once_equals_eager(epoch):
+    """Every switch that adds a field to the look-ahead's product, together: the 3-D loss's graph, the refine table, the
+    contrastive loss's teacher feature and a moving teacher under the fused tail -- before switch_ep (phase "@e": the
+    teacher's forward is M's head, so P holds its geometry and neither pseudo labels nor feature) and after it ("@2")."""
+    from geot_amd import train_step as ts, graph_step as gs
+    cfg = dict(ts.NTM_CFG, threed_k=8, use_3d_loss=True, pseudo_refine="max", use_contrastive=True, contrast_samples=256,
+               ema_teacher=True, fused_tail=True)
+    batches = [_fix_batch(3), _fix_batch(400)]
+    tag = "@e" if epoch == 1 else "@2"
+    runs = {}
+    for mode in ("eager", "graph"):
+        torch.manual_seed(5)
+        step = ts.build_fixmatch(DEV, seg_cfg=SMALL, cfg=cfg, use_ddp=False)
+        call = gs.GraphedFixMatchStep(step, warmup=1) if mode == "graph" else step
+        call.set_epoch(epoch)
+        assert step.phase == tag
+        torch.manual_seed(11)
+        out = []
+        for i in range(3):
+            cur, nxt = batches[i % 2], batches[(i + 1) % 2]
+            out.append({k: v.clone() for k, v in call(cur[0], cur[1], next_batches=nxt).items()})
+        torch.cuda.synchronize()
+        if mode == "graph":
+            assert call.captured and set(call.graphs) == {"P" + tag, "M" + tag}, sorted(call.graphs)
+            assert all(set(call.node_types[k]) == {"kernel"} for k in call.graphs), call.node_types
+            pre = call.pre
+            made = {k for k in ts.BatchWork.FIELDS if pre.made(k)}
+            assert made == ({"geom_s", "geom_t", "knn", "refine_nbr"} if epoch == 1 else {"geom_s", "knn", "refine_nbr"}), made
+            assert pre.refine_nbr.dtype == torch.int32 and len(pre.knn) == 2 and all(torch.is_tensor(t) for t in pre.knn)
+        state = _state(step)
+        state.update({"teacher." + k: v.detach().clone() for k, v in step.model_t.state_dict().items()})
+        runs[mode] = (out, state)
+    for i, (a, b) in enumerate(zip(runs["eager"][0], runs["graph"][0])):
+        assert {"kept", "contrast", "anchors"} <= set(a) and set(a) == set(b)
+        for k in a:
+            assert torch.equal(a[k], b[k]), (i, k, float(a[k]), float(b[k]))
+    _same(runs["eager"][1], runs["graph"][1])
+
+
 def test_fixmatch_eager_calls_between_replays_share_the_ema_buffer():
     """An eager iteration on a step that a GraphedFixMatchStep wraps updates ema_t IN its buffer (the captured graph holds that
     very tensor): replay, eager, replay equals three eager iterations -- bench.py runs exactly this sequence of legs."""

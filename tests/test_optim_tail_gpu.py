@@ -440,7 +440,8 @@ def test_graphed_equals_eager_with_a_moving_teacher_across_the_switch():
         if mode == "graph":
             assert {"P@e", "M@e", "P@2", "M@2"} <= set(call.graphs) and "P" not in call.graphs, sorted(call.graphs)
             assert all(set(call.node_types[k]) == {"kernel"} for k in call.graphs), call.node_types
-            assert "pseudo" not in call._pres["@e"] and "feat_t" not in call._pres["@e"] and "geom_t" in call._pres["@e"]
+            pre_e = call._pres["@e"]
+            assert pre_e.pseudo is None and pre_e.feat_t is None and pre_e.geom_t is not None
             assert inside and all(w == ("M@e",) for w in inside), inside      # the teacher's forward: inside M, never inside P
         state = _state(step)
         state.update({"teacher." + k: v.detach().clone() for k, v in step.model_t.state_dict().items()})

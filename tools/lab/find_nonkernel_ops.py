@@ -26,7 +26,7 @@ else:
     d, u = _fix_batch(3, 4096 if small else 24000)
     bodies = {"P": lambda: step.lookahead_work(d, u)}
     pre = step.lookahead_work(d, u)
-    bodies["M"] = lambda: step.student_iteration(d, u, pre["geom_s"], pre["pseudo"], pre["knn"], ema_in_place=True)
+    bodies["M"] = lambda: step.student_iteration(d, u, pre)
 for name, fn in bodies.items():
     fn(); fn(); torch.cuda.synchronize()
     with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA], with_stack=False, record_shapes=True) as prof:

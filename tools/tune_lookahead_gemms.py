@@ -71,8 +71,7 @@ def main():
             pre = step.lookahead_work(data, data_u)                         # selection off: nothing recorded
             torch.cuda.synchronize()
             tunable.tuning_enable(True)                                     # the student's forward is tuned beside the FPS ...
-            step.student_iteration(data, data_u, pre["geom_s"], pre["pseudo"], pre["knn"],
-                                   after_forward=lambda: tunable.tuning_enable(False))      # ... and nothing behind it
+            step.student_iteration(data, data_u, pre, after_forward=lambda: tunable.tuning_enable(False))      # ... and nothing behind it
     else:
         cls = torch.zeros(b, 1, dtype=torch.long, device=dev)
         target = torch.from_numpy(region_labels(xyz)).to(dev)
