@@ -1386,6 +1386,26 @@ GEOT_EXPORT int geot_ntm_correct_grad(int b, int n, int c, float lam, const floa
     return hipGetLastError();
 }
 
+// host-only: what geot_ntm_sig_t_mean[_grad_raw] and geot_ntm_correct[_grad] launch for a shape on `cus` compute units
+// (<= 0: the current device's), from the plan the run-time-C launchers read (ntm_generic.hip: gen_sig_plan, gen_blocks).
+// Returns the form (0 nothing to launch or arguments out of range, 1 wave per point, 2 lane per point, 3 matrix cores,
+// 4 the specialised C = 17 kernels, -1 a launch that would be refused) and fills out[0..n_out) with
+// form, CP | CPAD, tails, ksplit, blocks, LDS bytes, blocks of gen_correct_*.
+GEOT_EXPORT int geot_ntm_generic_plan(int b, int n, int c, int backward, int cus, long long *out, int n_out)
+{
+    (void)backward;                          // (both directions launch the same geometry)
+    if (b < 1 || n < 1 || (c != GEOT_NTM_C && !ntm_generic_c(c))) return 0;
+    long long v[7] = {4, 0, 0, 0, 0, 0, 0};
+    if (c != GEOT_NTM_C) {
+        const GenSigPlan pl = gen_sig_plan(b, n, c, cus);
+        v[0] = pl.form, v[1] = pl.cp, v[2] = pl.tails, v[3] = pl.ksplit, v[4] = pl.blocks, v[5] = (long long)pl.lds;
+        v[6] = gen_blocks((long long)b * n);
+    }
+    if (out)
+        for (int i = 0; i < n_out && i < 7; ++i) out[i] = v[i];
+    return (int)v[0];
+}
+
 GEOT_EXPORT int geot_ntm_class_anchors(int b, int n, int c, const float *eta, float *class_T, float *v_star, void *stream)
 {
     if (b < 1 || n < 1 || c < 1 || c > 1024 || !eta || !class_T) return hipErrorInvalidValue;

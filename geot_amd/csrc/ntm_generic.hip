@@ -264,7 +264,7 @@ __global__ __launch_bounds__(GEN_MT) void gen_sig_t_mean_mfma_kernel(int total_p
         return pt * GEN_RS + g * CPAD + (d - g * c);
     };
     const long long tiles = ((long long)total_pts + 31) / 32, tstride = (long long)nb * GEN_MW;
-    const unsigned last4 = (unsigned)total_pts * (unsigned)cc - 4u;     // (host: B N C^2 < 2^30, >= 4)
+    const unsigned last4 = (unsigned)total_pts * (unsigned)cc - 4u;     // (gen_sig_plan: 4 <= B N C^2 < 2^30)
     long long t = (long long)wb * GEN_MW + wave;
     if (t >= tiles || kt1 <= kt0) return;
     auto point = [&](long long tl, bool &ok, unsigned &pbase) {
@@ -516,42 +516,37 @@ __global__ __launch_bounds__(256) void gen_correct_bwd_kernel(int total_pts, int
         atomicAdd(grad_E + e, (gen_lds[e] + gen_lds[cc + e]) + (gen_lds[2 * cc + e] + gen_lds[3 * cc + e]));
 }
 
-static inline int gen_blocks(long long total_pts)
+// ---- the launch plan ---------------------------------------------------------------------------------------------------
+// Every launch decision of gen_sig_t_mean and of the two gen_correct_* launches, in one place: the launchers below and the
+// host-only query geot_ntm_generic_plan (ntm.hip) both read it, so the query cannot drift from what runs.
+int gen_blocks(long long total_pts)
 {
     long long blocks = (total_pts + 3) / 4;
     return (int)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks));   // 8 workgroups per CU, grid-stride beyond
 }
 
-template <int CP>
-static hipError_t launch_sig_rows(bool backward, int b, int n, int c, const float *p, const float *W, const float *cm,
-                                  const float *grad_out, float *out, hipStream_t s)
+static inline int gen_cpad(int c) { return c <= 8 ? 8 : (c <= 16 ? 16 : 32); }
+
+// the lane-per-point form: CP = C rounded up to 8, 256 points per workgroup, 8 workgroups per CU and grid-stride beyond
+static GenSigPlan plan_sig_rows(long long total_pts, int c, long long cus)
 {
-    const size_t lds = (size_t)(((c * c + 3) & ~3) + 4 * 64 * (CP + 1)) * sizeof(float);    // <= 38 KB
-    long long blocks = ((long long)b * n + 255) / 256;
-    const long long cap = 8LL * device_cus();
-    if (blocks > cap) blocks = cap;
-    if (backward)
-        hipLaunchKernelGGL((gen_sig_t_mean_rows_kernel<CP, true>), dim3((int)blocks), dim3(256), lds, s, b * n, n, c, p, W, cm,
-                           grad_out, out);
-    else
-        hipLaunchKernelGGL((gen_sig_t_mean_rows_kernel<CP, false>), dim3((int)blocks), dim3(256), lds, s, b * n, n, c, p, W, cm,
-                           grad_out, out);
-    return hipGetLastError();
+    GenSigPlan pl = {GEN_FORM_ROWS, (c + 7) / 8 * 8, 0, 1, 0, 0};
+    pl.lds = (size_t)(((c * c + 3) & ~3) + 4 * 64 * (pl.cp + 1)) * sizeof(float);    // <= 38 KB
+    pl.blocks = (total_pts + 255) / 256;
+    const long long cap = 8LL * cus;
+    if (pl.blocks > cap) pl.blocks = cap;
+    return pl;
 }
 
-template <int CPAD>
-static hipError_t launch_sig_mfma(bool backward, int b, int n, int c, const float *p, const float *W, const float *cm,
-                                  const float *grad_out, float *out, hipStream_t s)
+// the matrix-core form; form GEN_FORM_REFUSED where no split fits (fewer CUs than ranges)
+static GenSigPlan plan_sig_mfma(long long total_pts, int c, long long cus)
 {
-    constexpr int NG = 32 / CPAD;
+    GenSigPlan pl = {GEN_FORM_MFMA, gen_cpad(c), (c & 3) != 0 ? 1 : 0, 1, 0, 0};
+    const int NG = 32 / pl.cp;
     const int nkt = (c + NG - 1) / NG, ng = (c + 7) / 8;
-    const bool tails = (c & 3) != 0;
-    const void *fn = backward ? (tails ? (const void *)gen_sig_t_mean_mfma_kernel<CPAD, true, true> : (const void *)gen_sig_t_mean_mfma_kernel<CPAD, true, false>)
-                              : (tails ? (const void *)gen_sig_t_mean_mfma_kernel<CPAD, false, true> : (const void *)gen_sig_t_mean_mfma_kernel<CPAD, false, false>);
-    const long long tiles = ((long long)b * n + 31) / 32;
+    const long long tiles = (total_pts + 31) / 32;
     // ranges of row tiles (a workgroup stages the weights of one): the fewest whose weights fit beside the 16 waves' tiles and
     // that leave the last round of a range's waves >= 85 % full (one workgroup per CU: 88+ registers x 1024 threads)
-    const long long cus = device_cus();
     auto lds_of = [&](int ks) {
         const int per = (nkt + ks - 1) / ks;
         return ((size_t)per * ng * 256 + (size_t)per * 32 + (size_t)GEN_MW * 32 * GEN_RS) * sizeof(float);
@@ -562,15 +557,73 @@ static hipError_t launch_sig_mfma(bool backward, int b, int n, int c, const floa
         const long long waves = cus / ksplit * GEN_MW, rounds = (tiles + waves - 1) / (waves > 0 ? waves : 1);
         if (waves > 0 && (tiles <= waves || tiles * 100 >= rounds * waves * 85 || ksplit >= 4)) break;
     }
-    const size_t lds = lds_of(ksplit);
-    if (lds > 160 * 1024 || cus < ksplit) return hipErrorInvalidValue;
-    hipError_t e = allow_big_lds(fn, lds);
-    if (e != hipSuccess) return e;
+    pl.ksplit = ksplit;
+    pl.lds = lds_of(ksplit);
+    if (pl.lds > 160 * 1024 || cus < ksplit) {
+        pl.form = GEN_FORM_REFUSED;
+        return pl;
+    }
     long long nb = cus / ksplit;             // workgroups per range
     if (nb > (tiles + GEN_MW - 1) / GEN_MW) nb = (tiles + GEN_MW - 1) / GEN_MW;
-    const long long blocks = nb * ksplit;
+    pl.blocks = nb * ksplit;
+    return pl;
+}
+
+// the wave-per-point form: persistent workgroups, as many per CU as the staged weights ((C+1) C^2 floats each) leave room
+// for in LDS: the inner loop is a chain of LDS reads, it needs waves to hide behind (2 per SIMD measured 0.23 TB/s at C = 16)
+static GenSigPlan plan_sig_wave(long long total_pts, int c, long long cus)
+{
+    GenSigPlan pl = {GEN_FORM_WAVE, 0, 0, 1, 0, 0};
+    pl.lds = (size_t)(c + 1) * c * c * sizeof(float);        // 135 KB at C = 32
+    pl.blocks = (total_pts + 3) / 4;
+    long long per_cu = (160 * 1024) / (long long)(pl.lds + 512);
+    per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
+    const long long cap = per_cu * cus;
+    if (pl.blocks > cap) pl.blocks = cap;
+    return pl;
+}
+
+GenSigPlan gen_sig_plan(int b, int n, int c, int cus)
+{
+    const long long total_pts = (long long)b * n, elems = total_pts * c * c;
+    if (total_pts <= 0 || c < 1 || c > GEN_MAXC) return GenSigPlan{GEN_FORM_NONE, 0, 0, 0, 0, 0};
+    if (cus <= 0) cus = device_cus();
+    const char *impl = getenv("GEOT_NTM_GENERIC");      // A/B tests: "mfma" / "rows" = the lane-per-point kernel / "wave" = the wave-per-point kernel
+    const bool small = elems < 0x7fffffffLL * 4LL;
+    // the MFMA form from C = 6 up (kernel times at 8 x 24000 points, C = 5: 18 / 32 us against the lane-per-point form's
+    // 17 / 30; C = 7: 20 / 41 against 33 / 64 -- profiles/r05_ntm_generic.txt)
+    const bool want_mfma = impl && impl[0] == 'm' ? true : (impl && (impl[0] == 'r' || impl[0] == 'w') ? false : c >= 6);
+    // (the kernel clamps its gradient loads to the buffer's last four elements: it needs four)
+    if (want_mfma && elems < (1LL << 30) && elems >= 4) return plan_sig_mfma(total_pts, c, cus);
+    if (!(impl && impl[0] == 'w') && small) return plan_sig_rows(total_pts, c, cus);
+    return plan_sig_wave(total_pts, c, cus);
+}
+
+template <int CP>
+static hipError_t launch_sig_rows(const GenSigPlan &pl, bool backward, int b, int n, int c, const float *p, const float *W,
+                                  const float *cm, const float *grad_out, float *out, hipStream_t s)
+{
+    if (backward)
+        hipLaunchKernelGGL((gen_sig_t_mean_rows_kernel<CP, true>), dim3((int)pl.blocks), dim3(256), pl.lds, s, b * n, n, c, p, W, cm,
+                           grad_out, out);
+    else
+        hipLaunchKernelGGL((gen_sig_t_mean_rows_kernel<CP, false>), dim3((int)pl.blocks), dim3(256), pl.lds, s, b * n, n, c, p, W, cm,
+                           grad_out, out);
+    return hipGetLastError();
+}
+
+template <int CPAD>
+static hipError_t launch_sig_mfma(const GenSigPlan &pl, bool backward, int b, int n, int c, const float *p, const float *W,
+                                  const float *cm, const float *grad_out, float *out, hipStream_t s)
+{
+    const bool tails = pl.tails != 0;
+    const void *fn = backward ? (tails ? (const void *)gen_sig_t_mean_mfma_kernel<CPAD, true, true> : (const void *)gen_sig_t_mean_mfma_kernel<CPAD, true, false>)
+                              : (tails ? (const void *)gen_sig_t_mean_mfma_kernel<CPAD, false, true> : (const void *)gen_sig_t_mean_mfma_kernel<CPAD, false, false>);
+    hipError_t e = allow_big_lds(fn, pl.lds);
+    if (e != hipSuccess) return e;
+    const int ksplit = pl.ksplit;
 #define GEOT_GEN_SIG(BW, TL)                                                                                                   \
-    hipLaunchKernelGGL((gen_sig_t_mean_mfma_kernel<CPAD, BW, TL>), dim3((int)blocks), dim3(GEN_MT), lds, s, b * n, n, c, ksplit, p, W, \
+    hipLaunchKernelGGL((gen_sig_t_mean_mfma_kernel<CPAD, BW, TL>), dim3((int)pl.blocks), dim3(GEN_MT), pl.lds, s, b * n, n, c, ksplit, p, W, \
                        cm, grad_out, out)
     if (backward) { if (tails) GEOT_GEN_SIG(true, true); else GEOT_GEN_SIG(true, false); }
     else { if (tails) GEOT_GEN_SIG(false, true); else GEOT_GEN_SIG(false, false); }
@@ -581,37 +634,27 @@ static hipError_t launch_sig_mfma(bool backward, int b, int n, int c, const floa
 hipError_t gen_sig_t_mean(bool backward, int b, int n, int c, const float *p, const float *W, const float *cm,
                           const float *grad_out, float *out, hipStream_t s)
 {
-    const char *impl = getenv("GEOT_NTM_GENERIC");      // A/B tests: "mfma" / "rows" = the lane-per-point kernel / "wave" = the wave-per-point kernel
-    const bool small = (long long)b * n * c * c < 0x7fffffffLL * 4LL;
-    // the MFMA form from C = 6 up (kernel times at 8 x 24000 points, C = 5: 18 / 32 us against the lane-per-point form's
-    // 17 / 30; C = 7: 20 / 41 against 33 / 64 -- profiles/r05_ntm_generic.txt)
-    const bool want_mfma = impl && impl[0] == 'm' ? true : (impl && (impl[0] == 'r' || impl[0] == 'w') ? false : c >= 6);
-    if (want_mfma && (long long)b * n * c * c < (1LL << 30)) {
-        if (c <= 8) return launch_sig_mfma<8>(backward, b, n, c, p, W, cm, grad_out, out, s);
-        if (c <= 16) return launch_sig_mfma<16>(backward, b, n, c, p, W, cm, grad_out, out, s);
-        return launch_sig_mfma<32>(backward, b, n, c, p, W, cm, grad_out, out, s);
+    const GenSigPlan pl = gen_sig_plan(b, n, c, 0);
+    if (pl.form == GEN_FORM_NONE) return hipSuccess;
+    if (pl.form == GEN_FORM_REFUSED) return hipErrorInvalidValue;
+    if (pl.form == GEN_FORM_MFMA) {
+        if (pl.cp == 8) return launch_sig_mfma<8>(pl, backward, b, n, c, p, W, cm, grad_out, out, s);
+        if (pl.cp == 16) return launch_sig_mfma<16>(pl, backward, b, n, c, p, W, cm, grad_out, out, s);
+        return launch_sig_mfma<32>(pl, backward, b, n, c, p, W, cm, grad_out, out, s);
     }
-    if (!(impl && impl[0] == 'w') && small) {
-        if (c <= 8) return launch_sig_rows<8>(backward, b, n, c, p, W, cm, grad_out, out, s);
-        if (c <= 16) return launch_sig_rows<16>(backward, b, n, c, p, W, cm, grad_out, out, s);
-        if (c <= 24) return launch_sig_rows<24>(backward, b, n, c, p, W, cm, grad_out, out, s);
-        return launch_sig_rows<32>(backward, b, n, c, p, W, cm, grad_out, out, s);
+    if (pl.form == GEN_FORM_ROWS) {
+        if (pl.cp == 8) return launch_sig_rows<8>(pl, backward, b, n, c, p, W, cm, grad_out, out, s);
+        if (pl.cp == 16) return launch_sig_rows<16>(pl, backward, b, n, c, p, W, cm, grad_out, out, s);
+        if (pl.cp == 24) return launch_sig_rows<24>(pl, backward, b, n, c, p, W, cm, grad_out, out, s);
+        return launch_sig_rows<32>(pl, backward, b, n, c, p, W, cm, grad_out, out, s);
     }
-    const size_t lds = (size_t)(c + 1) * c * c * sizeof(float);        // 135 KB at C = 32
     const void *fn = backward ? (const void *)gen_sig_t_mean_kernel<true> : (const void *)gen_sig_t_mean_kernel<false>;
-    hipError_t e = allow_big_lds(fn, lds);
+    hipError_t e = allow_big_lds(fn, pl.lds);
     if (e != hipSuccess) return e;
-    // persistent workgroups, as many per CU as the staged weights ((C+1) C^2 floats each) leave room for in LDS:
-    // the inner loop is a chain of LDS reads, it needs waves to hide behind (2 per SIMD measured 0.23 TB/s at C = 16)
-    long long blocks = ((long long)b * n + 3) / 4;
-    long long per_cu = (160 * 1024) / (long long)(lds + 512);
-    per_cu = per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu);
-    const long long cap = per_cu * device_cus();
-    if (blocks > cap) blocks = cap;
     if (backward)
-        hipLaunchKernelGGL(gen_sig_t_mean_kernel<true>, dim3((int)blocks), dim3(256), lds, s, b * n, n, c, p, W, cm, grad_out, out);
+        hipLaunchKernelGGL(gen_sig_t_mean_kernel<true>, dim3((int)pl.blocks), dim3(256), pl.lds, s, b * n, n, c, p, W, cm, grad_out, out);
     else
-        hipLaunchKernelGGL(gen_sig_t_mean_kernel<false>, dim3((int)blocks), dim3(256), lds, s, b * n, n, c, p, W, cm, grad_out, out);
+        hipLaunchKernelGGL(gen_sig_t_mean_kernel<false>, dim3((int)pl.blocks), dim3(256), pl.lds, s, b * n, n, c, p, W, cm, grad_out, out);
     return hipGetLastError();
 }
 

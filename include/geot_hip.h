@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 28
+#define GEOT_ABI_VERSION 29
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -571,6 +571,13 @@ int geot_ntm_correct(int b, int n, int c, float lam, const float *logits, const 
 int geot_ntm_correct_grad(int b, int n, int c, float lam, const float *logits, const float *ins_T,
                           const float *ema_t, const float *grad_out, float *grad_logits,
                           float *grad_ins_T, float *grad_ema_t, void *stream);
+/* Host-only (ABI 29): what the four entry points above launch for (b, n, c) on a device of `cus` compute units (<= 0: the
+ * current device's), under GEOT_NTM_GENERIC as the launch reads it.  Returns the form of sig_t_mean -- 0 nothing to launch
+ * (b * n == 0 or arguments out of range), 1 a wave per point, 2 a lane per point, 3 the matrix-core form, 4 the specialised
+ * c == 17 kernels, -1 a launch that would be refused -- and fills out[0 .. min(n_out, 7)) with: form, CP (form 2) or CPAD
+ * (form 3), tails (form 3: c % 4 != 0), ksplit (ranges of row tiles, form 3), workgroups, dynamic LDS bytes, and the
+ * workgroups of geot_ntm_correct[_grad] for c != 17.  `backward` selects _grad_raw (both launch the same geometry). */
+int geot_ntm_generic_plan(int b, int n, int c, int backward, int cus, long long *out, int n_out);
 /* Class anchors, train.py:505-526: class_T (c,c) row cc = eta[b*, :, n*] of the point with the largest
  * eta[b, cc, n] (eta (b,c,n) fp32: the weak view's soft-max), the first maximum in flattened (b, n) order as
  * torch.argmax picks it; v_star (c, nullable) receives the maxima (the multi-rank exchange compares them). */

@@ -162,6 +162,22 @@ def test_host_only_planning_entry_points(monkeypatch):
     monkeypatch.setenv("GEOT_GATHER_IMPL", "plain")             # the environment switch moves the plan with the dispatch
     assert lib.geot_gather_plan(8, 384, 8192, 24000, gp, 5) == 1
     monkeypatch.delenv("GEOT_GATHER_IMPL")
+    # run-time-C NTM kernels (ABI 29): form, CP | CPAD, tails, ksplit, blocks, LDS bytes, gen_correct blocks on 256 CUs
+    monkeypatch.delenv("GEOT_NTM_GENERIC", raising=False)
+    npl = (ctypes.c_longlong * 7)(*([-7] * 7))
+    assert lib.geot_ntm_generic_plan(2, 70001, 13, 0, 256, npl, 7) == 3 and list(npl) == [3, 16, 1, 4, 256, 4 * (2 * 2 * 256 + 2 * 32 + 16 * 32 * 36), 2048]
+    assert lib.geot_ntm_generic_plan(2, 700, 5, 1, 256, npl, 7) == 2 and list(npl) == [2, 8, 0, 1, 6, 4 * (28 + 256 * 9), 350]
+    short = (ctypes.c_longlong * 7)(*([-7] * 7))
+    assert lib.geot_ntm_generic_plan(2, 700, 17, 0, 256, short, 2) == 4 and list(short) == [4, 0] + [-7] * 5
+    assert lib.geot_ntm_generic_plan(2, 700, 13, 0, 256, None, 0) == 3
+    for args in ((0, 700, 13), (2, 0, 13), (2, 700, 0), (2, 700, 33), (-1, 700, 13)):
+        untouched = (ctypes.c_longlong * 7)(*([-7] * 7))
+        assert lib.geot_ntm_generic_plan(*args, 0, 256, untouched, 7) == 0 and list(untouched) == [-7] * 7
+    monkeypatch.setenv("GEOT_NTM_GENERIC", "wave")               # the environment switch moves the plan with the dispatch
+    assert lib.geot_ntm_generic_plan(2, 700, 13, 0, 256, npl, 7) == 1 and list(npl) == [1, 0, 0, 1, 350, 4 * 14 * 169, 350]
+    monkeypatch.setenv("GEOT_NTM_GENERIC", "mfma")               # fewer than four output elements never reach the MFMA form
+    assert lib.geot_ntm_generic_plan(1, 3, 1, 1, 256, None, 0) == 2 and lib.geot_ntm_generic_plan(1, 4, 1, 1, 256, None, 0) == 3
+    monkeypatch.delenv("GEOT_NTM_GENERIC")
 
 
 def test_grid_search_plan_entry_points(monkeypatch):

@@ -29,6 +29,8 @@ PINNED = {
     "geot_scatter_grad_plan": ([I, I, I, L, I, I, P, I], I),
     # (int b, int c, int m_table, long long n_out_elems, long long *out, int n_out): host array, no stream
     "geot_gather_plan": ([I, I, I, L, P, I], I),
+    # (int b, int n, int c, int backward, int cus, long long *out, int n_out): host array, no stream
+    "geot_ntm_generic_plan": ([I, I, I, I, I, P, I], I),
     "geot_knn_grid_ws_bytes": ([I, I], L),                      # long long (int b, int nr)
     "geot_error_string": ([I], ctypes.c_char_p),                # const char * (int hip_error)
 }
@@ -51,7 +53,7 @@ def test_every_entry_is_bound_as_derived_after_load():
     build.build()
     lib = _lib.load()
     entries, _ = _header.parse()
-    assert len(entries) == len(_lib.SIGNATURES) >= 157
+    assert len(entries) == len(_lib.SIGNATURES) >= 158
     assert len(_lib.PROTOTYPES) + len(_lib.PLAIN) + 3 == len(entries)
     assert sorted(_lib.exported_symbols()) == sorted(e.name for e in entries)
     for e in entries:

@@ -383,10 +383,20 @@ def test_any_class_count_at_full_size_against_fp64(Cn, impl, monkeypatch):
     """140 002 points: more point tiles than resident waves (every wave walks several tiles, the next tile's inputs in flight),
     a last tile of 2 points, C = 32 with its weights split over two workgroup ranges -- forward and d raw of the run-time-C
     sig_t_mean against the same arithmetic in fp64 (transformer.py:1111-1131: heads, clamp, L1 norm over o)."""
-    from geot_amd import ntm
+    from geot_amd import ntm, _lib
+    import ctypes
     monkeypatch.setenv("GEOT_NTM_GENERIC", impl)
     torch.manual_seed(Cn)
     B, N = 2, 70001
+    # pinned from the library's plan on this device: the form, and under "mfma" that every wave walks several point tiles --
+    # at C = 20 and 32 this is the multi-tile case of the 32-row tiles, at C = 32 with its weights split over ranges
+    plan = (ctypes.c_longlong * 7)()
+    form = _lib.load().geot_ntm_generic_plan(B, N, Cn, 1, 0, plan, 7)
+    assert form == (3 if impl == "mfma" else 2) and plan[0] == form
+    if impl == "mfma":
+        cpad, ksplit, blocks = plan[1], plan[3], plan[4]
+        assert cpad == (8 if Cn <= 8 else 16 if Cn <= 16 else 32) and (B * N + 31) // 32 > blocks // ksplit * 16
+        assert ksplit >= 2 or Cn != 32
     p = torch.softmax(torch.randn(B, Cn, N, device=DEV) * 2, 1)
     cm = torch.softmax(torch.randn(Cn, Cn, device=DEV), 1)
     mod = ntm.Ins_T_mean(nclasses=Cn).to(DEV)
