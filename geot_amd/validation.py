@@ -44,6 +44,13 @@ label of their n + 1 nearest vertices (geot_scan_refine, csrc/scan_refine.hip: s
     preds = refine_scans(predict_scans(logits, batch), batch, n=10, parts=cls2parts)     # in place, the same views
     preds = predict_scans(logits, batch, refine=10)          # also vote_scans, validate_scans, validate_scans_voted
     pred = part_seg_refinement(pred, pos, cls, cls2parts, n=10)                         # the reference's dense (B, N) form
+
+Look-ahead and replay -- validate_scans, validate_scans_voted and vote_scans with lookahead=G / graph=True (off by default):
+up to G passes are drawn ahead (the same batch() calls in the same order), their coordinate-only work runs as one
+prefetch_geometry over the concatenated positions beside the forward pass in flight (pass_schedule, _passes), and with graph
+that call and the forward pass replay from hipGraphs (graph_eval.GraphedForward).  Same values, bit for bit:
+
+    out = validate_scans_voted(model, scans, cfg, graph=True, lookahead=True)    # one FPS launch per group of num_votes passes
 """
 import logging
 
@@ -51,7 +58,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, graph_eval, streams
 from .ext._common import call, knn_workspace, need, ptr
 from .openpoints.dataset.scan_set import _to_device
 from .pointnet2 import pointnet2_utils as pt_utils
@@ -544,23 +551,198 @@ def _report(out, cfg):
     return out["whole_macc"], out["whole_miou"], out["whole_mdsc"]
 
 
-def _passes(model, batcher, groups, repeats, draws):
+def _replay_switches(graph, lookahead, num_votes, model, what):
+    """The `graph` / `lookahead` keywords of validate_scans, validate_scans_voted and vote_scans, checked before any device
+    call -> (G, the GraphedForward or None).  lookahead: False / 0 (off), True (G = max(num_votes, 1): a voted group's passes
+    share one geometry call) or an int G >= 1; graph: False, True (the model's own wrapper, graph_eval.graphed_forward) or a
+    GraphedForward built on the model; graph without lookahead runs at G = 1 (a replay needs a static geometry).  TypeError
+    for another type (a bool is no int: graph=1 is refused like lookahead=2.0), ValueError for G < 0 or
+    G > graph_eval.MAX_LOOKAHEAD."""
+    if not isinstance(graph, (bool, graph_eval.GraphedForward)):
+        raise TypeError("%s: graph must be a bool or a GraphedForward, got %r" % (what, graph))
+    if isinstance(lookahead, bool):
+        g = max(int(num_votes), 1) if lookahead else 0
+    elif isinstance(lookahead, (int, np.integer)):
+        g = int(lookahead)
+    else:
+        raise TypeError("%s: lookahead must be a bool or an int, got %r" % (what, lookahead))
+    if g < 0:
+        raise ValueError("%s: lookahead must be >= 0, got %r" % (what, lookahead))
+    if graph is not False:
+        g = max(g, 1)
+    if g > graph_eval.MAX_LOOKAHEAD:
+        raise ValueError("%s: at most %d passes are drawn ahead, got lookahead = %d" % (what, graph_eval.MAX_LOOKAHEAD, g))
+    if isinstance(graph, graph_eval.GraphedForward) and graph.model is not model:
+        raise ValueError("%s: the GraphedForward was built on another model" % what)
+    return g, graph if isinstance(graph, graph_eval.GraphedForward) else graph_eval.graphed_forward(model) if graph else None
+
+
+def pass_schedule(group_sizes, repeats, lookahead):
+    """The order of a whole-scan run as pure host logic: groups of group_sizes scans, each `repeats` passes, G = lookahead
+    passes drawn ahead -> (passes, ops); passes: (group number, first pass of its group, last pass of its group); ops in
+    execution order: ("draw", k) -- batcher.batch() for pass k, ALWAYS in pass order, so the host generators and the DeviceDraws
+    counters see today's sequence of calls, only earlier; ("geometry", (k, ...)) -- one prefetch_geometry over these passes'
+    positions concatenated; ("forward", k).  The passes are cut into chunks of G.  A chunk is drawn at once, and its passes with
+    a full batch (as many scans as the largest group) share one geometry call; a shorter batch is left out and computes its
+    geometry in line.  The first chunk is announced before anything runs; every other one in front of the forward pass of
+    the last pass before it, beside which its geometry runs."""
+    repeats, g = int(repeats), int(lookahead)
+    need(g >= 1, "pass_schedule: lookahead >= 1 (without it _passes runs its own loop)")
+    passes = [(group, k == 0, k + 1 == repeats) for group in range(len(group_sizes)) for k in range(repeats)]
+    n, ops = len(passes), []
+    if not n:
+        return passes, ops
+    full = max(int(s) for s in group_sizes)
+
+    def chunk(start):
+        members = range(start, min(start + g, n))
+        ops.extend(("draw", k) for k in members)
+        shared = tuple(k for k in members if int(group_sizes[passes[k][0]]) == full)
+        if shared:
+            ops.append(("geometry", shared))
+    chunk(0)
+    for k in range(n):
+        if (k + 1) % g == 0 and k + 1 < n:
+            chunk(k + 1)
+        ops.append(("forward", k))
+    return passes, ops
+
+
+class _Shared:
+    """One concatenated geometry (None: the model has none to give) and the positions it was computed from: pass `index` takes
+    its slice only for the very tensor that was concatenated, unedited -- a static geometry has no identities of its own, so
+    this is where they are checked.  ready: the event behind the work, when a side stream did it."""
+
+    def __init__(self, geometry, positions, ready=None):
+        self.geometry, self.ready = geometry, ready
+        self.sources = [(p, p._version) for p in positions]
+        self.rows = np.concatenate([[0], np.cumsum([int(p.shape[0]) for p in positions])]).tolist()
+
+    def slice_for(self, index, pos):
+        src, version = self.sources[index]
+        if self.geometry is None or src is not pos or pos._version != version:
+            return None
+        return self.geometry.slice(self.rows[index], self.rows[index + 1])
+
+
+_AHEAD_STREAMS = {}     # device -> the stream the eager look-ahead geometry runs on
+
+
+class _EagerAhead:
+    """The look-ahead of _passes on eager launches: the concatenated geometry on a side stream of its own (the model's side
+    stream is waited for by every forward pass that computes its geometry in line), as a static Geometry this object vouches
+    for; the forward pass waits for its event."""
+
+    def __init__(self, model):
+        self.model = model
+
+    def start(self, batches):
+        positions = [b["pos"] for b in batches]
+        dev = positions[0].device
+        seg = getattr(self.model, "segmentor", self.model)
+        if not (hasattr(self.model, "prefetch_geometry") and positions[0].is_cuda and getattr(seg, "overlap", True)
+                and streams.may_fork(dev)):
+            return _Shared(None, positions)
+        main = torch.cuda.current_stream(dev)
+        if dev not in _AHEAD_STREAMS:
+            _AHEAD_STREAMS[dev] = torch.cuda.Stream(device=dev)
+        side = _AHEAD_STREAMS[dev]
+        cat = positions[0] if len(positions) == 1 else torch.cat(positions, 0)
+        side.wait_stream(main)              # the batches are joined, the concatenation is queued: beside what follows on main
+        with torch.cuda.stream(side):
+            geometry = self.model.prefetch_geometry(cat, inline=True)
+            ready = streams.event()
+            ready.record(side)
+        cat.record_stream(side)
+        for _, t in graph_eval.tree_tensors(geometry):      # side-stream memory the current stream will read
+            t.record_stream(main)
+        return _Shared(geometry, positions, ready)
+
+    def forward(self, data, share, next_batches):
+        token = self.start(next_batches) if next_batches else None
+        geometry = None
+        if share is not None:
+            shared, index = share
+            if shared.ready is not None:
+                torch.cuda.current_stream(data["pos"].device).wait_event(shared.ready)
+            geometry = shared.slice_for(index, data["pos"])
+        out = self.model(data) if geometry is None else self.model(data, geometry=geometry)
+        return out[0], token
+
+
+class _GraphedAhead:
+    """The look-ahead of _passes on a graph_eval.GraphedForward: P on its side stream, F replayed over the pass's slice."""
+
+    def __init__(self, graphed):
+        self.graphed = graphed
+
+    def start(self, batches):
+        positions = [b["pos"] for b in batches]
+        return _Shared(self.graphed.lookahead(positions), positions)
+
+    def forward(self, data, share, next_batches):
+        geometry = None
+        if share is not None:
+            self.graphed.join()             # the slice below reads P's product
+            geometry = share[0].slice_for(share[1], data["pos"])
+        positions = [b["pos"] for b in next_batches] if next_batches else None
+        out = self.graphed(data, geometry, next_positions=positions)
+        return out[0], _Shared(self.graphed.ahead, positions) if positions else None
+
+
+def _passes(model, batcher, groups, repeats, draws, lookahead=0, graphed=None, runner=None):
     """The look-ahead loop of every whole-scan pass: each list of scan numbers in `groups` runs through the model `repeats`
     times, each time on a freshly drawn batch -> (batch, logits, first pass of its group, last pass of its group) per pass.
     The next pass's batch is queued BEFORE the current forward pass -- beside it when the batcher has a side stream -- and
     the host draws (np.random.choice) happen inside batch(): seeded runs are equal only while this order holds.  draws goes to
-    every batch() call as it is."""
+    every batch() call as it is.
+    lookahead = G >= 1 (pass_schedule): up to G passes are drawn ahead -- the same batch() calls in the same order -- and
+    their coordinate-only work (Group, the largest FPS, the index plan) runs as ONE prefetch_geometry over their concatenated
+    positions beside the forward pass in flight; each pass takes its Geometry.slice.  graphed: a graph_eval.GraphedForward
+    -- that geometry call and every forward pass replay from hipGraphs, and the logits of a pass are a fixed buffer the next
+    pass overwrites (a consumer uses them before it asks for the next pass).  runner: the object that does both (tests)."""
     passes = [(ids, k == 0, k + 1 == repeats) for ids in groups for k in range(repeats)]
-    data = batcher.batch(passes[0][0], draws=draws) if passes else None
-    for k, (_, first, last) in enumerate(passes):
-        batcher.join(data)
-        ahead = batcher.batch(passes[k + 1][0], draws=draws) if k + 1 < len(passes) else None
-        logits, _, _ = model(data)
-        yield data, logits, first, last
-        data = ahead
+    if not lookahead:
+        data = batcher.batch(passes[0][0], draws=draws) if passes else None
+        for k, (_, first, last) in enumerate(passes):
+            batcher.join(data)
+            ahead = batcher.batch(passes[k + 1][0], draws=draws) if k + 1 < len(passes) else None
+            logits, _, _ = model(data)
+            yield data, logits, first, last
+            data = ahead
+        return
+    if runner is None:
+        runner = _GraphedAhead(graphed) if graphed is not None else _EagerAhead(model)
+    batches, shares, joined, announced, ran = {}, {}, set(), None, False
+
+    def join(k):
+        if k not in joined:
+            batcher.join(batches[k])
+            joined.add(k)
+    for op, arg in pass_schedule([len(ids) for ids in groups], repeats, lookahead)[1]:
+        if op == "draw":
+            batches[arg] = batcher.batch(passes[arg][0], draws=draws)
+        elif op == "geometry":
+            for j in arg:
+                join(j)
+            if not ran:                     # the first chunk: no forward pass is in flight to run beside
+                token = runner.start([batches[j] for j in arg])
+                shares.update((j, (token, i)) for i, j in enumerate(arg))
+                ran = True
+            else:                           # started by the forward pass that follows, beside it
+                announced = arg
+        else:
+            upcoming, announced, ran = announced, None, True
+            join(arg)
+            data = batches.pop(arg)
+            joined.discard(arg)
+            logits, token = runner.forward(data, shares.pop(arg, None), [batches[j] for j in upcoming] if upcoming else None)
+            if upcoming:
+                shares.update((j, (token, i)) for i, j in enumerate(upcoming))
+            yield (data, logits) + passes[arg][1:]
 
 
-def _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_refine, parts, what):
+def _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_refine, parts, what, lookahead=0, graphed=None):
     """The body of validate_scans (num_votes = 0: one pass per batch, scored by geot_scan_predict) and validate_scans_voted
     (num_votes passes per batch, summed by geot_scan_vote and scored on the last): batches of batch_size scans in `indices`'
     order through _passes, counted into one SegMetrics; with n_refine the labels are taken, refined and counted instead."""
@@ -569,7 +751,7 @@ def _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_r
     groups = [order[at:at + int(batch_size)] for at in range(0, len(order), int(batch_size))]
     metrics = SegMetrics(c, batcher.device)
     votes = None
-    for data, logits, first, last in _passes(model, batcher, groups, max(num_votes, 1), draws):
+    for data, logits, first, last in _passes(model, batcher, groups, max(num_votes, 1), draws, lookahead, graphed):
         if num_votes and first:
             votes = ScanVotes(data, c)
         if not last:
@@ -587,16 +769,19 @@ def _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_r
 
 @torch.no_grad()
 def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, num_votes=0, data_transform=None, refine=0,
-                   parts=None):
+                   parts=None, graph=False, lookahead=0):
     """validate() without a loader: scans a DeviceScanSet (or a ValBatcher built on one, reused from epoch to epoch),
     batches of batch_size scans in the sequential sampler's order (the last, shorter batch is kept: drop_last is false for
     `val`), or of the scans `indices` names (a rank's shard).  cfg.num_points sizes the sample, cfg.num_classes (default
     17) the counts.  Same log lines, return value and dtypes as validate().  stream: the next batch is built on that side
     stream while the current one runs through the model.  num_votes and data_transform are accepted and unused, as in the
     reference.  refine (0: off -- cfg.refine is not read; True: n = 10; an int: n) and parts: the per-vertex labels are taken,
-    refined (refine_scans) and counted against the scans' labels with geot_seg_confusion."""
+    refined (refine_scans) and counted against the scans' labels with geot_seg_confusion.  graph, lookahead
+    (_replay_switches, _passes): the passes' geometry computed ahead and the forward passes replayed from hipGraphs -- the
+    same values; off by default."""
     from .openpoints.dataset.val_batch import ValBatcher
     n_refine = _refine_n(refine, "validate_scans")
+    lookahead, graphed = _replay_switches(graph, lookahead, 0, model, "validate_scans")
     model.eval()
     c = _cfg(cfg, "num_classes", 17)
     if isinstance(scans, ValBatcher):
@@ -605,7 +790,7 @@ def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, n
     else:
         need(_cfg(cfg, "num_points") is not None, "validate_scans: cfg.num_points (the sample size) is missing")
         batcher = ValBatcher(scans, _cfg(cfg, "num_points"), c, stream=stream)
-    return _validate(model, batcher, cfg, c, batch_size, indices, 0, None, n_refine, parts, "validate_scans")
+    return _validate(model, batcher, cfg, c, batch_size, indices, 0, None, n_refine, parts, "validate_scans", lookahead, graphed)
 
 
 def _scan_labels(batch):
@@ -665,16 +850,18 @@ class ScanVotes:
 
 
 @torch.no_grad()
-def vote_scans(model, batcher, idx, num_votes, draws=None, refine=0, parts=None):
+def vote_scans(model, batcher, idx, num_votes, draws=None, refine=0, parts=None, graph=False, lookahead=0):
     """The voted per-vertex labels of the scans `idx` of a VoteBatcher's set: list of (1, M_i) int64 tensors, as predict_scans
     returns them.  num_votes model passes, each on a freshly drawn batch of the same scans (draws: a DeviceDraws for these
     batches; default: the batcher's); the next batch is built beside the forward pass when the batcher has a side stream.
-    refine (0: off, True: n = 10, an int: n) and parts: the voted labels then go through refine_scans."""
+    refine (0: off, True: n = 10, an int: n) and parts: the voted labels then go through refine_scans.  graph, lookahead: as
+    for validate_scans; lookahead=True runs ONE geometry call for all num_votes passes."""
     need(int(num_votes) >= 1, "vote_scans: num_votes >= 1")
     n_refine = _refine_n(refine, "vote_scans")
+    lookahead, graphed = _replay_switches(graph, lookahead, int(num_votes), model, "vote_scans")
     model.eval()
     votes = preds = None
-    for data, logits, first, last in _passes(model, batcher, [idx], int(num_votes), draws):
+    for data, logits, first, last in _passes(model, batcher, [idx], int(num_votes), draws, lookahead, graphed):
         if first:
             votes = ScanVotes(data, logits.shape[1])
         preds = votes.add(logits, data, last=last, want_pred=last)
@@ -683,20 +870,22 @@ def vote_scans(model, batcher, idx, num_votes, draws=None, refine=0, parts=None)
 
 @torch.no_grad()
 def validate_scans_voted(model, scans, cfg, num_votes=None, vote=None, batch_size=2, indices=None, stream=None, draws=None,
-                         refine=0, parts=None):
+                         refine=0, parts=None, graph=False, lookahead=0):
     """validate_scans with votes: every batch of scans runs through the model num_votes times, each time freshly sampled and
     under the `vote` transform list, and is scored on the arg-max of the summed whole-scan probabilities.  scans: a
     DeviceScanSet, or a VoteBatcher built on one.  num_votes defaults to cfg.num_votes, vote to cfg.datatransforms.vote when
     present (else VoteBatcher's default, the yaml's [PointCloudScaling]); the lists' kwargs to cfg.datatransforms.kwargs.
     num_votes < 1 raises ValueError: validate_scans is the un-voted call.  The next vote's batch is built on `stream` beside
     the current forward pass.  Same log lines, return value and dtypes as validate().  refine, parts: as for validate_scans,
-    on the voted labels."""
+    on the voted labels.  graph, lookahead: as for validate_scans; lookahead=True draws a group's num_votes passes at once
+    and runs one geometry call for them."""
     from .openpoints.dataset.vote_batch import DEFAULT_VOTE, TOOTH_VIEW_KWARGS, VoteBatcher
     n_refine = _refine_n(refine, "validate_scans_voted")
     num_votes = _cfg(cfg, "num_votes", 0) if num_votes is None else num_votes
     if num_votes is None or int(num_votes) < 1:
         raise ValueError("validate_scans_voted: num_votes must be >= 1, got %r (validate_scans is the un-voted call)" % (num_votes,))
     num_votes = int(num_votes)
+    lookahead, graphed = _replay_switches(graph, lookahead, num_votes, model, "validate_scans_voted")
     model.eval()
     c = _cfg(cfg, "num_classes", 17)
     if isinstance(scans, VoteBatcher):
@@ -711,4 +900,5 @@ def validate_scans_voted(model, scans, cfg, num_votes=None, vote=None, batch_siz
         kwargs = _cfg(transforms, "kwargs") if transforms is not None else None
         batcher = VoteBatcher(scans, _cfg(cfg, "num_points"), c, vote=DEFAULT_VOTE if vote is None else vote,
                               kwargs=TOOTH_VIEW_KWARGS if kwargs is None else kwargs, stream=stream, draws=draws)
-    return _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_refine, parts, "validate_scans_voted")
+    return _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_refine, parts, "validate_scans_voted",
+                     lookahead, graphed)
