@@ -241,6 +241,18 @@ class _Graphed:
         tags = {k[k.index("@"):] if "@" in k else "" for k in self.graphs}
         return any(("M" + t in self.graphs or "M2" + t in self.graphs) and "P" + t in self.graphs for t in tags)
 
+    def state_dict(self):
+        """The wrapped step's state_dict() (refused under capture, like the step's)."""
+        return self.step.state_dict()
+
+    def load_state_dict(self, state):
+        """The wrapped step's load_state_dict(): every tensor is restored in place, so the captured graphs go on reading and
+        writing the restored memory; nothing is captured anew.  A look-ahead in flight is waited for (it reads what the load
+        writes) and, once the state has been accepted, dropped: the next call runs P in line for its batch -- same results."""
+        self._join_pending()
+        self.step.load_state_dict(state)
+        self._pre_next = self._pre_tag = self._announced = None
+
     def _join_pending(self):
         """The current stream waits for the P of the previous call (its product, and its reads of P's static inputs)."""
         if self._pending:

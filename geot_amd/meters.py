@@ -56,6 +56,28 @@ class FixMatchMeters:
         for t in (self.counts, self.f32, self.f64, self.i64):
             t.zero_()
 
+    _BUFFERS = ("counts", "f32", "f64", "i64", "ema_t_corr")
+
+    def state_dict(self):
+        """The epoch so far: copies of the five device buffers, made on the current stream (no synchronisation).  ema_t is
+        the step's buffer and travels with the step."""
+        from . import checkpoint as ck
+        ck.refuse_capture("FixMatchMeters")
+        return {k: ck.copied(getattr(self, k)) for k in self._BUFFERS}
+
+    def restore(self, r, state, key="meters"):
+        """The first half of load_state_dict: check `state` and hand the writes to r (a checkpoint.Restore)."""
+        r.keys(state, self._BUFFERS, key)
+        for k in self._BUFFERS:
+            r.tensor("%s.%s" % (key, k), getattr(self, k), state[k])
+
+    def load_state_dict(self, state):
+        """Checked first (ValueError naming the key), then copied into the buffers (a captured iteration holds them)."""
+        from . import checkpoint as ck
+        r = ck.Restore()
+        self.restore(r, state)
+        r.commit()
+
     def update(self, label_u_aug, logits_u_aug, y_u, prob_s, loss, sup, unsup, threed, ema_t_corr=None, feat=None,
                identity=None):
         """One iteration, on the current stream: label_u_aug (B_u, N) int64 pseudo labels, logits_u_aug (B_u, N) fp32 their

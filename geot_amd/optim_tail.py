@@ -29,7 +29,8 @@ graph serves every call of a window.  The gradients are still dropped after ever
 by update calls only: between two updates they hold the norm of the last window's sum.  A window that an epoch cuts off is
 not lost: restart() returns the counter to 0 and keeps the sum, which joins the next window, as the reference's num_iter = 0
 (train.py:435) against its zero_grad() (train.py:664) has it.  `tail.window` and `tail.accumulator` are public: a checkpoint
-in the middle of a window saves both and hands them back with accumulator.copy_() and restart(window=n).  Which parameters
+in the middle of a window saves both and hands them back with accumulator.copy_() and restart(window=n) -- which is what
+state_dict() / load_state_dict() below do, in place and checked first (geot_amd/checkpoint.py).  Which parameters
 an open window holds is followed on the host, by the eager calls (a replayed graph has its set fixed); a caller that changes the
 set of parameters with gradients between a replay and an eager call of one window starts that window with restart(drop=True).
 
@@ -243,6 +244,65 @@ class OptimTail:
             self._step_views[i] = view
         self._states = [opt.state for opt in self.optimizers]
         return True
+
+    def create_state(self, indices):
+        """The state of these parameters (indices into self.params), as the first step() that finds their gradients creates
+        it: what a load fills in a fresh tail (geot_amd/checkpoint.py)."""
+        self._bind_state(sorted(set(indices) | set(self._bound or ())))
+
+    def state_dict(self):
+        """What the tail keeps beside the optimizers' state (which the optimizers' entries of a step's state hold, step
+        counters included): total_norm / clip_coef, and under accumulate > 1 the open window -- the accumulator, the device
+        counter `window` and the host's view of it (_calls, _pending).  Copies on the current stream, no synchronisation."""
+        from . import checkpoint as ck
+        ck.refuse_capture("OptimTail")
+        if self._kept:
+            raise RuntimeError("OptimTail.state_dict: composite() holds the gradients of an open window (the oracle's own "
+                               "form of accumulate > 1, which no step runs: not saved)")
+        out = {"accumulate": self.accumulate, "total_norm": ck.copied(self.total_norm), "clip_coef": ck.copied(self.clip_coef)}
+        if self.accumulate > 1:
+            out.update(accumulator=ck.copied(self.accumulator), window=ck.copied(self.window), _calls=self._calls,
+                       _pending=sorted(self._pending))
+        return out
+
+    def restore(self, r, state, key="tail"):
+        """The first half of load_state_dict: check `state` and hand the writes to r (a checkpoint.Restore)."""
+        windowed = ("accumulator", "window", "_calls", "_pending") if self.accumulate > 1 else ()
+        r.keys(state, ("accumulate", "total_norm", "clip_coef") + windowed, key)
+        if state["accumulate"] != self.accumulate:
+            raise ValueError("%s.accumulate: the state was saved with %r, the tail is built with %r"
+                             % (key, state["accumulate"], self.accumulate))
+        r.tensor(key + ".total_norm", self.total_norm, state["total_norm"])
+        r.tensor(key + ".clip_coef", self.clip_coef, state["clip_coef"])
+        if not windowed:
+            return
+        r.tensor(key + ".accumulator", self.accumulator, state["accumulator"])
+        r.tensor(key + ".window", self.window, state["window"])
+        # The host's view of the window is followed by eager calls only: a state taken behind replays carries the view of the
+        # last call that ran in python.  The device counter is the truth, and a load may read it (a state on the device: one
+        # synchronisation): the host resumes from it.  _pending stays the saved set -- with a fixed set of parameters, the one
+        # case a replay serves, it is the set of every call.
+        pending = state["_pending"]
+        calls = int(state["window"])
+        for name, v in (("_calls", r.number(key + "._calls", state["_calls"], int)), ("window", calls)):
+            if not 0 <= v < self.accumulate:
+                raise ValueError("%s.%s: %r is no call of a window of %d" % (key, name, v, self.accumulate))
+        if not isinstance(pending, list) or any(isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < len(self.params)
+                                                for i in pending):
+            raise ValueError("%s._pending: expected a list of parameter indices below %d, got %r" % (key, len(self.params), pending))
+
+        def host():
+            self._calls, self._pending = calls, set(pending)
+            self._composite_calls, self._kept = calls, {}          # (as restart(window=calls) leaves the oracle's count)
+        r.then(host)
+
+    def load_state_dict(self, state):
+        """state_dict()'s counterpart: checked first (ValueError naming the key), then copied into the tensors that exist --
+        a captured graph holds the accumulator, the counter and the scalars."""
+        from . import checkpoint as ck
+        r = ck.Restore()
+        self.restore(r, state)
+        r.commit()
 
     # ---- the table ----------------------------------------------------------------------------------------------------------
     def _build(self, active, grads):

@@ -1,6 +1,7 @@
 """The training steps the BASELINE configs time, composed from the mirrored modules -- the part of
 examples/segmentation/train.py that drives the hot path, and nothing else of the driver (no loaders,
-logging, checkpoints; the epoch meters only on request, computed on the device):
+logging, files; the epoch meters only on request, computed on the device; state_dict() / load_state_dict() hand a step's
+whole state out and take it back in place, geot_amd/checkpoint.py writes it to a file):
 
 * ``SupervisedStep``  -- configs[2]/[3]: forward of the segmentor on a batch of clouds, Poly1FocalLoss,
   backward, (DDP gradient all-reduce when wrapped,) clip + AdamW step (train.py:436-452, 646-657).
@@ -345,6 +346,70 @@ class _UpdateWindow:
             if self.tail is not None:
                 self.tail.restart()
 
+    # ---- what a checkpoint keeps of the window (geot_amd/checkpoint.py) ----
+    def window_state(self, modules):
+        """-> {"window_calls", "tail", "grads"}: the torch form's count, the tail's state_dict() (None without a tail) and --
+        in the torch form inside an open window only -- the .grad of `modules`' parameters ({name: module}), which hold the
+        window's partial sum.  (The fused tail sums in its accumulator and the gradients are dropped after every call.)"""
+        from . import checkpoint as ck
+        grads = None
+        if not self.fused and self._window_calls > 0:
+            grads = {name: {n: ck.copied(p.grad) for n, p in _unwrapped(m).named_parameters() if p.grad is not None}
+                     for name, m in modules.items()}
+        return {"window_calls": self._window_calls, "tail": self.tail.state_dict() if self.tail is not None else None,
+                "grads": grads}
+
+    def restore_window(self, r, state, modules):
+        """window_state()'s counterpart, first half: checks, and hands the writes to r (a checkpoint.Restore)."""
+        calls = r.number("window_calls", state["window_calls"], int)
+        if not 0 <= calls < self.step_per_update or (self.fused and calls):
+            raise ValueError("window_calls: %r is no call of this step's window (step_per_update %d, %s form)"
+                             % (calls, self.step_per_update, "fused" if self.fused else "torch"))
+        if (state["tail"] is None) != (self.tail is None):
+            raise ValueError("tail: %s key 'tail' (the step is built %s a tail)"
+                             % (("missing", "with") if self.tail is not None else ("unexpected", "without")))
+        if self.tail is not None:
+            self.tail.restore(r, state["tail"])
+        grads = state["grads"]
+        if (grads is not None) != (not self.fused and calls > 0):
+            raise ValueError("grads: %s key 'grads' (the torch form carries its open window in .grad, and only there)"
+                             % ("unexpected" if grads is not None else "missing"))
+        writes = []
+        if grads is not None:
+            r.keys(grads, list(modules), "grads")
+        for name, m in modules.items():
+            own = dict(_unwrapped(m).named_parameters())
+            saved = grads[name] if grads is not None else {}
+            r.keys(saved, (), "grads.%s" % name, optional=list(own))
+            for n, p in own.items():
+                if n in saved:
+                    r.check("grads.%s.%s" % (name, n), p, saved[n])
+                writes.append((p, saved.get(n)))
+
+        def host():
+            self._window_calls = calls
+            if self.fused:
+                return
+            for p, g in writes:        # (outside a window the torch form holds no gradient: zero_grad(set_to_none=True))
+                if g is None:
+                    p.grad = None
+                elif p.grad is None:
+                    p.grad = g.detach().to(p.device, copy=True)
+                else:
+                    p.grad.copy_(g)
+        r.then(host)
+
+
+def _check_head(r, state, keys, kind, layout):
+    """The head of a step's state: its keys, the format version, the kind of step and the layout cfg keys."""
+    from . import checkpoint as ck
+    r.keys(state, keys, "")
+    if state["format"] != ck.FORMAT:
+        raise ValueError("format: the state has format %r, this package reads %r" % (state["format"], ck.FORMAT))
+    if state["kind"] != kind:
+        raise ValueError("kind: the state is a %s's, the step is a %s" % (state["kind"], kind))
+    ck.same_layout(state["layout"], layout)
+
 
 class _Cut:
     """A forward with the segmentor cutting its autograd graph at the transformer blocks (cut_at_blocks / take_cut), for a
@@ -540,6 +605,36 @@ class SupervisedStep(_UpdateWindow):
     def sync_modules(self):
         return [self.model]
 
+    _STATE_KEYS = ("format", "kind", "layout", "model", "optimizer", "window_calls", "tail", "grads")
+
+    def layout(self):
+        """The constructor arguments that fix the layout of state_dict()."""
+        return {"step_per_update": self.step_per_update, "fused_tail": self.fused}
+
+    def state_dict(self):
+        """Everything a resumed run needs of this step ("Checkpoints"): the model (unwrapped), the
+        optimizer in torch's own layout, the open step_per_update window.  Copies made on the current stream, no
+        synchronisation; between any two calls, not under stream capture."""
+        from . import checkpoint as ck
+        ck.refuse_capture("SupervisedStep")
+        out = {"format": ck.FORMAT, "kind": "SupervisedStep", "layout": self.layout(), "model": ck.module_state(self.model),
+               "optimizer": ck.optimizer_state(self.optimizer)}
+        out.update(self.window_state({"model": self.model}))
+        return out
+
+    def load_state_dict(self, state):
+        """state_dict()'s counterpart: everything is checked first (ValueError naming the key; the step is left as it was),
+        then every tensor that exists is written in place -- a captured graph holds them -- and optimizer state that does not
+        exist yet is created as the first eager call would.  A queued look-ahead is dropped."""
+        from . import checkpoint as ck
+        r = ck.Restore()
+        _check_head(r, state, self._STATE_KEYS, "SupervisedStep", self.layout())
+        r.module("model", self.model, state["model"])
+        r.optimizer("optimizer", self.optimizer, state["optimizer"], self.tail if self.fused else None)
+        self.restore_window(r, state, {"model": self.model})
+        r.then(lambda: setattr(self, "_geometry", None))
+        r.commit()
+
     def __call__(self, pos, cls, target, next_pos=None, class_weights=None):
         """pos (B,N,3) f32, cls (B,1) int64 jaw id, target (B,N) int64 -> detached loss.
         class_weights (B, C) f32: data['class_weights'], required by (and only read under) criterion="Weight_CELoss".
@@ -691,6 +786,72 @@ class FixMatchNTMStep(_UpdateWindow):
 
     def sync_modules(self):
         return [self.model, self.T_predictor]
+
+    _STATE_KEYS = ("format", "kind", "layout", "model", "model_t", "T_predictor", "optimizer", "T_optimizer", "ema_t", "cm",
+                   "epoch", "window_calls", "tail", "grads", "contrast", "meters")
+    _LAYOUT_KEYS = ("num_classes", "step_per_update", "fused_tail", "ema_teacher", "use_contrastive", "contrast_samples")
+
+    def layout(self):
+        """The cfg keys that fix the layout of state_dict(), and the width of the segmentor's head feature (None: a
+        segmentor without one)."""
+        out = {k: self.cfg[k] for k in self._LAYOUT_KEYS}
+        try:
+            out["head_width"] = int(_unwrapped(self.model).segmentor.seg_head[1].num_features)
+        except (AttributeError, IndexError, TypeError):
+            out["head_width"] = None
+        return out
+
+    def _stepped(self):
+        return {"model": self.model, "T_predictor": self.T_predictor}
+
+    def state_dict(self):
+        """Everything a resumed run needs of this step ("Checkpoints"): student, teacher and T_predictor
+        (unwrapped), both optimizers in torch's own layout, ema_t, cm, the epoch, the open step_per_update window, the
+        contrastive loss's bank and counters, the meters' buffers.  Copies made on the current stream, no synchronisation;
+        between any two calls -- inside an open window too --, not under stream capture."""
+        from . import checkpoint as ck
+        ck.refuse_capture("FixMatchNTMStep")
+        out = {"format": ck.FORMAT, "kind": "FixMatchNTMStep", "layout": self.layout(),
+               "model": ck.module_state(self.model), "model_t": ck.module_state(self.model_t),
+               "T_predictor": ck.module_state(self.T_predictor),
+               "optimizer": ck.optimizer_state(self.optimizer), "T_optimizer": ck.optimizer_state(self.T_optimizer),
+               "ema_t": ck.copied(self.ema_t), "cm": ck.copied(self.cm), "epoch": self.epoch,
+               "contrast": self.contrast.state_dict() if self.contrast is not None else None,
+               "meters": self.meters.state_dict() if self.meters is not None else None}
+        out.update(self.window_state(self._stepped()))
+        return out
+
+    def load_state_dict(self, state):
+        """state_dict()'s counterpart: everything is checked first (ValueError naming the key; the step is left as it was),
+        then every tensor that exists is written in place -- a captured graph holds them -- and optimizer state that does not
+        exist yet is created as the first eager call would.  The epoch is set as it was saved, WITHOUT restart_window(): the
+        window is the saved one.  A queued look-ahead is dropped: the next call computes its batch work in line."""
+        from . import checkpoint as ck
+        r = ck.Restore()
+        _check_head(r, state, self._STATE_KEYS, "FixMatchNTMStep", self.layout())
+        for key, module in (("model", self.model), ("model_t", self.model_t), ("T_predictor", self.T_predictor)):
+            r.module(key, module, state[key])
+        tail = self.tail if self.fused else None
+        r.optimizer("optimizer", self.optimizer, state["optimizer"], tail)
+        r.optimizer("T_optimizer", self.T_optimizer, state["T_optimizer"], tail)
+        r.tensor("ema_t", self.ema_t, state["ema_t"])
+        r.tensor("cm", self.cm, state["cm"])
+        epoch = state["epoch"]
+        if epoch is not None:
+            r.number("epoch", epoch, int)
+        for key, part in (("contrast", self.contrast), ("meters", self.meters)):
+            if (state[key] is None) != (part is None):
+                raise ValueError("%s: %s key %r (the step is built %s it)"
+                                 % ((key, "missing", key, "with") if part is not None else (key, "unexpected", key, "without")))
+            if part is not None:
+                part.restore(r, state[key], key)
+        self.restore_window(r, state, self._stepped())
+
+        def host():
+            self.epoch = epoch
+            self._geometry = (None, None)
+        r.then(host)
+        r.commit()
 
     def set_epoch(self, epoch):
         """The epoch of the iterations that follow (train.py's loop variable): above cfg switch_ep the pseudo labels come

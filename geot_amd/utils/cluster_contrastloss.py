@@ -152,6 +152,35 @@ class nativeContrastLoss_t(nn.Module):
         self.draw_counter = torch.tensor([first - (1 << 64) if first >= 1 << 63 else first], dtype=torch.long).to(device)
         self.anchors = None
 
+    def state_dict(self, *args, **kw):
+        """What the loss carries from call to call: the bank, the queue pointer and the draw counter on the device (copies
+        made on the current stream, no synchronisation), and the draws' seed.  (The bank is a plain attribute as in the
+        reference, no registered buffer: nn.Module's own state_dict -- what any argument asks for -- is empty.)"""
+        if args or kw:
+            return super().state_dict(*args, **kw)
+        from .. import checkpoint as ck
+        ck.refuse_capture("nativeContrastLoss_t")
+        return {"point_queue": ck.copied(self.point_queue), "point_queue_ptr": ck.copied(self.point_queue_ptr),
+                "draw_counter": ck.copied(self.draw_counter), "seed": self.seed}
+
+    def restore(self, r, state, key="contrast"):
+        """The first half of load_state_dict: check `state` and hand the writes to r (a checkpoint.Restore)."""
+        r.keys(state, ("point_queue", "point_queue_ptr", "draw_counter", "seed"), key)
+        if state["seed"] != self.seed:
+            raise ValueError("%s.seed: the state was saved with %r, the loss is built with %r (cfg contrast_seed)"
+                             % (key, state["seed"], self.seed))
+        for k in ("point_queue", "point_queue_ptr", "draw_counter"):
+            r.tensor("%s.%s" % (key, k), getattr(self, k), state[k])
+
+    def load_state_dict(self, state, *args, **kw):
+        """Checked first (ValueError naming the key), then copied into the three device tensors, none of which is rebound."""
+        if args or kw:
+            return super().load_state_dict(state, *args, **kw)
+        from .. import checkpoint as ck
+        r = ck.Restore()
+        self.restore(r, state)
+        r.commit()
+
     def _host_perms(self, score, b, s):
         """The reference's draws: the counts are read back, randperm(K_b) per cloud and then randperm(A) from the global
         generator, in that order (:1249, :1210)."""
