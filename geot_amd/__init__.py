@@ -5,6 +5,7 @@ interpolation hot path behind the reference's operator API.
     from geot_amd.pointops.functions import pointops        # fps, knn, ...
     from geot_amd.knn_cuda import KNN
     import geot_amd.aliases; geot_amd.aliases.install()     # reference import names -> this package
+    from geot_amd import fit, train_one_epoch, epoch_batches, LrSchedule      # the training driver (fit.py, schedule.py)
 
 The compute path is libgeot_hip.so (C ABI in include/geot_hip.h); there is no CPU fallback.
 """
@@ -44,3 +45,15 @@ def graph_replay_is_safe():
     import): hipGraph packet capture is then off for certain and any captured graph replays correctly.  Otherwise graph_step
     (and bench.py's own captures) inspect every graph and accept kernel nodes only."""
     return _EXPORTED_BEFORE_IMPORT == "0"
+
+
+# The training driver's names, bound on first use (importing the package itself imports nothing else: the switch above has to
+# be set before anything touches HIP).  `fit` needs no entry: geot_amd.fit is the module, and the module is callable.
+_EXPORTS = {"train_one_epoch": "fit", "epoch_batches": "fit", "LrSchedule": "schedule"}
+
+
+def __getattr__(name):
+    if name in _EXPORTS:
+        import importlib
+        return getattr(importlib.import_module("." + _EXPORTS[name], __name__), name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -31,7 +31,8 @@ checked on the host (the very tensors the previous call announced, unedited); ot
 loader, no look-ahead at all -- P runs for the current batch on the current stream before M.
 
 A learning-rate schedule reaches a captured AdamW step through memory: make `lr` a float32 device tensor in the optimizer's
-parameter groups and fill_ it between calls (tests/test_graph_step_gpu.py); a python float is baked into the graph.
+parameter groups and fill_ it between calls (tests/test_graph_step_gpu.py; geot_amd/schedule.py LrSchedule does both for the
+configured schedule, and fit.py installs it before the first call); a python float is baked into the graph.
 Inputs are copied into static buffers before every replay; shapes are fixed by the first call (another shape is an error:
 build another wrapper).  The first `warmup` executions of each graph's body run eagerly over the same buffers, the next
 one captures.  N > 1: DistributedDataParallel itself is not captured (its reducer is host logic); a step built on the bare
