@@ -27,6 +27,7 @@
 #include "geot_common.h"
 #include "geot_hip.h"
 #include "knn_grid.h"
+#include "scan_finish.h"
 #include "seg_metrics.h"
 #include <cstdlib>
 
@@ -78,27 +79,7 @@ __device__ __forceinline__ int sp_argmax(float v, int c)
     return __builtin_ctzll(__ballot(in && v == mx));     // c >= 1: lane 0 is in, so the ballot is not empty
 }
 
-// the same rule over one row of a summed tile, serially in one lane
-__device__ __forceinline__ int sp_argmax_row(const float *row, int c)
-{
-    float best = row[0];
-    int at = 0;
-    bool nan = best != best;
-    for (int k = 1; k < c; ++k) {
-        const float x = row[k];
-        if (!nan && (x != x || x > best)) { best = x; at = k; nan = x != x; }
-    }
-    return at;
-}
-
-// Between a wave's LDS writes and its other lanes' reads of them: the hardware keeps one wave's LDS accesses in order, this
-// keeps the compiler from moving them across.
-__device__ __forceinline__ void sp_wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+// (the same rule over one row of a summed tile, and the wave's LDS ordering: scan_finish.h)
 
 constexpr int SP_PREDICT = 0, SP_VOTE_ROW = 1, SP_VOTE_TILE = 2;     // what a kernel does with the interpolated values
 

@@ -9,7 +9,7 @@ from .grid_sample import grid_subsampling  # noqa: F401
 from .tooth_prep import pc_norm, prepare_sample  # noqa: F401
 from .fixmatch_batch import (TOOTH_VIEW_KWARGS, DeviceScanSet, FixMatchBatcher, cloud_sample_batch, draw_view_params,  # noqa: F401
                              fixmatch_views)
-from .sample_draw import DeviceDraws, ViewDrawHandle, sample_draw  # noqa: F401
+from .sample_draw import DeviceDraws, ViewDrawHandle, cover_passes, sample_draw, sample_draw_cover  # noqa: F401
 from .val_batch import ValBatcher, draw_val_sel  # noqa: F401
 from .view_program import ViewProgram, pack_fixed_jobs, pack_program_jobs, view_program_views  # noqa: F401
 from .view_draw import DrawLayout, view_draw, view_program_draw, view_program_views_drawn  # noqa: F401

@@ -6,6 +6,9 @@ a batch in one launch.
 These are NOT numpy's draws: the kernel is a counter-based generator (Philox4x32-10 under a keyed bijection, the contract is
 in include/geot_hip.h), so a row depends on (seed, draw id) alone and is the same in every process, on every device, in any
 launch order.  The batchers' default stays the reference's host draws; they take `draws=DeviceDraws(seed)` to switch.
+
+Covering draws (geot_sample_draw_cover): sample_draw_cover(..., p) is window p of the draw id's permutation of the whole scan,
+so cover_passes(sizes, m) = max ceil(n / m) passes show a model every vertex once (ScanBatcher.cover, validation.cover_scans).
 """
 import contextlib
 
@@ -18,31 +21,56 @@ from .scan_set import DeviceScanSet
 _MASK64 = (1 << 64) - 1
 
 
+def _draw(entry, scans, scan_ids, m, seed, draw_base, *more):
+    """The arguments and outputs geot_sample_draw and geot_sample_draw_cover share; more: what follows draw_base."""
+    need(isinstance(scans, DeviceScanSet), "%s: scans must be a DeviceScanSet" % entry)
+    dev = scans.device
+    if scan_ids is None:
+        ids_dev, s = None, len(scans)
+    elif isinstance(scan_ids, torch.Tensor):
+        need(scan_ids.dtype == torch.int64 and scan_ids.dim() == 1 and scan_ids.device == dev and scan_ids.is_contiguous(),
+             "%s: scan_ids as a tensor must be (S,) int64, contiguous, on the scans' device" % entry)
+        ids_dev, s = scan_ids, int(scan_ids.shape[0])
+    else:
+        ids = np.ascontiguousarray(np.asarray(scan_ids, dtype=np.int64).reshape(-1))
+        ids_dev, s = torch.from_numpy(ids).pin_memory().to(dev, non_blocking=True), ids.size
+    m = int(m)
+    need(1 <= s <= 65535, "%s: 1 to 65535 slots, got %d" % (entry, s))
+    need(m >= 1, "%s: m >= 1" % entry)
+    sel = torch.empty((s, m), dtype=torch.int64, device=dev)
+    bad = torch.empty(s, dtype=torch.int32, device=dev)
+    call("geot_" + entry, dev, s, m, len(scans), int(scans.points.shape[0]), ptr(scans.offsets), ptr(ids_dev),
+         int(seed) & _MASK64, int(draw_base) & _MASK64, *more, ptr(sel), ptr(bad))
+    return sel, bad
+
+
 def sample_draw(scans, scan_ids, m, seed, draw_base):
     """geot_sample_draw: scans a DeviceScanSet; scan_ids: the set scan of every slot -- S ints on the host, an (S,) int64
     tensor on the scans' device (used as it is) or None (slot i is scan i, S = len(scans)); slot i draws m vertex indices
     of its scan with the draw id draw_base + i -> (sel (S, m) int64, bad (S,) int32), both on the device, queued on the
     current stream without a host synchronisation.  A slot whose id lies outside the set gets a row of zeros and bad = 2
     (nothing is checked on the host: the sizes live on the device)."""
-    need(isinstance(scans, DeviceScanSet), "sample_draw: scans must be a DeviceScanSet")
-    dev = scans.device
-    if scan_ids is None:
-        ids_dev, s = None, len(scans)
-    elif isinstance(scan_ids, torch.Tensor):
-        need(scan_ids.dtype == torch.int64 and scan_ids.dim() == 1 and scan_ids.device == dev and scan_ids.is_contiguous(),
-             "sample_draw: scan_ids as a tensor must be (S,) int64, contiguous, on the scans' device")
-        ids_dev, s = scan_ids, int(scan_ids.shape[0])
-    else:
-        ids = np.ascontiguousarray(np.asarray(scan_ids, dtype=np.int64).reshape(-1))
-        ids_dev, s = torch.from_numpy(ids).pin_memory().to(dev, non_blocking=True), ids.size
-    m = int(m)
-    need(1 <= s <= 65535, "sample_draw: 1 to 65535 slots, got %d" % s)
-    need(m >= 1, "sample_draw: m >= 1")
-    sel = torch.empty((s, m), dtype=torch.int64, device=dev)
-    bad = torch.empty(s, dtype=torch.int32, device=dev)
-    call("geot_sample_draw", dev, s, m, len(scans), int(scans.points.shape[0]), ptr(scans.offsets), ptr(ids_dev),
-         int(seed) & _MASK64, int(draw_base) & _MASK64, ptr(sel), ptr(bad))
-    return sel, bad
+    return _draw("sample_draw", scans, scan_ids, m, seed, draw_base)
+
+
+MAX_PASS = (1 << 31) - 1        # include/geot_hip.h geot_sample_draw_cover
+
+
+def sample_draw_cover(scans, scan_ids, m, seed, draw_base, p):
+    """geot_sample_draw_cover: sample_draw's arguments and results for pass p (0 .. 2^31 - 1) of a covering draw -- slot i's
+    row holds positions p m .. p m + m - 1 (mod n_i) of ONE permutation of its scan's n_i vertices, the permutation of the
+    draw id draw_base + i.  Passes 0 .. cover_passes([n_i], m) - 1 of the same ids name every vertex of every slot; for
+    n_i >= m pass 0 is sample_draw's row.  Positions past n_i are wrap-around fill (the start of the permutation again)."""
+    need(isinstance(p, (int, np.integer)) and not isinstance(p, bool) and 0 <= int(p) <= MAX_PASS,
+         "sample_draw_cover: the pass must be an int in 0..%d, got %r" % (MAX_PASS, p))
+    return _draw("sample_draw_cover", scans, scan_ids, m, seed, draw_base, int(p))
+
+
+def cover_passes(sizes, m):
+    """How many passes of m samples cover scans of `sizes` vertices: max ceil(n / m) (host arithmetic)."""
+    sizes, m = [int(n) for n in sizes], int(m)
+    need(m >= 1 and len(sizes) >= 1 and all(n >= 1 for n in sizes), "cover_passes: m >= 1 and at least one scan of n >= 1 vertices")
+    return max(-(-n // m) for n in sizes)
 
 
 class DeviceDraws:

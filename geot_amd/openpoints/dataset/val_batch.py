@@ -26,6 +26,7 @@ import torch
 from ...ext._common import need
 from .batcher import Batcher
 from .fixmatch_batch import TOOTH_VIEW_KWARGS, _kw, draw_view_params, fixmatch_views
+from .sample_draw import DeviceDraws, cover_passes, on_stream, sample_draw_cover
 
 
 def draw_val_sel(sizes, num_points):
@@ -74,7 +75,42 @@ class ScanBatcher(Batcher):
 
     def join(self, batch):
         """Hand a batch built on the side stream to the CURRENT stream (Batcher._join)."""
-        self._join(batch[key] for key in self.join_keys)
+        self._join(batch[key] for key in self.join_keys + (("sel",) if "sel" in batch else ()))
+
+    def cover(self, idx, rounds=1, draws=None):
+        """The covering batches of the scans `idx`: a generator of rounds * P batches, P = cover_passes(their sizes, m), per
+        round in pass order.  Each is what batch() returns for the same idx plus "sel" -- the (B, m) int64 device tensor of the
+        pass's vertex indices (geot_sample_draw_cover) -- and "cover" = (pass, P, round).  The samples of a round's P passes
+        partition every scan: each vertex is sample j of exactly one pass with pass * m + j < its scan's size (the positions
+        past that are wrap-around fill, which keeps every cloud at m points); validation.ScanCover puts the model's output
+        for a sample on the vertex it names.
+        draws: a DeviceDraws (default: the constructor's) -- there is no host-draw form, ValueError without one, before any
+        device call.  len(idx) draw ids are taken once per round, when the round's first batch is built; a slot keeps its id
+        for all P passes, so the counter advances by len(idx) * rounds over the whole generator.  Under
+        DeviceDraws(views=True) a VoteBatcher's vote parameters are drawn from the slot's id as in batch(): one view per round,
+        shared by its passes; otherwise the vote list draws on the host per pass, as in batch()."""
+        ids, who = self._ids(idx), type(self).__name__
+        draws = self.draws if draws is None else draws
+        if not isinstance(draws, DeviceDraws):
+            raise ValueError("%s.cover: a covering draw is a device draw -- pass draws=DeviceDraws(seed) here or to the "
+                             "constructor (there is no host-draw form), got %r" % (who, draws))
+        if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or int(rounds) < 1:
+            raise ValueError("%s.cover: rounds must be an int >= 1, got %r" % (who, rounds))
+        return self._cover(ids, int(rounds), draws)
+
+    def _cover(self, ids, rounds, draws):
+        passes = cover_passes([self.scans.sizes[i] for i in ids], self.m)
+        ids_dev = None
+        for rnd in range(rounds):
+            base = draws.take(len(ids))
+            for p in range(passes):
+                with on_stream(self.stream):
+                    if ids_dev is None:
+                        ids_dev = torch.from_numpy(np.asarray(ids, dtype=np.int64)).pin_memory().to(self.device, non_blocking=True)
+                    sel, _ = sample_draw_cover(self.scans, ids_dev, self.m, draws.seed, base, p)
+                out = self._batch(ids, (len(ids),), sel, self._cover_params(ids, draws, base), ids_dev, False)
+                out["sel"], out["cover"] = sel, (p, passes, rnd)
+                yield out
 
 
 class ValBatcher(ScanBatcher):
@@ -102,6 +138,9 @@ class ValBatcher(ScanBatcher):
         weak = draw_view_params("train_w", self.kwargs)                   # the `val` list: nothing is drawn
         sel, params, ids_dev = self._draw(ids, (("sel", sel, len(ids)),), [weak] * len(ids), draws, None)
         return self._batch(ids, (len(ids),), sel, params, ids_dev, check)
+
+    def _cover_params(self, ids, draws, base):
+        return [draw_view_params("train_w", self.kwargs)] * len(ids)    # as batch(): the `val` list draws nothing
 
     def _pack(self, shape, params):
         return [(i, i, p) for i, p in enumerate(params)]

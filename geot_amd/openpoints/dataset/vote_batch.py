@@ -56,6 +56,12 @@ class VoteBatcher(ScanBatcher):
             params = [self.val_program.draw(self.m)] * len(ids) + params
         return self._batch(ids, (len(ids),), sel, params, ids_dev, check)
 
+    def _cover_params(self, ids, draws, base):
+        """The view parameters of one covering pass (ScanBatcher.cover): the vote list applied per pass, as batch() does."""
+        if draws.views:     # drawn where they are used, under the slots' ids
+            return ViewDrawHandle(draws.seed, base, len(ids))
+        return [self.val_program.draw(self.m)] * len(ids) + [self.program.draw(self.m) for _ in ids]
+
     def _jobs(self, b):
         """Output rows [0, b) the `val` views, [b, 2 b) the voted ones; a slot's two jobs draw under the slot's id."""
         jobs = [(i, i, self.val_program) for i in range(b)] + [(i, b + i, self.program) for i in range(b)]

@@ -37,6 +37,16 @@ the whole scans and summed before the arg-max (geot_scan_vote: geot_scan_predict
     votes = ScanVotes(batch, num_classes); votes.add(logits, batch); ...; votes.add(logits, batch, last=True, want_pred=True)
     metrics.update_from_votes(votes, logits, batch)          # the last add(), counted into the epoch's rows
 
+Covering passes -- every vertex predicted directly.  Independent samples cover a scan badly: at M = 100 000 vertices and
+N = 16 000 samples a pass misses a vertex with probability 1 - N / M = 0.84, so after num_votes = 10 passes 0.84^10 = 17.5 % of
+the vertices were never seen by the model, and every label is interpolated.  P = ceil(M / N) = 7 passes whose samples partition
+the scan (geot_sample_draw_cover: consecutive windows of one permutation; ScanBatcher.cover) show it every vertex once, and
+geot_scan_cover puts the model's probabilities on the very vertex a sample is -- no neighbour search, no interpolation:
+
+    preds = cover_scans(model, ValBatcher(scans, n, draws=DeviceDraws(seed)), idx)           # P passes, each vertex its own value
+    out = validate_scans_covered(model, scans, cfg, draws=DeviceDraws(seed))                 # validate()'s values from them
+    cover = ScanCover(batch, num_classes); [cover.add(logits, batch, last=...) for batch in batcher.cover(idx)]
+
 Refinement -- the config's `refine` and the reference's part_seg_refinement (train.py:57-73), which it defines and never
 calls: the vertices of a class with fewer than n members in its scan, or of a class the jaw does not allow, take the majority
 label of their n + 1 nearest vertices (geot_scan_refine, csrc/scan_refine.hip: six launches per batch, no synchronisation):
@@ -690,7 +700,7 @@ class _GraphedAhead:
         return out[0], _Shared(self.graphed.ahead, positions) if positions else None
 
 
-def _passes(model, batcher, groups, repeats, draws, lookahead=0, graphed=None, runner=None):
+def _passes(model, batcher, groups, repeats, draws, lookahead=0, graphed=None, runner=None, feed=None):
     """The look-ahead loop of every whole-scan pass: each list of scan numbers in `groups` runs through the model `repeats`
     times, each time on a freshly drawn batch -> (batch, logits, first pass of its group, last pass of its group) per pass.
     The next pass's batch is queued BEFORE the current forward pass -- beside it when the batcher has a side stream -- and
@@ -700,13 +710,17 @@ def _passes(model, batcher, groups, repeats, draws, lookahead=0, graphed=None, r
     their coordinate-only work (Group, the largest FPS, the index plan) runs as ONE prefetch_geometry over their concatenated
     positions beside the forward pass in flight; each pass takes its Geometry.slice.  graphed: a graph_eval.GraphedForward
     -- that geometry call and every forward pass replay from hipGraphs, and the logits of a pass are a fixed buffer the next
-    pass overwrites (a consumer uses them before it asks for the next pass).  runner: the object that does both (tests)."""
+    pass overwrites (a consumer uses them before it asks for the next pass).  runner: the object that does both (tests).
+    feed: a callable k -> the batch of pass k, asked in pass order, in place of batcher.batch() (the covering passes)."""
     passes = [(ids, k == 0, k + 1 == repeats) for ids in groups for k in range(repeats)]
+    if feed is None:
+        def feed(k):
+            return batcher.batch(passes[k][0], draws=draws)
     if not lookahead:
-        data = batcher.batch(passes[0][0], draws=draws) if passes else None
+        data = feed(0) if passes else None
         for k, (_, first, last) in enumerate(passes):
             batcher.join(data)
-            ahead = batcher.batch(passes[k + 1][0], draws=draws) if k + 1 < len(passes) else None
+            ahead = feed(k + 1) if k + 1 < len(passes) else None
             logits, _, _ = model(data)
             yield data, logits, first, last
             data = ahead
@@ -721,7 +735,7 @@ def _passes(model, batcher, groups, repeats, draws, lookahead=0, graphed=None, r
             joined.add(k)
     for op, arg in pass_schedule([len(ids) for ids in groups], repeats, lookahead)[1]:
         if op == "draw":
-            batches[arg] = batcher.batch(passes[arg][0], draws=draws)
+            batches[arg] = feed(arg)
         elif op == "geometry":
             for j in arg:
                 join(j)
@@ -902,3 +916,144 @@ def validate_scans_voted(model, scans, cfg, num_votes=None, vote=None, batch_siz
                               kwargs=TOOTH_VIEW_KWARGS if kwargs is None else kwargs, stream=stream, draws=draws)
     return _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_refine, parts, "validate_scans_voted",
                      lookahead, graphed)
+
+
+class ScanCover:
+    """The sums of one batch of scans under covering passes (ScanBatcher.cover): ScanVotes' accumulator -- fp32 (sum of the
+    scans' vertices, C), vertex-major, slot after slot -- its out_offsets and the work table, made once; every add() is one
+    geot_scan_cover call, which puts the model's probabilities for sample j of a pass on the vertex that sample IS: no search, no
+    interpolation.  batch: any batch of the scans covered; every later batch must name the same scans in the same slots.
+    Nothing here synchronises with the host."""
+
+    def __init__(self, batch, num_classes):
+        need(isinstance(batch, dict) and all(k in batch for k in ("scans", "sizes", "scan_ids")),
+             "ScanCover: batch must come from a ValBatcher's or VoteBatcher's cover()")
+        c = _need_classes(num_classes, "ScanCover")
+        self.scans, self.sizes, self.c = batch["scans"], [int(m) for m in batch["sizes"]], c
+        need(1 <= len(self.sizes) <= SCAN_MAX_SLOTS, "ScanCover: 1 .. %d scans" % SCAN_MAX_SLOTS)
+        dev = self.device = self.scans.device
+        self.acc = torch.empty((sum(self.sizes), c), dtype=torch.float32, device=dev)      # round 0 stores
+        self.out_offsets = _out_offsets(self.sizes, dev)
+        self.work = _to_device(scan_work_table(self.sizes), dev)
+        self.rounds, self.finished = 0, False
+
+    def add(self, logits, batch, last=False, counts=None, want_pred=False):
+        """One pass: the model's logits (B, C, m) on `batch`, one of cover()'s.  get_pred_whole's soft-max, then one
+        geot_scan_cover call: the probabilities of every sample that owns a vertex (batch["sel"], batch["cover"]) are stored in
+        (round 0) or added to that vertex's row.  last (legal on the last pass of a round alone): the arg-max of the sums is
+        taken; then counts (rows of a SegMetrics buffer, ADDED to) and want_pred (-> list of (1, M_i) int64 labels, as
+        predict_scans returns them) are allowed."""
+        what = "ScanCover.add"
+        need(not self.finished, "%s: the last pass has been added" % what)
+        need(last or (counts is None and not want_pred), "%s: counts and predictions come with the last pass (last=True)" % what)
+        need(isinstance(batch, dict) and all(k in batch for k in ("sel", "cover", "scans", "sizes", "scan_ids")),
+             "%s: batch must come from a ValBatcher's or VoteBatcher's cover() (sel, cover, scans, sizes, scan_ids)" % what)
+        p, passes, rnd = (int(v) for v in batch["cover"])
+        need(0 <= p < passes and rnd >= 0, "%s: batch cover = (pass, passes, round), got %r" % (what, batch["cover"]))
+        need(not last or p + 1 == passes, "%s: the arg-max is taken on the last pass of a round (pass %d of %d)" % (what, p, passes))
+        need(batch["scans"] is self.scans and [int(m) for m in batch["sizes"]] == self.sizes,
+             "%s: every pass's batch holds the same scans in the same slots" % what)
+        dev, b = self.device, len(self.sizes)
+        need(torch.is_tensor(logits), "%s: logits must be a torch.Tensor" % what)
+        need(logits.is_cuda, "%s: CPU not supported (logits must live on the GPU)" % what)
+        need(logits.dim() == 3 and logits.shape[1] == self.c and logits.dtype == torch.float32, "%s: fp32 logits (B, %d, N)" % (what, self.c))
+        need(logits.device == dev, "%s: logits on %s, the scans on %s" % (what, logits.device, dev))
+        n = int(logits.shape[2])
+        need(logits.shape[0] == b and n >= 1, "%s: %d logits rows for a batch of %d scans, N >= 1" % (what, logits.shape[0], b))
+        sel, scan_ids = batch["sel"], batch["scan_ids"]
+        need(torch.is_tensor(sel) and sel.device == dev and sel.dtype == torch.int64 and tuple(sel.shape) == (b, n),
+             "%s: batch sel must be (B, N) int64 on %s" % (what, dev))
+        need(torch.is_tensor(scan_ids) and scan_ids.device == dev and scan_ids.dtype == torch.int64 and tuple(scan_ids.shape) == (b,),
+             "%s: batch scan_ids must be (B,) int64 on %s" % (what, dev))
+        prob = F.softmax(logits, dim=1).contiguous()
+        sel, scan_ids = sel.contiguous(), scan_ids.contiguous()
+        pred = torch.empty(sum(self.sizes), dtype=torch.int64, device=dev) if want_pred else None
+        mode = (_lib.VOTE_SET if rnd == 0 else 0) | (_lib.VOTE_FINISH if last else 0)
+        call("geot_scan_cover", dev, b, self.c, n, len(self.scans), int(self.scans.points.shape[0]), ptr(self.scans.labels),
+             ptr(self.scans.offsets), ptr(scan_ids), ptr(sel), ptr(prob), p, int(self.work.shape[0]), ptr(self.work),
+             ptr(self.out_offsets), ptr(self.acc), mode, ptr(pred), ptr(counts))
+        if p + 1 == passes:
+            self.rounds = rnd + 1
+        self.finished = bool(last)
+        return [q.view(1, -1) for q in torch.split(pred, self.sizes)] if want_pred else None
+
+    def probabilities(self):
+        """Per scan the (M_i, C) mean over the complete rounds so far: the accumulator's rows times 1 / rounds."""
+        need(self.rounds >= 1, "ScanCover.probabilities: no complete round yet")
+        return list(torch.split(self.acc * (1.0 / self.rounds), self.sizes))
+
+
+def _rounds(rounds, what):
+    if isinstance(rounds, bool) or not isinstance(rounds, (int, np.integer)) or int(rounds) < 1:
+        raise ValueError("%s: rounds must be an int >= 1, got %r" % (what, rounds))
+    return int(rounds)
+
+
+def _cover_run(model, batcher, idx, rounds, interpolate, draws, graph, lookahead, what, num_classes=None, counts=None, want_pred=True):
+    """The covering passes of one batch of scans through _passes: rounds * P forward passes on batcher.cover(idx, ...)'s
+    batches, summed by a ScanCover (interpolate: a ScanVotes, geot_scan_vote on the same batches) and finished on the last
+    -> (the labels or None, the last batch, the class count).  lookahead=True is G = P: one geometry call per round."""
+    from .openpoints.dataset.sample_draw import cover_passes
+    ids = [int(i) for i in idx]
+    feed = batcher.cover(ids, rounds, draws)                # the checks of idx, rounds and draws, before any device call
+    passes = cover_passes([batcher.scans.sizes[i] for i in ids], batcher.m)
+    lookahead, graphed = _replay_switches(graph, lookahead, passes, model, what)
+    sums = preds = data = None
+    for data, logits, first, last in _passes(model, batcher, [ids], passes * rounds, None, lookahead, graphed,
+                                             feed=lambda k: next(feed)):
+        if first:
+            sums = (ScanVotes if interpolate else ScanCover)(data, logits.shape[1] if num_classes is None else num_classes)
+        preds = sums.add(logits, data, last=last, counts=counts if last else None, want_pred=want_pred and last)
+    return preds, data, sums.c
+
+
+@torch.no_grad()
+def cover_scans(model, batcher, idx, rounds=1, interpolate=False, draws=None, refine=0, parts=None, graph=False, lookahead=0):
+    """The per-vertex labels of the scans `idx` of a ValBatcher's or VoteBatcher's set from covering passes: list of (1, M_i)
+    int64 tensors, as predict_scans returns them.  P = cover_passes(sizes, m) model passes per round whose samples partition
+    every scan (batcher.cover), so each vertex takes the arg-max of the probabilities the model produced for that very vertex,
+    summed over `rounds` independent covers -- geot_scan_cover, no neighbour search and no interpolation.  draws: a DeviceDraws
+    for these batches (default: the batcher's; ValueError without one).  interpolate=True sends the same batches through
+    ScanVotes / geot_scan_vote instead: a vertex gets its own pass's value (weight about 1 at distance about 0) plus P - 1
+    interpolated ones.  refine, parts: the labels then go through refine_scans.  graph, lookahead: as for vote_scans;
+    lookahead=True runs one geometry call per round."""
+    n_refine = _refine_n(refine, "cover_scans")
+    rounds = _rounds(rounds, "cover_scans")
+    model.eval()
+    preds, data, c = _cover_run(model, batcher, idx, rounds, interpolate, draws, graph, lookahead, "cover_scans")
+    return refine_scans(preds, data, n_refine, parts, num_classes=c) if n_refine else preds
+
+
+@torch.no_grad()
+def validate_scans_covered(model, scans, cfg, rounds=1, interpolate=False, batch_size=2, indices=None, stream=None, draws=None,
+                           refine=0, parts=None, graph=False, lookahead=0):
+    """validate_scans scored on covering passes: every batch of scans runs through the model rounds * P times (cover_scans),
+    each vertex scored on the class the model gave that very vertex.  scans: a DeviceScanSet (a ValBatcher is built on it:
+    cfg.num_points, cfg.num_classes), or a ValBatcher / VoteBatcher built on one (a VoteBatcher applies its vote list per
+    pass).  draws: a DeviceDraws (default: the batcher's; ValueError without one).  Same log lines, return value and dtypes as
+    validate().  interpolate, refine, parts, graph, lookahead: as for cover_scans."""
+    from .openpoints.dataset.val_batch import ScanBatcher, ValBatcher
+    what = "validate_scans_covered"
+    n_refine = _refine_n(refine, what)
+    rounds = _rounds(rounds, what)
+    need(int(batch_size) >= 1, "%s: batch_size >= 1" % what)
+    model.eval()
+    c = _cfg(cfg, "num_classes", 17)
+    if isinstance(scans, ScanBatcher):
+        batcher = scans
+        need(stream is None or stream is batcher.stream, "%s: the batcher was built for another stream" % what)
+    else:
+        need(_cfg(cfg, "num_points") is not None, "%s: cfg.num_points (the sample size) is missing" % what)
+        batcher = ValBatcher(scans, _cfg(cfg, "num_points"), c, stream=stream, draws=draws)
+    order = list(range(len(batcher))) if indices is None else [int(i) for i in indices]
+    metrics = SegMetrics(c, batcher.device)
+    for at in range(0, len(order), int(batch_size)):
+        ids = order[at:at + int(batch_size)]
+        if n_refine:
+            preds, data, _ = _cover_run(model, batcher, ids, rounds, interpolate, draws, graph, lookahead, what, c)
+            _count_refined(metrics, preds, data, n_refine, parts)
+        else:
+            rows = metrics._rows(len(ids))
+            _cover_run(model, batcher, ids, rounds, interpolate, draws, graph, lookahead, what, c, counts=rows, want_pred=False)
+            metrics.mandible += [batcher.cls_host[i] == 0 for i in ids]
+    return _report(metrics.read(), cfg)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 29
+#define GEOT_ABI_VERSION 30
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -859,6 +859,32 @@ int geot_scan_vote(int b, int c, int n, int n_scans, long long total, const floa
                    int n_work, const int *work, const long long *out_offsets, float *acc, int mode, long long *pred,
                    long long *counts, void *ws, long long ws_bytes, void *stream);
 
+/* ---- whole-scan predictions from covering passes: every vertex predicted directly (ABI 30) ---------------------------------
+ * Independent samples cover a scan badly: with M = 100 000 vertices and n = 16 000 samples one pass misses a vertex with
+ * probability 1 - n / M = 0.84, so after 10 voted passes 0.84^10 = 17.5 % of the vertices were never seen by the model and
+ * every label is interpolated.  P = ceil(M / n) = 7 passes whose samples PARTITION the scan show the model every vertex once.
+ * geot_sample_draw_cover (below, with geot_sample_draw) draws such passes; geot_scan_cover takes a pass's soft-max to the
+ * vertices it names: no neighbour search, no interpolation, no workspace, no float atomics.
+ * Arguments as geot_scan_vote's, with sel (b, n) int64 -- the pass's vertex indices, local to each slot's scan, as
+ * geot_sample_draw_cover wrote them -- and pass (>= 0) in place of points, known and the workspace.  prob (b, c, n)
+ * channel-first, acc / out_offsets / mode / pred / counts / work as there.  With n_s the size of slot s's scan:
+ *   scatter (one launch, grid (ceil(n / 256), b)): sample j of slot s OWNS its vertex iff q = pass * n + j < n_s (64-bit) and
+ *   0 <= sel[s][j] < n_s; a position with q >= n_s is wrap-around fill and owns nothing.  An owner writes row r =
+ *   out_offsets[s] + sel[s][j] of acc: acc[r][k] = prob[s][k][j] with GEOT_VOTE_SET, acc[r][k] = acc[r][k] + prob[s][k][j]
+ *   (one fp32 addition) without.  Non-owners write nothing.  Over passes 0 .. ceil(n_s / n) - 1 of one cover every row has
+ *   exactly one writer; GEOT_VOTE_SET marks the first ROUND and is passed to every pass of it.  The owners of one call must
+ *   name distinct vertices per slot (geot_sample_draw_cover's do): rows are written without atomics.
+ *   finish (GEOT_VOTE_FINISH with pred and / or counts; a second launch over the work table): pred and / or counts from the
+ *   sums, by geot_scan_vote's rule -- first maximum, a NaN wins, counts laid out and ADDED to as geot_seg_confusion's (integer
+ *   atomics only; counts needs labels).  It reads every row the work table names, so the last pass of a cover carries it.
+ * Skip rules: geot_scan_vote's (an unusable slot or work record is neither read, written nor counted).  Refusals:
+ * geot_scan_vote's (b, c, n, n_scans, total, n_work ranges; offsets, scan_ids, prob, acc, out_offsets NULL; counts without
+ * labels; an unknown mode bit; pred or counts without GEOT_VOTE_FINISH; work NULL or not 16-byte aligned), sel NULL, and
+ * pass < 0; all hipErrorInvalidValue before any launch.  b = 0 or n_work = 0: nothing to do. */
+int geot_scan_cover(int b, int c, int n, int n_scans, long long total, const int *labels, const long long *offsets,
+                    const long long *scan_ids, const long long *sel, const float *prob, int pass, int n_work, const int *work,
+                    const long long *out_offsets, float *acc, int mode, long long *pred, long long *counts, void *stream);
+
 /* ---- whole-scan predictions refined by their neighbours' majority (ABI 22) ---------------------------------------------------
  * geot_scan_refine: part_seg_refinement (train.py:57-73) for b batch slots, on per-vertex labels as geot_scan_predict /
  * geot_scan_vote write them, in a number of launches (six) that depends neither on b, nor on the scans' sizes, nor on what the
@@ -963,6 +989,16 @@ int geot_view_program(int j, int m, int n_rows, int n_out, int n_noise, int n_ma
  * before any launch. */
 int geot_sample_draw(int s, int m, int n_scans, long long total, const long long *offsets, const long long *scan_ids,
                      unsigned long long seed, unsigned long long draw_base, long long *sel, int *bad, void *stream);
+/* (ABI 30) geot_sample_draw_cover: the same arguments, slot / bad / scan-table rules, launch shape and integer arithmetic,
+ * plus pass, 0 <= pass <= 2^31 - 1.  With sigma_d the walked bijection above (b = max(10, bit length of n - 1), the eight
+ * Feistel rounds, applied again while the value is >= n) used for EVERY n >= 1 -- the multiply-high draw of n < m is not:
+ *   q = pass * m + j (64-bit),   sel[i][j] = sigma_d(q mod n).
+ * So for n >= m pass 0 is geot_sample_draw's row for the same id; passes 0 .. ceil(n / m) - 1 together name every vertex of
+ * [0, n) (consecutive windows of one permutation); positions with q >= n are wrap-around fill that keeps the cloud at m
+ * points and re-uses the start of the permutation.  pass < 0 is refused like the other arguments. */
+int geot_sample_draw_cover(int s, int m, int n_scans, long long total, const long long *offsets, const long long *scan_ids,
+                           unsigned long long seed, unsigned long long draw_base, int pass, long long *sel, int *bad,
+                           void *stream);
 
 /* ---- the batchers' view parameters, jitter noise and colour masks drawn on the device (ABI 20) -----------------------------------
  * geot_view_draw: what ViewProgram.draw draws per item on the host (a handful of scalars per view; an (m, 3) normal row per
