@@ -202,6 +202,26 @@ def _record(epoch, lr, stats, seconds, clouds):
     return rec
 
 
+VAL_WHOLE = ("interp", "covered", "decoded")
+
+
+def _val_whole(cfg, num_votes, graph, lookahead):
+    """cfg.val_whole, checked before the first epoch: how a whole scan gets its labels from the sampled points in fit()'s
+    validation -- "interp" (default: validate_scans / validate_scans_voted, get_pred_whole's interpolation), "covered"
+    (validate_scans_covered: ceil(M / num_points) forward passes whose samples partition the scan) or "decoded"
+    (validate_scans_decoded: one forward pass, the last decoder stage at every vertex).  Votes belong to "interp"; "decoded"
+    has neither graph nor lookahead."""
+    mode = _cfg(cfg, "val_whole", "interp")
+    mode = "interp" if mode is None else mode
+    if mode not in VAL_WHOLE:
+        raise ValueError("fit: cfg.val_whole must be one of %s, got %r" % (", ".join(VAL_WHOLE), mode))
+    if mode != "interp" and num_votes > 0:
+        raise ValueError("fit: cfg.val_whole=%r takes no votes (cfg.num_votes=%d): votes are summed interpolations" % (mode, num_votes))
+    if mode == "decoded" and (graph is not False or lookahead):
+        raise ValueError("fit: cfg.val_whole='decoded' has no graph / lookahead form")
+    return mode
+
+
 def fit(step, batcher, cfg, val=None, test=None, ckpt_dir=None, resume=None, log=logging.info, draws=None, generator=None,
         prior=True, graph=False, lookahead=0, refine=0, parts=None, val_stream=None):
     """Train `step` over `batcher` for the configured epochs -> {"epoch", "best", "best_epoch", "records", "schedule", "generator"}.
@@ -219,7 +239,8 @@ def fit(step, batcher, cfg, val=None, test=None, ckpt_dir=None, resume=None, log
     val: a DeviceScanSet (or a ValBatcher / VoteBatcher on one).  Every val_freq epochs and at the last one the STUDENT
     (step.model) runs validation.validate_scans -- validate_scans_voted when cfg.num_votes > 0 -- with graph / lookahead /
     refine / parts / val_stream passed through, and the training run's random streams are put back (_protected): a run with
-    validation trains to the bits of a run without.  "Best" is the highest validation mIoU so far.  test: scored the same way
+    validation trains to the bits of a run without.  cfg.val_whole (_val_whole; ValueError before the first epoch for
+    an unknown value): "interp" (default) is that, "covered" runs validate_scans_covered, "decoded" validate_scans_decoded.  "Best" is the highest validation mIoU so far.  test: scored the same way
     at every save, on the student as it stands, and reported as test_*.
     ckpt_dir: at test_freq epochs, at the last epoch and at every new best, checkpoint.save writes
     <ckpt_dir>/<run_name>_ckpt_latest.pt (the step's whole state, `draws`, the generators, epoch, best, best_epoch and the
@@ -236,6 +257,8 @@ def fit(step, batcher, cfg, val=None, test=None, ckpt_dir=None, resume=None, log
     process group of more than one rank, and what LrSchedule refuses."""
     import torch.distributed as dist
     from .openpoints.utils import ckpt_util
+    num_votes = int(_cfg(cfg, "num_votes", 0) or 0)
+    val_whole = _val_whole(cfg, num_votes, graph, lookahead)       # an unknown value: ValueError before anything is touched
     inner = _inner(step)
     fixmatch = _is_fixmatch(step)
     if fixmatch and (_cfg(cfg, "supervised_epochs", 0) or 0) > 0:
@@ -275,14 +298,23 @@ def fit(step, batcher, cfg, val=None, test=None, ckpt_dir=None, resume=None, log
     elif fixmatch and prior:
         compute_prior(step, batcher, epoch_batches(*sizes, generator=generator))
     val_cfg = {k: _cfg(cfg, k) for k in ("num_points", "num_classes", "datatransforms") if _cfg(cfg, k) is not None}
-    num_votes = int(_cfg(cfg, "num_votes", 0) or 0)
 
     def score(scans, epoch):
         from . import validation
         vcfg = dict(val_cfg, epoch=epoch, epochs=epochs, num_votes=num_votes)
-        kw = dict(batch_size=int(_cfg(cfg, "batch_size_val", 2) or 2), stream=val_stream, refine=refine, parts=parts, graph=graph,
-                  lookahead=lookahead)
-        fn = validation.validate_scans_voted if num_votes > 0 else validation.validate_scans
+        kw = dict(batch_size=int(_cfg(cfg, "batch_size_val", 2) or 2), stream=val_stream, refine=refine, parts=parts)
+        if val_whole == "interp":
+            fn = validation.validate_scans_voted if num_votes > 0 else validation.validate_scans
+            kw.update(graph=graph, lookahead=lookahead)
+        elif val_whole == "covered":
+            # a covering draw is a device draw: a batcher handed in brings its own, a bare scan set gets a fresh counter per
+            # validation, so every validation of a run covers the scans in the same way
+            from .openpoints.dataset.sample_draw import DeviceDraws
+            fn = validation.validate_scans_covered
+            kw.update(graph=graph, lookahead=lookahead,
+                      draws=None if getattr(scans, "draws", None) is not None else DeviceDraws(int(_cfg(cfg, "seed", 0) or 0)))
+        else:
+            fn = validation.validate_scans_decoded
         return _protected(dev, draws, lambda: fn(inner.model, scans, vcfg, **kw))
     records = []
     epoch = start - 1

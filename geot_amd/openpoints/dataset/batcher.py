@@ -97,9 +97,10 @@ class Batcher:
     def _views(self, raw, packed):
         return view_program_views(raw, packed[0], packed[1], packed[2])
 
-    def _batch(self, ids, shape, sel, params, ids_dev, check):
+    def _batch(self, ids, shape, sel, params, ids_dev, check, affine=False):
         """Queue one batch: params a ViewDrawHandle or one host entry per JOB.  check=True reads the bad-index flags back
-        (one host sync) and raises IndexError."""
+        (one host sync) and raises IndexError.  affine=True: the batcher's _affine(views, *shape) is added to the result --
+        tensors the views launch writes anyway, so the batch costs the same."""
         handle = isinstance(params, ViewDrawHandle)
         packed = None if handle else self._pack(shape, params)
         with on_stream(self.stream):
@@ -110,6 +111,8 @@ class Batcher:
             else:
                 v = self._views(s["raw"], packed)
             out = self._result(s, v, self.scans.cls.index_select(0, s["scan_ids"]).view(-1, 1), ids, *shape)
+            if affine:
+                out.update(self._affine(v, *shape))
         if check:
             if self.stream is not None:
                 self.stream.synchronize()

@@ -75,7 +75,13 @@ class ScanBatcher(Batcher):
 
     def join(self, batch):
         """Hand a batch built on the side stream to the CURRENT stream (Batcher._join)."""
-        self._join(batch[key] for key in self.join_keys + (("sel",) if "sel" in batch else ()))
+        self._join(batch[key] for key in self.join_keys + tuple(k for k in ("sel", "view_center", "view_scale") if k in batch))
+
+    def _affine(self, v, b):
+        """The `val` view's centre-and-normalise of every slot, as the views launch wrote it: pos = (raw - view_center) /
+        view_scale per coordinate (for a VoteBatcher: pos_search).  With pc_norm's center / scale in front it takes ANY vertex
+        of the slot's scan to the model's coordinates (validation.decode_scans, geot_scan_decode_front)."""
+        return {"view_center": v["view_center"][:b], "view_scale": v["view_scale"][:b]}
 
     def cover(self, idx, rounds=1, draws=None):
         """The covering batches of the scans `idx`: a generator of rounds * P batches, P = cover_passes(their sizes, m), per
@@ -130,14 +136,15 @@ class ValBatcher(ScanBatcher):
         super().__init__(scans, num_points, num_classes, kwargs, stream, draws)
         need(int(_kw(kwargs, "gravity_dim")) in (0, 1, 2), "ValBatcher: gravity_dim must be 0, 1 or 2")
 
-    def batch(self, idx, sel=None, check=False, draws=None):
+    def batch(self, idx, sel=None, check=False, draws=None, affine=False):
         """idx: scan numbers within the set; sel (B, m) vertex indices per scan, default the reference's draws
         (draw_val_sel's statements) or, with draws (a DeviceDraws; default: the constructor's), geot_sample_draw's.
-        check=True reads the bad-index flags back (one host sync) and raises IndexError."""
+        check=True reads the bad-index flags back (one host sync) and raises IndexError.  affine=True adds the slots' view
+        affine (ScanBatcher._affine): view_center (B, 3), view_scale (B,); the default key set is unchanged."""
         ids = self._ids(idx)
         weak = draw_view_params("train_w", self.kwargs)                   # the `val` list: nothing is drawn
         sel, params, ids_dev = self._draw(ids, (("sel", sel, len(ids)),), [weak] * len(ids), draws, None)
-        return self._batch(ids, (len(ids),), sel, params, ids_dev, check)
+        return self._batch(ids, (len(ids),), sel, params, ids_dev, check, affine)
 
     def _cover_params(self, ids, draws, base):
         return [draw_view_params("train_w", self.kwargs)] * len(ids)    # as batch(): the `val` list draws nothing

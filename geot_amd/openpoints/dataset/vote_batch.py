@@ -45,16 +45,17 @@ class VoteBatcher(ScanBatcher):
         self.program = ViewProgram(VAL_LIST + self.vote, kwargs)       # NotImplementedError for what the kernel cannot do
         super().__init__(scans, num_points, num_classes, kwargs, stream, draws)
 
-    def batch(self, idx, sel=None, params=None, check=False, draws=None):
+    def batch(self, idx, sel=None, params=None, check=False, draws=None, affine=False):
         """idx: scan numbers within the set; sel (B, m) vertex indices per scan and params (per scan one ViewProgram.draw
         result of the `val` + `vote` list, VoteBatcher.program) default to the reference's draws; draws: a DeviceDraws for
         this call (default: the constructor's).  check=True reads the bad-index flags back (one host sync) and raises
-        IndexError."""
+        IndexError.  affine=True adds view_center (B, 3) / view_scale (B,) of the `val` views -- the affine behind pos_search,
+        not behind the voted pos; the default key set is unchanged."""
         ids = self._ids(idx)
         sel, params, ids_dev = self._draw(ids, (("sel", sel, len(ids)),), params, draws, lambda slot: self.program.draw(self.m))
         if not isinstance(params, ViewDrawHandle):          # per job: the `val` views (nothing is drawn), then the voted ones
             params = [self.val_program.draw(self.m)] * len(ids) + params
-        return self._batch(ids, (len(ids),), sel, params, ids_dev, check)
+        return self._batch(ids, (len(ids),), sel, params, ids_dev, check, affine)
 
     def _cover_params(self, ids, draws, base):
         """The view parameters of one covering pass (ScanBatcher.cover): the vote list applied per pass, as batch() does."""

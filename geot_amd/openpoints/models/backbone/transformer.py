@@ -454,6 +454,8 @@ class PointTransformer_seg_T(nn.Module):
         self.cut_at_blocks = False        # detach the decoder from the blocks for a two-phase backward (see _forward, take_cut)
         self.keep_head_feature = False    # keep seg_head[1]'s output of every forward as self.head_feature (see _forward)
         self.head_feature = None
+        self.keep_decode_state = False    # keep what decode_front_params needs of every forward as self.decode_state (see _forward)
+        self.decode_state = None
         self._cut = None
 
         self.group_divider = Group(num_group=self.num_group, group_size=self.group_size)
@@ -687,21 +689,94 @@ class PointTransformer_seg_T(nn.Module):
         f_l1 = self._fp(self.propogation_1, center_pts[0], center, center_pts_trans[0], inter_feats[0], plan.fp1)
         f_l2 = self.dgcnn_pro_2(center_trans, f_l3, center_pts_trans[1], f_l2, plan.dg2)
         f_l1 = self.dgcnn_pro_1(center_pts_trans[1], f_l2, center_pts_trans[0], f_l1, plan.dg1)
+        if self.keep_decode_state:
+            # everything the last stage reads besides the query points (validation.decode_scans): the 8192 centres, their
+            # features and the jaw classes -- references, nothing is copied
+            self.decode_state = (f_l1, center_pts[0], cls_label)
         f_l0 = self._fp(self.propogation_0, center_original, center_pts[0], f_l0, f_l1, plan.fp0)
 
-        head = self.seg_head                     # conv -> BatchNorm1d -> Dropout -> conv; the BatchNorm as one fused op
-        if self.dense != "reference" and isinstance(head[0], PointwiseConv1d):
-            y = pointwise(head[0].weight.view(head[0].out_channels, -1), f_l0)       # the bias goes through bn_act
-            feat = bn_act(head[1], y, relu=False, pre_bias=head[0].bias)
-        else:
-            feat = bn_act(head[1], head[0](f_l0), relu=False)
+        feat = self._head_feature(f_l0)
         if self.keep_head_feature:
             # the 128-wide per-point feature the contrastive loss reads (train_step cfg use_contrastive): the BatchNorm's
             # output in front of the Dropout, (B, 128, N) channel-first, still attached to the graph
             self.head_feature = feat
-        logit = head[3](head[2](feat))
+        logit = self.seg_head[3](self.seg_head[2](feat))
         correction = self.T_linear(T) if T is not None else None
         return logit, correction, self.sigma, f_l0
+
+    def _head_feature(self, f_l0):
+        """seg_head up to its BatchNorm: (B, trans_dim, L) -> (B, 128, L)."""
+        head = self.seg_head                     # conv -> BatchNorm1d -> Dropout -> conv; the BatchNorm as one fused op
+        if self.dense != "reference" and isinstance(head[0], PointwiseConv1d):
+            y = pointwise(head[0].weight.view(head[0].out_channels, -1), f_l0)       # the bias goes through bn_act
+            return bn_act(head[1], y, relu=False, pre_bias=head[0].bias)
+        return bn_act(head[1], head[0](f_l0), relu=False)
+
+    def _decode_first_stage(self):
+        """propogation_0's first stage as (conv, BatchNorm module, has ReLU) when it is conv (no bias) -> BatchNorm -> ReLU
+        (or without the ReLU), the form geot_scan_decode_front folds; NotImplementedError for anything else."""
+        first = list(self.propogation_0.mlp.children())[0]
+        mods = list(first.named_children())
+        names = [n for n, _ in mods]
+        ok = (names[:2] == ["conv", "bn"] and first.conv.bias is None and first.conv.kernel_size in ((1,), (1, 1))
+              and len(mods) <= 3 and all(isinstance(mod, nn.ReLU) for _, mod in mods[2:]))
+        bn = first.bn.bn if ok and hasattr(first.bn, "bn") else None
+        if not (ok and isinstance(bn, nn.modules.batchnorm._BatchNorm) and bn.running_mean is not None and bn.running_var is not None):
+            raise NotImplementedError("decode: propogation_0's first stage must be conv (no bias) -> BatchNorm (running "
+                                      "statistics) -> ReLU, got %s" % first)
+        return first.conv, bn, len(mods) == 3
+
+    @torch.no_grad()
+    def decode_front_params(self):
+        """The last decoder stage up to its first activation, folded for geot_scan_decode_front (include/geot_hip.h), from the
+        state the last forward kept under keep_decode_state -> dict: known (B, m, 3) the centres; a (B, m, c_out) the first
+        convolution applied to their features, point-major; skip_const (B, c_out) the one-hot columns' contribution for every
+        slot's jaw; w_xyz (c_out, 3); ch_scale, ch_shift (c_out) the eval BatchNorm; relu.  All fp32, contiguous.  Eval mode
+        only (ValueError when self.training): in training mode the BatchNorm ties a point's value to the batch.  Independent
+        of GEOT_DENSE / GEOT_FP_LAYOUT: the parameters are the module's own."""
+        if self.training:
+            raise ValueError("decode_front_params: eval mode only (model.eval()): a training-mode BatchNorm ties every point to its batch")
+        if self.decode_state is None:
+            raise ValueError("decode_front_params: no kept state -- set keep_decode_state = True before the forward pass")
+        conv, bn, relu = self._decode_first_stage()
+        f_l1, centres, cls_label = self.decode_state
+        c = f_l1.shape[1]
+        w = conv.weight.view(conv.out_channels, -1).float()
+        if w.shape[1] != c + 5:
+            raise NotImplementedError("decode: the first convolution must read the known features, one_hot(cls, 2) and xyz "
+                                      "(%d + 5 columns), got %d" % (c, w.shape[1]))
+        rstd = torch.rsqrt(bn.running_var.float() + bn.eps)
+        scale = (bn.weight.float() * rstd) if bn.weight is not None else rstd
+        shift = -bn.running_mean.float() * scale
+        if bn.bias is not None:
+            shift = bn.bias.float() + shift
+        jaw = cls_label.reshape(-1).long()
+        return {"known": centres.contiguous(), "a": pointwise_to_cl(w[:, :c].contiguous(), f_l1).contiguous(),
+                "skip_const": w[:, c:c + 2].t().contiguous().index_select(0, jaw).contiguous(),
+                "w_xyz": w[:, c + 2:c + 5].contiguous(), "ch_scale": scale.contiguous(), "ch_shift": shift.contiguous(),
+                "relu": relu}
+
+    @torch.no_grad()
+    def decode_tail(self, z):
+        """The rest of the last stage on rows geot_scan_decode_front wrote: z (V, c_out) point-major, the first stage's
+        activations of V query points -> the logits (nclasses, V) of those points as one (1, V) cloud: propogation_0's
+        remaining stages (the second convolution reads the rows as a transposed operand) and seg_head, the existing code.
+        Eval mode only."""
+        if self.training:
+            raise ValueError("decode_tail: eval mode only (model.eval())")
+        layers = list(self.propogation_0.mlp.children())
+        if len(layers) > 1:
+            if next(iter(layers[1].named_children()))[0] != "conv" or layers[1].conv.kernel_size not in ((1,), (1, 1)):
+                raise NotImplementedError("decode: propogation_0's second stage must start with a 1x1 convolution")
+            conv2 = layers[1].conv
+            y = pointwise_from_cl(conv2.weight.view(conv2.out_channels, -1), z.unsqueeze(0))
+            if conv2.bias is not None:
+                y = y + conv2.bias.view(1, -1, 1)
+            f = shared_mlp_nd(layers[1:], y, first_conv_done=True)
+        else:
+            f = z.t().contiguous().unsqueeze(0)
+        feat = self._head_feature(f)
+        return self.seg_head[3](self.seg_head[2](feat))[0]
 
 
 TOOTH_SEG_CFG = dict(trans_dim=384, depth=12, num_heads=4, group_size=32, num_group=512, encoder_dims=256,

@@ -55,6 +55,18 @@ label of their n + 1 nearest vertices (geot_scan_refine, csrc/scan_refine.hip: s
     preds = predict_scans(logits, batch, refine=10)          # also vote_scans, validate_scans, validate_scans_voted
     pred = part_seg_refinement(pred, pos, cls, cls2parts, n=10)                         # the reference's dense (B, N) form
 
+Decoding -- every vertex predicted directly from ONE forward pass.  Everything of PointTransformer_seg_T up to the features of
+its 8192 centres depends on the sample alone; the last decoder stage (propogation_0, seg_head) is a pure function of a query's
+position, and in eval mode nothing ties the query set to the sampled set.  geot_scan_decode_front (csrc/scan_decode.hip) takes
+every vertex through the batch's two normalisations, finds its three nearest centres and writes the stage's first activations
+point-major, chunk by chunk; the model's own code finishes the stage and the head, geot_scan_decode_finish takes the arg-max:
+
+    preds = decode_scans(model, ValBatcher(scans, n), idx)                      # one batch(), one forward, then the chunks
+    out = validate_scans_decoded(model, scans, cfg)                             # validate()'s values from them
+
+These are the model's own decoder values at those positions; how decoded labels compare with interpolated or covered ones on
+real scans has not been measured (there are no trained weights here).
+
 Look-ahead and replay -- validate_scans, validate_scans_voted and vote_scans with lookahead=G / graph=True (off by default):
 up to G passes are drawn ahead (the same batch() calls in the same order), their coordinate-only work runs as one
 prefetch_geometry over the concatenated positions beside the forward pass in flight (pass_schedule, _passes), and with graph
@@ -1055,5 +1067,155 @@ def validate_scans_covered(model, scans, cfg, rounds=1, interpolate=False, batch
         else:
             rows = metrics._rows(len(ids))
             _cover_run(model, batcher, ids, rounds, interpolate, draws, graph, lookahead, what, c, counts=rows, want_pred=False)
+            metrics.mandible += [batcher.cls_host[i] == 0 for i in ids]
+    return _report(metrics.read(), cfg)
+
+
+# ---- whole scans decoded at full resolution from one backbone pass (csrc/scan_decode.hip) ------------------------------------------
+DECODE_RECORD = 256     # vertices per work record: geot_scan_decode_front takes a record 256 vertices at a time, one lane each
+
+
+def decode_work_table(sizes, chunk=32768, record=DECODE_RECORD):
+    """The work records of geot_scan_decode_front / geot_scan_decode_finish for batch slots of `sizes` vertices, decoded in
+    chunks of at most `chunk` vertices -> ((G, 4) int32 host array of (slot, first vertex, vertex count, first output row),
+    [(first record, record count, rows)] per chunk).  The vertices of all slots, slot after slot, are cut every `chunk`
+    vertices -- a boundary may fall inside a scan -- and every piece into records of at most `record` vertices; a record's
+    rows are counted from the start of ITS chunk, so one (chunk, c_out) buffer serves every chunk.  Every vertex of every slot
+    lies in exactly one record."""
+    sizes = [int(m) for m in sizes]
+    need(all(1 <= m <= MAX_VERTICES for m in sizes), "decode_work_table: 1 .. %d vertices per scan" % MAX_VERTICES)
+    need(isinstance(chunk, (int, np.integer)) and not isinstance(chunk, bool) and 1 <= int(chunk) <= MAX_VERTICES and int(record) >= 1,
+         "decode_work_table: chunk must be an int in 1 .. %d, record >= 1" % MAX_VERTICES)
+    chunk, record = int(chunk), int(record)
+    rows, chunks, at, n_rec, first_rec = [], [], 0, 0, 0       # at: vertices handed out so far
+    for slot, m in enumerate(sizes):
+        v = 0
+        while v < m:
+            used = at % chunk
+            take = min(m - v, chunk - used)
+            first = np.arange(v, v + take, record, dtype=np.int64)
+            part = np.empty((first.size, 4), dtype=np.int64)
+            part[:, 0], part[:, 1], part[:, 2], part[:, 3] = slot, first, np.minimum(record, v + take - first), used + first - v
+            rows.append(part)
+            n_rec += first.size
+            at += take
+            v += take
+            if at % chunk == 0:
+                chunks.append((first_rec, n_rec - first_rec, chunk))
+                first_rec = n_rec
+    if at % chunk:
+        chunks.append((first_rec, n_rec - first_rec, at % chunk))
+    table = np.concatenate(rows) if rows else np.zeros((0, 4), dtype=np.int64)
+    return np.ascontiguousarray(table.astype(np.int32)), chunks
+
+
+def _decode_run(model, batcher, ids, c, draws, chunk, what, counts=None, want_pred=True, debug=None, sel=None):
+    """One batch of scans decoded: one batch() with the view affine, one forward pass that keeps the last stage's inputs, then
+    per chunk of vertices geot_scan_decode_front, the model's decode_tail and geot_scan_decode_finish
+    -> (the labels as predict_scans returns them or None, the batch).  No host synchronisation.
+    debug (tests): a list; per chunk a dict is appended -- work (the chunk's records, host), logits (C, rows), and the kernel's
+    optional outputs q / idx / weight (rows, 3); first comes a dict of the batch's own logits "forward" (B, C, N), the folded
+    "params" and the kept "state".  sel: the
+    batch's vertex samples, given."""
+    seg = getattr(model, "segmentor", model)
+    need(hasattr(seg, "decode_front_params") and hasattr(seg, "decode_tail"),
+         "%s: the model has no last stage to decode with (PointTransformer_seg_T.decode_front_params / decode_tail)" % what)
+    if seg.training:
+        raise ValueError("%s: eval mode only (model.eval()): a training-mode BatchNorm ties every point to its batch" % what)
+    data = batcher.batch(ids, sel=sel, draws=draws, affine=True)
+    batcher.join(data)
+    if "pos_search" in data:            # a VoteBatcher: the affine describes the `val` view, so that is the view decoded
+        data = dict(data, pos=data["pos_search"])
+    keep, seg.keep_decode_state = seg.keep_decode_state, True
+    try:
+        forward = model(data)[0]
+        p, state = seg.decode_front_params(), seg.decode_state
+    finally:
+        seg.keep_decode_state, seg.decode_state = keep, None
+    scans, sizes = data["scans"], [int(m) for m in data["sizes"]]
+    dev, b = scans.device, len(sizes)
+    need(1 <= b <= SCAN_MAX_SLOTS, "%s: 1 .. %d scans per batch" % (what, SCAN_MAX_SLOTS))
+    m, c_out = int(p["a"].shape[1]), int(p["a"].shape[2])
+    need(tuple(p["known"].shape) == (b, m, 3) and m >= 3, "%s: the model kept %s centres for %d scans (at least 3 each)" %
+         (what, tuple(p["known"].shape), b))
+    table, chunks = decode_work_table(sizes, chunk)
+    work = _to_device(table, dev)
+    scan_ids = data["scan_ids"].contiguous()
+    center, scale = data["center"].contiguous(), data["scale"].contiguous()
+    vcenter, vscale = data["view_center"].contiguous(), data["view_scale"].contiguous()
+    out_offs = _out_offsets(sizes, dev) if want_pred else None
+    pred = torch.empty(sum(sizes), dtype=torch.int64, device=dev) if want_pred else None
+    z = torch.empty((max(r for _, _, r in chunks), c_out), dtype=torch.float32, device=dev)
+    n_scans, total = len(scans), int(scans.points.shape[0])
+    if debug is not None:
+        debug.append({"forward": forward, "params": p, "state": state})
+    for first, count, rows in chunks:
+        recs = ptr(work) + 16 * first
+        seen = None
+        if debug is not None:
+            seen = {"q": torch.empty((rows, 3), dtype=torch.float32, device=dev), "idx": torch.empty((rows, 3), dtype=torch.int32, device=dev),
+                    "weight": torch.empty((rows, 3), dtype=torch.float32, device=dev)}
+        call("geot_scan_decode_front", dev, b, m, c_out, int(p["relu"]), n_scans, total, ptr(scans.points), ptr(scans.offsets),
+             ptr(scan_ids), ptr(center), ptr(scale), ptr(vcenter), ptr(vscale), ptr(p["known"]), ptr(p["a"]), ptr(p["skip_const"]),
+             ptr(p["w_xyz"]), ptr(p["ch_scale"]), ptr(p["ch_shift"]), count, recs, rows, ptr(z),
+             *((ptr(seen["q"]), ptr(seen["idx"]), ptr(seen["weight"])) if seen else (None, None, None)))
+        logits = seg.decode_tail(z[:rows]).contiguous()
+        if seen is not None:
+            debug.append(dict(seen, work=table[first:first + count], logits=logits))
+        need(tuple(logits.shape) == (c, rows) and logits.dtype == torch.float32, "%s: the head gave %s logits for %d classes and %d "
+             "vertices" % (what, tuple(logits.shape), c, rows))
+        call("geot_scan_decode_finish", dev, b, c, n_scans, total, ptr(scans.labels), ptr(scans.offsets), ptr(scan_ids), count, recs,
+             rows, ptr(logits), ptr(out_offs), ptr(pred), ptr(counts))
+    return ([q.view(1, -1) for q in torch.split(pred, sizes)] if want_pred else None), data
+
+
+@torch.no_grad()
+def decode_scans(model, batcher, idx, refine=0, parts=None, chunk=32768, draws=None):
+    """The per-vertex labels of the scans `idx` of a ValBatcher's or VoteBatcher's set, every vertex predicted directly from
+    ONE forward pass: list of (1, M_i) int64 tensors, as predict_scans returns them.  The model sees one sampled batch; its
+    last decoder stage (propogation_0, seg_head) is then evaluated at EVERY vertex of the scans -- geot_scan_decode_front takes
+    a vertex through the batch's two normalisations, finds its three nearest of the model's 8192 centres and writes the
+    stage's first activations, the model's own code does the rest (decode_tail), geot_scan_decode_finish takes the arg-max --
+    `chunk` vertices at a time (what bounds the (chunk, 1536) fp32 buffer: 201 MB at the default).  Eval mode only (ValueError
+    for a model in training mode).  A VoteBatcher's batch is decoded on its `val` view; votes and rounds do not apply.  refine
+    (0: off, True: n = 10, an int: n) and parts: the labels then go through refine_scans.  draws: a DeviceDraws for the
+    batch (default: the batcher's).  What this computes is the model's own decoder at those positions; how decoded labels
+    compare with interpolated or covered ones on real scans has not been measured (there are no trained weights here)."""
+    n_refine = _refine_n(refine, "decode_scans")
+    seg = getattr(model, "segmentor", model)
+    c = _need_classes(getattr(seg, "nclasses", batcher.c), "decode_scans")
+    preds, data = _decode_run(model, batcher, [int(i) for i in idx], c, draws, chunk, "decode_scans")
+    return refine_scans(preds, data, n_refine, parts, num_classes=c) if n_refine else preds
+
+
+@torch.no_grad()
+def validate_scans_decoded(model, scans, cfg, batch_size=2, indices=None, stream=None, draws=None, refine=0, parts=None, chunk=32768):
+    """validate_scans scored on decoded labels (decode_scans): per batch of scans one batch() and one forward pass, then the
+    last decoder stage at every vertex, counted by geot_scan_decode_finish.  scans: a DeviceScanSet (a ValBatcher is built on
+    it: cfg.num_points, cfg.num_classes), or a ValBatcher / VoteBatcher built on one.  Same log lines, return value and
+    dtypes as validate().  refine, parts: as for validate_scans; chunk, draws: as for decode_scans.  No host synchronisation
+    beyond validate_scans' (the final read of the counts)."""
+    from .openpoints.dataset.val_batch import ScanBatcher, ValBatcher
+    what = "validate_scans_decoded"
+    n_refine = _refine_n(refine, what)
+    need(int(batch_size) >= 1, "%s: batch_size >= 1" % what)
+    model.eval()                        # as validate_scans; decode_scans itself refuses a model in training mode
+    c = _need_classes(_cfg(cfg, "num_classes", 17), what)
+    if isinstance(scans, ScanBatcher):
+        batcher = scans
+        need(stream is None or stream is batcher.stream, "%s: the batcher was built for another stream" % what)
+    else:
+        need(_cfg(cfg, "num_points") is not None, "%s: cfg.num_points (the sample size) is missing" % what)
+        batcher = ValBatcher(scans, _cfg(cfg, "num_points"), c, stream=stream, draws=draws)
+    order = list(range(len(batcher))) if indices is None else [int(i) for i in indices]
+    metrics = SegMetrics(c, batcher.device)
+    for at in range(0, len(order), int(batch_size)):
+        ids = order[at:at + int(batch_size)]
+        if n_refine:
+            preds, data = _decode_run(model, batcher, ids, c, draws, chunk, what)
+            _count_refined(metrics, preds, data, n_refine, parts)
+        else:
+            rows = metrics._rows(len(ids))
+            _decode_run(model, batcher, ids, c, draws, chunk, what, counts=rows, want_pred=False)
             metrics.mandible += [batcher.cls_host[i] == 0 for i in ids]
     return _report(metrics.read(), cfg)

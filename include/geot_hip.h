@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 30
+#define GEOT_ABI_VERSION 31
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -884,6 +884,61 @@ int geot_scan_vote(int b, int c, int n, int n_scans, long long total, const floa
 int geot_scan_cover(int b, int c, int n, int n_scans, long long total, const int *labels, const long long *offsets,
                     const long long *scan_ids, const long long *sel, const float *prob, int pass, int n_work, const int *work,
                     const long long *out_offsets, float *acc, int mode, long long *pred, long long *counts, void *stream);
+
+/* ---- whole scans decoded at full resolution from one backbone pass (ABI 31) ---------------------------------------------------
+ * PointTransformer_seg_T's last decoder stage (propogation_0, seg_head) is a pure function of a query's position once the
+ * backbone has produced the features of its m centres (m = 8192 as configured): three_nn against the centres, the
+ * inverse-distance interpolation, the skip channels [one_hot(cls), xyz], two 1x1 convolutions with BatchNorm, the head.  In eval
+ * mode nothing ties the query set to the sampled set, so one forward pass plus this stage at every vertex predicts every vertex
+ * directly -- where geot_scan_cover pays ceil(M / n) forward passes.  What this establishes is that the values are the model's
+ * own decoder applied to those positions; the accuracy of decoded against interpolated or covered labels on real scans has
+ * not been measured (there are no trained weights here).
+ * The scans lie concatenated as for geot_scan_predict (points, offsets, scan_ids, the skip rules of slots and work records); no
+ * workspace, no host synchronisation, one launch per call, no atomics in front, integer atomics only in finish.
+ * work: n_work records of four int32 on the device, 16-byte aligned -- (slot, first vertex, vertex count, first output row):
+ * geot_scan_predict's record with its fourth word in use.  Vertex first + i of the record owns row [3] + i of the call's
+ * row-indexed arrays (z, q, idx, weight; the columns of logits), rows of them in all: the caller bounds z by decoding a batch in
+ * chunks of vertices, a chunk boundary may fall inside a scan, and both entry points of a chunk take the same records.  A
+ * record whose rows do not lie in [0, rows) is skipped like one whose slot, first vertex or count is out of range: nothing of
+ * it is read, written or counted.  Records must not share rows.
+ *
+ * geot_scan_decode_front, for every vertex p of every record, slot s:
+ *   query position  r = (p - center[s]) / scale[s]  (pc_norm: center (b, 3), scale (b), geot_cloud_sample_batch's statements),
+ *   then  q = (r - view_center[s]) / view_scale[s]  (the `val` view's centre-and-normalise: view_center (b, 3), view_scale (b)
+ *   as geot_fixmatch_views / geot_view_program write them): per coordinate the same four single fp32 operations the batcher
+ *   applies to a sampled vertex, so a vertex that is sample j of the batch gets the bits of pos[s][j];
+ *   the three of the slot's m centres known (b, m, 3) smallest by (d2, index), d2 = ((dx dx) + (dy dy)) + (dz dz) un-contracted
+ *   -- geot_three_nn's contract (a NaN vertex gets three entries (+inf, index 0)) -- and geot_fp_weights' weights statement for
+ *   statement: r_t = 1 / (sqrt(d2_t) + 1e-8), w_t = r_t / ((r_0 + r_1) + r_2);
+ *   one point-major row of c_out channels, channel k:
+ *     z[row][k] = act(ch_scale[k] * (((w_0 a[i_0][k] + w_1 a[i_1][k]) + w_2 a[i_2][k]) + skip_const[s][k]
+ *                                    + ((W_xyz[k][0] q_x + W_xyz[k][1] q_y) + W_xyz[k][2] q_z)) + ch_shift[k])
+ *   every operation rounded, left to right; act = torch.relu (a NaN stays NaN) with relu = 1, the identity with relu = 0.
+ *   a (b, m, c_out): the stage's first convolution already applied to the centres' features, point-major; skip_const
+ *   (b, c_out): the one-hot columns' contribution for the slot's jaw; W_xyz (c_out, 3): the xyz columns; ch_scale / ch_shift
+ *   (c_out): the folded eval BatchNorm.  Any c_out >= 1: rows are stored four channels per lane where c_out is a multiple of 4
+ *   and a, z, skip_const, W_xyz, ch_scale and ch_shift are 16-byte aligned, one channel per lane otherwise -- the same values.
+ *   q (rows, 3) fp32, idx (rows, 3) int32, weight (rows, 3) fp32: optional (NULL) copies of the search, for tests.
+ *   One writer per element: the same call gives the same bits.
+ *   0 <= b <= 65535, m >= 3, c_out >= 1, relu 0 or 1, n_scans >= 1, total >= 1, n_work >= 0, 0 <= rows <= 2^31 - 1, no NULL among
+ *   points .. ch_shift and z, work not NULL and 16-byte aligned; anything else is hipErrorInvalidValue before any launch.
+ *   b = 0, n_work = 0 or rows = 0: nothing to do.  (No class count: the stage in front of the head does not know one.)
+ *
+ * geot_scan_decode_finish: logits (c, rows) channel-first -- the head's output for the chunk as a (1, rows) cloud -- over the
+ * same records: the arg-max of every column by geot_scan_vote's rule (first maximum, a NaN wins);
+ *   pred (optional): pred[out_offsets[s] + v] = class for vertex v of slot s, out_offsets (b) int64 on the device;
+ *   counts (optional; needs labels): row s of b rows of c (c + 1) + 1 int64, laid out and ADDED to as geot_seg_confusion's.
+ *   0 <= b <= 65535, 1 <= c <= GEOT_NTM_MAX_C, n_scans >= 1, total >= 1, n_work >= 0, 0 <= rows <= 2^31 - 1, offsets, scan_ids
+ *   and logits not NULL, pred or counts (or both) given, out_offsets with pred, labels with counts, work not NULL and 16-byte
+ *   aligned; anything else is hipErrorInvalidValue before any launch.  b = 0, n_work = 0 or rows = 0: nothing to do. */
+int geot_scan_decode_front(int b, int m, int c_out, int relu, int n_scans, long long total, const float *points,
+                           const long long *offsets, const long long *scan_ids, const float *center, const float *scale,
+                           const float *view_center, const float *view_scale, const float *known, const float *a,
+                           const float *skip_const, const float *w_xyz, const float *ch_scale, const float *ch_shift, int n_work,
+                           const int *work, long long rows, float *z, float *q, int *idx, float *weight, void *stream);
+int geot_scan_decode_finish(int b, int c, int n_scans, long long total, const int *labels, const long long *offsets,
+                            const long long *scan_ids, int n_work, const int *work, long long rows, const float *logits,
+                            const long long *out_offsets, long long *pred, long long *counts, void *stream);
 
 /* ---- whole-scan predictions refined by their neighbours' majority (ABI 22) ---------------------------------------------------
  * geot_scan_refine: part_seg_refinement (train.py:57-73) for b batch slots, on per-vertex labels as geot_scan_predict /
