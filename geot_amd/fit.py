@@ -222,6 +222,14 @@ def _val_whole(cfg, num_votes, graph, lookahead):
     return mode
 
 
+def _val_teeth3ds(cfg):
+    """cfg.val_teeth3ds, checked before the first epoch: a bool (default False); anything else is a ValueError."""
+    on = _cfg(cfg, "val_teeth3ds", False)
+    if not isinstance(on, bool):
+        raise ValueError("fit: cfg.val_teeth3ds must be a bool, got %r" % (on,))
+    return on
+
+
 def fit(step, batcher, cfg, val=None, test=None, ckpt_dir=None, resume=None, log=logging.info, draws=None, generator=None,
         prior=True, graph=False, lookahead=0, refine=0, parts=None, val_stream=None):
     """Train `step` over `batcher` for the configured epochs -> {"epoch", "best", "best_epoch", "records", "schedule", "generator"}.
@@ -240,8 +248,11 @@ def fit(step, batcher, cfg, val=None, test=None, ckpt_dir=None, resume=None, log
     (step.model) runs validation.validate_scans -- validate_scans_voted when cfg.num_votes > 0 -- with graph / lookahead /
     refine / parts / val_stream passed through, and the training run's random streams are put back (_protected): a run with
     validation trains to the bits of a run without.  cfg.val_whole (_val_whole; ValueError before the first epoch for
-    an unknown value): "interp" (default) is that, "covered" runs validate_scans_covered, "decoded" validate_scans_decoded.  "Best" is the highest validation mIoU so far.  test: scored the same way
-    at every save, on the student as it stands, and reported as test_*.
+    an unknown value): "interp" (default) is that, "covered" runs validate_scans_covered, "decoded" validate_scans_decoded.
+    cfg.val_teeth3ds (a bool, default False; ValueError before the first epoch for anything else): the validation's final
+    labels also go through a validation.ToothScores, the record gains val_tsa, val_tsa_instance, val_tla, val_tir and val_score
+    (the 3DTeethSeg challenge's scores) and one more line is logged; "best" and the checkpoints are untouched.  "Best" is the
+    highest validation mIoU so far.  test: scored the same way at every save, on the student as it stands, and reported as test_*.
     ckpt_dir: at test_freq epochs, at the last epoch and at every new best, checkpoint.save writes
     <ckpt_dir>/<run_name>_ckpt_latest.pt (the step's whole state, `draws`, the generators, epoch, best, best_epoch and the
     sampler generator's state) and ckpt_util.save_checkpoint the reference-layout <run_name>_ckpt_latest.pth, copied to
@@ -259,6 +270,7 @@ def fit(step, batcher, cfg, val=None, test=None, ckpt_dir=None, resume=None, log
     from .openpoints.utils import ckpt_util
     num_votes = int(_cfg(cfg, "num_votes", 0) or 0)
     val_whole = _val_whole(cfg, num_votes, graph, lookahead)       # an unknown value: ValueError before anything is touched
+    val_teeth = _val_teeth3ds(cfg)
     inner = _inner(step)
     fixmatch = _is_fixmatch(step)
     if fixmatch and (_cfg(cfg, "supervised_epochs", 0) or 0) > 0:
@@ -299,10 +311,13 @@ def fit(step, batcher, cfg, val=None, test=None, ckpt_dir=None, resume=None, log
         compute_prior(step, batcher, epoch_batches(*sizes, generator=generator))
     val_cfg = {k: _cfg(cfg, k) for k in ("num_points", "num_classes", "datatransforms") if _cfg(cfg, k) is not None}
 
-    def score(scans, epoch):
+    def score(scans, epoch, teeth=False):
+        """-> validate()'s three-tuple; with teeth (macc, miou, mdsc, the dict of ToothScores.read())."""
         from . import validation
         vcfg = dict(val_cfg, epoch=epoch, epochs=epochs, num_votes=num_votes)
         kw = dict(batch_size=int(_cfg(cfg, "batch_size_val", 2) or 2), stream=val_stream, refine=refine, parts=parts)
+        if teeth:
+            kw["teeth"] = validation.ToothScores(val_cfg.get("num_classes", 17), scans.device)
         if val_whole == "interp":
             fn = validation.validate_scans_voted if num_votes > 0 else validation.validate_scans
             kw.update(graph=graph, lookahead=lookahead)
@@ -315,7 +330,15 @@ def fit(step, batcher, cfg, val=None, test=None, ckpt_dir=None, resume=None, log
                       draws=None if getattr(scans, "draws", None) is not None else DeviceDraws(int(_cfg(cfg, "seed", 0) or 0)))
         else:
             fn = validation.validate_scans_decoded
-        return _protected(dev, draws, lambda: fn(inner.model, scans, vcfg, **kw))
+
+        def run():
+            triple = fn(inner.model, scans, vcfg, **kw)
+            if not teeth:
+                return triple
+            out = kw["teeth"].read()
+            validation.report_tooth_scores(out, vcfg)
+            return tuple(triple) + (out,)
+        return _protected(dev, draws, run)
     records = []
     epoch = start - 1
     for epoch in range(start, epochs + 1):
@@ -330,8 +353,11 @@ def fit(step, batcher, cfg, val=None, test=None, ckpt_dir=None, resume=None, log
         last = epoch == epochs
         is_best = False
         if val is not None and (epoch % val_freq == 0 or last):
-            macc, miou, mdsc = (float(v) for v in score(val, epoch))
+            scored = score(val, epoch, val_teeth)
+            macc, miou, mdsc = (float(v) for v in scored[:3])
             rec.update(val_miou=miou, val_dsc=mdsc, val_acc=macc)
+            if val_teeth:
+                rec.update(("val_" + k, scored[3][k]) for k in ("tsa", "tsa_instance", "tla", "tir", "score"))
             if best is None or miou > best:
                 is_best, best, best_epoch = True, miou, epoch
                 best_all = {"miou": miou, "dsc": mdsc, "acc": macc}

@@ -67,6 +67,17 @@ point-major, chunk by chunk; the model's own code finishes the stage and the hea
 These are the model's own decoder values at those positions; how decoded labels compare with interpolated or covered ones on
 real scans has not been measured (there are no trained weights here).
 
+Teeth3DS challenge scores -- TSA, TLA and TIR, what results on this dataset are published in (tooth_scores_from_moments has
+the definitions).  Two of the three need geometry the confusion counts do not hold: geot_tooth_moments (csrc/tooth_scores.hip)
+takes per scan and class the count, position sum and extent of the labelled and of the predicted vertices in one launch per
+batch, integers only; every validator takes teeth= and sends each batch's final labels through it:
+
+    teeth = ToothScores(num_classes, device)
+    validate_scans(model, scans, cfg, teeth=teeth)           # also _voted, _covered, _decoded; the three-tuple as before
+    out = teeth.read()                                       # one device-to-host copy: out["tsa"], out["tla"], out["tir"], out["score"]
+    teeth.update(preds, batch)                               # any labels predict_scans / vote_scans / ... returned
+    geo = tooth_instances(preds, batch, num_classes)         # per scan and class: predicted count, centroid, box (device tensors)
+
 Look-ahead and replay -- validate_scans, validate_scans_voted and vote_scans with lookahead=G / graph=True (off by default):
 up to G passes are drawn ahead (the same batch() calls in the same order), their coordinate-only work runs as one
 prefetch_geometry over the concatenated positions beside the forward pass in flight (pass_schedule, _passes), and with graph
@@ -304,6 +315,20 @@ def _scan_refine(pred, n, c, points, offsets, scan_ids, n_scans, out_offs, allow
     return stats
 
 
+def _flat_labels(preds, sizes, dev):
+    """Per-scan int64 label tensors as one flat buffer, slot after slot -> (flat, views): the very memory when they are
+    contiguous views of one buffer in that order (what predict_scans and its kin return; views = True), a concatenated copy
+    otherwise."""
+    at, views = preds[0].storage_offset(), True
+    for p, m in zip(preds, sizes):
+        views = (views and p.is_contiguous() and p.untyped_storage().data_ptr() == preds[0].untyped_storage().data_ptr()
+                 and p.storage_offset() == at)
+        at += m
+    if views:
+        return torch.empty(0, dtype=torch.int64, device=dev).set_(preds[0].untyped_storage(), preds[0].storage_offset(), (sum(sizes),), (1,)), True
+    return torch.cat([p.reshape(-1) for p in preds]), False
+
+
 @torch.no_grad()
 def refine_scans(preds, batch, n=10, parts=None, stats=False, num_classes=None):
     """part_seg_refinement (train.py:57-73) on whole scans: preds as predict_scans / vote_scans return them -- per scan of the
@@ -338,17 +363,8 @@ def refine_scans(preds, batch, n=10, parts=None, stats=False, num_classes=None):
          "with the scans)" % dev)
     need(torch.is_tensor(batch["scan_ids"]) and batch["scan_ids"].device == dev and batch["scan_ids"].dtype == torch.int64 and
          tuple(batch["scan_ids"].shape) == (b,), "refine_scans: batch scan_ids must be (B,) int64 on %s" % dev)
-    at, views = preds[0].storage_offset(), True         # views of one buffer, slot after slot?
-    for p, m in zip(preds, sizes):
-        views = (views and p.is_contiguous() and p.untyped_storage().data_ptr() == preds[0].untyped_storage().data_ptr()
-                 and p.storage_offset() == at)
-        at += m
-    if views:
-        flat = torch.empty(0, dtype=torch.int64, device=dev).set_(preds[0].untyped_storage(), preds[0].storage_offset(), (sum(sizes),), (1,))
-        out = list(preds)
-    else:
-        flat = torch.cat([p.reshape(-1) for p in preds])
-        out = [f.view(p.shape) for f, p in zip(torch.split(flat, sizes), preds)]
+    flat, views = _flat_labels(preds, sizes, dev)
+    out = list(preds) if views else [f.view(p.shape) for f, p in zip(torch.split(flat, sizes), preds)]
     st = _scan_refine(flat, n, c, scans.points, scans.offsets, batch["scan_ids"].contiguous(), len(scans), _out_offsets(sizes, dev),
                       allowed, b, stats)
     return (out, st) if stats else out
@@ -502,22 +518,25 @@ class SegMetrics:
         need(len(flags) == len(batch["sizes"]), "SegMetrics.%s: one jaw flag per scan" % what)
         return flags, self._rows(len(flags))
 
-    def update_from_scans(self, logits, batch):
+    def update_from_scans(self, logits, batch, want_pred=False):
         """Count one ValBatcher batch from the model's logits (B, C, N): update_from_logits' counts, from the scans where
         they lie -- one geot_scan_predict call whatever B and the scans' sizes, the jaws from the batch's host flags, no
-        host synchronisation."""
+        host synchronisation.  want_pred: the same call also writes the labels -> as predict_scans returns them."""
         flags, rows = self._scan_rows(batch, "update_from_scans")
-        _scan_launch(logits, batch, self.c, "SegMetrics.update_from_scans", counts=rows)
+        preds = _scan_launch(logits, batch, self.c, "SegMetrics.update_from_scans", counts=rows, want_pred=want_pred)
         self.mandible += flags
+        return preds
 
-    def update_from_votes(self, votes, logits, batch):
+    def update_from_votes(self, votes, logits, batch, want_pred=False):
         """Count one batch of scans from its votes: `votes` (a ScanVotes of C classes) holds the earlier passes, the model's
         logits on `batch` are the last one -- votes.add(logits, batch, last=True) with this epoch's next rows as counts, one
-        geot_scan_vote call; the jaws from the batch's host flags, no host synchronisation."""
+        geot_scan_vote call; the jaws from the batch's host flags, no host synchronisation.  want_pred: the same call also
+        writes the voted labels -> as vote_scans returns them."""
         need(votes.c == self.c, "SegMetrics.update_from_votes: the votes have %d classes, the counts %d" % (votes.c, self.c))
         flags, rows = self._scan_rows(batch, "update_from_votes")
-        votes.add(logits, batch, last=True, counts=rows)
+        preds = votes.add(logits, batch, last=True, counts=rows, want_pred=want_pred)
         self.mandible += flags
+        return preds
 
     def read(self):
         """The epoch so far, in one device-to-host copy: per scan "acc_list" (0-d fp32 tensors), "miou_list" / "mdsc_list"
@@ -768,11 +787,14 @@ def _passes(model, batcher, groups, repeats, draws, lookahead=0, graphed=None, r
             yield (data, logits) + passes[arg][1:]
 
 
-def _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_refine, parts, what, lookahead=0, graphed=None):
+def _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_refine, parts, what, lookahead=0, graphed=None,
+              teeth=None):
     """The body of validate_scans (num_votes = 0: one pass per batch, scored by geot_scan_predict) and validate_scans_voted
     (num_votes passes per batch, summed by geot_scan_vote and scored on the last): batches of batch_size scans in `indices`'
-    order through _passes, counted into one SegMetrics; with n_refine the labels are taken, refined and counted instead."""
+    order through _passes, counted into one SegMetrics; with n_refine the labels are taken, refined and counted instead.
+    teeth (a ToothScores): the call that counts also writes the labels, and every batch's final labels go through teeth.update."""
     need(int(batch_size) >= 1, "%s: batch_size >= 1" % what)
+    _need_teeth(teeth, c, batcher.device, what)
     order = list(range(len(batcher))) if indices is None else [int(i) for i in indices]
     groups = [order[at:at + int(batch_size)] for at in range(0, len(order), int(batch_size))]
     metrics = SegMetrics(c, batcher.device)
@@ -785,17 +807,19 @@ def _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_r
         elif n_refine:
             preds = (votes.add(logits, data, last=True, want_pred=True) if num_votes else
                      _scan_launch(logits, data, c, what, want_pred=True))
-            _count_refined(metrics, preds, data, n_refine, parts)
+            preds = _count_refined(metrics, preds, data, n_refine, parts)
         elif num_votes:
-            metrics.update_from_votes(votes, logits, data)
+            preds = metrics.update_from_votes(votes, logits, data, want_pred=teeth is not None)
         else:
-            metrics.update_from_scans(logits, data)
+            preds = metrics.update_from_scans(logits, data, want_pred=teeth is not None)
+        if last and teeth is not None:
+            teeth.update(preds, data)
     return _report(metrics.read(), cfg)
 
 
 @torch.no_grad()
 def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, num_votes=0, data_transform=None, refine=0,
-                   parts=None, graph=False, lookahead=0):
+                   parts=None, graph=False, lookahead=0, teeth=None):
     """validate() without a loader: scans a DeviceScanSet (or a ValBatcher built on one, reused from epoch to epoch),
     batches of batch_size scans in the sequential sampler's order (the last, shorter batch is kept: drop_last is false for
     `val`), or of the scans `indices` names (a rank's shard).  cfg.num_points sizes the sample, cfg.num_classes (default
@@ -804,7 +828,9 @@ def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, n
     reference.  refine (0: off -- cfg.refine is not read; True: n = 10; an int: n) and parts: the per-vertex labels are taken,
     refined (refine_scans) and counted against the scans' labels with geot_seg_confusion.  graph, lookahead
     (_replay_switches, _passes): the passes' geometry computed ahead and the forward passes replayed from hipGraphs -- the
-    same values; off by default."""
+    same values; off by default.  teeth: a ToothScores (None: off, and every call is as without the keyword) -- each batch's
+    final labels, after refine where that is on, also go through teeth.update; geot_scan_predict then writes the labels in the
+    call that counts them.  The return value stays the three-tuple: the caller reads teeth.read()."""
     from .openpoints.dataset.val_batch import ValBatcher
     n_refine = _refine_n(refine, "validate_scans")
     lookahead, graphed = _replay_switches(graph, lookahead, 0, model, "validate_scans")
@@ -816,7 +842,8 @@ def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, n
     else:
         need(_cfg(cfg, "num_points") is not None, "validate_scans: cfg.num_points (the sample size) is missing")
         batcher = ValBatcher(scans, _cfg(cfg, "num_points"), c, stream=stream)
-    return _validate(model, batcher, cfg, c, batch_size, indices, 0, None, n_refine, parts, "validate_scans", lookahead, graphed)
+    return _validate(model, batcher, cfg, c, batch_size, indices, 0, None, n_refine, parts, "validate_scans", lookahead, graphed,
+                     teeth)
 
 
 def _scan_labels(batch):
@@ -832,9 +859,11 @@ def _scan_labels(batch):
 
 
 def _count_refined(metrics, preds, batch, n, parts):
-    """The validators' refine leg: refine the batch's per-vertex labels and count them against the scans' labels."""
+    """The validators' refine leg: refine the batch's per-vertex labels and count them against the scans' labels
+    -> the refined labels."""
     preds = refine_scans(preds, batch, n, parts, num_classes=metrics.c)
     metrics.update(preds, _scan_labels(batch), [0 if m else 1 for m in batch["mandible"]])
+    return preds
 
 
 class ScanVotes:
@@ -896,7 +925,7 @@ def vote_scans(model, batcher, idx, num_votes, draws=None, refine=0, parts=None,
 
 @torch.no_grad()
 def validate_scans_voted(model, scans, cfg, num_votes=None, vote=None, batch_size=2, indices=None, stream=None, draws=None,
-                         refine=0, parts=None, graph=False, lookahead=0):
+                         refine=0, parts=None, graph=False, lookahead=0, teeth=None):
     """validate_scans with votes: every batch of scans runs through the model num_votes times, each time freshly sampled and
     under the `vote` transform list, and is scored on the arg-max of the summed whole-scan probabilities.  scans: a
     DeviceScanSet, or a VoteBatcher built on one.  num_votes defaults to cfg.num_votes, vote to cfg.datatransforms.vote when
@@ -904,7 +933,8 @@ def validate_scans_voted(model, scans, cfg, num_votes=None, vote=None, batch_siz
     num_votes < 1 raises ValueError: validate_scans is the un-voted call.  The next vote's batch is built on `stream` beside
     the current forward pass.  Same log lines, return value and dtypes as validate().  refine, parts: as for validate_scans,
     on the voted labels.  graph, lookahead: as for validate_scans; lookahead=True draws a group's num_votes passes at once
-    and runs one geometry call for them."""
+    and runs one geometry call for them.  teeth: as for validate_scans, on the voted labels (the last geot_scan_vote call writes
+    them beside the counts)."""
     from .openpoints.dataset.vote_batch import DEFAULT_VOTE, TOOTH_VIEW_KWARGS, VoteBatcher
     n_refine = _refine_n(refine, "validate_scans_voted")
     num_votes = _cfg(cfg, "num_votes", 0) if num_votes is None else num_votes
@@ -927,7 +957,7 @@ def validate_scans_voted(model, scans, cfg, num_votes=None, vote=None, batch_siz
         batcher = VoteBatcher(scans, _cfg(cfg, "num_points"), c, vote=DEFAULT_VOTE if vote is None else vote,
                               kwargs=TOOTH_VIEW_KWARGS if kwargs is None else kwargs, stream=stream, draws=draws)
     return _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_refine, parts, "validate_scans_voted",
-                     lookahead, graphed)
+                     lookahead, graphed, teeth)
 
 
 class ScanCover:
@@ -1038,12 +1068,13 @@ def cover_scans(model, batcher, idx, rounds=1, interpolate=False, draws=None, re
 
 @torch.no_grad()
 def validate_scans_covered(model, scans, cfg, rounds=1, interpolate=False, batch_size=2, indices=None, stream=None, draws=None,
-                           refine=0, parts=None, graph=False, lookahead=0):
+                           refine=0, parts=None, graph=False, lookahead=0, teeth=None):
     """validate_scans scored on covering passes: every batch of scans runs through the model rounds * P times (cover_scans),
     each vertex scored on the class the model gave that very vertex.  scans: a DeviceScanSet (a ValBatcher is built on it:
     cfg.num_points, cfg.num_classes), or a ValBatcher / VoteBatcher built on one (a VoteBatcher applies its vote list per
     pass).  draws: a DeviceDraws (default: the batcher's; ValueError without one).  Same log lines, return value and dtypes as
-    validate().  interpolate, refine, parts, graph, lookahead: as for cover_scans."""
+    validate().  interpolate, refine, parts, graph, lookahead: as for cover_scans.  teeth: as for validate_scans (the last pass's
+    finish writes the labels beside the counts)."""
     from .openpoints.dataset.val_batch import ScanBatcher, ValBatcher
     what = "validate_scans_covered"
     n_refine = _refine_n(refine, what)
@@ -1059,15 +1090,19 @@ def validate_scans_covered(model, scans, cfg, rounds=1, interpolate=False, batch
         batcher = ValBatcher(scans, _cfg(cfg, "num_points"), c, stream=stream, draws=draws)
     order = list(range(len(batcher))) if indices is None else [int(i) for i in indices]
     metrics = SegMetrics(c, batcher.device)
+    _need_teeth(teeth, c, batcher.device, what)
     for at in range(0, len(order), int(batch_size)):
         ids = order[at:at + int(batch_size)]
         if n_refine:
             preds, data, _ = _cover_run(model, batcher, ids, rounds, interpolate, draws, graph, lookahead, what, c)
-            _count_refined(metrics, preds, data, n_refine, parts)
+            preds = _count_refined(metrics, preds, data, n_refine, parts)
         else:
             rows = metrics._rows(len(ids))
-            _cover_run(model, batcher, ids, rounds, interpolate, draws, graph, lookahead, what, c, counts=rows, want_pred=False)
+            preds, data, _ = _cover_run(model, batcher, ids, rounds, interpolate, draws, graph, lookahead, what, c, counts=rows,
+                                        want_pred=teeth is not None)
             metrics.mandible += [batcher.cls_host[i] == 0 for i in ids]
+        if teeth is not None:
+            teeth.update(preds, data)
     return _report(metrics.read(), cfg)
 
 
@@ -1189,12 +1224,14 @@ def decode_scans(model, batcher, idx, refine=0, parts=None, chunk=32768, draws=N
 
 
 @torch.no_grad()
-def validate_scans_decoded(model, scans, cfg, batch_size=2, indices=None, stream=None, draws=None, refine=0, parts=None, chunk=32768):
+def validate_scans_decoded(model, scans, cfg, batch_size=2, indices=None, stream=None, draws=None, refine=0, parts=None, chunk=32768,
+                           teeth=None):
     """validate_scans scored on decoded labels (decode_scans): per batch of scans one batch() and one forward pass, then the
     last decoder stage at every vertex, counted by geot_scan_decode_finish.  scans: a DeviceScanSet (a ValBatcher is built on
     it: cfg.num_points, cfg.num_classes), or a ValBatcher / VoteBatcher built on one.  Same log lines, return value and
     dtypes as validate().  refine, parts: as for validate_scans; chunk, draws: as for decode_scans.  No host synchronisation
-    beyond validate_scans' (the final read of the counts)."""
+    beyond validate_scans' (the final read of the counts).  teeth: as for validate_scans (every chunk's finish writes its
+    labels beside the counts)."""
     from .openpoints.dataset.val_batch import ScanBatcher, ValBatcher
     what = "validate_scans_decoded"
     n_refine = _refine_n(refine, what)
@@ -1209,13 +1246,245 @@ def validate_scans_decoded(model, scans, cfg, batch_size=2, indices=None, stream
         batcher = ValBatcher(scans, _cfg(cfg, "num_points"), c, stream=stream, draws=draws)
     order = list(range(len(batcher))) if indices is None else [int(i) for i in indices]
     metrics = SegMetrics(c, batcher.device)
+    _need_teeth(teeth, c, batcher.device, what)
     for at in range(0, len(order), int(batch_size)):
         ids = order[at:at + int(batch_size)]
         if n_refine:
             preds, data = _decode_run(model, batcher, ids, c, draws, chunk, what)
-            _count_refined(metrics, preds, data, n_refine, parts)
+            preds = _count_refined(metrics, preds, data, n_refine, parts)
         else:
             rows = metrics._rows(len(ids))
-            _decode_run(model, batcher, ids, c, draws, chunk, what, counts=rows, want_pred=False)
+            preds, data = _decode_run(model, batcher, ids, c, draws, chunk, what, counts=rows, want_pred=teeth is not None)
             metrics.mandible += [batcher.cls_host[i] == 0 for i in ids]
+        if teeth is not None:
+            teeth.update(preds, data)
     return _report(metrics.read(), cfg)
+
+
+# ---- the Teeth3DS challenge scores: TSA, TLA, TIR (csrc/tooth_scores.hip) -----------------------------------------------------------
+TOOTH_ENTRIES = 21          # int64 per class in a geot_tooth_moments row (include/geot_hip.h); the row ends with two slot entries
+TOOTH_BIAS = 1 << 30        # the extents are stored as max(q + 2^30) and max(2^30 - q)
+TOOTH_SCALE = 65536.0       # q = rint((p - center) * 65536)
+TLA_PENALTY = 5.0           # a true tooth's normalised distance when the scan has no predicted tooth (the challenge's penalty)
+TIR_RADIUS = 0.5            # a true tooth is identified when its nearest predicted centroid lies closer than half its size
+# The moments kernel is set by launch cost and atomics, not by memory (profiles/tooth_scores_timing.txt), and one vertex costs a
+# lane far less than geot_scan_predict's search: its records are cut longer, one vertex per lane of a 256-thread workgroup.
+TOOTH_CHUNK_MIN = 256
+
+
+def _mean(values):
+    values = [v for v in values if not np.isnan(v)]
+    return float(np.mean(values)) if values else float("nan")
+
+
+def tooth_scores_from_moments(moments, centers, num_classes, mandible):
+    """ToothScores.read()'s host half (no device needed; numpy float64): moments (S, 21 C + 2) int64 as geot_tooth_moments
+    writes them, centers (S, 3) the origin each scan was quantised around, mandible (S,) the jaw flags -> a dict.
+
+    These definitions restate the published 3DTeethSeg'22 evaluation; the challenge's own script was not available to test
+    against, so agreement with it is not tested.  Teeth are the classes 1 .. C - 1.  Per scan and class, from the moments:
+    centroid = center + (sum / count) / 65536; size of a TRUE tooth = its per-axis extent (max - min) / 65536, a 3-vector;
+    G = the true teeth present, P = the predicted teeth present.  A true tooth with a zero extent on any axis is `degenerate`:
+    reported, and left out of TLA and TIR (numerators and denominators).  Per scan:
+      tla           for every true tooth t the predicted tooth u* whose centroid is nearest in plain Euclidean distance (the
+                    lowest class among equals), d_t = ||(g_t - p_u*) / size_t||_2 divided per axis; with P empty d_t = 5;
+                    the mean of d_t over G (NaN for a scan whose true teeth are all degenerate);
+      tir           the share of G with d_t < 0.5 and u* == t;
+      tsa           the agreement of (label != 0) with (pred != 0) over the usable vertices with a label in [0, C):
+                    (tooth on both sides + gingiva on both sides) / vertices -- the micro-averaged F1 of the tooth / gingiva
+                    split, as the challenge's script scores a jaw;
+      tsa_instance  the mean over G (degenerate teeth included) of 2 hit_t / (n_label_t + n_pred_t), the per-tooth F1 of the
+                    challenge paper's text.
+    Over the epoch: "tla", "tsa", "tsa_instance" are means over the scans that have a true tooth (tla: one that is not
+    degenerate); "tir" is pooled, hits over all true teeth; "exp_neg_tla" = exp(-tla); "score" = (tsa + exp_neg_tla + tir) / 3.
+    Also returned: the per-scan lists "tsa_list", "tsa_instance_list", "tla_list", "tir_list", "teeth_list" (|G| without the
+    degenerate) and "hits_list"; per jaw "mandible_tsa" ... "maxillary_tir" (tir pooled per jaw); "degenerate" [(scan, class)];
+    "unusable" (positions that were not finite or lay 16384 units or more from their centre; a warning is logged when it is not
+    zero) and "scans"."""
+    c = int(num_classes)
+    words = TOOTH_ENTRIES * c + 2
+    rows = np.asarray(moments, dtype=np.int64).reshape(-1, words)
+    centers = np.asarray(centers, dtype=np.float64).reshape(-1, 3)
+    need(len(mandible) == rows.shape[0] == centers.shape[0], "ToothScores: %d jaw flags and %d centres for %d scans" %
+         (len(mandible), centers.shape[0], rows.shape[0]))
+    tsa_l, tsai_l, tla_l, tir_l, teeth_l, hits_l, degenerate = [], [], [], [], [], [], []
+    for i, row in enumerate(rows):
+        m = row[:TOOTH_ENTRIES * c].reshape(c, TOOTH_ENTRIES)
+        both, n_label, n_pred, hit = int(row[-2]), m[:, 0], m[:, 10], m[:, 20]
+        G = [k for k in range(1, c) if n_label[k] > 0]
+        P = [k for k in range(1, c) if n_pred[k] > 0]
+        if not G:
+            for lst in (tsa_l, tsai_l, tla_l, tir_l):
+                lst.append(float("nan"))
+            teeth_l.append(0)
+            hits_l.append(0)
+            continue
+        tsa_l.append((both + int(hit[0])) / int(n_label.sum()))
+        tsai_l.append(float(np.mean([2.0 * hit[k] / (n_label[k] + n_pred[k]) for k in G])))
+        p_cent = np.array([centers[i] + (m[k, 11:14] / float(n_pred[k])) / TOOTH_SCALE for k in P]).reshape(-1, 3)
+        dist, hits, used = [], 0, 0
+        for t in G:
+            size = (m[t, 4:7] + m[t, 7:10] - 2 * TOOTH_BIAS) / TOOTH_SCALE
+            if (size == 0).any():
+                degenerate.append((i, t))
+                continue
+            used += 1
+            if not P:
+                dist.append(TLA_PENALTY)
+                continue
+            g = centers[i] + (m[t, 1:4] / float(n_label[t])) / TOOTH_SCALE
+            u = int(np.argmin(np.sqrt(((p_cent - g) ** 2).sum(1))))         # the first minimum: the lowest class among equals
+            d = float(np.sqrt((((g - p_cent[u]) / size) ** 2).sum()))
+            dist.append(d)
+            hits += int(d < TIR_RADIUS and P[u] == t)
+        tla_l.append(float(np.mean(dist)) if used else float("nan"))
+        tir_l.append(hits / used if used else float("nan"))
+        teeth_l.append(used)
+        hits_l.append(hits)
+    unusable = int(rows[:, -1].sum()) if len(rows) else 0
+    if unusable:
+        logging.warning("ToothScores: %d vertex positions were not finite or lay 16384 units or more from their centre; they "
+                        "are in no score" % unusable)
+
+    def over(sel):
+        teeth = sum(teeth_l[i] for i in sel)
+        return dict(tsa=_mean([tsa_l[i] for i in sel]), tsa_instance=_mean([tsai_l[i] for i in sel]),
+                    tla=_mean([tla_l[i] for i in sel]), tir=sum(hits_l[i] for i in sel) / teeth if teeth else float("nan"))
+    out = over(range(len(rows)))
+    out["exp_neg_tla"] = float(np.exp(-out["tla"]))
+    out["score"] = (out["tsa"] + out["exp_neg_tla"] + out["tir"]) / 3.0
+    for jaw, lower in (("mandible", True), ("maxillary", False)):
+        for key, v in over([i for i, flag in enumerate(mandible) if bool(flag) == lower]).items():
+            out["%s_%s" % (jaw, key)] = v
+    out.update(tsa_list=tsa_l, tsa_instance_list=tsai_l, tla_list=tla_l, tir_list=tir_l, teeth_list=teeth_l, hits_list=hits_l,
+               degenerate=degenerate, unusable=unusable, scans=len(rows))
+    return out
+
+
+def _tooth_launch(preds, batch, c, rows, what):
+    """One geot_tooth_moments call: the per-scan labels `preds` of a ValBatcher / VoteBatcher batch against the scans' own
+    labels and positions, read in place from the set, ADDED into `rows` (b, 21 c + 2) int64.  No host synchronisation."""
+    need(isinstance(batch, dict) and all(k in batch for k in ("center", "scan_ids", "scans", "sizes")),
+         "%s: batch must come from ValBatcher.batch / VoteBatcher.batch (center, scan_ids, scans, sizes)" % what)
+    scans, sizes = batch["scans"], [int(m) for m in batch["sizes"]]
+    dev, b = scans.device, len(sizes)
+    need(isinstance(preds, (list, tuple)) and len(preds) == b and 1 <= b <= SCAN_MAX_SLOTS,
+         "%s: one prediction tensor per scan of the batch (1 .. %d)" % (what, SCAN_MAX_SLOTS))
+    for p, m in zip(preds, sizes):
+        need(torch.is_tensor(p) and p.dtype == torch.int64, "%s: the predictions must be int64 tensors" % what)
+        need(p.numel() == m, "%s: %d predictions for a scan of %d vertices" % (what, p.numel(), m))
+        need(p.is_cuda and p.device == dev, "%s: CPU not supported (the predictions must live on %s, with the scans)" % (what, dev))
+    for key, dt, shape in (("center", torch.float32, (b, 3)), ("scan_ids", torch.int64, (b,))):
+        need(torch.is_tensor(batch[key]) and batch[key].device == dev and batch[key].dtype == dt and tuple(batch[key].shape) == shape,
+             "%s: batch %s must be a %s %s tensor on %s" % (what, key, shape, dt, dev))
+    flat, _ = _flat_labels(preds, sizes, dev)
+    center, scan_ids = batch["center"].contiguous(), batch["scan_ids"].contiguous()
+    work = _to_device(scan_work_table(sizes, min_chunk=TOOTH_CHUNK_MIN), dev)
+    call("geot_tooth_moments", dev, b, c, len(scans), int(scans.points.shape[0]), ptr(scans.points), ptr(scans.labels),
+         ptr(scans.offsets), ptr(scan_ids), ptr(center), int(work.shape[0]), ptr(work), ptr(_out_offsets(sizes, dev)), ptr(flat),
+         ptr(rows))
+    return center
+
+
+class ToothScores:
+    """The Teeth3DS challenge scores of one epoch -- TSA, TLA, TIR (tooth_scores_from_moments) -- from moments taken on the
+    device: a (scans, 21 C + 2) int64 buffer and the (scans, 3) fp32 centres the scans were quantised around (capacities double
+    as scans arrive; both stay on the device until read()), and each scan's jaw, kept on the host.  update() does not
+    synchronise with the host."""
+
+    def __init__(self, num_classes, device):
+        c = _need_classes(num_classes, "ToothScores")
+        dev = torch.device(device)
+        need(dev.type == "cuda", "ToothScores: the moments live on a GPU, got device %s" % dev)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.c, self.words, self.device = c, TOOTH_ENTRIES * c + 2, dev
+        self.moments = torch.zeros((8, self.words), dtype=torch.int64, device=dev)
+        self.centers = torch.zeros((8, 3), dtype=torch.float32, device=dev)
+        self.mandible = []
+
+    @property
+    def scans(self):
+        return len(self.mandible)
+
+    def reset(self):
+        """A new epoch."""
+        self.moments.zero_()
+        self.mandible = []
+
+    def _rows(self, b):
+        """The (zero) moment rows and the centre rows of the next b scans."""
+        n0 = self.scans
+        if n0 + b > self.moments.shape[0]:
+            cap = max(n0 + b, 2 * self.moments.shape[0])
+            for name in ("moments", "centers"):
+                old = getattr(self, name)
+                grown = torch.zeros((cap, old.shape[1]), dtype=old.dtype, device=self.device)
+                grown[:n0].copy_(old[:n0])
+                setattr(self, name, grown)
+        return self.moments[n0:n0 + b], self.centers[n0:n0 + b]
+
+    def update(self, preds, batch):
+        """One batch: preds as predict_scans / vote_scans / cover_scans / decode_scans return them -- per scan of the batch a
+        (1, M_i) int64 tensor -- and the ValBatcher / VoteBatcher batch they belong to (its scans, scan_ids, sizes, center and
+        jaw flags).  One geot_tooth_moments call, no host synchronisation."""
+        need(isinstance(batch, dict) and "mandible" in batch and "scans" in batch and "sizes" in batch,
+             "ToothScores.update: batch must come from ValBatcher.batch / VoteBatcher.batch")
+        need(batch["scans"].device == self.device, "ToothScores.update: the scans on %s, the moments on %s" %
+             (batch["scans"].device, self.device))
+        flags = [bool(m) for m in batch["mandible"]]
+        need(len(flags) == len(batch["sizes"]), "ToothScores.update: one jaw flag per scan")
+        rows, centers = self._rows(len(flags))
+        centers.copy_(_tooth_launch(preds, batch, self.c, rows, "ToothScores.update"))
+        self.mandible += flags
+
+    def read(self):
+        """The epoch so far, in one device-to-host copy (the moments and the centres travel as one buffer) -> the dict of
+        tooth_scores_from_moments."""
+        n = self.scans
+        packed = torch.cat([self.moments[:n].view(torch.uint8).reshape(n, -1), self.centers[:n].view(torch.uint8).reshape(n, -1)], 1).cpu().numpy()
+        moments = np.ascontiguousarray(packed[:, :8 * self.words]).view(np.int64)
+        centers = np.ascontiguousarray(packed[:, 8 * self.words:]).view(np.float32)
+        return tooth_scores_from_moments(moments, centers, self.c, self.mandible)
+
+
+def _need_teeth(teeth, c, dev, what):
+    """The validators' teeth= keyword: None or a ToothScores of the same class count on the scans' device."""
+    if teeth is None:
+        return
+    need(isinstance(teeth, ToothScores), "%s: teeth must be a ToothScores or None, got %r" % (what, type(teeth).__name__))
+    dev = torch.device(dev)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    need(teeth.c == int(c) and teeth.device == dev, "%s: teeth counts %d classes on %s, the validation %d on %s" %
+         (what, teeth.c, teeth.device, int(c), dev))
+
+
+@torch.no_grad()
+def tooth_instances(preds, batch, num_classes):
+    """The geometry of the predicted teeth, for users who want more than the scores: preds and batch as ToothScores.update takes
+    them -> a dict of device tensors, per scan of the batch and class: "count" (B, C) int64 predicted vertices; "centroid"
+    (B, C, 3) fp64; "box_min" / "box_max" (B, C, 3) fp64, the axis-aligned box -- in the scans' coordinates, to the 2^-16 of a
+    unit the moments resolve, NaN for a class that was not predicted.  The same single geot_tooth_moments launch, then a few
+    torch statements on the (B, 21 C + 2) row buffer; no host synchronisation."""
+    c = _need_classes(num_classes, "tooth_instances")
+    need(isinstance(batch, dict) and "scans" in batch and "sizes" in batch, "tooth_instances: batch must come from ValBatcher.batch")
+    dev, b = batch["scans"].device, len(batch["sizes"])
+    rows = torch.zeros((b, TOOTH_ENTRIES * c + 2), dtype=torch.int64, device=dev)
+    center = _tooth_launch(preds, batch, c, rows, "tooth_instances").double().view(b, 1, 3)
+    m = rows[:, :TOOTH_ENTRIES * c].view(b, c, TOOTH_ENTRIES)
+    count = m[:, :, 10]
+    empty = (count == 0).view(b, c, 1)
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    centroid = center + (m[:, :, 11:14].double() / count.double().view(b, c, 1)) / TOOTH_SCALE
+    box_max = center + (m[:, :, 14:17] - TOOTH_BIAS).double() / TOOTH_SCALE
+    box_min = center + (TOOTH_BIAS - m[:, :, 17:20]).double() / TOOTH_SCALE
+    return {"count": count.clone(), "centroid": torch.where(empty, nan, centroid), "box_min": torch.where(empty, nan, box_min),
+            "box_max": torch.where(empty, nan, box_max)}
+
+
+def report_tooth_scores(out, cfg):
+    """The one log line of the challenge scores, in the style of validate's three."""
+    epoch = "%s/%s" % (_cfg(cfg, "epoch"), _cfg(cfg, "epochs"))
+    logging.info(f"Test Epoch [{epoch}],TSA {out['tsa']:.5f}, TSA(instance) {out['tsa_instance']:.5f}, TLA {out['tla']:.5f}, "
+                 f"TIR {out['tir']:.5f}, score {out['score']:.5f}")

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 31
+#define GEOT_ABI_VERSION 32
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -974,6 +974,36 @@ long long geot_scan_refine_ws_bytes(int b, long long total_out, int n);
 int geot_scan_refine(int b, int c, int n, int n_scans, long long total, const float *points, const long long *offsets,
                      const long long *scan_ids, const long long *out_offsets, const unsigned *allowed, long long *pred,
                      int *stats, void *ws, long long ws_bytes, void *stream);
+
+/* ---- per-tooth moments of whole-scan labels: what the 3DTeethSeg challenge scores are made of (ABI 32) ------------------------
+ * geot_tooth_moments: for b batch slots, per class the vertex count, the position sum and the axis-aligned extent of the
+ * LABELLED and of the PREDICTED vertices, and their overlap -- everything TSA, TLA and TIR need (geot_amd/validation.py
+ * tooth_scores_from_moments) -- in one launch whatever the batch holds, no host synchronisation, integer atomics only.
+ * The scans lie concatenated as for geot_scan_predict (points (total, 3) fp32, labels (total) int32, offsets, scan_ids, the
+ * work records (slot, first vertex, vertex count, ignored) of scan_work_table, one workgroup each, and their skip rules: an
+ * unusable slot or record is neither read nor counted); pred: int64 per vertex, vertex v of slot s at out_offsets[s] + v, as
+ * geot_scan_predict / geot_scan_vote / geot_scan_cover / geot_scan_decode_finish / geot_scan_refine leave it; center (b, 3)
+ * fp32: the batch's `center`, the origin the slot's positions are quantised around.
+ * Per vertex v of slot s: d = points[v] - center[s], one fp32 subtraction per axis; the position is USABLE iff all three d are
+ * finite and |d| < 16384; q = rint(d * 65536.0f), ties to even, a 64-bit integer per axis (|q| < 2^30; the resolution is
+ * 2^-16 of a coordinate unit).  An unusable vertex adds 1 to the slot's last counter and nothing else.  A usable one joins the
+ * label side of class k iff labels[v] == k, the prediction side of class k iff pred[v] == k, k in [0, c); a value outside
+ * [0, c) on one side leaves the other side untouched.
+ * moments: b rows of 21 c + 2 int64, zeroed by the caller; counts and sums are ADDED to and extents MAX-combined, so calls
+ * over parts of a work table give the bits of one call over the whole.  Per class k, entries 21 k + ...
+ *   [0] label-side vertex count   [1..3] sum of q per axis   [4..6] max(q + 2^30) per axis   [7..9] max(2^30 - q) per axis
+ *   [10..19] the same ten entries of the prediction side      [20] vertices with label == pred == k
+ * (both extent entries are positive wherever the count is: a zero row is the empty state, min = 2^30 - entry); the row ends
+ * with [21 c] the vertices with label in [1, c) and pred in [1, c), and [21 c + 1] the unusable positions.
+ * Everything is an integer: no result depends on the order of arrival, and a numpy restatement gives the same bits.
+ * GEOT_TOOTH_MOMENTS_IMPL=basic (read at every call) takes the straightforward form -- one LDS atomic per lane and entry --
+ * in place of the one that combines equal classes inside a wave first; the same bits.
+ * 0 <= b <= 65535 (0: nothing to do), 1 <= c <= GEOT_NTM_MAX_C, n_scans >= 1, total >= 1, n_work >= 0 (0: nothing to do), no
+ * NULL among points, labels, offsets, scan_ids, center, out_offsets, pred and moments, work not NULL and 16-byte aligned;
+ * anything else is hipErrorInvalidValue before any launch. */
+int geot_tooth_moments(int b, int c, int n_scans, long long total, const float *points, const int *labels,
+                       const long long *offsets, const long long *scan_ids, const float *center, int n_work, const int *work,
+                       const long long *out_offsets, const long long *pred, long long *moments, void *stream);
 
 /* ---- transform lists as per-view programs (ABI 16) ---------------------------------------------------------------------------
  * geot_view_program: geot_fixmatch_views for ANY list of the reference's point transforms that keeps the point count
