@@ -11,6 +11,23 @@
 // statistics, SyncBatchNorm's all-reduce) is O(C) and stays in the Python wrapper (geot_amd/fused_norm.py).
 //
 // Algorithmic bytes: apply 8 B/element; backward reduce 8 B, backward apply 12 B; FP front end 4 (C n + C m) + 24 n + 4 Cs n.
+//
+// The Encoder's folds (geot_bn_*_seg, geot_thin_*): the same passes over x + a per-(channel, segment) addend that is never
+// added in memory (same bytes as above, + 4 B per segment), and act(bn(W x)) for J <= 8 input rows with W x never stored
+// (apply 4 B/element written, backward 4 B/element read; x itself is J rows, L2-resident).
+// Resources on gfx950 (-Rpass-analysis=kernel-resource-usage; no kernel uses scratch or AGPRs):
+//   kernel                          VGPRs                              LDS B/block   waves/SIMD
+//   bn_stats_seg                    20                                 32            8
+//   bn_apply_seg                    17                                 0             8
+//   bn_bwd_reduce_seg               34                                 64            8
+//   bn_sums_f64                     17                                 0             8
+//   bn_bwd_apply_seg<8|4|2|1>       40 40 40 38                        0             8
+//   thin_moments<1..8>              17 37 53 61 98 86 104 126          64 .. 1408    8 8 8 8 4 5 4 4
+//   thin_bn_sums                    52                                 640           8
+//   thin_bn_apply<1..8>             16 34 44 54 64 66 74 82            0             8 8 8 8 8 7 6 5
+//   thin_bn_bwd_reduce<1..8>        43 55 67 81 93 105 117 129         96 .. 320     8 8 7 5 5 4 4 3
+//   thin_bn_bwd_sums                12                                 0             8
+//   thin_bn_wgrad                   32                                 0             8
 #include "geot_common.h"
 #include "geot_hip.h"
 
@@ -170,6 +187,412 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_apply_kernel(int c, int l, 
         for (int e = blockIdx.x * BN_THREADS + threadIdx.x; e < l; e += gridDim.x * BN_THREADS)
             dx[base + e] = one(x[base + e], dz[base + e]);
     }
+}
+
+// ---- the four passes over x + seg[.., e / n]: a per-(batch, channel, segment) addend, never added in memory ---------------
+// (the Encoder's second BatchNorm: x = W_f . per-point features, seg = W_g . pooled, n points per group.)  l % n == 0 and
+// n % 4 == 0: a float4 of a row lies in ONE segment; the segment is found from the ABSOLUTE column, so a slice boundary may
+// fall inside one.  Rows are 16-byte aligned (the launchers check): float4 traffic only.
+__global__ __launch_bounds__(BN_THREADS) void bn_stats_seg_kernel(int c, int l, int n, const float *__restrict__ x,
+                                                                  const float *__restrict__ seg, float *__restrict__ partial)
+{
+    const int bi = blockIdx.z, cc = blockIdx.y;
+    const size_t rowi = (size_t)bi * c + cc;
+    const float *row = x + rowi * l;
+    const float *srow = seg + rowi * (l / n);
+    const int per = (((l + gridDim.x - 1) / gridDim.x) + 3) & ~3;
+    const int e0 = blockIdx.x * per, e1 = min(l, e0 + per);
+    float s = 0.f, ss = 0.f;
+    const float p = e0 < e1 ? row[e0] + srow[e0 / n] : 0.f;
+    for (int v = (e0 >> 2) + threadIdx.x; v < (e1 >> 2); v += BN_THREADS) {
+        float4 q = reinterpret_cast<const float4 *>(row)[v];
+        const float a = srow[(unsigned)(v << 2) / (unsigned)n];
+        q.x = (q.x + a) - p; q.y = (q.y + a) - p; q.z = (q.z + a) - p; q.w = (q.w + a) - p;
+        s += (q.x + q.y) + (q.z + q.w);
+        ss = fmaf(q.x, q.x, fmaf(q.y, q.y, fmaf(q.z, q.z, fmaf(q.w, q.w, ss))));
+    }
+    float *dst = partial + (rowi * gridDim.x + blockIdx.x) * 4;
+    bn_block_store2(s, ss, dst);
+    if (threadIdx.x == 0) { dst[2] = p; dst[3] = (float)max(e1 - e0, 0); }
+}
+
+__global__ __launch_bounds__(BN_THREADS) void bn_apply_seg_kernel(int c, int l, int n, int relu, const float *__restrict__ x,
+                                                                  const float *__restrict__ seg, const float *__restrict__ scale,
+                                                                  const float *__restrict__ shift, float *__restrict__ out)
+{
+    const int bi = blockIdx.z, cc = blockIdx.y;
+    const size_t rowi = (size_t)bi * c + cc;
+    const size_t base = rowi * l;
+    const float *srow = seg + rowi * (l / n);
+    const float a = scale[cc], b = shift[cc];
+    const float lo = relu ? 0.f : -INFINITY;
+    const int vec = l >> 2;
+    for (int v = blockIdx.x * BN_THREADS + threadIdx.x; v < vec; v += gridDim.x * BN_THREADS) {
+        float4 q = reinterpret_cast<const float4 *>(x + base)[v];
+        const float t = srow[(unsigned)(v << 2) / (unsigned)n];
+        q.x = max_nan(fmaf(q.x + t, a, b), lo);
+        q.y = max_nan(fmaf(q.y + t, a, b), lo);
+        q.z = max_nan(fmaf(q.z + t, a, b), lo);
+        q.w = max_nan(fmaf(q.w + t, a, b), lo);
+        reinterpret_cast<float4 *>(out + base)[v] = q;
+    }
+}
+
+__global__ __launch_bounds__(BN_THREADS) void bn_bwd_reduce_seg_kernel(int c, int l, int n, int relu, const float *__restrict__ x,
+                                                                       const float *__restrict__ seg,
+                                                                       const float *__restrict__ dz,
+                                                                       const float *__restrict__ scale,
+                                                                       const float *__restrict__ shift,
+                                                                       const float *__restrict__ mean,
+                                                                       const float *__restrict__ rstd,
+                                                                       double *__restrict__ partial)
+{
+    const int bi = blockIdx.z, cc = blockIdx.y;
+    const size_t rowi = (size_t)bi * c + cc;
+    const size_t base = rowi * l;
+    const float *srow = seg + rowi * (l / n);
+    const float a = scale[cc], b = shift[cc], mu = mean[cc], r = rstd[cc];
+    const int per = (((l + gridDim.x - 1) / gridDim.x) + 3) & ~3;
+    const int e0 = blockIdx.x * per, e1 = min(l, e0 + per);
+    // the sums are carried in fp64 from the first add: sum g of a single channel is a sum of terms of both signs, and what
+    // fp32 partial sums round away (an ulp of their own size each) can exceed 2e-5 of a result that cancelled
+    double s = 0.0, sx = 0.0;
+    auto one = [&](float xv, float gv) {
+        const float g = (!relu || fmaf(xv, a, b) > 0.f) ? gv : 0.f;
+        s += (double)g;
+        sx = fma((double)g, (double)((xv - mu) * r), sx);
+    };
+    for (int v = (e0 >> 2) + threadIdx.x; v < (e1 >> 2); v += BN_THREADS) {
+        const float4 q = reinterpret_cast<const float4 *>(x + base)[v];
+        const float4 g = reinterpret_cast<const float4 *>(dz + base)[v];
+        const float t = srow[(unsigned)(v << 2) / (unsigned)n];
+        one(q.x + t, g.x); one(q.y + t, g.y); one(q.z + t, g.z); one(q.w + t, g.w);
+    }
+    __shared__ double red[BN_THREADS / 64][2];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        s += __shfl_xor(s, d);
+        sx += __shfl_xor(sx, d);
+    }
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = s; red[threadIdx.x >> 6][1] = sx; }
+    __syncthreads();
+    if (threadIdx.x < 2)
+        partial[(rowi * gridDim.x + blockIdx.x) * 2 + threadIdx.x] =
+            (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+// backward apply + the addend's gradient: rows = (b, c, segment) of n elements, LPR adjacent lanes of one wave per row (as
+// segment_sum_kernel); dseg[row] = the row's sum of dx: lane sub-sums, then a butterfly -- one writer, fixed order
+template <int LPR>
+__global__ __launch_bounds__(256) void bn_bwd_apply_seg_kernel(long long rows, int n, int groups, int c, int relu,
+                                                               const float *__restrict__ x, const float *__restrict__ seg,
+                                                               const float *__restrict__ dz, const float *__restrict__ scale,
+                                                               const float *__restrict__ shift, const float *__restrict__ mean,
+                                                               const float *__restrict__ rstd, const float *__restrict__ k0,
+                                                               const float *__restrict__ c1, const float *__restrict__ c2,
+                                                               float *__restrict__ dx, float *__restrict__ dseg)
+{
+    const long long gid = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long row = gid / LPR;
+    const int sub = (int)(gid % LPR);
+    if (row >= rows) return;                               // (LPR divides 64 and rows are whole lane groups: no partial group)
+    const int cc = (int)((row / groups) % c);
+    const float a = scale[cc], b = shift[cc], mu = mean[cc], r = rstd[cc], kk = k0[cc], m1 = c1[cc], m2 = c2[cc];
+    const float t = seg[row];
+    auto one = [&](float xv, float gv) {
+        xv += t;
+        const float g = (!relu || fmaf(xv, a, b) > 0.f) ? gv : 0.f;
+        return kk * (g - m1 - (xv - mu) * r * m2);
+    };
+    const float4 *xs = reinterpret_cast<const float4 *>(x + row * n);
+    const float4 *gs = reinterpret_cast<const float4 *>(dz + row * n);
+    float4 *ds = reinterpret_cast<float4 *>(dx + row * n);
+    float s = 0.f;
+    for (int v = sub; v < (n >> 2); v += LPR) {
+        const float4 q = xs[v], g = gs[v];
+        const float4 d = make_float4(one(q.x, g.x), one(q.y, g.y), one(q.z, g.z), one(q.w, g.w));
+        ds[v] = d;
+        s += (d.x + d.y) + (d.z + d.w);
+    }
+#pragma unroll
+    for (int o = 1; o < LPR; o <<= 1) s += __shfl_xor(s, o);
+    if (sub == 0) dseg[row] = s;
+}
+
+// ---- the thin first stage: act(bn(W x)) for x (J, l), J <= 8, W (c, J); y = W x is never stored ---------------------------
+// thin_y / thin_z are THE definitions of y and of the pre-activation: the apply pass and the backward pass both call them,
+// so they agree on every bit, hence on every ReLU mask.  y is the fp64 dot product rounded once (J <= 8 fp64 fmas per element
+// are nothing beside the 4 bytes it is not stored in): it then differs from the exact w x, whose mean the moments give, by
+// half an ulp -- and not at all in the mean of a single column, where z = (y - mean) scale + beta is exactly beta although
+// scale = gamma / sqrt(eps) (y scale + shift would lose |y| scale / 2^24 there).
+template <int J>
+__device__ __forceinline__ double thin_yd(const float (&w)[J], const float (&xv)[J])
+{
+    double y = (double)w[0] * (double)xv[0];
+#pragma unroll
+    for (int j = 1; j < J; ++j) y = fma((double)w[j], (double)xv[j], y);
+    return y;
+}
+template <int J>
+__device__ __forceinline__ float thin_y(const float (&w)[J], const float (&xv)[J]) { return (float)thin_yd<J>(w, xv); }
+__device__ __forceinline__ float thin_z(float y, float mu, float a, float be) { return fmaf(y - mu, a, be); }
+
+constexpr int THIN_MOM_THREADS = 256;
+// partial[slice][0 .. J) = sum x'_i, [J + i J + k] = sum x'_i x'_k (both triangles written), x' = x - x[:, 0], in fp64
+template <int J>
+__global__ __launch_bounds__(THIN_MOM_THREADS) void thin_moments_kernel(int l, const float *__restrict__ x, double *__restrict__ partial)
+{
+    constexpr int K = J + J * (J + 1) / 2;
+    const int per = (l + gridDim.x - 1) / gridDim.x;
+    const int e0 = blockIdx.x * per, e1 = min(l, e0 + per);
+    double p[J], acc[K];
+#pragma unroll
+    for (int j = 0; j < J; ++j) p[j] = (double)x[(size_t)j * l];
+#pragma unroll
+    for (int k = 0; k < K; ++k) acc[k] = 0.0;
+    for (int e = e0 + threadIdx.x; e < e1; e += THIN_MOM_THREADS) {
+        double d[J];
+#pragma unroll
+        for (int j = 0; j < J; ++j) d[j] = (double)x[(size_t)j * l + e] - p[j];
+        int k = J;
+#pragma unroll
+        for (int i = 0; i < J; ++i) {
+            acc[i] += d[i];
+#pragma unroll
+            for (int m = i; m < J; ++m, ++k) acc[k] = fma(d[i], d[m], acc[k]);
+        }
+    }
+    __shared__ double red[THIN_MOM_THREADS / 64][K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double v = acc[k];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double *dst = partial + (size_t)blockIdx.x * (J + J * J);
+        int k = J;
+        for (int i = 0; i < J; ++i) {
+            dst[i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
+            for (int m = i; m < J; ++m, ++k) {
+                const double v = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+                dst[J + i * J + m] = v;
+                dst[J + m * J + i] = v;
+            }
+        }
+    }
+}
+
+// every block adds the slices up in a fixed order (thread t < J + J J owns one moment), block 0 writes mom = p, sum x',
+// sum x' x'^T; then one thread per channel: s1 = w . sum x', s2 = w (sum x' x'^T) w^T about q = w . p, and
+// sum y = s1 + l q, sum y^2 = s2 + 2 q s1 + l q^2 as bn_sums_shifted_kernel rebuilds them
+__global__ __launch_bounds__(256) void thin_bn_sums_kernel(int c, int j, int l, int s, const double *__restrict__ partial,
+                                                           const float *__restrict__ w, const float *__restrict__ x,
+                                                           double *__restrict__ mom, double *__restrict__ sums)
+{
+    __shared__ double m[8 + 64], p[8];
+    const int k = j + j * j;
+    if ((int)threadIdx.x < k) {
+        double a = 0.0;
+        for (int t = 0; t < s; ++t) a += partial[(size_t)t * k + threadIdx.x];
+        m[threadIdx.x] = a;
+        if (blockIdx.x == 0) mom[j + threadIdx.x] = a;
+    }
+    if ((int)threadIdx.x < j) {
+        p[threadIdx.x] = (double)x[(size_t)threadIdx.x * l];
+        if (blockIdx.x == 0) mom[threadIdx.x] = p[threadIdx.x];
+    }
+    __syncthreads();
+    const int ch = blockIdx.x * 256 + threadIdx.x;
+    if (ch >= c) return;
+    double q = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int i = 0; i < j; ++i) {
+        const double wi = (double)w[(size_t)ch * j + i];
+        q += wi * p[i];
+        s1 += wi * m[i];
+        double t = 0.0;
+        for (int u = 0; u < j; ++u) t += (double)w[(size_t)ch * j + u] * m[j + i * j + u];
+        s2 += wi * t;
+    }
+    const double n = (double)l;
+    sums[2 * ch] = s1 + n * q;
+    sums[2 * ch + 1] = s2 + 2.0 * q * s1 + n * q * q;
+}
+
+constexpr int THIN_CH = 8;       // channels per workgroup of the apply pass: x's float4s are loaded once for all of them
+// grid (gx, ceil(c / THIN_CH)); l % 4 == 0 and aligned tensors take float4s (vec4 != 0), anything else scalars
+template <int J>
+__global__ __launch_bounds__(BN_THREADS) void thin_bn_apply_kernel(int c, int l, int relu, int vec4, const float *__restrict__ w,
+                                                                   const float *__restrict__ x, const float *__restrict__ mean,
+                                                                   const float *__restrict__ scale, const float *__restrict__ beta,
+                                                                   float *__restrict__ out)
+{
+    const int c0 = blockIdx.y * THIN_CH, nch = min(THIN_CH, c - c0);
+    const float lo = relu ? 0.f : -INFINITY;
+    if (vec4) {
+        for (int v = blockIdx.x * BN_THREADS + threadIdx.x; v < (l >> 2); v += gridDim.x * BN_THREADS) {
+            float xv[4][J];
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+                const float4 q = reinterpret_cast<const float4 *>(x + (size_t)j * l)[v];
+                xv[0][j] = q.x; xv[1][j] = q.y; xv[2][j] = q.z; xv[3][j] = q.w;
+            }
+            for (int cl = 0; cl < nch; ++cl) {
+                float wr[J];
+#pragma unroll
+                for (int j = 0; j < J; ++j) wr[j] = w[(size_t)(c0 + cl) * J + j];
+                const float mu = mean[c0 + cl], a = scale[c0 + cl], b = beta[c0 + cl];
+                reinterpret_cast<float4 *>(out + (size_t)(c0 + cl) * l)[v] =
+                    make_float4(max_nan(thin_z(thin_y<J>(wr, xv[0]), mu, a, b), lo), max_nan(thin_z(thin_y<J>(wr, xv[1]), mu, a, b), lo),
+                                max_nan(thin_z(thin_y<J>(wr, xv[2]), mu, a, b), lo), max_nan(thin_z(thin_y<J>(wr, xv[3]), mu, a, b), lo));
+            }
+        }
+    } else {
+        for (int e = blockIdx.x * BN_THREADS + threadIdx.x; e < l; e += gridDim.x * BN_THREADS) {
+            float xv[J];
+#pragma unroll
+            for (int j = 0; j < J; ++j) xv[j] = x[(size_t)j * l + e];
+            for (int cl = 0; cl < nch; ++cl) {
+                float wr[J];
+#pragma unroll
+                for (int j = 0; j < J; ++j) wr[j] = w[(size_t)(c0 + cl) * J + j];
+                out[(size_t)(c0 + cl) * l + e] = max_nan(thin_z(thin_y<J>(wr, xv), mean[c0 + cl], scale[c0 + cl], beta[c0 + cl]), lo);
+            }
+        }
+    }
+}
+
+// backward: ONE pass over dz (c, l) and x: per (channel, slice) sum g, sum g xhat, sum g x_j; y through thin_y.
+// grid (S, c); partial[(ch * S + slice) * (2 + J) + {0, 1, 2 + j}], fp64.  The sums g x_j are ACCUMULATED in fp64 (a product
+// of two floats is exact there): the weight gradient subtracts c1 sum x_j from them, which cancels most of both when the
+// columns are few or alike -- all of both for a single column, where the gradient is exactly zero.  sum g and sum g xhat are
+// carried in fp64 too: c1 = sum g / l multiplies sum x_j there, (mean / std of x) l times larger than what is left.
+template <int J>
+__global__ __launch_bounds__(BN_THREADS) void thin_bn_bwd_reduce_kernel(int l, int relu, int vec4, const double *__restrict__ mom,
+                                                                        const float *__restrict__ w,
+                                                                        const float *__restrict__ x, const float *__restrict__ dz,
+                                                                        const float *__restrict__ scale,
+                                                                        const float *__restrict__ beta,
+                                                                        const float *__restrict__ mean,
+                                                                        const float *__restrict__ rstd, double *__restrict__ partial)
+{
+    constexpr int K = 2 + J;
+    const int cc = blockIdx.y;
+    const float *grow = dz + (size_t)cc * l;
+    const float a = scale[cc], b = beta[cc], mu = mean[cc], r = rstd[cc];
+    float wr[J];
+    double s = 0.0, sx = 0.0, acc[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) { wr[j] = w[(size_t)cc * J + j]; acc[j] = 0.0; }
+    // xhat for the SUMS in fp64, from the unrounded y and -- where the statistics were this rank's alone (mom given) -- about
+    // their exact mean w . (p + S / l): the fp32 mean[c] misses it by up to |mean| 2^-25, which sum g xhat would collect l times
+    double mud = (double)mu;
+    if (mom) {
+        mud = 0.0;
+#pragma unroll
+        for (int j = 0; j < J; ++j) mud += (double)wr[j] * (mom[j] + mom[J + j] / (double)l);
+    }
+    const double rd = (double)r;
+    const int per = (((l + gridDim.x - 1) / gridDim.x) + 3) & ~3;
+    const int e0 = blockIdx.x * per, e1 = min(l, e0 + per);
+    auto one = [&](const float (&xv)[J], float gv) {
+        const double yd = thin_yd<J>(wr, xv);
+        const float g = (!relu || thin_z((float)yd, mu, a, b) > 0.f) ? gv : 0.f;
+        s += (double)g;
+        sx = fma((double)g, (yd - mud) * rd, sx);
+#pragma unroll
+        for (int j = 0; j < J; ++j) acc[j] = fma((double)g, (double)xv[j], acc[j]);
+    };
+    int tail = e0 + threadIdx.x;                           // first element the scalar loop takes
+    if (vec4) {
+        const int v1 = e1 >> 2;
+        for (int v = (e0 >> 2) + threadIdx.x; v < v1; v += BN_THREADS) {
+            float xv[4][J];
+#pragma unroll
+            for (int j = 0; j < J; ++j) {
+                const float4 q = reinterpret_cast<const float4 *>(x + (size_t)j * l)[v];
+                xv[0][j] = q.x; xv[1][j] = q.y; xv[2][j] = q.z; xv[3][j] = q.w;
+            }
+            const float4 g = reinterpret_cast<const float4 *>(grow)[v];
+            one(xv[0], g.x); one(xv[1], g.y); one(xv[2], g.z); one(xv[3], g.w);
+        }
+        tail = (v1 << 2) + threadIdx.x;
+    }
+    for (int e = tail; e < e1; e += BN_THREADS) {
+        float xv[J];
+#pragma unroll
+        for (int j = 0; j < J; ++j) xv[j] = x[(size_t)j * l + e];
+        one(xv, grow[e]);
+    }
+    __shared__ double red[BN_THREADS / 64][K];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        s += __shfl_xor(s, o);
+        sx += __shfl_xor(sx, o);
+    }
+    if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6][0] = s; red[threadIdx.x >> 6][1] = sx; }
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        double v = acc[j];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][2 + j] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < K)
+        partial[((size_t)cc * gridDim.x + blockIdx.x) * K + threadIdx.x] =
+            (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+// one thread per (channel, sum): the S slice partials added in fp64, ascending
+__global__ __launch_bounds__(256) void thin_bn_bwd_sums_kernel(int c, int j, int s, const double *__restrict__ partial,
+                                                               double *__restrict__ local, double *__restrict__ gx)
+{
+    const int k = 2 + j, t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= c * k) return;
+    const int ch = t / k, q = t - ch * k;
+    double a = 0.0;
+    for (int u = 0; u < s; ++u) a += partial[((size_t)ch * s + u) * k + q];
+    if (q < 2) local[2 * ch + q] = a;
+    else gx[(size_t)ch * j + q - 2] = a;
+}
+
+// dw[c][i] = scale_c (gx[c][i] - c1_c sum x_i - c2_c sum xhat_c x_i), everything in fp64: c1, c2 = sums / n (the all-reduced
+// sum g, sum g xhat; n = 0: running statistics, dw = scale gx) -- NOT their fp32 roundings: the three terms cancel by a
+// factor (mean / std of x)^2.  From the moments about the pivot p, with x' = x - p and d = w . p - mu:
+//   sum x_i = S_i + l p_i,   sum (y - mu) x_i = sum (w . x' + d) (x'_i + p_i) = w . M_i + p_i (w . S) + d (S_i + l p_i)
+// mu = the mean the statistics were taken with: w . (p + S / l) exactly when they are this rank's alone (local_mean),
+// else (SyncBatchNorm over several ranks) its fp32 value mean[c] -- as thin_bn_bwd_reduce_kernel took it for sum g xhat.
+__global__ __launch_bounds__(256) void thin_bn_wgrad_kernel(int c, int j, int l, int local_mean, const float *__restrict__ w,
+                                                            const double *__restrict__ mom, const double *__restrict__ gx,
+                                                            const double *__restrict__ sums, double count,
+                                                            const double *__restrict__ count_dev,
+                                                            const float *__restrict__ scale, const float *__restrict__ mean,
+                                                            const float *__restrict__ rstd, float *__restrict__ dw)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= c * j) return;
+    const int ch = t / j, i = t - ch * j;
+    double v = gx[t];
+    const double cnt = count_dev ? *count_dev : count;
+    if (mom && cnt > 0.0) {
+        const double n = (double)l;
+        const double *p = mom, *s1 = mom + j, *m2 = mom + 2 * j;
+        double q = 0.0, ws = 0.0, wm = 0.0;
+        for (int u = 0; u < j; ++u) {
+            const double wu = (double)w[(size_t)ch * j + u];
+            q += wu * p[u];
+            ws += wu * s1[u];
+            wm += wu * m2[u * j + i];
+        }
+        const double mu = local_mean ? q + ws / n : (double)mean[ch];
+        const double d = q - mu, sxi = s1[i] + n * p[i];
+        const double yx = wm + p[i] * ws + d * sxi;
+        v -= (sums[2 * ch] / cnt) * sxi + (sums[2 * ch + 1] / cnt) * ((double)rstd[ch] * yx);
+    }
+    dw[t] = (float)((double)scale[ch] * v);
 }
 
 // ---- FP front end: y[b,c,e] = sum_t w[e,t] A[b,c,idx[e,t]] + sum_k Wb[c,k] skip[b,k,e], + its BatchNorm sums -----
@@ -566,6 +989,29 @@ __global__ __launch_bounds__(64) void bn_sums_kernel(int b, int c, int s, const 
     }
 }
 
+// the same for the fp64 (b, c, S, 2) partials of bn_bwd_reduce_seg_kernel
+__global__ __launch_bounds__(64) void bn_sums_f64_kernel(int b, int c, int s, const double *__restrict__ partial,
+                                                         double *__restrict__ sums)
+{
+    const int ch = blockIdx.x, lane = threadIdx.x;
+    double a0 = 0.0, a1 = 0.0;
+    for (int t = lane; t < b * s; t += 64) {
+        const int bi = t / s, sl = t - bi * s;
+        const double2 v = reinterpret_cast<const double2 *>(partial)[((size_t)bi * c + ch) * s + sl];
+        a0 += v.x;
+        a1 += v.y;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        a0 += __shfl_xor(a0, o);
+        a1 += __shfl_xor(a1, o);
+    }
+    if (lane == 0) {
+        sums[2 * ch] = a0;
+        sums[2 * ch + 1] = a1;
+    }
+}
+
 // the same for the shifted statistics records (s1, s2, pivot, count) of bn_stats_kernel / fp_front_kernel: every record is
 // turned back into (sum x, sum x^2) in fp64 before it is added
 __global__ __launch_bounds__(64) void bn_sums_shifted_kernel(int b, int c, int s, const float *__restrict__ partial,
@@ -677,6 +1123,160 @@ GEOT_EXPORT int geot_bn_bwd_apply(int b, int c, int l, int relu, const float *x,
                        scale, shift, mean, rstd, k0, c1, c2, dx);
     return hipGetLastError();
 }
+
+static bool bn_seg_ok(int b, int c, int l, int n)
+{
+    return bn_dims_ok(b, c, l) && n >= 4 && n <= 256 && (n & 3) == 0 && l % n == 0;
+}
+static bool aligned16(const void *a, const void *b = nullptr, const void *c = nullptr)
+{
+    return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0;
+}
+
+GEOT_EXPORT int geot_bn_stats_seg(int b, int c, int l, int n, const float *x, const float *seg, float *partial, void *stream)
+{
+    if (!bn_seg_ok(b, c, l, n) || !x || !seg || !partial || !aligned16(x)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bn_stats_seg_kernel, dim3(bn_slices_for(b, c, l), c, b), dim3(BN_THREADS), 0, (hipStream_t)stream, c, l, n, x,
+                       seg, partial);
+    return hipGetLastError();
+}
+
+GEOT_EXPORT int geot_bn_apply_seg(int b, int c, int l, int n, int relu, const float *x, const float *seg, const float *scale,
+                                  const float *shift, float *out, void *stream)
+{
+    if (!bn_seg_ok(b, c, l, n) || !x || !seg || !scale || !shift || !out || !aligned16(x, out)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bn_apply_seg_kernel, dim3(bn_gx(l), c, b), dim3(BN_THREADS), 0, (hipStream_t)stream, c, l, n, relu, x, seg,
+                       scale, shift, out);
+    return hipGetLastError();
+}
+
+GEOT_EXPORT int geot_bn_bwd_reduce_seg(int b, int c, int l, int n, int relu, const float *x, const float *seg, const float *dz,
+                                       const float *scale, const float *shift, const float *mean, const float *rstd,
+                                       double *partial, void *stream)
+{
+    if (!bn_seg_ok(b, c, l, n) || !x || !seg || !dz || !scale || !shift || !mean || !rstd || !partial ||
+        !aligned16(x, dz, partial))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bn_bwd_reduce_seg_kernel, dim3(bn_slices_for(b, c, l), c, b), dim3(BN_THREADS), 0, (hipStream_t)stream, c, l,
+                       n, relu, x, seg, dz, scale, shift, mean, rstd, partial);
+    return hipGetLastError();
+}
+
+GEOT_EXPORT int geot_bn_sums_f64(int b, int c, int s, const double *partial, double *sums, void *stream)
+{
+    if (b < 1 || c < 1 || s < 1 || !partial || !sums || !aligned16(partial)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(bn_sums_f64_kernel, dim3(c), dim3(64), 0, (hipStream_t)stream, b, c, s, partial, sums);
+    return hipGetLastError();
+}
+
+GEOT_EXPORT int geot_bn_bwd_apply_seg(int b, int c, int l, int n, int relu, const float *x, const float *seg, const float *dz,
+                                      const float *scale, const float *shift, const float *mean, const float *rstd,
+                                      const float *k0, const float *c1, const float *c2, float *dx, float *dseg, void *stream)
+{
+    if (!bn_seg_ok(b, c, l, n) || !x || !seg || !dz || !scale || !shift || !mean || !rstd || !k0 || !c1 || !c2 || !dx || !dseg ||
+        !aligned16(x, dz, dx))
+        return hipErrorInvalidValue;
+    const int groups = l / n;
+    const long long rows = (long long)b * c * groups;
+    const int lpr = n >= 32 ? 8 : (n >= 16 ? 4 : (n >= 8 ? 2 : 1));
+    const long long blocks = (rows * lpr + 255) / 256;
+    if (blocks > 0x7fffffffLL) return hipErrorInvalidValue;
+#define GEOT_BAS(L) hipLaunchKernelGGL(bn_bwd_apply_seg_kernel<L>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, rows, n, \
+                                       groups, c, relu, x, seg, dz, scale, shift, mean, rstd, k0, c1, c2, dx, dseg)
+    if (lpr == 8) GEOT_BAS(8); else if (lpr == 4) GEOT_BAS(4); else if (lpr == 2) GEOT_BAS(2); else GEOT_BAS(1);
+#undef GEOT_BAS
+    return hipGetLastError();
+}
+
+#define GEOT_THIN_J(J, CALL)                                                                                      \
+    switch (J) {                                                                                                  \
+    case 1: CALL(1); break;                                                                                       \
+    case 2: CALL(2); break;                                                                                       \
+    case 3: CALL(3); break;                                                                                       \
+    case 4: CALL(4); break;                                                                                       \
+    case 5: CALL(5); break;                                                                                       \
+    case 6: CALL(6); break;                                                                                       \
+    case 7: CALL(7); break;                                                                                       \
+    default: CALL(8); break;                                                                                      \
+    }
+static bool thin_ok(int c, int j, int l) { return c >= 1 && c <= 65535 * THIN_CH && j >= 1 && j <= 8 && l >= 1; }
+
+GEOT_EXPORT int geot_thin_moments_slices(int l)
+{
+    if (l < 1) return -1;
+    const int s = (l + 2047) / 2048;
+    return s > 64 ? 64 : s;
+}
+
+GEOT_EXPORT int geot_thin_moments(int j, int l, const float *x, double *partial, void *stream)
+{
+    if (!thin_ok(1, j, l) || !x || !partial) return hipErrorInvalidValue;
+    const dim3 grid(geot_thin_moments_slices(l));
+#define GEOT_TM(JV) hipLaunchKernelGGL(thin_moments_kernel<JV>, grid, dim3(THIN_MOM_THREADS), 0, (hipStream_t)stream, l, x, partial)
+    GEOT_THIN_J(j, GEOT_TM)
+#undef GEOT_TM
+    return hipGetLastError();
+}
+
+GEOT_EXPORT int geot_thin_bn_sums(int c, int j, int l, int s, const double *partial, const float *w, const float *x, double *mom,
+                                  double *sums, void *stream)
+{
+    if (!thin_ok(c, j, l) || s < 1 || !partial || !w || !x || !mom || !sums) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(thin_bn_sums_kernel, dim3((c + 255) / 256), dim3(256), 0, (hipStream_t)stream, c, j, l, s, partial, w, x, mom,
+                       sums);
+    return hipGetLastError();
+}
+
+GEOT_EXPORT int geot_thin_bn_apply(int c, int j, int l, int relu, const float *w, const float *x, const float *mean,
+                                   const float *scale, const float *beta, float *out, void *stream)
+{
+    if (!thin_ok(c, j, l) || !w || !x || !mean || !scale || !beta || !out) return hipErrorInvalidValue;
+    const int vec4 = (l & 3) == 0 && aligned16(x, out);
+    int gx = ((vec4 ? l >> 2 : l) + BN_THREADS - 1) / BN_THREADS;
+    gx = gx > 256 ? 256 : gx;
+    const dim3 grid(gx, (c + THIN_CH - 1) / THIN_CH);
+#define GEOT_TA(JV) hipLaunchKernelGGL(thin_bn_apply_kernel<JV>, grid, dim3(BN_THREADS), 0, (hipStream_t)stream, c, l, relu, vec4, w, \
+                                       x, mean, scale, beta, out)
+    GEOT_THIN_J(j, GEOT_TA)
+#undef GEOT_TA
+    return hipGetLastError();
+}
+
+GEOT_EXPORT int geot_thin_bn_bwd_slices(int c, int l) { return (c >= 1 && c <= 65535 && l >= 1) ? bn_slices_for(1, c, l) : -1; }
+
+GEOT_EXPORT int geot_thin_bn_bwd_reduce(int c, int j, int l, int relu, const double *mom, const float *w, const float *x, const float *dz,
+                                        const float *scale, const float *beta, const float *mean, const float *rstd,
+                                        double *partial, void *stream)
+{
+    if (!thin_ok(c, j, l) || c > 65535 || !w || !x || !dz || !scale || !beta || !mean || !rstd || !partial)
+        return hipErrorInvalidValue;
+    const int vec4 = (l & 3) == 0 && aligned16(x, dz);
+    const dim3 grid(bn_slices_for(1, c, l), c);
+#define GEOT_TR(JV) hipLaunchKernelGGL(thin_bn_bwd_reduce_kernel<JV>, grid, dim3(BN_THREADS), 0, (hipStream_t)stream, l, relu, vec4, mom, w, \
+                                       x, dz, scale, beta, mean, rstd, partial)
+    GEOT_THIN_J(j, GEOT_TR)
+#undef GEOT_TR
+    return hipGetLastError();
+}
+
+GEOT_EXPORT int geot_thin_bn_bwd_sums(int c, int j, int s, const double *partial, double *local, double *gx, void *stream)
+{
+    if (!thin_ok(c, j, 1) || s < 1 || !partial || !local || !gx) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(thin_bn_bwd_sums_kernel, dim3((c * (2 + j) + 255) / 256), dim3(256), 0, (hipStream_t)stream, c, j, s, partial,
+                       local, gx);
+    return hipGetLastError();
+}
+
+GEOT_EXPORT int geot_thin_bn_wgrad(int c, int j, int l, int local_mean, const float *w, const double *mom, const double *gx,
+                                   const double *sums, double count, const double *count_dev, const float *scale,
+                                   const float *mean, const float *rstd, float *dw, void *stream)
+{
+    if (!thin_ok(c, j, l) || !w || !gx || !scale || !dw || (mom && (!sums || !mean || !rstd))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(thin_bn_wgrad_kernel, dim3((c * j + 255) / 256), dim3(256), 0, (hipStream_t)stream, c, j, l, local_mean, w,
+                       mom, gx, sums, count, count_dev, scale, mean, rstd, dw);
+    return hipGetLastError();
+}
+#undef GEOT_THIN_J
 
 GEOT_EXPORT int geot_bn_sums_shifted(int b, int c, int s, const float *partial, double *sums, void *stream)
 {

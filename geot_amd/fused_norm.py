@@ -64,6 +64,9 @@ class _ChannelsFirst:
     act(x * scale + shift); bwd_sums -> this rank's (C, 2) fp64 sum g, sum g * xhat; bwd_apply -> scale (g - c1 - xhat c2)."""
     channel_dim = 1
 
+    def extent(self, x):
+        return x.shape[1], x.numel() // x.shape[1]
+
     def stat_sums(self, x, partial, sums):
         b, c, l = x.shape
         if partial is None:
@@ -101,6 +104,9 @@ class _PointMajor:
     """The same passes over x (B, L, C), C % 4 == 0: csrc/channels_last.hip, the b * l rows of c channels cut into tiles."""
     channel_dim = 2
 
+    def extent(self, x):
+        return x.shape[2], x.numel() // x.shape[2]
+
     def stat_sums(self, x, partial, sums):
         b, l, c = x.shape
         if partial is None:
@@ -135,9 +141,10 @@ class _PointMajor:
 _CF, _CL = _ChannelsFirst(), _PointMajor()
 
 
-def _bwd_coef(local, count, group):
+def _bwd_coef(local, count, group, with_sums=False):
     """local (C, 2) fp64: this rank's sum g, sum g * xhat -> coef (4, C) = g_gamma, g_beta, c1, c2: the parameters'
-    gradients from this rank's sums, the means c1 / c2 that the input's gradient subtracts from those of all ranks."""
+    gradients from this rank's sums, the means c1 / c2 that the input's gradient subtracts from those of all ranks.
+    with_sums: -> (coef, the fp64 sums of all ranks that c1, c2 are the means of)."""
     c, dev = local.shape[0], local.device
     sums = local
     if group is not None:
@@ -148,7 +155,7 @@ def _bwd_coef(local, count, group):
     on_dev = torch.is_tensor(count)                                          # batch statistics: they depend on x (count > 0)
     call("geot_bn_bwd_coef", dev, c, ptr(local), ptr(sums), 0.0 if on_dev else float(count), ptr(count) if on_dev else None,
          ptr(coef[0]), ptr(coef[1]), ptr(coef[2]), ptr(coef[3]))
-    return coef
+    return (coef, sums) if with_sums else coef
 
 
 def _pre_bias_grad(scale, coef, count):
@@ -187,13 +194,13 @@ def _batch_statistics(bn, x, gamma, beta, partial, pre_bias, layout):
     """Training-mode statistics of x in `layout` for the module `bn`: the stats pass (unless `partial` came with x), the
     all-reduce under SyncBatchNorm, mean / rstd / scale / shift and the running-statistics update.
     -> (stats (4, C) = mean, rstd, scale, shift; count; group)."""
-    c = x.shape[layout.channel_dim]
+    c, per_channel = layout.extent(x)
     dev = x.device
     group = _sync_group(bn)
     with torch.no_grad():
         sums = torch.empty((c, 2), dtype=torch.float64, device=dev)
         layout.stat_sums(x, partial, sums)
-        count = float(x.numel() // c)
+        count = float(per_channel)
         count_dev = None
         if group is not None:                  # SyncBatchNorm: sums and element counts of all ranks (counts may differ);
             import torch.distributed as dist   # the total stays on the device: no host synchronisation
@@ -257,16 +264,182 @@ def _bn_act(layout, bn, x, relu, partial, pre_bias):
     return _BnActFn.apply(layout, x, gamma, beta, *stats, relu, count, group, pre_bias)
 
 
-def bn_act(bn, x, relu=True, partial=None, pre_bias=None):
+def bn_act(bn, x, relu=True, partial=None, pre_bias=None, seg=None):
     """act(bn(x)) for x (B, C, L) float32 on the GPU; `partial` (B, C, S, 4): per-slice statistics records (shifted
     sums, pivot, count) when the producer of x already formed them (fp_front).  `pre_bias` (C,): act(bn(x + pre_bias[:, None])) without the add --
     the bias of the convolution in front: under batch statistics it cancels in the output (only the running mean sees
-    it, and its gradient is exactly zero), under running statistics it folds into the shift."""
+    it, and its gradient is exactly zero), under running statistics it folds into the shift.  `seg` (B, C, G), L = G n:
+    act(bn(x + seg[..., None])) over the G segments of n columns, the add folded into the passes (bn_act_seg)."""
+    if seg is not None:
+        return bn_act_seg(bn, x, seg, relu=relu, pre_bias=pre_bias)
     if not _covered(bn, x):
         from .pointnet2.pytorch_utils import batch_norm_nd
         y = batch_norm_nd(bn, x if pre_bias is None else x + pre_bias.view(1, -1, 1))
         return torch.relu(y) if relu else y
     return _bn_act(_CF, bn, x, relu, partial, pre_bias)
+
+
+class _ChannelsFirstSeg(_ChannelsFirst):
+    """The channels-first passes over x + seg[..., None] for x (B, C, G n) and an addend seg (B, C, G) that is never added
+    in memory (geot_bn_*_seg): the statistics of one call (`seg` bound), and the three other passes as functions of it."""
+
+    def __init__(self, seg=None):
+        self.seg = seg
+
+    def stat_sums(self, x, partial, sums):
+        b, c, l = x.shape
+        partial = torch.empty((b, c, int(_lib.load().geot_bn_slices(b, c, l)), 4), dtype=torch.float32, device=x.device)
+        call("geot_bn_stats_seg", x.device, b, c, l, l // self.seg.shape[2], ptr(x), ptr(self.seg), ptr(partial))
+        call("geot_bn_sums_shifted", x.device, b, c, partial.shape[2], ptr(partial), ptr(sums))
+
+    @staticmethod
+    def apply_seg(x, seg, relu, scale, shift):
+        b, c, l = x.shape
+        out = torch.empty_like(x)
+        call("geot_bn_apply_seg", x.device, b, c, l, l // seg.shape[2], int(relu), ptr(x), ptr(seg), ptr(scale), ptr(shift), ptr(out))
+        return out
+
+    @staticmethod
+    def bwd_sums_seg(x, seg, dz, relu, scale, shift, mean, rstd):
+        b, c, l = x.shape
+        dev = x.device
+        slices = int(_lib.load().geot_bn_slices(b, c, l))
+        partial = torch.empty((b, c, slices, 2), dtype=torch.float64, device=dev)
+        call("geot_bn_bwd_reduce_seg", dev, b, c, l, l // seg.shape[2], int(relu), ptr(x), ptr(seg), ptr(dz), ptr(scale), ptr(shift),
+             ptr(mean), ptr(rstd), ptr(partial))
+        local = torch.empty((c, 2), dtype=torch.float64, device=dev)
+        call("geot_bn_sums_f64", dev, b, c, slices, ptr(partial), ptr(local))
+        return local
+
+    @staticmethod
+    def bwd_apply_seg(x, seg, dz, relu, scale, shift, mean, rstd, c1, c2):
+        b, c, l = x.shape
+        dx = torch.empty_like(x)
+        dseg = torch.empty_like(seg)
+        call("geot_bn_bwd_apply_seg", x.device, b, c, l, l // seg.shape[2], int(relu), ptr(x), ptr(seg), ptr(dz), ptr(scale),
+             ptr(shift), ptr(mean), ptr(rstd), ptr(scale), ptr(c1), ptr(c2), ptr(dx), ptr(dseg))
+        return dx, dseg
+
+
+class _BnActSegFn(Function):
+    """_BnActFn for act(bn(x + seg[..., None])), channels-first: the input's gradient and, from the same pass, the addend's
+    (its sums over each segment)."""
+
+    @staticmethod
+    def forward(ctx, x, seg, gamma, beta, mean, rstd, scale, shift, relu, count, group, pre_bias=None):
+        out = _ChannelsFirstSeg.apply_seg(x, seg, relu, scale, shift)
+        ctx.save_for_backward(x, seg, scale, shift, mean, rstd)
+        ctx.cfg = (bool(relu), count, group, pre_bias is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dz):
+        x, seg, scale, shift, mean, rstd = ctx.saved_tensors
+        relu, count, group, has_pre_bias = ctx.cfg
+        dz = _fresh16(dz)
+        coef = _bwd_coef(_ChannelsFirstSeg.bwd_sums_seg(x, seg, dz, relu, scale, shift, mean, rstd), count, group)
+        dx, dseg = _ChannelsFirstSeg.bwd_apply_seg(x, seg, dz, relu, scale, shift, mean, rstd, coef[2], coef[3])
+        g_pre = _pre_bias_grad(scale, coef, count) if has_pre_bias else None
+        return dx, dseg, coef[0], coef[1], None, None, None, None, None, None, None, g_pre
+
+
+def _seg_covered(bn, x, seg):
+    """the geot_bn_*_seg kernels' tensors: what add_last_broadcast covers (fp32, 4 <= n <= 256, n % 4 == 0), 16-byte aligned"""
+    if not (_covered(bn, x) and torch.is_tensor(seg) and seg.is_cuda and seg.dtype == torch.float32 and seg.dim() == 3
+            and seg.shape[:2] == x.shape[:2] and seg.shape[2] > 0 and x.shape[2] % seg.shape[2] == 0):
+        return False
+    n = x.shape[2] // seg.shape[2]
+    return 4 <= n <= 256 and n % 4 == 0
+
+
+def bn_act_seg(bn, x, seg, relu=True, pre_bias=None):
+    """act(bn(x + seg[..., None] (+ pre_bias))) for x (B, C, G n) and a per-(channel, segment) addend seg (B, C, G): the
+    broadcast add in front of the BatchNorm is folded into its four passes, and the addend's gradient (the sums of the
+    input's over each segment) leaves with the backward apply pass.  Tensors the kernels do not cover:
+    add_last_broadcast, then bn_act."""
+    covered = _seg_covered(bn, x, seg)
+    if covered:
+        x, seg = x.contiguous(), seg.contiguous()
+        covered = _aligned16(x)
+    if not covered:
+        b, c, l = x.shape
+        return bn_act(bn, add_last_broadcast(x.reshape(b, c, seg.shape[2], -1), seg).reshape(b, c, l), relu=relu, pre_bias=pre_bias)
+    gamma, beta = _affine(bn, x.shape[1], x.device)
+    stats, count, group = _module_statistics(bn, x, gamma, beta, None, pre_bias, _ChannelsFirstSeg(seg.detach()))
+    return _BnActSegFn.apply(x, seg, gamma, beta, *stats, relu, count, group, pre_bias)
+
+
+class _ThinStage:
+    """The statistics of y = w x, x (J, L), J <= 8, w (C, J), from the J + J^2 moments of x (geot_thin_moments,
+    geot_thin_bn_sums): y is never formed.  `mom` = the moments of the last stat_sums call, for the weight gradient."""
+
+    def __init__(self, w):
+        self.w = w
+        self.mom = None
+
+    def extent(self, x):
+        return self.w.shape[0], x.shape[1]
+
+    def stat_sums(self, x, partial, sums):
+        (c, j), l = self.w.shape, x.shape[1]
+        s = int(_lib.load().geot_thin_moments_slices(l))
+        partial = torch.empty((s, j + j * j), dtype=torch.float64, device=x.device)
+        call("geot_thin_moments", x.device, j, l, ptr(x), ptr(partial))
+        self.mom = torch.empty(2 * j + j * j, dtype=torch.float64, device=x.device)
+        call("geot_thin_bn_sums", x.device, c, j, l, s, ptr(partial), ptr(self.w), ptr(x), ptr(self.mom), ptr(sums))
+
+
+class _ThinBnActFn(Function):
+    """out (C, L) = act(bn(w x)) written straight from x (J, L); backward: ONE pass over dz for the BatchNorm's sums and
+    sum g x_j, the weight gradient finished from those and the moments of x -- the gradient of w x is never written.
+    x gets no gradient here (thin_bn_act sends an x that needs one down the old path)."""
+
+    @staticmethod
+    def forward(ctx, w, x, mom, gamma, beta, mean, rstd, scale, shift, relu, count, group, pre_bias=None):
+        (c, j), l = w.shape, x.shape[1]
+        out = torch.empty((c, l), dtype=torch.float32, device=x.device)
+        b32 = beta.detach().float().contiguous()        # the kernels form (y - mean) scale + beta: `shift` is not used
+        call("geot_thin_bn_apply", x.device, c, j, l, int(relu), ptr(w), ptr(x), ptr(mean), ptr(scale), ptr(b32), ptr(out))
+        ctx.save_for_backward(w, x, mom, scale, b32, mean, rstd)
+        ctx.cfg = (bool(relu), count, group, pre_bias is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, dz):
+        w, x, mom, scale, b32, mean, rstd = ctx.saved_tensors
+        relu, count, group, has_pre_bias = ctx.cfg
+        (c, j), l, dev = w.shape, x.shape[1], x.device
+        dz = dz.contiguous()
+        s = int(_lib.load().geot_thin_bn_bwd_slices(c, l))
+        partial = torch.empty((c, s, 2 + j), dtype=torch.float64, device=dev)
+        call("geot_thin_bn_bwd_reduce", dev, c, j, l, int(relu), ptr(mom if group is None else None), ptr(w), ptr(x), ptr(dz),
+             ptr(scale), ptr(b32), ptr(mean), ptr(rstd), ptr(partial))
+        local = torch.empty((c, 2), dtype=torch.float64, device=dev)
+        gx = torch.empty((c, j), dtype=torch.float64, device=dev)
+        call("geot_thin_bn_bwd_sums", dev, c, j, s, ptr(partial), ptr(local), ptr(gx))
+        coef, sums = _bwd_coef(local, count, group, with_sums=True)
+        dw = torch.empty((c, j), dtype=torch.float32, device=dev)
+        on_dev = torch.is_tensor(count)
+        call("geot_thin_bn_wgrad", dev, c, j, l, int(group is None), ptr(w), ptr(mom), ptr(gx), ptr(sums),
+             0.0 if on_dev else float(count), ptr(count) if on_dev else None, ptr(scale), ptr(mean), ptr(rstd), ptr(dw))
+        g_pre = _pre_bias_grad(scale, coef, count) if has_pre_bias else None
+        return dw, None, None, coef[0], coef[1], None, None, None, None, None, None, None, g_pre
+
+
+def thin_bn_act(bn, w, x, pre_bias=None, relu=True):
+    """act(bn(w @ x (+ pre_bias[:, None]))) -> (C, L) for w (C, J), x (J, L) with J <= 8 input rows that need no gradient
+    (the Encoder's Conv1d(3, 128) -> BatchNorm -> ReLU over the points' coordinates): batch statistics from the J x J second
+    moments of x, the output written straight from x, one backward pass (csrc/bnrelu.hip, "the thin first stage").
+    Anything else -- x needs a gradient, J > 8, CPU, other dtypes: thin_mm, then bn_act."""
+    if not (isinstance(bn, nn.modules.batchnorm._BatchNorm) and w.is_cuda and x.is_cuda and w.dtype == torch.float32
+            and x.dtype == torch.float32 and w.dim() == 2 and x.dim() == 2 and 1 <= x.shape[0] <= 8 and w.shape[0] <= 65535
+            and x.numel() > 0 and not x.requires_grad):
+        return bn_act(bn, thin_mm(w, x).unsqueeze(0), relu=relu, pre_bias=pre_bias).squeeze(0)
+    w, x = w.contiguous(), x.contiguous()
+    gamma, beta = _affine(bn, w.shape[0], x.device)
+    stage = _ThinStage(w.detach())
+    stats, count, group = _module_statistics(bn, x, gamma, beta, None, pre_bias, stage)
+    return _ThinBnActFn.apply(w, x, stage.mom, gamma, beta, *stats, relu, count, group, pre_bias)
 
 
 def _skip_args(skip, wb):

@@ -38,7 +38,7 @@ from .transformer_ops import (Group, fps, fps_downsample, graph_feature, get_gra
 from .geometry import EdgeEntry, FpEntry, Geometry, IndexPlan
 from .... import streams
 from ....ntm import sig_t_mean  # noqa: F401  (transformer.py:1099-1131 lives in ntm.py)
-from ....fused_norm import bn_act, fp_front, fp_front_eligible, max_last, add_last_broadcast, thin_mm, add_channel_bias
+from ....fused_norm import bn_act, fp_front, fp_front_eligible, max_last, add_last_broadcast, thin_mm, add_channel_bias, thin_bn_act
 from ....fused_norm import (fp_front_cl, fp_front_cl_eligible, bn_act_cl, fp_stage_cl, pointwise_to_cl, pointwise_from_cl,
                             local_spatial_order, ReverseIndex)
 from ....fused_norm import linear as lean_linear, res_ln, res_ln_eligible, qkv_split, softmax_last
@@ -272,8 +272,17 @@ class Encoder(nn.Module):
         # BatchNorm goes through bn_act's pre_bias (cancels under batch statistics).  f0, h0 = the tensors without it.
         x = point_groups.reshape(L, 3).t()                                              # (3, L) view
         b1, b2 = self.first_conv[3].bias, self.second_conv[3].bias
-        f0 = conv(self.first_conv[3], norm_act(self.first_conv, conv(self.first_conv[0], x, bias=False),
-                                               self.first_conv[0].bias), bias=False)    # f = f0 + b1: (256, L)
+        # GEOT_ENCODER_FOLD (default on; 0 = the path below it bit for bit): work the result does not need is folded away --
+        # the first stage's (128, L) activation W0 x is never stored (thin_bn_act: statistics from the 3 x 3 moments of x, the
+        # output straight from x, one backward pass); the per-point half of second_conv[0] runs on r with the composite weight
+        # W_f W1b (K = 128 instead of 256: f0 is needed by the max alone); and the broadcast add of W_g pooled goes into the
+        # BatchNorm's passes (bn_act's seg), its gradient leaving with their backward apply pass.
+        fold = os.environ.get("GEOT_ENCODER_FOLD", "1") != "0"
+        if fold:
+            r = thin_bn_act(self.first_conv[1], self.first_conv[0].weight.squeeze(-1), x, self.first_conv[0].bias, relu=True)
+        else:
+            r = norm_act(self.first_conv, conv(self.first_conv[0], x, bias=False), self.first_conv[0].bias)
+        f0 = conv(self.first_conv[3], r, bias=False)                                    # f = f0 + b1: (256, L)
         c1 = f0.shape[0]
         pooled = max_last(f0.view(c1, bs * g, n))                                       # (256, BG), + b1 below
         if b1 is not None:
@@ -287,8 +296,14 @@ class Encoder(nn.Module):
             # (pre * 1.0: the two addends must not receive the SAME gradient tensor -- AccumulateGrad clones a shared one with a
             # device-to-device memcpy, a memcpy node when the step is captured; x1.0 is exact)
             pre = wb if pre is None else pre * 1.0 + wb
-        h = add_last_broadcast(conv(c2, f0, w_f, bias=False).view(-1, bs * g, n), torch.mm(w_g, pooled))
-        h0 = conv(self.second_conv[3], norm_act(self.second_conv, h.view(-1, L), pre), bias=False)  # (C_enc, L)
+        if fold:
+            h_part = torch.mm(torch.mm(w_f, self.first_conv[3].weight.squeeze(-1)), r)  # (W_f W1b) r = W_f f0: (512, L)
+            hr = bn_act(self.second_conv[1], h_part.unsqueeze(0), relu=True, pre_bias=pre,
+                        seg=torch.mm(w_g, pooled).unsqueeze(0)).squeeze(0)
+        else:
+            h = add_last_broadcast(conv(c2, f0, w_f, bias=False).view(-1, bs * g, n), torch.mm(w_g, pooled))
+            hr = norm_act(self.second_conv, h.view(-1, L), pre)
+        h0 = conv(self.second_conv[3], hr, bias=False)                                  # (C_enc, L)
         out = max_last(h0.view(-1, bs * g, n))
         if b2 is not None:
             out = add_channel_bias(out, b2)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 32
+#define GEOT_ABI_VERSION 33
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -222,6 +222,58 @@ int geot_bn_bwd_reduce(int b, int c, int l, int relu, const float *x, const floa
 int geot_bn_bwd_apply(int b, int c, int l, int relu, const float *x, const float *dz, const float *scale,
                       const float *shift, const float *mean, const float *rstd, const float *k0, const float *c1,
                       const float *c2, float *dx, void *stream);
+/* The same four passes over x + seg[.., e / n]: x (b,c,l) with l = G n columns in G segments of n, seg (b,c,G) a
+ * per-(channel, segment) addend that is never added in memory (the Encoder's W_g pooled in front of its second
+ * BatchNorm).  4 <= n <= 256, n % 4 == 0, l % n == 0, every tensor 16-byte aligned; S = geot_bn_slices(b,c,l), a slice
+ * boundary may fall inside a segment.
+ *   geot_bn_stats_seg       the (s1, s2, pivot, count) records of x + seg, as geot_bn_stats
+ *   geot_bn_apply_seg       out = act((x + seg) * scale[c] + shift[c])
+ *   geot_bn_bwd_reduce_seg  partial (b,c,S,2) fp64 = (sum g, sum g xhat) carried in fp64 from the first add, mask and xhat
+ *                           from x + seg; geot_bn_sums_f64 adds them up as geot_bn_sums does the fp32 ones
+ *   geot_bn_bwd_apply_seg   dx as geot_bn_bwd_apply, and dseg (b,c,G) = the sum of dx over each segment (one writer per
+ *                           element, fixed order) */
+int geot_bn_stats_seg(int b, int c, int l, int n, const float *x, const float *seg, float *partial, void *stream);
+int geot_bn_apply_seg(int b, int c, int l, int n, int relu, const float *x, const float *seg, const float *scale,
+                      const float *shift, float *out, void *stream);
+int geot_bn_bwd_reduce_seg(int b, int c, int l, int n, int relu, const float *x, const float *seg, const float *dz,
+                           const float *scale, const float *shift, const float *mean, const float *rstd, double *partial,
+                           void *stream);
+int geot_bn_sums_f64(int b, int c, int s, const double *partial, double *sums, void *stream);
+int geot_bn_bwd_apply_seg(int b, int c, int l, int n, int relu, const float *x, const float *seg, const float *dz,
+                          const float *scale, const float *shift, const float *mean, const float *rstd, const float *k0,
+                          const float *c1, const float *c2, float *dx, float *dseg, void *stream);
+/* relu(bn(W x)) for a thin first stage, x (j,l) with j <= 8 input rows, W (c,j): y = W x is never stored (the Encoder's
+ * Conv1d(3, 128) -> BatchNorm -> ReLU).  y[c][e] = the fp64 dot product w[c] . x[:, e] rounded to fp32, by one device
+ * function in every kernel that forms it, so forward and backward agree on every sign.
+ *   geot_thin_moments        partial (S, j + j j) fp64 per slice of columns (S = geot_thin_moments_slices(l)): sums of
+ *                            x' = x - p and of x' x'^T about the pivot p = x's first column
+ *   geot_thin_bn_sums        mom (2 j + j j) fp64 = p, sum x', sum x' x'^T over all slices; sums (c,2) fp64 = (sum y,
+ *                            sum y^2) rebuilt from w mom about q = w p, the input of geot_bn_finalize
+ *   geot_thin_bn_apply       out (c,l) = act((y - mean[c]) * scale[c] + beta[c])
+ *   geot_thin_bn_bwd_reduce  partial (c, S', 2 + j) fp64 = per slice (S' = geot_thin_bn_bwd_slices(c,l)) sum g, sum g xhat,
+ *                            sum g x_j (all carried in fp64), g = dz masked by [(y - mean) scale + beta > 0] when relu; xhat of
+ *                            the sums from the unrounded y, about the exact mean w (p + sum x' / l) when mom is given
+ *                            (the statistics were this rank's alone), else (NULL) about mean[c]
+ *   geot_thin_bn_bwd_sums    local (c,2) fp64 = sum g, sum g xhat (the input of geot_bn_bwd_coef); gx (c,j) fp64 = sum g x_j
+ *   geot_thin_bn_wgrad       dw (c,j) = scale[c] (gx - c1[c] sum x_j - c2[c] sum xhat x_j) in fp64: c1, c2 = sums / n, sums
+ *                            (c,2) fp64 = the (all-reduced) sum g, sum g xhat, n = count_dev ? *count_dev : count; the
+ *                            sums over x from mom; xhat about the exact mean w (p + sum x' / l) when local_mean (the
+ *                            statistics were this rank's alone), else about mean[c].  mom NULL or n == 0 (running
+ *                            statistics): dw = scale gx */
+int geot_thin_moments_slices(int l);
+int geot_thin_moments(int j, int l, const float *x, double *partial, void *stream);
+int geot_thin_bn_sums(int c, int j, int l, int s, const double *partial, const float *w, const float *x, double *mom,
+                      double *sums, void *stream);
+int geot_thin_bn_apply(int c, int j, int l, int relu, const float *w, const float *x, const float *mean, const float *scale,
+                       const float *beta, float *out, void *stream);
+int geot_thin_bn_bwd_slices(int c, int l);
+int geot_thin_bn_bwd_reduce(int c, int j, int l, int relu, const double *mom, const float *w, const float *x, const float *dz,
+                            const float *scale, const float *beta, const float *mean, const float *rstd, double *partial,
+                            void *stream);
+int geot_thin_bn_bwd_sums(int c, int j, int s, const double *partial, double *local, double *gx, void *stream);
+int geot_thin_bn_wgrad(int c, int j, int l, int local_mean, const float *w, const double *mom, const double *gx,
+                       const double *sums, double count, const double *count_dev, const float *scale, const float *mean,
+                       const float *rstd, float *dw, void *stream);
 /* Residual add + LayerNorm of the transformer blocks (transformer.py:41-104: x + drop_path(branch), then norm; the
  * position embedding added between blocks, :395-400) as one pass each way over row-major (rows, c) tensors,
  * c in {128, 256, 384, 512, 768, 1024} (geot_res_ln_supported):
