@@ -7,6 +7,7 @@ interpolation hot path behind the reference's operator API.
     import geot_amd.aliases; geot_amd.aliases.install()     # reference import names -> this package
     from geot_amd import fit, train_one_epoch, epoch_batches, LrSchedule      # the training driver (fit.py, schedule.py)
     from geot_amd import ToothScores, tooth_scores_from_moments, tooth_instances     # the Teeth3DS challenge scores (validation.py)
+    from geot_amd import clean_scans, scan_components, scan_neighbours, teeth3ds_result  # connected teeth, the challenge's result
 
 The compute path is libgeot_hip.so (C ABI in include/geot_hip.h); there is no CPU fallback.
 """
@@ -51,7 +52,9 @@ def graph_replay_is_safe():
 # The training driver's names, bound on first use (importing the package itself imports nothing else: the switch above has to
 # be set before anything touches HIP).  `fit` needs no entry: geot_amd.fit is the module, and the module is callable.
 _EXPORTS = {"train_one_epoch": "fit", "epoch_batches": "fit", "LrSchedule": "schedule",
-            "ToothScores": "validation", "tooth_scores_from_moments": "validation", "tooth_instances": "validation"}
+            "ToothScores": "validation", "tooth_scores_from_moments": "validation", "tooth_instances": "validation",
+            "clean_scans": "validation", "scan_components": "validation", "scan_neighbours": "validation",
+            "teeth3ds_result": "validation"}
 
 
 def __getattr__(name):

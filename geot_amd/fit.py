@@ -231,7 +231,7 @@ def _val_teeth3ds(cfg):
 
 
 def fit(step, batcher, cfg, val=None, test=None, ckpt_dir=None, resume=None, log=logging.info, draws=None, generator=None,
-        prior=True, graph=False, lookahead=0, refine=0, parts=None, val_stream=None):
+        prior=True, graph=False, lookahead=0, refine=0, parts=None, val_stream=None, islands=None):
     """Train `step` over `batcher` for the configured epochs -> {"epoch", "best", "best_epoch", "records", "schedule", "generator"}.
 
     step / batcher: as train_one_epoch takes them.  cfg (a dict or an object with attributes): epochs, start_epoch (1),
@@ -246,9 +246,10 @@ def fit(step, batcher, cfg, val=None, test=None, ckpt_dir=None, resume=None, log
     step.cm in place; False keeps what the step holds.
     val: a DeviceScanSet (or a ValBatcher / VoteBatcher on one).  Every val_freq epochs and at the last one the STUDENT
     (step.model) runs validation.validate_scans -- validate_scans_voted when cfg.num_votes > 0 -- with graph / lookahead /
-    refine / parts / val_stream passed through, and the training run's random streams are put back (_protected): a run with
-    validation trains to the bits of a run without.  cfg.val_whole (_val_whole; ValueError before the first epoch for
-    an unknown value): "interp" (default) is that, "covered" runs validate_scans_covered, "decoded" validate_scans_decoded.
+    refine / parts / val_stream / islands passed through (islands: validation.clean_scans behind the refinement -- None / False:
+    off, True or a dict of its keyword arguments; anything else is a ValueError before the first epoch), and the training
+    run's random streams are put back (_protected): a run with validation trains to the bits of a run without.  cfg.val_whole
+    (_val_whole; ValueError before the first epoch for an unknown value): "interp" (default) is that, "covered" runs validate_scans_covered, "decoded" validate_scans_decoded.
     cfg.val_teeth3ds (a bool, default False; ValueError before the first epoch for anything else): the validation's final
     labels also go through a validation.ToothScores, the record gains val_tsa, val_tsa_instance, val_tla, val_tir and val_score
     (the 3DTeethSeg challenge's scores) and one more line is logged; "best" and the checkpoints are untouched.  "Best" is the
@@ -271,6 +272,8 @@ def fit(step, batcher, cfg, val=None, test=None, ckpt_dir=None, resume=None, log
     num_votes = int(_cfg(cfg, "num_votes", 0) or 0)
     val_whole = _val_whole(cfg, num_votes, graph, lookahead)       # an unknown value: ValueError before anything is touched
     val_teeth = _val_teeth3ds(cfg)
+    from . import validation
+    islands = validation._islands_kw(islands, "fit")              # a bad value: ValueError here, before the first epoch
     inner = _inner(step)
     fixmatch = _is_fixmatch(step)
     if fixmatch and (_cfg(cfg, "supervised_epochs", 0) or 0) > 0:
@@ -313,9 +316,10 @@ def fit(step, batcher, cfg, val=None, test=None, ckpt_dir=None, resume=None, log
 
     def score(scans, epoch, teeth=False):
         """-> validate()'s three-tuple; with teeth (macc, miou, mdsc, the dict of ToothScores.read())."""
-        from . import validation
         vcfg = dict(val_cfg, epoch=epoch, epochs=epochs, num_votes=num_votes)
         kw = dict(batch_size=int(_cfg(cfg, "batch_size_val", 2) or 2), stream=val_stream, refine=refine, parts=parts)
+        if islands is not None:
+            kw["islands"] = islands
         if teeth:
             kw["teeth"] = validation.ToothScores(val_cfg.get("num_classes", 17), scans.device)
         if val_whole == "interp":

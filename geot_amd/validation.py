@@ -78,6 +78,16 @@ batch, integers only; every validator takes teeth= and sends each batch's final 
     teeth.update(preds, batch)                               # any labels predict_scans / vote_scans / ... returned
     geo = tooth_instances(preds, batch, num_classes)         # per scan and class: predicted count, centroid, box (device tensors)
 
+Connected teeth -- one FDI class in one jaw is one tooth, one connected patch of the surface, and nothing above enforces it:
+every path labels each vertex on its own.  geot_scan_islands (csrc/scan_islands.hip: a lock-free union-find over a neighbour
+table of the whole scan, six launches per batch, integers only) splits the labels into connected pieces and hands every stray
+piece -- too small, of a class the jaw does not allow, or not the largest of its class -- to the label that surrounds it:
+
+    preds = clean_scans(preds, batch, min_size=10, keep_largest=True, parts=cls2parts)   # in place, the same views
+    comp = scan_components(preds, batch)                     # per vertex the first vertex of its piece
+    preds = predict_scans(logits, batch, islands=True)       # also vote_scans, cover_scans, decode_scans, the validators, fit()
+    result = teeth3ds_result(preds[0], comp[0], "lower")     # the challenge's labels (FDI) + instances, on the host
+
 Look-ahead and replay -- validate_scans, validate_scans_voted and vote_scans with lookahead=G / graph=True (off by default):
 up to G passes are drawn ahead (the same batch() calls in the same order), their coordinate-only work runs as one
 prefetch_geometry over the concatenated positions beside the forward pass in flight (pass_schedule, _passes), and with graph
@@ -280,15 +290,18 @@ def _scan_launch(logits, batch, num_classes, what, counts=None, want_pred=False,
 
 
 @torch.no_grad()
-def predict_scans(logits, batch, refine=0, parts=None):
+def predict_scans(logits, batch, refine=0, parts=None, islands=None):
     """The per-vertex labels of the batch's whole scans: list of (1, M_i) int64 tensors (views of one buffer), equal to
     get_pred_whole(logits, batch["pos"], batch["points"], batch["center"], batch["scale"]).  logits (B, C, N) fp32 on the
     scans' device, batch from ValBatcher.batch.  One geot_scan_predict call, no host synchronisation.  refine (0: off, True:
-    n = 10, an int: n) and parts: the labels then go through refine_scans."""
+    n = 10, an int: n) and parts: the labels then go through refine_scans.  islands (None / False: off, True: clean_scans'
+    defaults, a dict: its keyword arguments; anything else is a ValueError before any device call): the labels then, after
+    refine, go through clean_scans."""
     n_refine = _refine_n(refine, "predict_scans")
+    islands = _islands_kw(islands, "predict_scans")
     need(torch.is_tensor(logits) and logits.dim() == 3, "predict_scans: logits must be a (B, C, N) tensor")
     preds = _scan_launch(logits, batch, logits.shape[1], "predict_scans", want_pred=True)
-    return refine_scans(preds, batch, n_refine, parts, num_classes=logits.shape[1]) if n_refine else preds
+    return _finish_labels(preds, batch, n_refine, parts, islands, logits.shape[1])
 
 
 def _allowed_masks(parts, jaws, c, what):
@@ -395,6 +408,222 @@ def part_seg_refinement(pred, pos, cls, cls2parts, n=10):
     ids = _to_device(np.arange(bsz, dtype=np.int64), dev)
     _scan_refine(pred.view(-1), n, c, pos.contiguous().view(-1, 3), offsets, ids, bsz, offsets[:bsz], allowed, bsz, False)
     return pred
+
+
+# ---- connected pieces of whole-scan labels, stray islands relabelled (csrc/scan_islands.hip) ----------------------------------------
+ISLANDS_MAX_K = 32                  # include/geot_hip.h geot_scan_islands: entries per row of the neighbour table
+_CLEAN_KEYS = ("min_size", "keep_largest", "parts", "nbr", "k", "num_classes")
+
+
+def _clean_args(min_size, keep_largest, k, what, error=RuntimeError):
+    """clean_scans' host-only arguments -> (min_size, keep: True or a sorted tuple of classes, k)."""
+    def refuse(msg):
+        raise error("%s: %s" % (what, msg))
+    if isinstance(min_size, bool) or not isinstance(min_size, (int, np.integer)) or int(min_size) < 0:
+        refuse("min_size must be an int >= 0, got %r" % (min_size,))
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= ISLANDS_MAX_K - 1:
+        refuse("k must be an int in 1..%d (the table holds k + 1 entries per vertex), got %r" % (ISLANDS_MAX_K - 1, k))
+    if isinstance(keep_largest, bool):
+        keep = keep_largest
+    else:
+        try:
+            keep = tuple(sorted(set(keep_largest)))
+        except TypeError:
+            refuse("keep_largest must be a bool or an iterable of classes, got %r" % (keep_largest,))
+        if not all(isinstance(i, (int, np.integer)) and not isinstance(i, bool) and 0 <= int(i) < _lib.NTM_MAX_C for i in keep):
+            refuse("keep_largest must name classes in [0, %d), got %r" % (_lib.NTM_MAX_C, keep_largest))
+        keep = tuple(int(i) for i in keep)
+    return int(min_size), keep, int(k)
+
+
+def _islands_kw(islands, what):
+    """The `islands` keyword of predict_scans, vote_scans, cover_scans, decode_scans, the validators and fit(), checked before
+    any device call -> None (off: None or False) or the keyword arguments of clean_scans (True: {}, the defaults; a dict: its
+    items).  Anything else, an unknown key or a value clean_scans would refuse on the host: ValueError."""
+    if islands is None or islands is False:
+        return None
+    if islands is True:
+        return {}
+    if not isinstance(islands, dict):
+        raise ValueError("%s: islands must be None, a bool or a dict of clean_scans' keyword arguments, got %r" % (what, islands))
+    unknown = sorted(str(key) for key in islands if key not in _CLEAN_KEYS)
+    if unknown:
+        raise ValueError("%s: islands has no keyword %s (clean_scans takes %s)" % (what, ", ".join(unknown), ", ".join(_CLEAN_KEYS)))
+    _clean_args(islands.get("min_size", 10), islands.get("keep_largest", True), islands.get("k", 8), what + ": islands", ValueError)
+    return dict(islands)
+
+
+def _islands_batch(preds, batch, what):
+    """The checks clean_scans, scan_components and scan_neighbours share with refine_scans -> (scans, sizes, b, dev)."""
+    need(isinstance(batch, dict) and all(key in batch for key in ("scan_ids", "scans", "sizes")),
+         "%s: batch must come from ValBatcher.batch (scan_ids, scans, sizes)" % what)
+    scans, sizes = batch["scans"], [int(m) for m in batch["sizes"]]
+    b = len(sizes)
+    need(1 <= b <= SCAN_MAX_SLOTS, "%s: 1 .. %d scans per batch" % (what, SCAN_MAX_SLOTS))
+    if preds is not None:
+        need(isinstance(preds, (list, tuple)) and len(preds) == b, "%s: one prediction tensor per scan of the batch" % what)
+        for p, m in zip(preds, sizes):
+            need(torch.is_tensor(p) and p.dtype == torch.int64, "%s: the predictions must be int64 tensors" % what)
+            need(p.numel() == m, "%s: %d predictions for a scan of %d vertices" % (what, p.numel(), m))
+    dev = scans.device
+    if preds is not None:
+        need(all(p.is_cuda and p.device == dev for p in preds), "%s: CPU not supported (the predictions must live on %s, with "
+             "the scans)" % (what, dev))
+    need(torch.is_tensor(batch["scan_ids"]) and batch["scan_ids"].device == dev and batch["scan_ids"].dtype == torch.int64 and
+         tuple(batch["scan_ids"].shape) == (b,), "%s: batch scan_ids must be (B,) int64 on %s" % (what, dev))
+    return scans, sizes, b, dev
+
+
+def _scan_rows(batch, sizes, dev):
+    """Per slot the (M_s, 3) fp32 vertices of its scan: the batcher's zero-copy views when the batch carries them (read in
+    place), else gathered from the set on the device by the slots' scan ids.  No synchronisation either way."""
+    scans = batch["scans"]
+    views = batch.get("points")
+    if (isinstance(views, (list, tuple)) and len(views) == len(sizes) and
+            all(torch.is_tensor(p) and p.device == dev and p.dtype == torch.float32 and tuple(p.shape) == (m, 3) and p.is_contiguous()
+                for p, m in zip(views, sizes))):
+        return list(views)
+    b, total = len(sizes), sum(sizes)
+    slot = torch.repeat_interleave(torch.arange(b, device=dev), _to_device(np.asarray(sizes, dtype=np.int64), dev), output_size=total)
+    first = scans.offsets[batch["scan_ids"]] - _out_offsets(sizes, dev)
+    return list(torch.split(scans.points[first[slot] + torch.arange(total, device=dev)], sizes))
+
+
+@torch.no_grad()
+def scan_neighbours(batch, k=8):
+    """The neighbour table of the batch's whole scans: (sum M, k + 1) int32 on the device, slot after slot -- per vertex its
+    k + 1 nearest vertices of the same scan as indices local to the scan, itself included, in geot_knn_sorted's (d2, index)
+    order.  One geot_knn_sorted_ws call per slot (b = 1, nq = nr = M_s; the grid search at whole-scan sizes) on the scan's rows
+    of scans.points, read in place from the batcher's views; the sizes are the host's.  A scan of fewer than k + 1 vertices is
+    refused, so the table never holds the search's filler.  Nothing is cached: a scan met again is searched again."""
+    scans, sizes, b, dev = _islands_batch(None, batch, "scan_neighbours")
+    _, _, k = _clean_args(0, False, k, "scan_neighbours")
+    for m in sizes:
+        if m < k + 1:
+            raise ValueError("scan_neighbours: a scan of %d vertices has no %d nearest vertices (k + 1)" % (m, k + 1))
+    need(scans.points.is_cuda, "scan_neighbours: CPU not supported (the scans must live on the GPU)")
+    rows = _scan_rows(batch, sizes, dev)
+    nbr = torch.empty((sum(sizes), k + 1), dtype=torch.int32, device=dev)
+    dist2 = torch.empty((max(sizes), k + 1), dtype=torch.float32, device=dev)       # the search writes it; nobody reads it
+    at = 0
+    for p, m in zip(rows, sizes):
+        wp, wb, _keep = knn_workspace(dev, 1, m, m, k + 1)
+        call("geot_knn_sorted_ws", dev, 1, m, m, k + 1, ptr(p), ptr(p), ptr(nbr) + 4 * (k + 1) * at, ptr(dist2), wp, wb)
+        at += m
+    return nbr
+
+
+def _scan_islands(flat, nbr, c, min_size, keep, allowed, batch, sizes, b, dev, want_comp, want_stats):
+    """One geot_scan_islands call on the flat int64 label buffer; keep / allowed: host uint32 arrays or None."""
+    scans = batch["scans"]
+    need(torch.is_tensor(nbr) and nbr.device == dev and nbr.dtype == torch.int32 and nbr.dim() == 2 and nbr.is_contiguous() and
+         nbr.shape[0] == sum(sizes) and 1 <= nbr.shape[1] <= ISLANDS_MAX_K,
+         "geot_scan_islands: nbr must be a contiguous (%d, 1..%d) int32 tensor on %s" % (sum(sizes), ISLANDS_MAX_K, dev))
+    keep = _to_device(keep.view(np.int32), dev) if keep is not None else None
+    allowed = _to_device(allowed.view(np.int32), dev) if allowed is not None else None
+    nbytes = int(_lib.load().geot_scan_islands_ws_bytes(b, int(flat.numel()), c))
+    need(nbytes >= 0, "geot_scan_islands: no workspace for b = %d, c = %d, %d labels" % (b, c, flat.numel()))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    comp = torch.empty(flat.numel(), dtype=torch.int32, device=dev) if want_comp else None
+    stats = torch.empty((b, 4), dtype=torch.int32, device=dev) if want_stats else None
+    call("geot_scan_islands", dev, b, c, int(nbr.shape[1]), min(min_size, MAX_VERTICES), len(scans), int(scans.points.shape[0]), ptr(scans.offsets),
+         ptr(batch["scan_ids"].contiguous()), ptr(_out_offsets(sizes, dev)), ptr(nbr), ptr(keep), ptr(allowed), ptr(flat), ptr(comp),
+         ptr(stats), ptr(ws), nbytes)
+    return comp, stats
+
+
+@torch.no_grad()
+def scan_components(preds, batch, nbr=None, k=8, num_classes=None, stats=False):
+    """The connected pieces of whole-scan labels: per scan of the batch a (1, M_i) int32 tensor (views of one buffer) that
+    holds for every vertex the lowest vertex index of its piece -- the vertices of equal label it reaches through the
+    neighbour table.  preds as predict_scans and its kin return them; they are not touched.  nbr: scan_neighbours' table, or
+    any (sum M, 1..32) int32 table of scan-local indices (default: scan_neighbours(batch, k)).  A label outside [0, C) is a
+    piece of its own.  num_classes: default 32.  stats=True: also the (B, 4) int32 device tensor of geot_scan_islands (pieces
+    among the labels in [0, C), then three zeros).  One geot_scan_islands call in its components-only form (four launches),
+    no host synchronisation."""
+    scans, sizes, b, dev = _islands_batch(preds, batch, "scan_components")
+    c = _need_classes(32 if num_classes is None else num_classes, "scan_components")
+    if nbr is None:
+        nbr = scan_neighbours(batch, k)
+    flat, _ = _flat_labels(preds, sizes, dev)
+    comp, st = _scan_islands(flat, nbr, c, 0, None, None, batch, sizes, b, dev, True, stats)
+    out = [q.view(1, -1) for q in torch.split(comp, sizes)]
+    return (out, st) if stats else out
+
+
+@torch.no_grad()
+def clean_scans(preds, batch, min_size=10, keep_largest=True, parts=None, nbr=None, k=8, stats=False, num_classes=None):
+    """One FDI class in one jaw is one tooth, one connected patch of the surface: preds as predict_scans / vote_scans /
+    cover_scans / decode_scans return them -- per scan of the batch a (1, M_i) int64 tensor -- cleaned IN PLACE when they are
+    views of one buffer, slot after slot (a list that is not is concatenated and split again); returns the list, with
+    stats=True (list, (B, 4) int32 device tensor of pieces, islands, changed vertices, vertices of stranded islands per scan).
+    Per scan the labels fall into connected pieces over the neighbour table (scan_components).  A piece is an island when it
+    has fewer than min_size vertices, when parts does not allow its class for the scan's jaw, or when its class is kept to one
+    piece and it is not the largest (the lowest first vertex among equals); every island takes the label most of its
+    vertices' neighbours carry, counting only neighbours of another class that are in no island (the lowest label among
+    equals), and stays as it is when there is none.  One pass on the labels as they came in.
+    keep_largest: True -- every class from 1 up; class 0, the gingiva, may lie in pieces and is never kept to one -- or an
+    iterable of classes, or False.  parts: None or the reference's cls2parts, as for refine_scans.  nbr, k: as for
+    scan_components.  num_classes: default parts[-1][-1] + 1, 32 without parts.  One geot_scan_islands call (six launches)
+    behind the table's searches, no host synchronisation."""
+    min_size, keep, k = _clean_args(min_size, keep_largest, k, "clean_scans")
+    scans, sizes, b, dev = _islands_batch(preds, batch, "clean_scans")
+    if num_classes is None:
+        num_classes = 32 if parts is None else int(parts[-1][-1]) + 1
+    c = _need_classes(num_classes, "clean_scans")
+    allowed = None
+    if parts is not None:
+        need("mandible" in batch and len(batch["mandible"]) == b, "clean_scans: parts needs the batch's jaw flags (mandible)")
+        allowed = _allowed_masks(parts, [0 if m else 1 for m in batch["mandible"]], c, "clean_scans")
+    classes = range(1, c) if keep is True else () if keep is False else keep
+    need(all(i < c for i in classes), "clean_scans: keep_largest must name classes in [0, %d)" % c)
+    mask = sum(1 << i for i in classes)
+    keep_masks = np.full(b, mask, dtype=np.uint32) if mask else None
+    if nbr is None:
+        nbr = scan_neighbours(batch, k)
+    flat, views = _flat_labels(preds, sizes, dev)
+    out = list(preds) if views else [f.view(p.shape) for f, p in zip(torch.split(flat, sizes), preds)]
+    _, st = _scan_islands(flat, nbr, c, min_size, keep_masks, allowed, batch, sizes, b, dev, False, stats)
+    return (out, st) if stats else out
+
+
+def _finish_labels(preds, batch, n_refine, parts, islands, c):
+    """The tail of every label-returning call: refine_scans when refine is on, then clean_scans when islands is."""
+    if n_refine:
+        preds = refine_scans(preds, batch, n_refine, parts, num_classes=c)
+    if islands is not None:
+        preds = clean_scans(preds, batch, **dict({"num_classes": c}, **islands))
+    return preds
+
+
+FDI_FIRST = {"lower": (31, 41), "upper": (11, 21)}      # the FDI number of classes 1 and 9 per jaw (the dataset's label2id, inverted)
+
+
+def teeth3ds_result(labels, comp, jaw, patient=None):
+    """The 3DTeethSeg challenge's result dict of one scan, on the host: {"id_patient", "jaw", "labels", "instances"}.
+    labels (M,) the scan's classes 0 .. 16 and comp (M,) scan_components' output ON THOSE LABELS (after clean_scans), as
+    tensors (one device-to-host copy for both) or arrays; jaw "lower" or "upper".  "labels" are FDI numbers, the inverse of
+    the dataset's label2id for that jaw -- lower: 1..8 -> 31..38, 9..16 -> 41..48; upper: 1..8 -> 11..18, 9..16 -> 21..28;
+    0 -> 0 -- and "instances" is 0 for the gingiva and 1, 2, ... for the connected pieces of teeth by ascending first vertex:
+    a class that lies in two pieces is two instances.  Both are lists of M ints."""
+    if jaw not in FDI_FIRST:
+        raise ValueError("teeth3ds_result: jaw must be 'lower' or 'upper', got %r" % (jaw,))
+    if torch.is_tensor(labels) and torch.is_tensor(comp):
+        need(labels.numel() == comp.numel(), "teeth3ds_result: %d labels and %d components" % (labels.numel(), comp.numel()))
+        both = torch.stack([labels.reshape(-1).to(torch.int64), comp.reshape(-1).to(torch.int64)]).cpu().numpy()
+        lab, cmp_ = both[0], both[1]
+    else:
+        lab = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels).reshape(-1).astype(np.int64)
+        cmp_ = np.asarray(comp.cpu() if torch.is_tensor(comp) else comp).reshape(-1).astype(np.int64)
+        need(lab.size == cmp_.size, "teeth3ds_result: %d labels and %d components" % (lab.size, cmp_.size))
+    need(lab.size == 0 or (lab.min() >= 0 and lab.max() <= 16), "teeth3ds_result: labels must lie in 0 .. 16")
+    first, second = FDI_FIRST[jaw]
+    fdi = np.where(lab == 0, 0, np.where(lab <= 8, first - 1 + lab, second - 9 + lab))
+    tooth = lab > 0
+    roots = np.unique(cmp_[tooth])                      # ascending
+    instances = np.zeros(lab.size, dtype=np.int64)
+    instances[tooth] = np.searchsorted(roots, cmp_[tooth]) + 1
+    return {"id_patient": patient, "jaw": jaw, "labels": fdi.tolist(), "instances": instances.tolist()}
 
 
 def _mandible_flags(cls, b):
@@ -788,11 +1017,12 @@ def _passes(model, batcher, groups, repeats, draws, lookahead=0, graphed=None, r
 
 
 def _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_refine, parts, what, lookahead=0, graphed=None,
-              teeth=None):
+              teeth=None, islands=None):
     """The body of validate_scans (num_votes = 0: one pass per batch, scored by geot_scan_predict) and validate_scans_voted
     (num_votes passes per batch, summed by geot_scan_vote and scored on the last): batches of batch_size scans in `indices`'
     order through _passes, counted into one SegMetrics; with n_refine the labels are taken, refined and counted instead.
-    teeth (a ToothScores): the call that counts also writes the labels, and every batch's final labels go through teeth.update."""
+    teeth (a ToothScores): the call that counts also writes the labels, and every batch's final labels go through teeth.update.
+    islands (_islands_kw's dict or None): as n_refine, the labels are taken, cleaned behind the refinement and counted."""
     need(int(batch_size) >= 1, "%s: batch_size >= 1" % what)
     _need_teeth(teeth, c, batcher.device, what)
     order = list(range(len(batcher))) if indices is None else [int(i) for i in indices]
@@ -804,10 +1034,10 @@ def _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_r
             votes = ScanVotes(data, c)
         if not last:
             votes.add(logits, data)
-        elif n_refine:
+        elif n_refine or islands is not None:
             preds = (votes.add(logits, data, last=True, want_pred=True) if num_votes else
                      _scan_launch(logits, data, c, what, want_pred=True))
-            preds = _count_refined(metrics, preds, data, n_refine, parts)
+            preds = _count_refined(metrics, preds, data, n_refine, parts, islands)
         elif num_votes:
             preds = metrics.update_from_votes(votes, logits, data, want_pred=teeth is not None)
         else:
@@ -819,7 +1049,7 @@ def _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_r
 
 @torch.no_grad()
 def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, num_votes=0, data_transform=None, refine=0,
-                   parts=None, graph=False, lookahead=0, teeth=None):
+                   parts=None, graph=False, lookahead=0, teeth=None, islands=None):
     """validate() without a loader: scans a DeviceScanSet (or a ValBatcher built on one, reused from epoch to epoch),
     batches of batch_size scans in the sequential sampler's order (the last, shorter batch is kept: drop_last is false for
     `val`), or of the scans `indices` names (a rank's shard).  cfg.num_points sizes the sample, cfg.num_classes (default
@@ -830,9 +1060,12 @@ def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, n
     (_replay_switches, _passes): the passes' geometry computed ahead and the forward passes replayed from hipGraphs -- the
     same values; off by default.  teeth: a ToothScores (None: off, and every call is as without the keyword) -- each batch's
     final labels, after refine where that is on, also go through teeth.update; geot_scan_predict then writes the labels in the
-    call that counts them.  The return value stays the three-tuple: the caller reads teeth.read()."""
+    call that counts them.  The return value stays the three-tuple: the caller reads teeth.read().  islands (None / False: off,
+    and every call is as without the keyword; True or a dict: predict_scans' keyword): the labels are taken, cleaned
+    (clean_scans) behind the refinement, and counted with geot_seg_confusion; teeth sees the cleaned labels."""
     from .openpoints.dataset.val_batch import ValBatcher
     n_refine = _refine_n(refine, "validate_scans")
+    islands = _islands_kw(islands, "validate_scans")
     lookahead, graphed = _replay_switches(graph, lookahead, 0, model, "validate_scans")
     model.eval()
     c = _cfg(cfg, "num_classes", 17)
@@ -843,7 +1076,7 @@ def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, n
         need(_cfg(cfg, "num_points") is not None, "validate_scans: cfg.num_points (the sample size) is missing")
         batcher = ValBatcher(scans, _cfg(cfg, "num_points"), c, stream=stream)
     return _validate(model, batcher, cfg, c, batch_size, indices, 0, None, n_refine, parts, "validate_scans", lookahead, graphed,
-                     teeth)
+                     teeth, islands)
 
 
 def _scan_labels(batch):
@@ -858,10 +1091,10 @@ def _scan_labels(batch):
     return list(torch.split(scans.labels[index].to(torch.int64), sizes))
 
 
-def _count_refined(metrics, preds, batch, n, parts):
-    """The validators' refine leg: refine the batch's per-vertex labels and count them against the scans' labels
-    -> the refined labels."""
-    preds = refine_scans(preds, batch, n, parts, num_classes=metrics.c)
+def _count_refined(metrics, preds, batch, n, parts, islands=None):
+    """The validators' refine / islands leg: refine (n > 0) and clean (islands: _islands_kw's dict) the batch's per-vertex
+    labels and count them against the scans' labels -> the final labels."""
+    preds = _finish_labels(preds, batch, n, parts, islands, metrics.c)
     metrics.update(preds, _scan_labels(batch), [0 if m else 1 for m in batch["mandible"]])
     return preds
 
@@ -905,14 +1138,15 @@ class ScanVotes:
 
 
 @torch.no_grad()
-def vote_scans(model, batcher, idx, num_votes, draws=None, refine=0, parts=None, graph=False, lookahead=0):
+def vote_scans(model, batcher, idx, num_votes, draws=None, refine=0, parts=None, graph=False, lookahead=0, islands=None):
     """The voted per-vertex labels of the scans `idx` of a VoteBatcher's set: list of (1, M_i) int64 tensors, as predict_scans
     returns them.  num_votes model passes, each on a freshly drawn batch of the same scans (draws: a DeviceDraws for these
     batches; default: the batcher's); the next batch is built beside the forward pass when the batcher has a side stream.
     refine (0: off, True: n = 10, an int: n) and parts: the voted labels then go through refine_scans.  graph, lookahead: as
-    for validate_scans; lookahead=True runs ONE geometry call for all num_votes passes."""
+    for validate_scans; lookahead=True runs ONE geometry call for all num_votes passes.  islands: as for predict_scans."""
     need(int(num_votes) >= 1, "vote_scans: num_votes >= 1")
     n_refine = _refine_n(refine, "vote_scans")
+    islands = _islands_kw(islands, "vote_scans")
     lookahead, graphed = _replay_switches(graph, lookahead, int(num_votes), model, "vote_scans")
     model.eval()
     votes = preds = None
@@ -920,12 +1154,12 @@ def vote_scans(model, batcher, idx, num_votes, draws=None, refine=0, parts=None,
         if first:
             votes = ScanVotes(data, logits.shape[1])
         preds = votes.add(logits, data, last=last, want_pred=last)
-    return refine_scans(preds, data, n_refine, parts, num_classes=votes.c) if n_refine else preds
+    return _finish_labels(preds, data, n_refine, parts, islands, votes.c)
 
 
 @torch.no_grad()
 def validate_scans_voted(model, scans, cfg, num_votes=None, vote=None, batch_size=2, indices=None, stream=None, draws=None,
-                         refine=0, parts=None, graph=False, lookahead=0, teeth=None):
+                         refine=0, parts=None, graph=False, lookahead=0, teeth=None, islands=None):
     """validate_scans with votes: every batch of scans runs through the model num_votes times, each time freshly sampled and
     under the `vote` transform list, and is scored on the arg-max of the summed whole-scan probabilities.  scans: a
     DeviceScanSet, or a VoteBatcher built on one.  num_votes defaults to cfg.num_votes, vote to cfg.datatransforms.vote when
@@ -934,9 +1168,10 @@ def validate_scans_voted(model, scans, cfg, num_votes=None, vote=None, batch_siz
     the current forward pass.  Same log lines, return value and dtypes as validate().  refine, parts: as for validate_scans,
     on the voted labels.  graph, lookahead: as for validate_scans; lookahead=True draws a group's num_votes passes at once
     and runs one geometry call for them.  teeth: as for validate_scans, on the voted labels (the last geot_scan_vote call writes
-    them beside the counts)."""
+    them beside the counts).  islands: as for validate_scans, on the voted labels."""
     from .openpoints.dataset.vote_batch import DEFAULT_VOTE, TOOTH_VIEW_KWARGS, VoteBatcher
     n_refine = _refine_n(refine, "validate_scans_voted")
+    islands = _islands_kw(islands, "validate_scans_voted")
     num_votes = _cfg(cfg, "num_votes", 0) if num_votes is None else num_votes
     if num_votes is None or int(num_votes) < 1:
         raise ValueError("validate_scans_voted: num_votes must be >= 1, got %r (validate_scans is the un-voted call)" % (num_votes,))
@@ -957,7 +1192,7 @@ def validate_scans_voted(model, scans, cfg, num_votes=None, vote=None, batch_siz
         batcher = VoteBatcher(scans, _cfg(cfg, "num_points"), c, vote=DEFAULT_VOTE if vote is None else vote,
                               kwargs=TOOTH_VIEW_KWARGS if kwargs is None else kwargs, stream=stream, draws=draws)
     return _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_refine, parts, "validate_scans_voted",
-                     lookahead, graphed, teeth)
+                     lookahead, graphed, teeth, islands)
 
 
 class ScanCover:
@@ -1050,7 +1285,8 @@ def _cover_run(model, batcher, idx, rounds, interpolate, draws, graph, lookahead
 
 
 @torch.no_grad()
-def cover_scans(model, batcher, idx, rounds=1, interpolate=False, draws=None, refine=0, parts=None, graph=False, lookahead=0):
+def cover_scans(model, batcher, idx, rounds=1, interpolate=False, draws=None, refine=0, parts=None, graph=False, lookahead=0,
+                islands=None):
     """The per-vertex labels of the scans `idx` of a ValBatcher's or VoteBatcher's set from covering passes: list of (1, M_i)
     int64 tensors, as predict_scans returns them.  P = cover_passes(sizes, m) model passes per round whose samples partition
     every scan (batcher.cover), so each vertex takes the arg-max of the probabilities the model produced for that very vertex,
@@ -1058,26 +1294,28 @@ def cover_scans(model, batcher, idx, rounds=1, interpolate=False, draws=None, re
     for these batches (default: the batcher's; ValueError without one).  interpolate=True sends the same batches through
     ScanVotes / geot_scan_vote instead: a vertex gets its own pass's value (weight about 1 at distance about 0) plus P - 1
     interpolated ones.  refine, parts: the labels then go through refine_scans.  graph, lookahead: as for vote_scans;
-    lookahead=True runs one geometry call per round."""
+    lookahead=True runs one geometry call per round.  islands: as for predict_scans."""
     n_refine = _refine_n(refine, "cover_scans")
+    islands = _islands_kw(islands, "cover_scans")
     rounds = _rounds(rounds, "cover_scans")
     model.eval()
     preds, data, c = _cover_run(model, batcher, idx, rounds, interpolate, draws, graph, lookahead, "cover_scans")
-    return refine_scans(preds, data, n_refine, parts, num_classes=c) if n_refine else preds
+    return _finish_labels(preds, data, n_refine, parts, islands, c)
 
 
 @torch.no_grad()
 def validate_scans_covered(model, scans, cfg, rounds=1, interpolate=False, batch_size=2, indices=None, stream=None, draws=None,
-                           refine=0, parts=None, graph=False, lookahead=0, teeth=None):
+                           refine=0, parts=None, graph=False, lookahead=0, teeth=None, islands=None):
     """validate_scans scored on covering passes: every batch of scans runs through the model rounds * P times (cover_scans),
     each vertex scored on the class the model gave that very vertex.  scans: a DeviceScanSet (a ValBatcher is built on it:
     cfg.num_points, cfg.num_classes), or a ValBatcher / VoteBatcher built on one (a VoteBatcher applies its vote list per
     pass).  draws: a DeviceDraws (default: the batcher's; ValueError without one).  Same log lines, return value and dtypes as
     validate().  interpolate, refine, parts, graph, lookahead: as for cover_scans.  teeth: as for validate_scans (the last pass's
-    finish writes the labels beside the counts)."""
+    finish writes the labels beside the counts).  islands: as for validate_scans."""
     from .openpoints.dataset.val_batch import ScanBatcher, ValBatcher
     what = "validate_scans_covered"
     n_refine = _refine_n(refine, what)
+    islands = _islands_kw(islands, what)
     rounds = _rounds(rounds, what)
     need(int(batch_size) >= 1, "%s: batch_size >= 1" % what)
     model.eval()
@@ -1093,9 +1331,9 @@ def validate_scans_covered(model, scans, cfg, rounds=1, interpolate=False, batch
     _need_teeth(teeth, c, batcher.device, what)
     for at in range(0, len(order), int(batch_size)):
         ids = order[at:at + int(batch_size)]
-        if n_refine:
+        if n_refine or islands is not None:
             preds, data, _ = _cover_run(model, batcher, ids, rounds, interpolate, draws, graph, lookahead, what, c)
-            preds = _count_refined(metrics, preds, data, n_refine, parts)
+            preds = _count_refined(metrics, preds, data, n_refine, parts, islands)
         else:
             rows = metrics._rows(len(ids))
             preds, data, _ = _cover_run(model, batcher, ids, rounds, interpolate, draws, graph, lookahead, what, c, counts=rows,
@@ -1205,7 +1443,7 @@ def _decode_run(model, batcher, ids, c, draws, chunk, what, counts=None, want_pr
 
 
 @torch.no_grad()
-def decode_scans(model, batcher, idx, refine=0, parts=None, chunk=32768, draws=None):
+def decode_scans(model, batcher, idx, refine=0, parts=None, chunk=32768, draws=None, islands=None):
     """The per-vertex labels of the scans `idx` of a ValBatcher's or VoteBatcher's set, every vertex predicted directly from
     ONE forward pass: list of (1, M_i) int64 tensors, as predict_scans returns them.  The model sees one sampled batch; its
     last decoder stage (propogation_0, seg_head) is then evaluated at EVERY vertex of the scans -- geot_scan_decode_front takes
@@ -1215,26 +1453,29 @@ def decode_scans(model, batcher, idx, refine=0, parts=None, chunk=32768, draws=N
     for a model in training mode).  A VoteBatcher's batch is decoded on its `val` view; votes and rounds do not apply.  refine
     (0: off, True: n = 10, an int: n) and parts: the labels then go through refine_scans.  draws: a DeviceDraws for the
     batch (default: the batcher's).  What this computes is the model's own decoder at those positions; how decoded labels
-    compare with interpolated or covered ones on real scans has not been measured (there are no trained weights here)."""
+    compare with interpolated or covered ones on real scans has not been measured (there are no trained weights here).
+    islands: as for predict_scans."""
     n_refine = _refine_n(refine, "decode_scans")
+    islands = _islands_kw(islands, "decode_scans")
     seg = getattr(model, "segmentor", model)
     c = _need_classes(getattr(seg, "nclasses", batcher.c), "decode_scans")
     preds, data = _decode_run(model, batcher, [int(i) for i in idx], c, draws, chunk, "decode_scans")
-    return refine_scans(preds, data, n_refine, parts, num_classes=c) if n_refine else preds
+    return _finish_labels(preds, data, n_refine, parts, islands, c)
 
 
 @torch.no_grad()
 def validate_scans_decoded(model, scans, cfg, batch_size=2, indices=None, stream=None, draws=None, refine=0, parts=None, chunk=32768,
-                           teeth=None):
+                           teeth=None, islands=None):
     """validate_scans scored on decoded labels (decode_scans): per batch of scans one batch() and one forward pass, then the
     last decoder stage at every vertex, counted by geot_scan_decode_finish.  scans: a DeviceScanSet (a ValBatcher is built on
     it: cfg.num_points, cfg.num_classes), or a ValBatcher / VoteBatcher built on one.  Same log lines, return value and
     dtypes as validate().  refine, parts: as for validate_scans; chunk, draws: as for decode_scans.  No host synchronisation
     beyond validate_scans' (the final read of the counts).  teeth: as for validate_scans (every chunk's finish writes its
-    labels beside the counts)."""
+    labels beside the counts).  islands: as for validate_scans."""
     from .openpoints.dataset.val_batch import ScanBatcher, ValBatcher
     what = "validate_scans_decoded"
     n_refine = _refine_n(refine, what)
+    islands = _islands_kw(islands, what)
     need(int(batch_size) >= 1, "%s: batch_size >= 1" % what)
     model.eval()                        # as validate_scans; decode_scans itself refuses a model in training mode
     c = _need_classes(_cfg(cfg, "num_classes", 17), what)
@@ -1249,9 +1490,9 @@ def validate_scans_decoded(model, scans, cfg, batch_size=2, indices=None, stream
     _need_teeth(teeth, c, batcher.device, what)
     for at in range(0, len(order), int(batch_size)):
         ids = order[at:at + int(batch_size)]
-        if n_refine:
+        if n_refine or islands is not None:
             preds, data = _decode_run(model, batcher, ids, c, draws, chunk, what)
-            preds = _count_refined(metrics, preds, data, n_refine, parts)
+            preds = _count_refined(metrics, preds, data, n_refine, parts, islands)
         else:
             rows = metrics._rows(len(ids))
             preds, data = _decode_run(model, batcher, ids, c, draws, chunk, what, counts=rows, want_pred=teeth is not None)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 33
+#define GEOT_ABI_VERSION 34
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -1056,6 +1056,58 @@ int geot_scan_refine(int b, int c, int n, int n_scans, long long total, const fl
 int geot_tooth_moments(int b, int c, int n_scans, long long total, const float *points, const int *labels,
                        const long long *offsets, const long long *scan_ids, const float *center, int n_work, const int *work,
                        const long long *out_offsets, const long long *pred, long long *moments, void *stream);
+
+/* ---- whole-scan labels split into connected pieces, stray islands relabelled (ABI 34) ------------------------------------------
+ * geot_scan_islands: the connected components of equal-label vertices over a neighbour table of each whole scan, and the
+ * clean-up built on them -- a piece that is too small, of a class the jaw does not allow, or not the largest of a class that is
+ * kept to one piece takes the majority label of what surrounds it -- for b batch slots in a number of launches (six; four in
+ * the components-only form below) that depends neither on b, nor on the scans' sizes, nor on what the labels hold; no host
+ * synchronisation, nothing read back, kernels only (no memset node: the call captures as kernel nodes).
+ * offsets, scan_ids, out_offsets and the slots: as for geot_scan_refine; M_s is the vertex count of slot s's scan.  pred:
+ * int64, vertex v of slot s at pred[out_offsets[s] + v]; the slots' ranges must not overlap.  nbr: (total_out, k) int32, row
+ * out_offsets[s] + v lists neighbours of v as vertex indices local to the slot's scan; an entry that is negative, >= M_s or
+ * equal to v DOES NOT EXIST; duplicates are harmless for the components and count once each in a vote.  keep, allowed: (b)
+ * 32-bit class masks on the device, either may be NULL (keep NULL: no class is kept to its largest piece; allowed NULL: every
+ * class is allowed).  Per usable slot, with L the slot's labels as they arrive (a snapshot):
+ *   edges       {v, u} is an edge iff u is an existing entry of nbr[v] and 0 <= L[v] == L[u] < c.  The table is directed, the
+ *               edge is not: one entry in either row joins the two.
+ *   components  comp[v] (optional, (total_out) int32 laid out like pred; NULL: not written) = the lowest vertex index in v's
+ *               connected component.  A vertex whose label is outside [0, c) is its own component; it never becomes an
+ *               island, never votes and is never written.  comp describes the labels as they ARRIVED.
+ *   size        the vertices of a component; the LARGEST component of class i in the slot is the one of greatest size, the one
+ *               with the lowest root (= comp) among equals.
+ *   islands     a component of class i is an island iff size < min_size, or bit i of allowed[s] is clear, or bit i of keep[s]
+ *               is set and it is not the largest of its class.
+ *   votes       an island's vote is a count per class j over all v in the island and all existing entries u of nbr[v]
+ *               (forward entries only: rows of other vertices that name v do not count) with 0 <= L[u] < c, L[u] != i and u's
+ *               component not an island.  The island's new label is the class with the most votes, the lowest class among
+ *               equals; an island with no vote at all is STRANDED and keeps its label.  Counts are 32-bit: M_s k < 2^32.
+ *   write       every vertex of an island that is not stranded gets the new label.  All decisions are taken from the snapshot
+ *               before any label is written: one pass, not a fixed point.
+ * With min_size <= 1, keep NULL and allowed NULL nothing can be an island: pred is not written and the vote and write
+ * launches are left out -- the components-only form.  (keep given and all zero: six launches, nothing written either.)
+ * stats (optional): (b, 4) int32, WRITTEN (a skipped slot: zeros) -- components among the labels in [0, c), islands, vertices
+ * whose label changed, vertices in stranded islands.
+ * Integer atomics only and no result depends on their order -- canonical roots (the component minimum), packed (size, ~root)
+ * maxima, vote counts added per class -- so the same call gives the same bits and a numpy restatement gives them too.  The
+ * components come from a lock-free union-find by hooking: a root is only ever linked under a smaller vertex, by
+ * compare-and-swap on its own parent word, read with relaxed agent-scope atomics; hooking and flattening are separate
+ * launches; every loop ends by the decrease of a vertex index and no workgroup ever waits for another.
+ * GEOT_SCAN_ISLANDS_IMPL=basic (read at every call) counts the sizes with one atomic per vertex in place of the form that
+ * combines equal roots inside a wave first; the same bits.
+ * ws: geot_scan_islands_ws_bytes(b, total_out, c) bytes, 16-byte aligned, contents irrelevant; total_out = the length of pred
+ * (every out_offsets[s] + M_s <= total_out).  It holds per slot and class the largest piece, and per vertex a parent, a size
+ * and c vote counts.  A slot whose scan_ids entry lies outside [0, n_scans), whose offsets pair is not 0 <= lo < hi <= total
+ * with hi - lo <= 2^31 - 1, or whose out_offsets entry does not leave room for it in a ws_bytes-sized workspace -- (ws_bytes -
+ * geot_scan_islands_ws_bytes(b, 0, c)) / (4 (c + 2)) vertices -- is skipped: nothing of it is read or written.
+ * 0 <= b <= 65535 (0: nothing to do), 1 <= c <= GEOT_NTM_MAX_C, 1 <= k <= 32, min_size >= 0, n_scans >= 1, total >= 1, no NULL
+ * among offsets, scan_ids, out_offsets, nbr, pred and ws, ws 16-byte aligned, ws_bytes >= geot_scan_islands_ws_bytes(b, 0, c);
+ * anything else is hipErrorInvalidValue before any launch.  geot_scan_islands_ws_bytes: -1 for arguments outside these ranges
+ * or total_out < 0. */
+long long geot_scan_islands_ws_bytes(int b, long long total_out, int c);
+int geot_scan_islands(int b, int c, int k, int min_size, int n_scans, long long total, const long long *offsets,
+                      const long long *scan_ids, const long long *out_offsets, const int *nbr, const unsigned *keep,
+                      const unsigned *allowed, long long *pred, int *comp, int *stats, void *ws, long long ws_bytes, void *stream);
 
 /* ---- transform lists as per-view programs (ABI 16) ---------------------------------------------------------------------------
  * geot_view_program: geot_fixmatch_views for ANY list of the reference's point transforms that keeps the point count
