@@ -30,6 +30,7 @@ b^step and what is formed from them in double (lr / bc1, sqrt(bc2): one rounding
     p'      p1 - r: E_p1 + E_r + u |p'|
     t'      d t + (1 - d) p', or t + (1 - d)(p' - t): 2 u d |t| + (1 - d) E_p + 3 u (1 - d)(|p'| + |t|) + u |t'|
     int     a copy: 0.
+    slot    one workgroup's sum of squares, before the sqrt and the sum over the slots: (1 + chain) u of the slot (slot_error).
 """
 import math
 
@@ -55,6 +56,13 @@ def clip_coef(norm, max_norm):
 def norm_error(chain, u=U):
     """Relative bound of total_norm for this chain of additions."""
     return ((1 + chain) / 2 + 2) * u
+
+
+def slot_error(chain, u=U):
+    """Relative bound of ONE workgroup's fp32 sum of squares (a slot of the norm sweep) against its fp64 value, counted as
+    norm_error counts: every term is rounded once as a square and passes through at most `chain` additions, and all terms
+    are non-negative, so the sum's relative error is at most its worst term's: (1 + chain) u."""
+    return (1 + chain) * u
 
 
 def tail(records, groups, max_norm=None, decay=None, drop=(), u=U, chain=ANY_CHAIN, norm=None):
