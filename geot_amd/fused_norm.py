@@ -16,12 +16,14 @@ float, a 1-element device double under SyncBatchNorm (the total never visits the
 where the statistics do not depend on x.
 
 Further down: the small autograd ops that replace runs of torch launches around the dense layers (profiles/DESIGN_r01_r03.md 4.10) --
-``max_last``, ``add_last_broadcast``, ``thin_mm``, ``linear`` (bias gradient as column sums), ``res_ln`` (residual add +
+``max_last``, ``conv_max_last``, ``add_last_broadcast``, ``thin_mm``, ``linear`` (bias gradient as column sums), ``res_ln`` (residual add +
 LayerNorm), ``qkv_split`` (attention head split) and ``softmax_last``.  Each falls back to the torch composition where its
 kernel does not apply, so callers never branch.  The float4 kernels (segment max / sum, bn_pool, qkv_split) refuse storage
 that is not 16-byte aligned: a contiguous view can start at any element, and autograd can hand a backward such a
 gradient (a slice of a cat), so the forward wrappers check it (_aligned16) and the backwards copy (_fresh16).
 """
+import os
+
 import torch
 import torch.nn as nn
 from torch.autograd import Function
@@ -768,6 +770,53 @@ def max_last(x):
             and _aligned16(x)):
         return x.max(dim=-1)[0]
     return _SegmentMaxFn.apply(x, n)
+
+
+class _ConvMaxLastFn(Function):
+    """max over every group's n columns of w (Co, Ci) @ x (Ci, G n): the forward is the library GEMM and geot_segment_max, as
+    max_last(torch.mm(w, x).view(Co, G, n)) launches them; the backward goes from the max's one non-zero per (channel, group)
+    straight to the gradients of x and w (csrc/max_conv.hip) -- the dense (Co, G n) gradient of the product, n - 1 zeros in
+    n, is never written and no GEMM multiplies it."""
+
+    @staticmethod
+    def forward(ctx, w, x, n):
+        y = torch.mm(w, x)
+        co, g = y.shape[0], y.shape[1] // n
+        out = torch.empty((co, g), dtype=torch.float32, device=x.device)
+        arg = torch.empty((co, g), dtype=torch.uint8, device=x.device)
+        call("geot_segment_max", x.device, co * g, n, ptr(y), ptr(out), ptr(arg))
+        ctx.save_for_backward(w, x, arg)
+        ctx.n = n
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        w, x, arg = ctx.saved_tensors
+        (co, ci), g, n = w.shape, arg.shape[1], ctx.n
+        dout = dout.contiguous()                        # read by element: any alignment
+        gw = gx = None
+        if ctx.needs_input_grad[0]:
+            ws = torch.empty(int(_lib.load().geot_maxconv_ws_floats(co, ci, g, n)), dtype=torch.float32, device=x.device)
+            gw = torch.empty_like(w)
+            call("geot_maxconv_wgrad", x.device, co, ci, g, n, ptr(x), ptr(dout), ptr(arg), ptr(ws), ptr(gw))
+        if ctx.needs_input_grad[1]:
+            gx = torch.empty_like(x)
+            call("geot_maxconv_dgrad", x.device, co, ci, g, n, ptr(w), ptr(dout), ptr(arg), ptr(gx))
+        return gw, gx, None
+
+
+def conv_max_last(w, x, n):
+    """max_last(torch.mm(w, x).view(Co, G, n)) -> (Co, G) for w (Co, Ci), x (Ci, G n): a 1x1 convolution whose output feeds only
+    the max over each group's n points.  Same forward launches and bits; the backward skips the dense gradient of the product
+    (_ConvMaxLastFn).  Contiguous 16-byte aligned float32 GPU tensors with Co <= 1024, Ci % 4 == 0, n % 4 == 0, 4 <= n <= 256;
+    anything else, or GEOT_MAX_CONV=0 (read per call), takes that composition."""
+    ok = (os.environ.get("GEOT_MAX_CONV", "1") != "0" and w.is_cuda and x.is_cuda and w.dtype == torch.float32
+          and x.dtype == torch.float32 and w.dim() == 2 and x.dim() == 2 and w.is_contiguous() and x.is_contiguous()
+          and _aligned16(w) and _aligned16(x) and 1 <= w.shape[0] <= 1024 and w.shape[1] >= 4 and w.shape[1] % 4 == 0
+          and 4 <= n <= 256 and n % 4 == 0 and x.shape[1] > 0 and x.shape[1] % n == 0)
+    if not ok:
+        return max_last(torch.mm(w, x).view(w.shape[0], -1, n))
+    return _ConvMaxLastFn.apply(w, x, n)
 
 
 class _AddLastBroadcastFn(Function):

@@ -38,7 +38,7 @@ from .transformer_ops import (Group, fps, fps_downsample, graph_feature, get_gra
 from .geometry import EdgeEntry, FpEntry, Geometry, IndexPlan
 from .... import streams
 from ....ntm import sig_t_mean  # noqa: F401  (transformer.py:1099-1131 lives in ntm.py)
-from ....fused_norm import bn_act, fp_front, fp_front_eligible, max_last, add_last_broadcast, thin_mm, add_channel_bias, thin_bn_act
+from ....fused_norm import bn_act, fp_front, fp_front_eligible, max_last, conv_max_last, add_last_broadcast, thin_mm, add_channel_bias, thin_bn_act
 from ....fused_norm import (fp_front_cl, fp_front_cl_eligible, bn_act_cl, fp_stage_cl, pointwise_to_cl, pointwise_from_cl,
                             local_spatial_order, ReverseIndex)
 from ....fused_norm import linear as lean_linear, res_ln, res_ln_eligible, qkv_split, softmax_last
@@ -282,9 +282,14 @@ class Encoder(nn.Module):
             r = thin_bn_act(self.first_conv[1], self.first_conv[0].weight.squeeze(-1), x, self.first_conv[0].bias, relu=True)
         else:
             r = norm_act(self.first_conv, conv(self.first_conv[0], x, bias=False), self.first_conv[0].bias)
-        f0 = conv(self.first_conv[3], r, bias=False)                                    # f = f0 + b1: (256, L)
-        c1 = f0.shape[0]
-        pooled = max_last(f0.view(c1, bs * g, n))                                       # (256, BG), + b1 below
+        # conv_max_last (GEOT_MAX_CONV, default on; 0 = the two launches and their dense backward bit for bit): a convolution
+        # that feeds only the max over the group's points back-propagates from the max's one non-zero per (channel, group)
+        c1 = self.first_conv[3].weight.shape[0]
+        if fold:                                                                        # f0 is needed by the max alone
+            pooled = conv_max_last(self.first_conv[3].weight.squeeze(-1), r, n)         # (256, BG), + b1 below
+        else:
+            f0 = conv(self.first_conv[3], r, bias=False)                                # f = f0 + b1: (256, L)
+            pooled = max_last(f0.view(c1, bs * g, n))
         if b1 is not None:
             pooled = add_channel_bias(pooled, b1)
         c2 = self.second_conv[0]
@@ -303,8 +308,7 @@ class Encoder(nn.Module):
         else:
             h = add_last_broadcast(conv(c2, f0, w_f, bias=False).view(-1, bs * g, n), torch.mm(w_g, pooled))
             hr = norm_act(self.second_conv, h.view(-1, L), pre)
-        h0 = conv(self.second_conv[3], hr, bias=False)                                  # (C_enc, L)
-        out = max_last(h0.view(-1, bs * g, n))
+        out = conv_max_last(self.second_conv[3].weight.squeeze(-1), hr, n)              # max of h0 (C_enc, L) per group
         if b2 is not None:
             out = add_channel_bias(out, b2)
         return out.t().reshape(bs, g, self.encoder_channel)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 34
+#define GEOT_ABI_VERSION 35
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
@@ -368,6 +368,23 @@ int geot_colsum(int rows, int cols, const float *x, float *out, float *workspace
 int geot_rowdot_small_slices(int rows, int l);
 int geot_rowdot_small(int rows, int l, int j, const float *a, const float *b, float *partial, void *stream);
 int geot_segment_max_grad(long long rows, int n, const float *dy, const unsigned char *arg, float *dx, void *stream);
+/* The backward of  out = max over every group's n columns of (W x)  from the max's sparse gradient (ABI 35,
+ * csrc/max_conv.hip; Encoder, transformer.py:113 and :123-126: the 1x1 convolutions in front of the two group maxima):
+ * W (co, ci), x (ci, g n) with group k owning columns k n .. k n + n - 1, dout (co, g) the gradient of out, arg (co, g) as
+ * geot_segment_max wrote it for y = W x viewed (co, g, n).  All fp32, contiguous.
+ *   _dgrad   dx (ci, g n):  dx[c, k n + j] = sum over the o with arg[o, k] == j of dout[o, k] W[o, c], ascending o;
+ *            every element written exactly once, zeros included.
+ *   _wgrad   dW (co, ci):   dW[o, c] = sum over k of dout[o, k] x[c, k n + arg[o, k]]: chunks of groups leave fp32
+ *            partial sums in ws (geot_maxconv_ws_floats(co, ci, g, n) floats, contents on entry irrelevant), a finish
+ *            kernel adds the chunks in ascending order in fp64 and rounds once.  The chunking depends on the shapes alone
+ *            (GEOT_MAXCONV_CHUNK=<groups per chunk>, read per call by both, pins it for tests).
+ * No float atomics, kernel launches only, bit-identical from call to call.  hipErrorNotSupported (nothing launched) unless
+ * co <= 1024, ci % 4 == 0, 4 <= n <= 256, n % 4 == 0 and W, x, dx, ws, dW are 16-byte aligned; _ws_floats: -1. */
+int geot_maxconv_dgrad(int co, int ci, int g, int n, const float *W, const float *dout, const unsigned char *arg, float *dx,
+                       void *stream);
+long long geot_maxconv_ws_floats(int co, int ci, int g, int n);
+int geot_maxconv_wgrad(int co, int ci, int g, int n, const float *x, const float *dout, const unsigned char *arg, float *ws,
+                       float *dW, void *stream);
 int geot_fp_front_slices(int b, int c, int m, int n);
 int geot_fp_front(int b, int c, int m, int n, int cs, const float *A, const int *idx, const float *weight,
                   const float *skip, const float *Wb, float *y, float *partial, void *stream);
