@@ -8,6 +8,7 @@ interpolation hot path behind the reference's operator API.
     from geot_amd import fit, train_one_epoch, epoch_batches, LrSchedule      # the training driver (fit.py, schedule.py)
     from geot_amd import ToothScores, tooth_scores_from_moments, tooth_instances     # the Teeth3DS challenge scores (validation.py)
     from geot_amd import clean_scans, scan_components, scan_neighbours, teeth3ds_result  # connected teeth, the challenge's result
+    from geot_amd import mesh_neighbours                    # the scan meshes' one-ring tables for them (DeviceScanSet(faces=))
 
 The compute path is libgeot_hip.so (C ABI in include/geot_hip.h); there is no CPU fallback.
 """
@@ -54,7 +55,7 @@ def graph_replay_is_safe():
 _EXPORTS = {"train_one_epoch": "fit", "epoch_batches": "fit", "LrSchedule": "schedule",
             "ToothScores": "validation", "tooth_scores_from_moments": "validation", "tooth_instances": "validation",
             "clean_scans": "validation", "scan_components": "validation", "scan_neighbours": "validation",
-            "teeth3ds_result": "validation"}
+            "teeth3ds_result": "validation", "mesh_neighbours": "validation"}
 
 
 def __getattr__(name):

@@ -42,7 +42,8 @@ ABI_VERSION = CONSTANTS["GEOT_ABI_VERSION"]           # a library of another ver
 KNN_KMAX_HEAP = CONSTANTS["GEOT_KNN_KMAX_HEAP"]       # largest nsample of the heap-ordered kNN (knnquery_cuda, pointops.knn)
 KNN_KMAX_SORTED = CONSTANTS["GEOT_KNN_KMAX_SORTED"]   # largest k of the sorted kNN (knn_cuda.KNN, knn_point in 3-D)
 NTM_MAX_C = CONSTANTS["GEOT_NTM_MAX_C"]               # largest class count of the per-point kernels (NTM, criteria, meters)
-VIEW_JOB_WORDS = CONSTANTS["GEOT_VIEW_JOB_WORDS"]     # 32-bit words of one geot_fixmatch_views job record
+MESH_NEIGHBOURS_LANE_ROW = CONSTANTS["GEOT_MESH_NEIGHBOURS_LANE_ROW"]     # geot_mesh_neighbours: the longest raw row one lane tidies
+VIEW_JOB_WORDS = CONSTANTS["GEOT_VIEW_JOB_WORDS"]   # 32-bit words of one geot_fixmatch_views job record
 VIEW_REG_POINTS = CONSTANTS["GEOT_VIEW_REG_POINTS"]   # largest cloud geot_fixmatch_views holds in registers
 VIEW_MAX_OPS = CONSTANTS["GEOT_VIEW_MAX_OPS"]         # ops of one geot_view_program job
 VIEW_PROGRAM_JOB_WORDS = CONSTANTS["GEOT_VIEW_PROGRAM_JOB_WORDS"]

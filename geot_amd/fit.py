@@ -274,6 +274,9 @@ def fit(step, batcher, cfg, val=None, test=None, ckpt_dir=None, resume=None, log
     val_teeth = _val_teeth3ds(cfg)
     from . import validation
     islands = validation._islands_kw(islands, "fit")              # a bad value: ValueError here, before the first epoch
+    for held_out in (val, test):                                  # islands={"mesh": ...} on a set without faces: likewise
+        if held_out is not None:
+            validation._need_mesh(islands, held_out, "fit")
     inner = _inner(step)
     fixmatch = _is_fixmatch(step)
     if fixmatch and (_cfg(cfg, "supervised_epochs", 0) or 0) > 0:

@@ -14,13 +14,40 @@ def _to_device(host, dev):
     return torch.from_numpy(host).pin_memory().to(dev, non_blocking=True)
 
 
+def check_faces(faces, n):
+    """DeviceScanSet's host checks of `faces`, before any upload and before the device is looked at: one entry per scan, each
+    None (a scan without a mesh) or an (F_i >= 0, 3) integer array or tensor -> the entries as host tensors (None kept).  The
+    index VALUES are not checked: geot_mesh_neighbours ignores a face with an index outside its scan and counts it."""
+    need(isinstance(faces, (list, tuple)) and len(faces) == n,
+         "DeviceScanSet: faces must be a sequence with one entry per scan (%d): an (F, 3) integer array, or None" % n)
+    out = []
+    for i, f in enumerate(faces):
+        if f is None:
+            out.append(None)
+            continue
+        t = torch.as_tensor(f)
+        need(t.dim() == 2 and t.shape[1] == 3, "DeviceScanSet: faces[%d] must be (F, 3), got %s" % (i, tuple(t.shape)))
+        need(not t.is_floating_point() and not t.is_complex() and t.dtype != torch.bool,
+             "DeviceScanSet: faces[%d] must hold integer vertex indices, got %s" % (i, t.dtype))
+        out.append(t)
+    return out
+
+
 class DeviceScanSet:
     """The scans of one split on one device, built once: vertices concatenated (sum N, 3) float32, labels (sum N,) int32,
     offsets (n + 1,) int64, the jaw flag of every scan `cls` (n,) int64 (tooth_dataset.py:97, 0 = lower; default 0).
-    scans / labels: sequences of (N_i, 3) / (N_i,) arrays or tensors."""
+    scans / labels: sequences of (N_i, 3) / (N_i,) arrays or tensors.
+    faces (default None: the set holds no meshes and `faces`, `face_offsets`, `face_sizes` and `has_mesh` are None): a sequence
+    with one entry per scan, an (F_i, 3) integer array or tensor of vertex indices local to the scan (io.read_obj's second
+    result), or None for a scan without a mesh.  Stored concatenated: faces (sum F, 3) int32 and face_offsets (n + 1,) int64 on
+    the device, face_sizes and has_mesh host lists (None: face_sizes[i] = 0 and has_mesh[i] False; an empty (0, 3) array: a mesh
+    with no faces).  An index that does not fit int32 is stored as -1 or 2^31 - 1: outside every scan either way.
+    keep_tables(): validation.scan_neighbours and mesh_neighbours keep every scan's neighbour table on the set (off by
+    default)."""
 
-    def __init__(self, scans, labels, cls=None, device=None):
+    def __init__(self, scans, labels, cls=None, device=None, faces=None):
         need(len(scans) >= 1 and len(scans) == len(labels), "DeviceScanSet: one label array per scan, at least one scan")
+        meshes = None if faces is None else check_faces(faces, len(scans))
         dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         need(dev.type == "cuda", "DeviceScanSet: CPU not supported (the scans must live on the GPU)")
         pts = [torch.as_tensor(p) for p in scans]
@@ -37,9 +64,36 @@ class DeviceScanSet:
         self.labels = torch.cat([l.to(dev, torch.int32) for l in labs]).contiguous()
         self.offsets = torch.tensor(np.concatenate([[0], np.cumsum(self.sizes, dtype=np.int64)]), dtype=torch.int64).to(dev)
         self.cls = torch.tensor(cls, dtype=torch.int64).to(dev)
+        self.faces = self.face_offsets = self.face_sizes = self.has_mesh = None
+        if meshes is not None:
+            self.has_mesh = [f is not None for f in meshes]
+            self.face_sizes = [0 if f is None else int(f.shape[0]) for f in meshes]
+            host = [f.to(torch.int64).clamp(-1, 2 ** 31 - 1).to(torch.int32) for f in meshes if f is not None]
+            self.faces = (torch.cat(host) if host else torch.empty((0, 3), dtype=torch.int32)).to(dev).contiguous()
+            self.face_offsets = torch.tensor(np.concatenate([[0], np.cumsum(self.face_sizes, dtype=np.int64)]),
+                                             dtype=torch.int64).to(dev)
+        self._keep, self._tables = False, {}
 
     def __len__(self):
         return len(self.sizes)
+
+    def keep_tables(self, on=True):
+        """Switch the per-scan cache of neighbour tables on (or off; off drops what is kept).  While it is on,
+        validation.scan_neighbours and validation.mesh_neighbours keep each scan's (M_i, width) int32 table under (scan, "knn" |
+        "mesh", width), build only the missing ones and assemble a batch's table from the kept ones with device copies: the
+        bits of the uncached call.  Memory: 4 * width * M_i bytes per scan, kind and width (a scan of 1e5 vertices: 3.6 MB for
+        the nine-wide kNN table, 6.4 MB for the 16-wide mesh table), held until drop_tables().  The tables depend on the
+        vertices and faces alone: whoever changes `points` or `faces` in place calls drop_tables().  Only a batch that carries
+        the host scan ids ("ids", which the whole-scan batchers add to every batch they build while the switch is on, and
+        always for a set with faces) is served from the cache.  -> self."""
+        self._keep = bool(on)
+        if not self._keep:
+            self._tables = {}
+        return self
+
+    def drop_tables(self):
+        """Empty the cache of neighbour tables (the switch stays as it is)."""
+        self._tables = {}
 
     @classmethod
     def _merged(cls, a, b):
@@ -50,6 +104,15 @@ class DeviceScanSet:
         out.points, out.labels = torch.cat([a.points, b.points]), torch.cat([a.labels, b.labels])
         out.offsets = torch.cat([a.offsets, b.offsets[1:] + a.offsets[-1:]])
         out.cls = torch.cat([a.cls, b.cls])
+        out.faces = out.face_offsets = out.face_sizes = out.has_mesh = None
+        if a.faces is not None or b.faces is not None:          # the side without faces: mesh-less scans
+            parts = [(s.faces, s.face_sizes, s.has_mesh) if s.faces is not None else
+                     (torch.empty((0, 3), dtype=torch.int32, device=s.device), [0] * len(s), [False] * len(s)) for s in (a, b)]
+            out.faces = torch.cat([parts[0][0], parts[1][0]])
+            out.face_sizes, out.has_mesh = parts[0][1] + parts[1][1], parts[0][2] + parts[1][2]
+            out.face_offsets = torch.tensor(np.concatenate([[0], np.cumsum(out.face_sizes, dtype=np.int64)]),
+                                            dtype=torch.int64).to(a.device)
+        out._keep, out._tables = False, {}
         return out
 
 

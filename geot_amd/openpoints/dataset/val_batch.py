@@ -6,7 +6,8 @@ openpoints/dataset/build.py:30-50 collate_fn_val) plus validate's `.cuda()` and 
     pos (B, m, 3)   x (B, 3, m)   y (B, m) int64   cls (B, 1) int64   center (B, 3)   scale (B,)
     points / labels   lists of B views into the set's vertices (N_i, 3) fp32 and labels (N_i,) int32: nothing is copied
     scan_ids (B,) int64 on the device, scans (the set), sizes (the B vertex counts) and mandible (validate's `cls[ii] == 0`)
-    as host values
+    as host values; for a set that holds faces or keeps neighbour tables (DeviceScanSet(faces=), keep_tables()) also ids, the
+    scan numbers as host values: what validation.mesh_neighbours and the set's table cache go by
 
 The `val` list is the weak view's list: geot_cloud_sample_batch (5 launches) and geot_fixmatch_views with the "train_w"
 parameters (1), one gather of the jaw classes, two small pinned host-to-device copies -- the same number for every batch,
@@ -68,10 +69,13 @@ class ScanBatcher(Batcher):
 
     def _scan_keys(self, s, cls, ids):
         """Every key of a batch but the views' (pos, x, ...)."""
-        return {"y": s["y"], "cls": cls, "center": s["center"], "scale": s["scale"],
+        keys = {"y": s["y"], "cls": cls, "center": s["center"], "scale": s["scale"],
                 "points": [self._points[i] for i in ids], "labels": [self._labels[i] for i in ids],
                 "scan_ids": s["scan_ids"], "scans": self.scans, "sizes": [self.scans.sizes[i] for i in ids],
                 "mandible": [self.cls_host[i] == 0 for i in ids]}
+        if getattr(self.scans, "faces", None) is not None or getattr(self.scans, "_keep", False):
+            keys["ids"] = list(ids)         # only where something goes by them: a set without meshes and tables keeps its key set
+        return keys
 
     def join(self, batch):
         """Hand a batch built on the side stream to the CURRENT stream (Batcher._join)."""

@@ -88,6 +88,13 @@ piece -- too small, of a class the jaw does not allow, or not the largest of its
     preds = predict_scans(logits, batch, islands=True)       # also vote_scans, cover_scans, decode_scans, the validators, fit()
     result = teeth3ds_result(preds[0], comp[0], "lower")     # the challenge's labels (FDI) + instances, on the host
 
+The table is each vertex's nearest vertices in space (scan_neighbours) or, for a set built with faces=, the scan mesh's own
+one-ring (geot_mesh_neighbours, csrc/mesh_neighbours.hip: no search; two teeth in contact are not joined by it):
+
+    table = mesh_neighbours(batch, k=16)                     # (sum M, 16) int32; clean_scans(..., mesh=True) builds it itself
+    preds = predict_scans(logits, batch, islands={"mesh": True})
+    scans.keep_tables()                                      # keep every scan's table of either kind on the set (off by default)
+
 Look-ahead and replay -- validate_scans, validate_scans_voted and vote_scans with lookahead=G / graph=True (off by default):
 up to G passes are drawn ahead (the same batch() calls in the same order), their coordinate-only work runs as one
 prefetch_geometry over the concatenated positions beside the forward pass in flight (pass_schedule, _passes), and with graph
@@ -299,6 +306,8 @@ def predict_scans(logits, batch, refine=0, parts=None, islands=None):
     refine, go through clean_scans."""
     n_refine = _refine_n(refine, "predict_scans")
     islands = _islands_kw(islands, "predict_scans")
+    if isinstance(batch, dict):
+        _need_mesh(islands, batch.get("scans"), "predict_scans")
     need(torch.is_tensor(logits) and logits.dim() == 3, "predict_scans: logits must be a (B, C, N) tensor")
     preds = _scan_launch(logits, batch, logits.shape[1], "predict_scans", want_pred=True)
     return _finish_labels(preds, batch, n_refine, parts, islands, logits.shape[1])
@@ -412,7 +421,20 @@ def part_seg_refinement(pred, pos, cls, cls2parts, n=10):
 
 # ---- connected pieces of whole-scan labels, stray islands relabelled (csrc/scan_islands.hip) ----------------------------------------
 ISLANDS_MAX_K = 32                  # include/geot_hip.h geot_scan_islands: entries per row of the neighbour table
-_CLEAN_KEYS = ("min_size", "keep_largest", "parts", "nbr", "k", "num_classes")
+MESH_K = 16                         # mesh_neighbours' default width, and what mesh=True means
+_CLEAN_KEYS = ("min_size", "keep_largest", "parts", "nbr", "k", "num_classes", "mesh")
+
+
+def _mesh_width(mesh, what, error=RuntimeError):
+    """The `mesh` keyword of clean_scans and scan_components -> None (None or False: the kNN table) or the width of the mesh
+    table (True: MESH_K; an int in 1..32: that)."""
+    if mesh is None or mesh is False:
+        return None
+    if mesh is True:
+        return MESH_K
+    if not isinstance(mesh, (int, np.integer)) or not 1 <= int(mesh) <= ISLANDS_MAX_K:
+        raise error("%s: mesh must be None, a bool or an int in 1..%d (the width of the one-ring table), got %r" % (what, ISLANDS_MAX_K, mesh))
+    return int(mesh)
 
 
 def _clean_args(min_size, keep_largest, k, what, error=RuntimeError):
@@ -450,7 +472,17 @@ def _islands_kw(islands, what):
     if unknown:
         raise ValueError("%s: islands has no keyword %s (clean_scans takes %s)" % (what, ", ".join(unknown), ", ".join(_CLEAN_KEYS)))
     _clean_args(islands.get("min_size", 10), islands.get("keep_largest", True), islands.get("k", 8), what + ": islands", ValueError)
+    if _mesh_width(islands.get("mesh"), what + ": islands", ValueError) is not None and islands.get("nbr") is not None:
+        raise ValueError("%s: islands gives both mesh and nbr (one table or the other)" % what)
     return dict(islands)
+
+
+def _need_mesh(islands, scans, what):
+    """islands={"mesh": ...} on a set without faces: ValueError before the first forward pass (scans: the set, or a batcher)."""
+    if islands is not None and _mesh_width(islands.get("mesh"), what, ValueError) is not None:
+        if getattr(getattr(scans, "scans", scans), "faces", None) is None:
+            raise ValueError("%s: islands asks for the mesh table (mesh=%r) and the scan set holds no faces -- build it with "
+                             "DeviceScanSet(..., faces=)" % (what, islands["mesh"]))
 
 
 def _islands_batch(preds, batch, what):
@@ -495,13 +527,20 @@ def scan_neighbours(batch, k=8):
     k + 1 nearest vertices of the same scan as indices local to the scan, itself included, in geot_knn_sorted's (d2, index)
     order.  One geot_knn_sorted_ws call per slot (b = 1, nq = nr = M_s; the grid search at whole-scan sizes) on the scan's rows
     of scans.points, read in place from the batcher's views; the sizes are the host's.  A scan of fewer than k + 1 vertices is
-    refused, so the table never holds the search's filler.  Nothing is cached: a scan met again is searched again."""
+    refused, so the table never holds the search's filler.  By default nothing is cached and a scan met again is searched
+    again; after scans.keep_tables() every scan's table is kept on the set, only the missing ones are searched and the batch's
+    table is assembled from the kept ones (DeviceScanSet.keep_tables: the same bits, 4 (k + 1) M_i bytes per scan)."""
     scans, sizes, b, dev = _islands_batch(None, batch, "scan_neighbours")
     _, _, k = _clean_args(0, False, k, "scan_neighbours")
     for m in sizes:
         if m < k + 1:
             raise ValueError("scan_neighbours: a scan of %d vertices has no %d nearest vertices (k + 1)" % (m, k + 1))
     need(scans.points.is_cuda, "scan_neighbours: CPU not supported (the scans must live on the GPU)")
+    return _kept_or_built(batch, sizes, dev, "knn", k + 1, lambda part, part_sizes: (_knn_tables(part, part_sizes, dev, k), None))[0]
+
+
+def _knn_tables(batch, sizes, dev, k):
+    """scan_neighbours' searches: one geot_knn_sorted_ws call per slot."""
     rows = _scan_rows(batch, sizes, dev)
     nbr = torch.empty((sum(sizes), k + 1), dtype=torch.int32, device=dev)
     dist2 = torch.empty((max(sizes), k + 1), dtype=torch.float32, device=dev)       # the search writes it; nobody reads it
@@ -511,6 +550,89 @@ def scan_neighbours(batch, k=8):
         call("geot_knn_sorted_ws", dev, 1, m, m, k + 1, ptr(p), ptr(p), ptr(nbr) + 4 * (k + 1) * at, ptr(dist2), wp, wb)
         at += m
     return nbr
+
+
+def _kept_or_built(batch, sizes, dev, kind, width, build):
+    """The table cache of the set (DeviceScanSet.keep_tables) in front of build(batch, sizes) -> (table (sum M, width), stats
+    (B, 4) or None).  Off, or a batch without the host scan ids: build(batch, sizes) and nothing else.  On: the scans of the
+    batch that have no kept (scan, kind, width) table are built in ONE build call on a batch of just those, each table is kept
+    with an event recorded on the building stream, and the batch's table is the kept tables concatenated (device copies); a
+    stream other than the one that built a table waits for its event first."""
+    scans, ids = batch["scans"], batch.get("ids")
+    if not getattr(scans, "_keep", False) or ids is None:
+        return build(batch, sizes)
+    ids = [int(i) for i in ids]
+    need(len(ids) == len(sizes), "the batch's ids must name one scan per slot")
+    kept, stream = scans._tables, torch.cuda.current_stream(dev)
+    missing = [s for s, i in enumerate(ids) if (i, kind, width) not in kept and i not in ids[:s]]
+    if missing:
+        part = {"scans": scans, "sizes": [sizes[s] for s in missing], "ids": [ids[s] for s in missing],
+                "scan_ids": _to_device(np.asarray([ids[s] for s in missing], dtype=np.int64), dev)}
+        if isinstance(batch.get("points"), (list, tuple)) and len(batch["points"]) == len(sizes):
+            part["points"] = [batch["points"][s] for s in missing]
+        table, st = build(part, part["sizes"])
+        event = torch.cuda.Event()
+        event.record(stream)
+        for j, (s, rows) in enumerate(zip(missing, torch.split(table, part["sizes"]))):
+            kept[(ids[s], kind, width)] = (rows, None if st is None else st[j], event, stream)
+    tables, rows_st = [], []
+    for i in ids:
+        rows, st, event, built_on = kept[(i, kind, width)]
+        if built_on != stream:
+            stream.wait_event(event)
+            rows.record_stream(stream)
+        tables.append(rows)
+        rows_st.append(st)
+    return torch.cat(tables), (None if rows_st[0] is None else torch.stack(rows_st))
+
+
+@torch.no_grad()
+def mesh_neighbours(batch, k=MESH_K, stats=False):
+    """The one-ring neighbour table of the batch's whole scans from the set's triangles (DeviceScanSet(faces=)): (sum M, k) int32
+    on the device, slot after slot -- per vertex the distinct vertices it shares a face with, as indices local to the scan in
+    ascending order, the k lowest when there are more, -1 in every unused entry.  The surface's own graph: two teeth in contact
+    are not joined by it, as they are by scan_neighbours' Euclidean table, and it needs no search.  One geot_mesh_neighbours
+    call (seven launches), no host synchronisation; clean_scans and scan_components take the table as nbr= (or build it
+    themselves: mesh=).  stats=True: also the (B, 4) int32 device tensor of usable faces, ignored faces (an index outside the
+    scan), truncated vertices (more than k neighbours) and the longest row per scan.
+    k: an int in 1..32.  The default 16 rests on no measurement: the mean valence of a closed triangle mesh is 6, but no
+    Teeth3DS mesh has been looked at here -- stats[:, 2], the truncated vertices, says whether k is enough for yours.
+    The batch must carry the host scan ids ("ids": the whole-scan batchers add them for a set with faces; the face counts are
+    the host's).
+    ValueError, before any device call, when the set holds no faces or a scan of the batch has no mesh (has_mesh False).
+    After scans.keep_tables() every scan's table (and its stats row) is kept on the set and a scan met again costs a device
+    copy (DeviceScanSet.keep_tables: the same bits, 4 k M_i bytes per scan)."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= ISLANDS_MAX_K:
+        raise ValueError("mesh_neighbours: k must be an int in 1..%d, got %r" % (ISLANDS_MAX_K, k))
+    scans, sizes, b, dev = _islands_batch(None, batch, "mesh_neighbours")
+    if getattr(scans, "faces", None) is None:
+        raise ValueError("mesh_neighbours: the scan set holds no faces -- build it with DeviceScanSet(..., faces=)")
+    if batch.get("ids") is None or len(batch["ids"]) != b:
+        raise ValueError("mesh_neighbours: the batch must carry its %d scan numbers as host values (\"ids\", as ValBatcher.batch "
+                         "adds them): the face counts are the host's" % b)
+    ids = [int(i) for i in batch["ids"]]
+    for slot, i in enumerate(ids):
+        if not 0 <= i < len(scans) or not scans.has_mesh[i]:
+            raise ValueError("mesh_neighbours: batch slot %d (scan %d) has no mesh in this set" % (slot, i))
+    table, st = _kept_or_built(batch, sizes, dev, "mesh", int(k), lambda part, part_sizes: _mesh_tables(part, part_sizes, dev, int(k)))
+    return (table, st) if stats else table
+
+
+def _mesh_tables(batch, sizes, dev, k):
+    """One geot_mesh_neighbours call -> (table, stats)."""
+    scans, b, total_out = batch["scans"], len(sizes), sum(sizes)
+    counts = [scans.face_sizes[int(i)] for i in batch["ids"]]
+    batch_faces = sum(counts)
+    nbytes = int(_lib.load().geot_mesh_neighbours_ws_bytes(b, total_out, batch_faces))
+    need(nbytes >= 0, "geot_mesh_neighbours: no workspace for b = %d, %d vertices, %d faces" % (b, total_out, batch_faces))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    nbr = torch.empty((total_out, k), dtype=torch.int32, device=dev)
+    st = torch.empty((b, 4), dtype=torch.int32, device=dev)
+    face_out = _to_device(np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int64), dev)
+    call("geot_mesh_neighbours", dev, b, k, len(scans), int(scans.points.shape[0]), int(scans.faces.shape[0]), ptr(scans.faces),
+         ptr(scans.offsets), ptr(scans.face_offsets), ptr(batch["scan_ids"].contiguous()), ptr(_out_offsets(sizes, dev)), ptr(face_out),
+         batch_faces, ptr(nbr), ptr(st), ptr(ws), nbytes)
+    return nbr, st
 
 
 def _scan_islands(flat, nbr, c, min_size, keep, allowed, batch, sizes, b, dev, want_comp, want_stats):
@@ -533,18 +655,21 @@ def _scan_islands(flat, nbr, c, min_size, keep, allowed, batch, sizes, b, dev, w
 
 
 @torch.no_grad()
-def scan_components(preds, batch, nbr=None, k=8, num_classes=None, stats=False):
+def scan_components(preds, batch, nbr=None, k=8, num_classes=None, stats=False, mesh=None):
     """The connected pieces of whole-scan labels: per scan of the batch a (1, M_i) int32 tensor (views of one buffer) that
     holds for every vertex the lowest vertex index of its piece -- the vertices of equal label it reaches through the
     neighbour table.  preds as predict_scans and its kin return them; they are not touched.  nbr: scan_neighbours' table, or
     any (sum M, 1..32) int32 table of scan-local indices (default: scan_neighbours(batch, k)).  A label outside [0, C) is a
     piece of its own.  num_classes: default 32.  stats=True: also the (B, 4) int32 device tensor of geot_scan_islands (pieces
-    among the labels in [0, C), then three zeros).  One geot_scan_islands call in its components-only form (four launches),
-    no host synchronisation."""
+    among the labels in [0, C), then three zeros).  mesh (None / False: off): True or an int in 1..32 -- the table is
+    mesh_neighbours(batch, 16 or that width), the scan's own triangles; k is then ignored, and nbr with it is a RuntimeError.
+    One geot_scan_islands call in its components-only form (four launches), no host synchronisation."""
+    width = _mesh_width(mesh, "scan_components")
+    need(width is None or nbr is None, "scan_components: mesh and nbr are two tables -- give one")
     scans, sizes, b, dev = _islands_batch(preds, batch, "scan_components")
     c = _need_classes(32 if num_classes is None else num_classes, "scan_components")
     if nbr is None:
-        nbr = scan_neighbours(batch, k)
+        nbr = scan_neighbours(batch, k) if width is None else mesh_neighbours(batch, width)
     flat, _ = _flat_labels(preds, sizes, dev)
     comp, st = _scan_islands(flat, nbr, c, 0, None, None, batch, sizes, b, dev, True, stats)
     out = [q.view(1, -1) for q in torch.split(comp, sizes)]
@@ -552,7 +677,7 @@ def scan_components(preds, batch, nbr=None, k=8, num_classes=None, stats=False):
 
 
 @torch.no_grad()
-def clean_scans(preds, batch, min_size=10, keep_largest=True, parts=None, nbr=None, k=8, stats=False, num_classes=None):
+def clean_scans(preds, batch, min_size=10, keep_largest=True, parts=None, nbr=None, k=8, stats=False, num_classes=None, mesh=None):
     """One FDI class in one jaw is one tooth, one connected patch of the surface: preds as predict_scans / vote_scans /
     cover_scans / decode_scans return them -- per scan of the batch a (1, M_i) int64 tensor -- cleaned IN PLACE when they are
     views of one buffer, slot after slot (a list that is not is concatenated and split again); returns the list, with
@@ -564,9 +689,13 @@ def clean_scans(preds, batch, min_size=10, keep_largest=True, parts=None, nbr=No
     equals), and stays as it is when there is none.  One pass on the labels as they came in.
     keep_largest: True -- every class from 1 up; class 0, the gingiva, may lie in pieces and is never kept to one -- or an
     iterable of classes, or False.  parts: None or the reference's cls2parts, as for refine_scans.  nbr, k: as for
-    scan_components.  num_classes: default parts[-1][-1] + 1, 32 without parts.  One geot_scan_islands call (six launches)
-    behind the table's searches, no host synchronisation."""
+    scan_components.  num_classes: default parts[-1][-1] + 1, 32 without parts.  mesh: as for scan_components -- "connected"
+    then means connected over the scan's triangles (a set built with faces=), not over the 8 nearest vertices in space, which
+    join two teeth in contact.  One geot_scan_islands call (six launches) behind the table's searches or its
+    geot_mesh_neighbours call, no host synchronisation."""
     min_size, keep, k = _clean_args(min_size, keep_largest, k, "clean_scans")
+    width = _mesh_width(mesh, "clean_scans")
+    need(width is None or nbr is None, "clean_scans: mesh and nbr are two tables -- give one")
     scans, sizes, b, dev = _islands_batch(preds, batch, "clean_scans")
     if num_classes is None:
         num_classes = 32 if parts is None else int(parts[-1][-1]) + 1
@@ -580,7 +709,7 @@ def clean_scans(preds, batch, min_size=10, keep_largest=True, parts=None, nbr=No
     mask = sum(1 << i for i in classes)
     keep_masks = np.full(b, mask, dtype=np.uint32) if mask else None
     if nbr is None:
-        nbr = scan_neighbours(batch, k)
+        nbr = scan_neighbours(batch, k) if width is None else mesh_neighbours(batch, width)
     flat, views = _flat_labels(preds, sizes, dev)
     out = list(preds) if views else [f.view(p.shape) for f, p in zip(torch.split(flat, sizes), preds)]
     _, st = _scan_islands(flat, nbr, c, min_size, keep_masks, allowed, batch, sizes, b, dev, False, stats)
@@ -1075,6 +1204,7 @@ def validate_scans(model, scans, cfg, batch_size=2, indices=None, stream=None, n
     else:
         need(_cfg(cfg, "num_points") is not None, "validate_scans: cfg.num_points (the sample size) is missing")
         batcher = ValBatcher(scans, _cfg(cfg, "num_points"), c, stream=stream)
+    _need_mesh(islands, batcher, "validate_scans")
     return _validate(model, batcher, cfg, c, batch_size, indices, 0, None, n_refine, parts, "validate_scans", lookahead, graphed,
                      teeth, islands)
 
@@ -1148,6 +1278,7 @@ def vote_scans(model, batcher, idx, num_votes, draws=None, refine=0, parts=None,
     n_refine = _refine_n(refine, "vote_scans")
     islands = _islands_kw(islands, "vote_scans")
     lookahead, graphed = _replay_switches(graph, lookahead, int(num_votes), model, "vote_scans")
+    _need_mesh(islands, batcher, "vote_scans")
     model.eval()
     votes = preds = None
     for data, logits, first, last in _passes(model, batcher, [idx], int(num_votes), draws, lookahead, graphed):
@@ -1191,6 +1322,7 @@ def validate_scans_voted(model, scans, cfg, num_votes=None, vote=None, batch_siz
         kwargs = _cfg(transforms, "kwargs") if transforms is not None else None
         batcher = VoteBatcher(scans, _cfg(cfg, "num_points"), c, vote=DEFAULT_VOTE if vote is None else vote,
                               kwargs=TOOTH_VIEW_KWARGS if kwargs is None else kwargs, stream=stream, draws=draws)
+    _need_mesh(islands, batcher, "validate_scans_voted")
     return _validate(model, batcher, cfg, c, batch_size, indices, num_votes, draws, n_refine, parts, "validate_scans_voted",
                      lookahead, graphed, teeth, islands)
 
@@ -1298,6 +1430,7 @@ def cover_scans(model, batcher, idx, rounds=1, interpolate=False, draws=None, re
     n_refine = _refine_n(refine, "cover_scans")
     islands = _islands_kw(islands, "cover_scans")
     rounds = _rounds(rounds, "cover_scans")
+    _need_mesh(islands, batcher, "cover_scans")
     model.eval()
     preds, data, c = _cover_run(model, batcher, idx, rounds, interpolate, draws, graph, lookahead, "cover_scans")
     return _finish_labels(preds, data, n_refine, parts, islands, c)
@@ -1326,6 +1459,7 @@ def validate_scans_covered(model, scans, cfg, rounds=1, interpolate=False, batch
     else:
         need(_cfg(cfg, "num_points") is not None, "%s: cfg.num_points (the sample size) is missing" % what)
         batcher = ValBatcher(scans, _cfg(cfg, "num_points"), c, stream=stream, draws=draws)
+    _need_mesh(islands, batcher, what)
     order = list(range(len(batcher))) if indices is None else [int(i) for i in indices]
     metrics = SegMetrics(c, batcher.device)
     _need_teeth(teeth, c, batcher.device, what)
@@ -1457,6 +1591,7 @@ def decode_scans(model, batcher, idx, refine=0, parts=None, chunk=32768, draws=N
     islands: as for predict_scans."""
     n_refine = _refine_n(refine, "decode_scans")
     islands = _islands_kw(islands, "decode_scans")
+    _need_mesh(islands, batcher, "decode_scans")
     seg = getattr(model, "segmentor", model)
     c = _need_classes(getattr(seg, "nclasses", batcher.c), "decode_scans")
     preds, data = _decode_run(model, batcher, [int(i) for i in idx], c, draws, chunk, "decode_scans")
@@ -1485,6 +1620,7 @@ def validate_scans_decoded(model, scans, cfg, batch_size=2, indices=None, stream
     else:
         need(_cfg(cfg, "num_points") is not None, "%s: cfg.num_points (the sample size) is missing" % what)
         batcher = ValBatcher(scans, _cfg(cfg, "num_points"), c, stream=stream, draws=draws)
+    _need_mesh(islands, batcher, what)
     order = list(range(len(batcher))) if indices is None else [int(i) for i in indices]
     metrics = SegMetrics(c, batcher.device)
     _need_teeth(teeth, c, batcher.device, what)

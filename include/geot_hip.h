@@ -25,10 +25,11 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 35
+#define GEOT_ABI_VERSION 36
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
+#define GEOT_MESH_NEIGHBOURS_LANE_ROW 64   /* geot_mesh_neighbours: the longest raw row (two entries per face at the vertex) one lane tidies */
 
 /* ABI version / diagnostics. */
 int geot_abi_version(void);
@@ -1125,6 +1126,55 @@ long long geot_scan_islands_ws_bytes(int b, long long total_out, int c);
 int geot_scan_islands(int b, int c, int k, int min_size, int n_scans, long long total, const long long *offsets,
                       const long long *scan_ids, const long long *out_offsets, const int *nbr, const unsigned *keep,
                       const unsigned *allowed, long long *pred, int *comp, int *stats, void *ws, long long ws_bytes, void *stream);
+
+/* ---- one-ring neighbour tables of whole-scan triangle meshes (ABI 36) -----------------------------------------------------------
+ * geot_mesh_neighbours: for b batch slots the table geot_scan_islands reads, built from the scans' triangles and not from a
+ * spatial search -- seven launches whatever the slots, their sizes and their faces; no host synchronisation, nothing read back,
+ * kernels only (no memset node: the call captures as kernel nodes).
+ * offsets, scan_ids, out_offsets and the slots: as for geot_scan_islands; M_s is the vertex count of slot s's scan.  faces:
+ * (total_faces, 3) int32 vertex indices local to their scan, the scans' faces concatenated; face_offsets (n_scans + 1): scan i's
+ * faces are rows face_offsets[i] .. face_offsets[i + 1] of faces.  face_out_offsets (b + 1, device): the prefix of the slots'
+ * face counts within this batch (slot s has face_out_offsets[s + 1] - face_out_offsets[s] faces); batch_faces: the same total
+ * as a host value -- every usable slot's pair lies in [0, batch_faces].  nbr: (total_out, k) int32, WRITTEN, laid out exactly
+ * as geot_scan_islands reads it.  Per usable slot:
+ *   usable face  a face is usable iff all three of its indices lie in [0, M_s).  Any other face is IGNORED as a whole and counted;
+ *                an index outside that range is never used as an address.
+ *   row          row out_offsets[s] + v holds the DISTINCT vertices u != v that share a usable face with v, in ASCENDING index
+ *                order; more than k of them: the k lowest (v is TRUNCATED).  Every unused entry is -1; a vertex in no usable
+ *                face has a row of -1.  A usable face with a repeated index contributes its remaining distinct pair (none when
+ *                all three are equal); v itself is never stored.  Duplicate faces and either winding change nothing.
+ * stats (optional): (b, 4) int32, WRITTEN (a skipped slot: zeros) -- usable faces, ignored faces, truncated vertices, the longest
+ * row written (the most entries other than -1 in a row of the slot: at most k).
+ * Every output is an integer and depends on the SET of the slot's faces only -- not on their order, on the order of a face's
+ * corners or on the schedule -- so the same call gives the same bits and a numpy restatement gives them too.  Integer atomics
+ * only (raw degrees, fill cursors, the stats).  The form: per face 2 is added to the raw degree of each corner; an exclusive
+ * scan of the raw degrees over all vertex rows (block-local scan, scan of the block sums, add: no look-back, no workgroup ever
+ * waits for another); per face each corner reserves two entries of its raw row on a cursor and stores the two other corners;
+ * per vertex the k lowest distinct values of its raw row are extracted by repeated "smallest value greater than the last one
+ * written", with one round more to detect truncation.  A raw row of at most GEOT_MESH_NEIGHBOURS_LANE_ROW entries (that many / 2
+ * faces at the vertex) is walked by one lane, a longer one by a whole wave.  Every loop is bounded by a count known at its start.
+ * GEOT_MESH_NEIGHBOURS_IMPL=basic (read at every call): a lane per vertex whatever the row, one stats atomic per lane in place
+ * of the form combined inside the wave; the same bits.
+ * ws: geot_mesh_neighbours_ws_bytes(b, total_out, batch_faces) bytes, 16-byte aligned, contents irrelevant; total_out = the
+ * rows of nbr (every out_offsets[s] + M_s <= total_out).  It holds the 6 batch_faces raw entries (24 batch_faces bytes, rounded up
+ * to 16) and total_out + total_out / 4096 + 2 units of 16 bytes: per vertex row its row start and its cursor, per started 4096
+ * rows a block sum, and the grand total (a whole unit per row, so that the size names total_out exactly: the call is not told
+ * total_out and takes its vertex capacity from ws_bytes).  A slot whose scan_ids entry lies outside [0, n_scans), whose offsets
+ * pair is not 0 <= lo < hi <= total with hi - lo <= 2^31 - 1, whose out_offsets entry does not leave room for it in a
+ * ws_bytes-sized workspace -- the total_out that geot_mesh_neighbours_ws_bytes(b, total_out, batch_faces) = ws_bytes names --,
+ * whose face_offsets pair is not 0 <= lo <= hi <= total_faces, or whose face_out_offsets pair is not 0 <= a <= z <= batch_faces
+ * with z - a = hi - lo is skipped: nothing of it is read or written.  The usable slots' ranges of rows must not overlap
+ * (overlapping ranges give wrong rows, never an access outside nbr or ws).
+ * 0 <= b <= 65535 (0: nothing to do), 1 <= k <= 32, n_scans >= 1, total >= 1, total_faces >= 0, 0 <= batch_faces,
+ * 6 batch_faces <= 2^31 - 1, no NULL among offsets, face_offsets, scan_ids, out_offsets, face_out_offsets, nbr and ws (faces may
+ * be NULL only when total_faces == 0), ws 16-byte aligned, ws_bytes >= geot_mesh_neighbours_ws_bytes(b, 0, batch_faces);
+ * anything else is hipErrorInvalidValue before any launch.  geot_mesh_neighbours_ws_bytes: -1 for arguments outside these
+ * ranges, total_out < 0 or total_out > 2^30. */
+long long geot_mesh_neighbours_ws_bytes(int b, long long total_out, long long batch_faces);
+int geot_mesh_neighbours(int b, int k, int n_scans, long long total, long long total_faces, const int *faces,
+                         const long long *offsets, const long long *face_offsets, const long long *scan_ids,
+                         const long long *out_offsets, const long long *face_out_offsets, long long batch_faces, int *nbr,
+                         int *stats, void *ws, long long ws_bytes, void *stream);
 
 /* ---- transform lists as per-view programs (ABI 16) ---------------------------------------------------------------------------
  * geot_view_program: geot_fixmatch_views for ANY list of the reference's point transforms that keeps the point count
