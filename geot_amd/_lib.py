@@ -43,6 +43,7 @@ KNN_KMAX_HEAP = CONSTANTS["GEOT_KNN_KMAX_HEAP"]       # largest nsample of the h
 KNN_KMAX_SORTED = CONSTANTS["GEOT_KNN_KMAX_SORTED"]   # largest k of the sorted kNN (knn_cuda.KNN, knn_point in 3-D)
 NTM_MAX_C = CONSTANTS["GEOT_NTM_MAX_C"]               # largest class count of the per-point kernels (NTM, criteria, meters)
 MESH_NEIGHBOURS_LANE_ROW = CONSTANTS["GEOT_MESH_NEIGHBOURS_LANE_ROW"]     # geot_mesh_neighbours: the longest raw row one lane tidies
+CURVATURE_MAX_SCAN = CONSTANTS["GEOT_CURVATURE_MAX_SCAN"]     # geot_mesh_angle_defects / geot_scan_ball_sum: vertices of one scan
 VIEW_JOB_WORDS = CONSTANTS["GEOT_VIEW_JOB_WORDS"]   # 32-bit words of one geot_fixmatch_views job record
 VIEW_REG_POINTS = CONSTANTS["GEOT_VIEW_REG_POINTS"]   # largest cloud geot_fixmatch_views holds in registers
 VIEW_MAX_OPS = CONSTANTS["GEOT_VIEW_MAX_OPS"]         # ops of one geot_view_program job

@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "libgeot_hip.so")
 VARIANTS = {"exact": (0, LIB), "fma": (1, os.path.join(HERE, "libgeot_hip_fma.so")),
             "fma_xy": (2, os.path.join(HERE, "libgeot_hip_fma_xy.so"))}
 
-SOURCES = ["fps.hip", "neighbors.hip", "knn_grid.hip", "gather_group.hip", "tile_scatter.hip", "ntm.hip", "ntm_generic.hip", "ntm_outlier.hip", "sa_mlp.hip", "dataprep.hip", "edgeconv.hip", "bnrelu.hip", "channels_last.hip", "loss.hip", "layernorm.hip", "meters.hip", "seg_metrics.hip", "views.hip", "scan_predict.hip", "scan_cover.hip", "scan_decode.hip", "view_program.hip", "sample_draw.hip", "view_draw.hip", "scan_refine.hip", "scan_islands.hip", "mesh_neighbours.hip", "tooth_scores.hip", "pseudo_refine.hip", "contrast.hip", "optim_tail.hip", "max_conv.hip"]
+SOURCES = ["fps.hip", "neighbors.hip", "knn_grid.hip", "gather_group.hip", "tile_scatter.hip", "ntm.hip", "ntm_generic.hip", "ntm_outlier.hip", "sa_mlp.hip", "dataprep.hip", "edgeconv.hip", "bnrelu.hip", "channels_last.hip", "loss.hip", "layernorm.hip", "meters.hip", "seg_metrics.hip", "views.hip", "scan_predict.hip", "scan_cover.hip", "scan_decode.hip", "view_program.hip", "sample_draw.hip", "view_draw.hip", "scan_refine.hip", "scan_islands.hip", "mesh_neighbours.hip", "mesh_curvature.hip", "tooth_scores.hip", "pseudo_refine.hip", "contrast.hip", "optim_tail.hip", "max_conv.hip"]
 HEADERS = ["geot_common.h", "ntm_generic.h", "tile_scatter.h", "knn_grid.h", "seg_metrics.h", "scan_finish.h", "views.h", "philox.h", "view_draw.h", "rix.h", os.path.join(ROOT, "include", "geot_hip.h")]
 
 # -ffp-contract=off: squared distances must be un-contracted IEEE fp32 so that

@@ -7,6 +7,7 @@ random draws -- view parameters, jitter noise, colour masks -- likewise (view_dr
 voting, the `val` view and the `val` + `vote` view of one sample (vote_batch)."""
 from .grid_sample import grid_subsampling  # noqa: F401
 from .io import read_obj  # noqa: F401
+from .scan_set import mesh_curvature  # noqa: F401
 from .tooth_prep import pc_norm, prepare_sample  # noqa: F401
 from .fixmatch_batch import (TOOTH_VIEW_KWARGS, DeviceScanSet, FixMatchBatcher, cloud_sample_batch, draw_view_params,  # noqa: F401
                              fixmatch_views)

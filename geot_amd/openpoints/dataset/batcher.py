@@ -8,7 +8,7 @@ import torch
 
 from ...ext._common import need
 from .sample_draw import DeviceDraws, ViewDrawHandle, draw_batch_sel, on_stream
-from .scan_set import DeviceScanSet, cloud_sample_batch, raise_bad_index
+from .scan_set import DeviceScanSet, _to_device, check_curvature, cloud_sample_batch, curvature_sample, raise_bad_index
 from .view_draw import DrawLayout, view_program_draw, view_program_views_drawn
 from .view_program import pack_program_jobs, view_program_views
 
@@ -16,11 +16,18 @@ from .view_program import pack_program_jobs, view_program_views
 class Batcher:
     """The shared body (module text).  A batcher defines _jobs(*shape) -> (jobs [(source row, output row, program)], rows of
     raw, output rows, view number per job or None, slot per job or None) and _result(sampled, views, cls, ids, *shape) -> what
-    batch() returns; one whose views do not all run on geot_view_program overrides _pack and _views."""
+    batch() returns; one whose views do not all run on geot_view_program overrides _pack and _views.
+    curvatures=True (every batcher's constructor; default False: not one launch, allocation, key or bit differs): every dict
+    of a batch also holds "curvatures" (B, m) float32 -- the set's curvature (DeviceScanSet.compute_curvature) at the slots'
+    sampled vertices, as the reference's datasets make data['curvatures'] (tooth_dataset.py:156-160, 320-359): abs, min-max
+    over the WHOLE scan, gathered at the sample; 0 for a scan whose max equals its min.  One more launch
+    (geot_curvature_sample) on the batcher's stream.  A set without computed curvature, or a scan of the batch without a mesh,
+    is a ValueError before any device call; check=True also raises for an index outside its scan seen by that launch."""
 
     stream = draws = None    # (the constructor's; None: the current stream, the reference's host draws)
+    curvatures = False
 
-    def __init__(self, scans, num_points, num_classes, stream, draws):
+    def __init__(self, scans, num_points, num_classes, stream, draws, curvatures=False):
         who = type(self).__name__
         need(isinstance(scans, DeviceScanSet), "%s: scans must be a DeviceScanSet" % who)
         need(scans.device.type == "cuda", "%s: CPU not supported (the scans must live on the GPU)" % who)
@@ -28,6 +35,7 @@ class Batcher:
         need(1 <= int(num_classes) <= 4096, "%s: num_classes must be in [1, 4096]" % who)
         self.scans, self.device = scans, scans.device
         self.m, self.c, self.stream, self.draws = int(num_points), int(num_classes), stream, draws
+        self.curvatures = bool(curvatures)
         self._layouts = {}          # batch shape -> DrawLayout (templates and plans on the device, built once)
         if stream is not None:      # once: the scans are ready; a batch itself depends on nothing the current stream does
             stream.wait_stream(torch.cuda.current_stream(self.device))
@@ -42,6 +50,8 @@ class Batcher:
         -> (sel (S, m) int64, host array or device tensor; params; the scan ids on the device when the device drew)"""
         draws = self.draws if draws is None else draws
         need(draws is None or isinstance(draws, DeviceDraws), "draws must be a DeviceDraws (or None: the reference's host draws)")
+        if self.curvatures:
+            check_curvature(self.scans, ids, type(self).__name__)
         runs, first = [], 0
         for name, rows, count in given:
             if rows is not None:
@@ -104,6 +114,9 @@ class Batcher:
         handle = isinstance(params, ViewDrawHandle)
         packed = None if handle else self._pack(shape, params)
         with on_stream(self.stream):
+            if self.curvatures:     # the sample on the device once, for both launches that read it
+                sel = (sel.to(self.device).contiguous() if isinstance(sel, torch.Tensor)
+                       else _to_device(np.ascontiguousarray(sel), self.device))
             s = cloud_sample_batch(self.scans, ids, sel, self.c, check=False, ids_dev=ids_dev)
             if handle:      # the parameters are drawn where they are used
                 layout = self._layout(*shape)
@@ -113,11 +126,20 @@ class Batcher:
             out = self._result(s, v, self.scans.cls.index_select(0, s["scan_ids"]).view(-1, 1), ids, *shape)
             if affine:
                 out.update(self._affine(v, *shape))
+            if self.curvatures:
+                cur, cur_bad = curvature_sample(self.scans, s["scan_ids"], sel)
+                self._add_curvatures(out, cur, *shape)
         if check:
             if self.stream is not None:
                 self.stream.synchronize()
             raise_bad_index(s["bad"], ids)
+            if self.curvatures:
+                raise_bad_index(cur_bad, ids)
         return out
+
+    def _add_curvatures(self, out, cur, *shape):
+        """Put the (slots, m) curvatures into what _result returned (a batcher that returns several dicts splits them)."""
+        out["curvatures"] = cur
 
     def _join(self, tensors):
         """Hand a batch built on the side stream to the CURRENT stream: it waits for the side stream, and the caching

@@ -179,12 +179,15 @@ class FixMatchBatcher(Batcher):
     id: view 0 labelled, 1 weak, 2 strong), no host generator is read, and with transforms=None the three configured lists
     run as ViewPrograms, which give the bits of geot_fixmatch_views.  draw() then returns a ViewDrawHandle in place of the
     parameters, batch(params=handle) replays it, and explicit params= still win.
+
+    curvatures=True: data and data_u each hold "curvatures" (Batcher's class text); both sets must hold their curvature, of one
+    radius, BEFORE the batcher is built (it copies the two sets into one), or call batcher.scans.compute_curvature().
     """
 
     programs = None          # kind -> ViewProgram when `transforms` routes the views through geot_view_program
 
     def __init__(self, labelled, unlabelled, num_points, num_classes=17, kwargs=TOOTH_VIEW_KWARGS, stream=None, transforms=None,
-                 draws=None):
+                 draws=None, curvatures=False):
         need(isinstance(labelled, DeviceScanSet) and isinstance(unlabelled, DeviceScanSet),
              "FixMatchBatcher: labelled and unlabelled must be DeviceScanSets")
         need(int(_kw(kwargs, "gravity_dim")) in (0, 1, 2), "FixMatchBatcher: gravity_dim must be 0, 1 or 2")
@@ -196,7 +199,11 @@ class FixMatchBatcher(Batcher):
             need(all(p.has_heights for p in self.programs.values()),
                  "FixMatchBatcher: every list needs a PointCloudCenterAndNormalize (heights is a feature key)")
         self._draw_programs = self.programs      # the lists device view draws run on (None: built when first needed)
-        super().__init__(DeviceScanSet._merged(labelled, unlabelled), num_points, num_classes, stream, draws)
+        super().__init__(DeviceScanSet._merged(labelled, unlabelled), num_points, num_classes, stream, draws, curvatures)
+
+    def _add_curvatures(self, out, cur, bl, bu):
+        """data's and data_u's: the weak and the strong view of an unlabelled item share its sample, so data_u gets one tensor."""
+        out[0]["curvatures"], out[1]["curvatures"] = cur[:bl], cur[bl:bl + bu]
 
     def _draw_view(self, kind):
         return draw_view_params(kind, self.kwargs) if self.programs is None else self.programs[kind].draw(self.m)

@@ -43,7 +43,9 @@ class DeviceScanSet:
     the device, face_sizes and has_mesh host lists (None: face_sizes[i] = 0 and has_mesh[i] False; an empty (0, 3) array: a mesh
     with no faces).  An index that does not fit int32 is stored as -1 or 2^31 - 1: outside every scan either way.
     keep_tables(): validation.scan_neighbours and mesh_neighbours keep every scan's neighbour table on the set (off by
-    default)."""
+    default).
+    compute_curvature(): the per-vertex discrete Gaussian curvature of the scans with a mesh (`curvature`, `curvature_range`,
+    `curvature_radius`, `defects`: None until it is called), what the batchers' curvatures=True gathers from."""
 
     def __init__(self, scans, labels, cls=None, device=None, faces=None):
         need(len(scans) >= 1 and len(scans) == len(labels), "DeviceScanSet: one label array per scan, at least one scan")
@@ -73,6 +75,8 @@ class DeviceScanSet:
             self.face_offsets = torch.tensor(np.concatenate([[0], np.cumsum(self.face_sizes, dtype=np.int64)]),
                                              dtype=torch.int64).to(dev)
         self._keep, self._tables = False, {}
+        self.curvature = self.curvature_range = self.curvature_radius = self.defects = self._curvature_keys = None
+        self._curvature_tables = None
 
     def __len__(self):
         return len(self.sizes)
@@ -92,8 +96,78 @@ class DeviceScanSet:
         return self
 
     def drop_tables(self):
-        """Empty the cache of neighbour tables (the switch stays as it is)."""
+        """Empty the cache of neighbour tables (the switch stays as it is).  The curvature arrays are no cache: they depend on
+        the vertices, the faces and the radius, and whoever changes `points` or `faces` in place calls compute_curvature()
+        again."""
         self._tables = {}
+
+    def compute_curvature(self, radius=0.1, stats=False):
+        """The discrete Gaussian curvature measure of every vertex of every scan with a mesh, on the device: what the
+        reference reads from files made offline with trimesh.curvature.discrete_gaussian_curvature_measure(mesh, mesh.vertices,
+        radius) (openpoints/dataset/io.py:51-57).  The definition and the rules for unusable faces are include/geot_hip.h's
+        (ABI 37), restated from trimesh's documentation; agreement with trimesh itself is not tested.
+            defect(v)    = 2 pi - the sum of the face angles at v (boundary vertices too; a vertex in no face: 2 pi)
+            curvature(v) = the sum of defect(u) over the scan's vertices u with |u - v| <= radius, v included
+        radius is in the scan's RAW units (the reference computes it before pc_norm).  One geot_mesh_angle_defects call over
+        all scans with a mesh (three launches) and one geot_scan_ball_sum call per such scan (seven launches), on the current
+        stream, without a host synchronisation.  Stores
+            curvature        (sum N,) float32, 0 in scans without a mesh
+            curvature_range  (n, 2) float32: min and max of |curvature| over each WHOLE scan (0, 0 without a mesh): what the
+                             batchers' "curvatures" are normalised with, (|cur| - min) / (max - min), 0 where max == min (the
+                             reference's commented code would give NaN there)
+            curvature_radius the radius, a float
+            defects          (sum N,) int64: the defects as integers, llrint(2 pi 2^32) - sum of llrint(angle 2^32)
+        and returns self -- with stats=True the (scans with a mesh, 4) int32 device tensor of usable, ignored (an index outside
+        the scan or a repeated one) and degenerate faces (a zero-length edge, a non-finite coordinate) and of vertices in no
+        usable face, in scan order.  Calling it again with another radius recomputes.  ValueError, before any device call, for
+        a set without faces and for a radius that is not a finite positive number.  The arrays are a pure function of the
+        vertices, the faces and the radius: whoever changes `points` or `faces` in place calls it again."""
+        r = check_radius(radius, "compute_curvature")
+        if self.faces is None:
+            raise ValueError("compute_curvature: the scan set holds no faces -- build it with DeviceScanSet(..., faces=)")
+        max_scan = _lib.CURVATURE_MAX_SCAN
+        meshed = [i for i, has in enumerate(self.has_mesh) if has]
+        for i in meshed:
+            if self.sizes[i] > max_scan:
+                raise ValueError("compute_curvature: scan %d has %d vertices, more than %d" % (i, self.sizes[i], max_scan))
+        dev, lib, total, n = self.device, _lib.load(), int(self.points.shape[0]), len(self)
+        if self._curvature_tables is None:         # once per set: the slots of the defect calls, 65535 scans at most each
+            starts = np.concatenate([[0], np.cumsum(self.sizes, dtype=np.int64)])
+            chunks = []
+            for first in range(0, len(meshed), 65535):
+                part = meshed[first:first + 65535]
+                counts = [self.face_sizes[i] for i in part]
+                chunks.append((len(part), sum(counts), _to_device(np.asarray(part, dtype=np.int64), dev),
+                               _to_device(starts[part].astype(np.int64), dev),
+                               _to_device(np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int64), dev)))
+            self._curvature_tables = (chunks, starts)
+        chunks, starts = self._curvature_tables
+        defects = torch.empty(total, dtype=torch.int64, device=dev)
+        cur = torch.empty(total, dtype=torch.float32, device=dev)
+        if len(meshed) < n:
+            defects.fill_(0)
+            cur.fill_(0)
+        keys = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        keys.fill_(-2 ** 31)                        # the key of 0.0 (min = max = 0): what a scan without a mesh keeps
+        st = torch.empty((len(meshed), 4), dtype=torch.int32, device=dev) if stats else None
+        nbytes = int(lib.geot_mesh_angle_defects_ws_bytes(total))
+        need(nbytes >= 0, "geot_mesh_angle_defects: no workspace for %d vertices" % total)
+        ws, row = torch.empty(nbytes, dtype=torch.uint8, device=dev), 0
+        for b, batch_faces, ids_dev, out_dev, face_out_dev in chunks:
+            call("geot_mesh_angle_defects", dev, b, n, total, int(self.faces.shape[0]), ptr(self.points), ptr(self.faces),
+                 ptr(self.offsets), ptr(self.face_offsets), ptr(ids_dev), ptr(out_dev), ptr(face_out_dev), batch_faces, total,
+                 ptr(defects), ptr(st[row:row + b]) if stats else None, ptr(ws), nbytes)
+            row += b
+        if meshed:
+            nbytes = int(lib.geot_scan_ball_sum_ws_bytes(max(self.sizes[i] for i in meshed)))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            for i in meshed:
+                lo, m = int(starts[i]), self.sizes[i]
+                call("geot_scan_ball_sum", dev, m, r, ptr(self.points[lo:lo + m]), ptr(defects[lo:lo + m]), ptr(cur[lo:lo + m]),
+                     ptr(keys[i]), ptr(ws), nbytes)
+        self.curvature, self.defects, self.curvature_radius, self._curvature_keys = cur, defects, r, keys
+        self.curvature_range = (keys & 0x7fffffff).view(torch.float32)          # a non-negative float's key: its bits, top bit set
+        return st if stats else self
 
     @classmethod
     def _merged(cls, a, b):
@@ -113,7 +187,68 @@ class DeviceScanSet:
             out.face_offsets = torch.tensor(np.concatenate([[0], np.cumsum(out.face_sizes, dtype=np.int64)]),
                                             dtype=torch.int64).to(a.device)
         out._keep, out._tables = False, {}
+        out.curvature = out.curvature_range = out.curvature_radius = out.defects = out._curvature_keys = None
+        out._curvature_tables = None
+        if (getattr(a, "curvature", None) is not None and getattr(b, "curvature", None) is not None
+                and a.curvature_radius == b.curvature_radius):      # both sides, the same radius: carried over; otherwise dropped
+            out.curvature, out.defects = torch.cat([a.curvature, b.curvature]), torch.cat([a.defects, b.defects])
+            out._curvature_keys = torch.cat([a._curvature_keys, b._curvature_keys])
+            out.curvature_range = torch.cat([a.curvature_range, b.curvature_range])
+            out.curvature_radius = a.curvature_radius
         return out
+
+
+def check_radius(radius, who):
+    """A finite positive number that stays one as a float32 -> float; ValueError otherwise (before any device call)."""
+    ok = isinstance(radius, (int, float, np.integer, np.floating)) and not isinstance(radius, (bool, np.bool_))
+    if ok:
+        with np.errstate(over="ignore"):
+            as32 = float(np.float32(radius))
+        ok = np.isfinite(as32) and as32 > 0.0
+    if not ok:
+        raise ValueError("%s: radius must be a finite positive number, got %r" % (who, radius))
+    return float(radius)
+
+
+def mesh_curvature(scans, radius=0.1):
+    """The functional form of DeviceScanSet.compute_curvature: computes the set's curvature with this radius unless it holds
+    it already -> the per-scan list of (M_i,) float32 views into scans.curvature (zeros for a scan without a mesh)."""
+    if not isinstance(scans, DeviceScanSet):
+        raise ValueError("mesh_curvature: scans must be a DeviceScanSet")
+    r = check_radius(radius, "mesh_curvature")
+    if scans.curvature is None or scans.curvature_radius != r:
+        scans.compute_curvature(r)
+    return list(torch.split(scans.curvature, scans.sizes))
+
+
+def check_curvature(scans, ids, who):
+    """What curvatures=True needs of a batch's scans, on the host: ValueError before any device call."""
+    if getattr(scans, "curvature", None) is None:
+        raise ValueError("%s: curvatures=True needs the set's curvature -- call scans.compute_curvature() first (for a "
+                         "FixMatchBatcher on both sets, with one radius, before it is built)" % who)
+    for slot, i in enumerate(ids):
+        if scans.has_mesh is None or not scans.has_mesh[int(i)]:
+            raise ValueError("%s: batch slot %d (scan %d) has no mesh in this set: it has no curvature" % (who, slot, int(i)))
+
+
+def curvature_sample(scans, ids_dev, sel_dev):
+    """geot_curvature_sample, one launch on the current stream: ids_dev (S,) int64 scan numbers and sel_dev (S, m) int64 vertex
+    indices local to each slot's scan, both on the device -> (curvatures (S, m) float32 = (|cur[sel]| - min) / (max - min)
+    with the min and max of |cur| over the slot's WHOLE scan, 0 where max == min; bad (S,) int32: 1 where an index lies
+    outside its scan (that entry is 0), 2 for a scan number outside the set)."""
+    need(getattr(scans, "curvature", None) is not None, "curvature_sample: call scans.compute_curvature() first")
+    dev = scans.device
+    need(ids_dev.dtype == torch.int64 and ids_dev.device == dev and ids_dev.dim() == 1 and ids_dev.is_contiguous(),
+         "curvature_sample: ids_dev must be a contiguous (S,) int64 tensor on %s" % dev)
+    s = int(ids_dev.shape[0])
+    need(sel_dev.dtype == torch.int64 and sel_dev.device == dev and sel_dev.dim() == 2 and sel_dev.is_contiguous() and
+         sel_dev.shape[0] == s and sel_dev.shape[1] >= 1 and 1 <= s <= 65535,
+         "curvature_sample: sel_dev must be a contiguous (S, m >= 1) int64 tensor on %s, 1 <= S <= 65535" % dev)
+    out = torch.empty(tuple(sel_dev.shape), dtype=torch.float32, device=dev)
+    bad = torch.empty(s, dtype=torch.int32, device=dev)
+    call("geot_curvature_sample", dev, s, int(sel_dev.shape[1]), len(scans), int(scans.points.shape[0]), ptr(scans.curvature),
+         ptr(scans._curvature_keys), ptr(scans.offsets), ptr(ids_dev), ptr(sel_dev), ptr(out), ptr(bad))
+    return out, bad
 
 
 def cloud_sample_batch(scans, scan_ids, sel, num_classes=17, check=True, ids_dev=None):

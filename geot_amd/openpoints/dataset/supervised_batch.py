@@ -39,12 +39,14 @@ class SupervisedBatcher(Batcher):
     samples of a batch in one geot_sample_draw launch on the batcher's stream (one draw id per slot) and np.random.choice
     is not called.  Given here it serves every batch, given to batch() / draw() that call; an explicit sel= still wins.
     With DeviceDraws(seed, views=True) the list's parameters are device draws too: no host generator is read, draw()
-    returns a ViewDrawHandle in place of the parameters, and batch(params=handle) replays it; an explicit params= wins."""
+    returns a ViewDrawHandle in place of the parameters, and batch(params=handle) replays it; an explicit params= wins.
+
+    curvatures=True adds "curvatures" (B, m) float32 (Batcher's class text)."""
 
     def __init__(self, scans, num_points, num_classes=17, transforms=DEFAULT_TRAIN, kwargs=DEFAULT_TRAIN_KWARGS, stream=None,
-                 draws=None):
+                 draws=None, curvatures=False):
         self.program = ViewProgram(transforms, kwargs)          # NotImplementedError for what the kernel cannot do
-        super().__init__(scans, num_points, num_classes, stream, draws)
+        super().__init__(scans, num_points, num_classes, stream, draws, curvatures)
 
     def __len__(self):
         return len(self.scans)

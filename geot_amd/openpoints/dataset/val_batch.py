@@ -28,6 +28,7 @@ from ...ext._common import need
 from .batcher import Batcher
 from .fixmatch_batch import TOOTH_VIEW_KWARGS, _kw, draw_view_params, fixmatch_views
 from .sample_draw import DeviceDraws, cover_passes, on_stream, sample_draw_cover
+from .scan_set import check_curvature
 
 
 def draw_val_sel(sizes, num_points):
@@ -51,8 +52,8 @@ class ScanBatcher(Batcher):
 
     join_keys = ("pos", "x", "y", "cls", "center", "scale", "scan_ids")
 
-    def __init__(self, scans, num_points, num_classes, kwargs, stream, draws):
-        super().__init__(scans, num_points, num_classes, stream, draws)
+    def __init__(self, scans, num_points, num_classes, kwargs, stream, draws, curvatures=False):
+        super().__init__(scans, num_points, num_classes, stream, draws, curvatures)
         self.kwargs = kwargs
         self.cls_host = [int(v) for v in scans.cls.cpu().tolist()]       # the one copy: validate's `cls[ii] == 0` per scan
         self._points = list(torch.split(scans.points, scans.sizes))      # views
@@ -79,7 +80,7 @@ class ScanBatcher(Batcher):
 
     def join(self, batch):
         """Hand a batch built on the side stream to the CURRENT stream (Batcher._join)."""
-        self._join(batch[key] for key in self.join_keys + tuple(k for k in ("sel", "view_center", "view_scale") if k in batch))
+        self._join(batch[key] for key in self.join_keys + tuple(k for k in ("sel", "view_center", "view_scale", "curvatures") if k in batch))
 
     def _affine(self, v, b):
         """The `val` view's centre-and-normalise of every slot, as the views launch wrote it: pos = (raw - view_center) /
@@ -101,6 +102,8 @@ class ScanBatcher(Batcher):
         shared by its passes; otherwise the vote list draws on the host per pass, as in batch()."""
         ids, who = self._ids(idx), type(self).__name__
         draws = self.draws if draws is None else draws
+        if self.curvatures:
+            check_curvature(self.scans, ids, who)
         if not isinstance(draws, DeviceDraws):
             raise ValueError("%s.cover: a covering draw is a device draw -- pass draws=DeviceDraws(seed) here or to the "
                              "constructor (there is no host-draw form), got %r" % (who, draws))
@@ -134,10 +137,12 @@ class ValBatcher(ScanBatcher):
     draws: None keeps the reference's np.random.choice per item on the host (draw_val_sel); a sample_draw.DeviceDraws draws
     the vertex samples of a batch in one geot_sample_draw launch on the batcher's stream (one draw id per slot) and
     np.random.choice is not called.  Given here it serves every batch, given to batch() that call; sel= still wins.
-    DeviceDraws(seed, views=True) is accepted and changes nothing: the `val` list draws no view parameter."""
+    DeviceDraws(seed, views=True) is accepted and changes nothing: the `val` list draws no view parameter.
 
-    def __init__(self, scans, num_points, num_classes=17, kwargs=TOOTH_VIEW_KWARGS, stream=None, draws=None):
-        super().__init__(scans, num_points, num_classes, kwargs, stream, draws)
+    curvatures=True adds "curvatures" (B, m) float32 to every batch, the covering ones too (Batcher's class text)."""
+
+    def __init__(self, scans, num_points, num_classes=17, kwargs=TOOTH_VIEW_KWARGS, stream=None, draws=None, curvatures=False):
+        super().__init__(scans, num_points, num_classes, kwargs, stream, draws, curvatures)
         need(int(_kw(kwargs, "gravity_dim")) in (0, 1, 2), "ValBatcher: gravity_dim must be 0, 1 or 2")
 
     def batch(self, idx, sel=None, check=False, draws=None, affine=False):

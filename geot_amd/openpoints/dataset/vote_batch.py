@@ -34,16 +34,18 @@ class VoteBatcher(ScanBatcher):
     NotImplementedError here, before any device call.
 
     stream / draws: as ValBatcher's; with DeviceDraws(seed, views=True) the vote list's parameters are device draws too, and
-    an explicit params= still wins.  Call `join(batch)` before the current stream reads a batch built on a side stream."""
+    an explicit params= still wins.  Call `join(batch)` before the current stream reads a batch built on a side stream.
+    curvatures=True adds "curvatures" (B, m) float32 to every batch, the covering ones too (Batcher's class text)."""
 
     join_keys = ScanBatcher.join_keys + ("pos_search",)
 
-    def __init__(self, scans, num_points, num_classes=17, vote=DEFAULT_VOTE, kwargs=TOOTH_VIEW_KWARGS, stream=None, draws=None):
+    def __init__(self, scans, num_points, num_classes=17, vote=DEFAULT_VOTE, kwargs=TOOTH_VIEW_KWARGS, stream=None, draws=None,
+                 curvatures=False):
         need(not isinstance(vote, str), "VoteBatcher: vote is a list of transform class names")
         self.vote = list(vote)
         self.val_program = ViewProgram(VAL_LIST, kwargs)
         self.program = ViewProgram(VAL_LIST + self.vote, kwargs)       # NotImplementedError for what the kernel cannot do
-        super().__init__(scans, num_points, num_classes, kwargs, stream, draws)
+        super().__init__(scans, num_points, num_classes, kwargs, stream, draws, curvatures)
 
     def batch(self, idx, sel=None, params=None, check=False, draws=None, affine=False):
         """idx: scan numbers within the set; sel (B, m) vertex indices per scan and params (per scan one ViewProgram.draw

@@ -25,10 +25,11 @@
 extern "C" {
 #endif
 
-#define GEOT_ABI_VERSION 36
+#define GEOT_ABI_VERSION 37
 #define GEOT_KNN_KMAX_HEAP 1024    /* largest nsample of geot_knnquery_heap / geot_knnquery_heap_ws */
 #define GEOT_KNN_KMAX_SORTED 4096  /* largest k of geot_knn_sorted / geot_knn_sorted_ws */
 #define GEOT_NTM_MAX_C 32   /* largest class count of the geot_ntm_* entry points */
+#define GEOT_CURVATURE_MAX_SCAN 16777216    /* geot_mesh_angle_defects / geot_scan_ball_sum: the most vertices of one scan (2^24) */
 #define GEOT_MESH_NEIGHBOURS_LANE_ROW 64   /* geot_mesh_neighbours: the longest raw row (two entries per face at the vertex) one lane tidies */
 
 /* ABI version / diagnostics. */
@@ -1175,6 +1176,86 @@ int geot_mesh_neighbours(int b, int k, int n_scans, long long total, long long t
                          const long long *offsets, const long long *face_offsets, const long long *scan_ids,
                          const long long *out_offsets, const long long *face_out_offsets, long long batch_faces, int *nbr,
                          int *stats, void *ws, long long ws_bytes, void *stream);
+
+/* ---- per-vertex discrete Gaussian curvature of whole-scan triangle meshes (ABI 37) ----------------------------------------------
+ * What the reference reads from files made offline with trimesh.curvature.discrete_gaussian_curvature_measure(mesh,
+ * mesh.vertices, radius) (openpoints/dataset/io.py:51-57), here from the device-resident scans.  The semantics are restated from
+ * trimesh's documentation; agreement with trimesh itself is NOT tested (it is not available where this was written).
+ *   angle      of a face (a, b, c) at corner a: atan2(|e1 x e2|, e1 . e2), e1 = b - a, e2 = c - a
+ *   defect(v)  2 pi - (the sum of the angles at v over all faces at v): boundary vertices too; a vertex in no face has 2 pi
+ *   curvature(v) = the sum of defect(u) over all vertices u of the same scan with |u - v| <= radius, v included; radius in the
+ *              scan's raw units
+ *   batch form (|cur[sel]| - min_s) / (max_s - min_s), min / max of |cur| over the WHOLE scan; 0 everywhere when max == min
+ *              (the reference's commented code would give NaN there)
+ * Rules of this library, where trimesh's behaviour cannot be looked up:
+ *   - a face with an index outside [0, M_s) or with a repeated index is IGNORED as a whole and counted; an index outside the
+ *     range is never used as an address
+ *   - every other face is USABLE; a usable face with a zero-length edge (two corners with equal coordinates) or a non-finite
+ *     coordinate is DEGENERATE: it contributes three zero angles and is counted (among the usable ones too)
+ *   - duplicate faces count twice: the result depends on the MULTISET of faces, not on their order, their winding or the order
+ *     of a face's corners
+ *   - a vertex with a non-finite coordinate is in nobody's ball, its own included (d2 <= r2 is false)
+ * All three entry points launch kernels only on the given stream: no memset node, no host synchronisation, no float atomic,
+ * nothing read back.
+ *
+ * geot_mesh_angle_defects: three launches.  The slot, offset and skip conventions are geot_mesh_neighbours' (offsets, scan_ids,
+ * out_offsets, face_offsets, face_out_offsets, batch_faces; ragged scans read in place); points: (total, 3) float32, the set's
+ * vertices.  total_out: the rows of defect_q, told (every usable slot has out_offsets[s] + M_s <= total_out).  defect_q:
+ * (total_out) long long, WRITTEN for the rows of the usable slots: llrint(2 pi 2^32) - sum of llrint((double)angle 2^32) over
+ * the usable faces' corners at the vertex, 2 pi taken from the double constant.  The three angles of a face are computed
+ * independently in un-contracted fp32, each from (corner, the two others) in the symmetric form above (the cross product's
+ * components only change sign and the dot product's products commute when the two others are swapped), with an atan2 of +, -,
+ * *, correctly rounded / and sqrtf alone (range reduction to |t| <= tan(pi / 8) and a ten-term Taylor polynomial: truncation
+ * below 4.5e-10; see csrc/mesh_curvature.hip) -- a numpy float32 restatement gives the same bits.  An angle whose |e1 x e2| or
+ * e1 . e2 overflows is 0.  The quantised angles are added with 64-bit INTEGER atomics into defect_q itself, zeroed by the first
+ * kernel: every word is independent of the schedule.
+ * stats (optional): (b, 4) int32, WRITTEN (a skipped slot: zeros) -- usable faces, ignored faces, degenerate faces, vertices in
+ * no usable face.
+ * Overflow: a vertex's sum is at most valence * pi * 2^32 < 2^63 for every valence a call can hold (batch_faces < 2^29).  The
+ * ball sum below adds at most M values: M * max |defect_q| must stay below 2^63 (2^24 vertices: |defect_q| < 2^39, a valence
+ * of 40 flat angles); it wraps modulo 2^64 beyond.
+ * ws: geot_mesh_angle_defects_ws_bytes(total_out) bytes (4 per row, rounded up to 16, plus 16: the valence counters), 16-byte
+ * aligned, contents irrelevant.  A slot is skipped -- nothing of it is read or written -- under geot_mesh_neighbours' rules,
+ * with total_out in place of the workspace's capacity, and when its scan has more than GEOT_CURVATURE_MAX_SCAN vertices.
+ * 0 <= b <= 65535 (0: nothing to do), n_scans >= 1, total >= 1, total_faces >= 0, 0 <= batch_faces, 6 batch_faces <= 2^31 - 1,
+ * 0 <= total_out <= 2^30, no NULL among points, offsets, face_offsets, scan_ids, out_offsets, face_out_offsets, defect_q and ws
+ * (faces may be NULL only when total_faces == 0), ws 16-byte aligned and large enough; anything else is hipErrorInvalidValue
+ * before any launch.  geot_mesh_angle_defects_ws_bytes: -1 for total_out outside [0, 2^30].
+ *
+ * geot_scan_ball_sum: for the M vertices of ONE scan, out[v] = (float)((double)S * 2^-32), S = the 64-bit integer sum of
+ * value[u] over all u with sqdist3(u, v) <= radius * radius, both sides in un-contracted fp32 (geot_distance_mode's
+ * expression), v itself included.  points: (M, 3) float32; value: (M) long long; out: (M) float32, WRITTEN; absminmax: two
+ * unsigned words, WRITTEN: the minimum and the maximum of |out| over the scan as order-preserving keys (a non-negative float's
+ * bits with the top bit set), by integer atomicMin / atomicMax.  It knows nothing about curvature.  Seven launches: the grid
+ * build of geot_ball_query_ws (cell edge >= 1.0001 radius, at most 32 cells per axis), a two-word init, and one query kernel
+ * that walks the 3 x 3 x 3 block of every vertex's cell, the vertices taken in the grid's record order: a lane per vertex (the
+ * lanes of a wave mostly share their block, so their loads coincide); GEOT_BALL_SUM_IMPL=basic (read at every call): a wave per
+ * vertex with a lane per candidate, the slower form on scan-sized meshes.  Integer sums: the same bits either way and on every
+ * call.  At most 32 cells per axis: on a scan of 60 mm and a radius of 0.1 a block holds on the order of a thousand candidates
+ * for a handful of members; a finer hashed grid is the open end.
+ * ws: geot_scan_ball_sum_ws_bytes(M) bytes (= geot_knn_grid_ws_bytes(1, M)), 16-byte aligned, contents irrelevant.
+ * 1 <= M <= GEOT_CURVATURE_MAX_SCAN, radius finite and > 0, no NULL, ws aligned and large enough; anything else is
+ * hipErrorInvalidValue before any launch.  geot_scan_ball_sum_ws_bytes: -1 for M outside that range.
+ *
+ * geot_curvature_sample: ONE launch.  curvature: (total) float32, the set's flat curvature; absminmax: (n_scans, 2) unsigned, the
+ * scans' key pairs as geot_scan_ball_sum wrote them; offsets / scan_ids (s): as for geot_cloud_sample_batch; sel: (s, m) int64
+ * vertex indices local to each slot's scan.  out: (s, m) float32, WRITTEN: (|curvature| - min) / (max - min) of the slot's
+ * scan in fp32, 0 everywhere unless max > min.  bad: (s) int32, WRITTEN: 0, 1 when an index lies outside the slot's scan (that
+ * entry is 0 and the index is never used as an address), 2 for an unusable slot (scan id or offsets pair, as
+ * geot_cloud_sample_batch: a row of zeros, nothing read).
+ * 0 <= s <= 65535 (0: nothing to do), m >= 1, n_scans >= 1, total >= 1, no NULL; anything else is hipErrorInvalidValue before any
+ * launch. */
+long long geot_mesh_angle_defects_ws_bytes(long long total_out);
+int geot_mesh_angle_defects(int b, int n_scans, long long total, long long total_faces, const float *points, const int *faces,
+                            const long long *offsets, const long long *face_offsets, const long long *scan_ids,
+                            const long long *out_offsets, const long long *face_out_offsets, long long batch_faces,
+                            long long total_out, long long *defect_q, int *stats, void *ws, long long ws_bytes, void *stream);
+long long geot_scan_ball_sum_ws_bytes(int m);
+int geot_scan_ball_sum(int m, float radius, const float *points, const long long *value, float *out, unsigned *absminmax,
+                       void *ws, long long ws_bytes, void *stream);
+int geot_curvature_sample(int s, int m, int n_scans, long long total, const float *curvature, const unsigned *absminmax,
+                          const long long *offsets, const long long *scan_ids, const long long *sel, float *out, int *bad,
+                          void *stream);
 
 /* ---- transform lists as per-view programs (ABI 16) ---------------------------------------------------------------------------
  * geot_view_program: geot_fixmatch_views for ANY list of the reference's point transforms that keeps the point count
