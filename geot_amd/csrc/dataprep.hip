@@ -76,6 +76,11 @@ struct GsGrid {
     u64 nx, nxy;
 };
 
+// (size_t)floor(x) as the reference's x86-64 build converts it: through a signed 64-bit integer, so an index of -1 -- the
+// fp32 origin can land above the minimum corner -- wraps to 2^64 - 1 and the key to that of cell (NX - 1, iy - 1, iz).
+// A plain float -> u64 conversion saturates at 0 per 32-bit half on the device and would give 2^32 - 1.
+__device__ __forceinline__ u64 gs_index(float x) { return (u64)(long long)floorf(x); }
+
 // grid_subsampling.cpp:24-31: originCorner = floor(minCorner * (1/sampleDl)) * sampleDl; NX, NY from maxCorner
 __device__ __forceinline__ GsGrid gs_grid(const uint32_t *hdr, float dl)
 {
@@ -85,8 +90,8 @@ __device__ __forceinline__ GsGrid gs_grid(const uint32_t *hdr, float dl)
     g.ox = floorf(ord2f(hdr[0]) * inv) * dl;
     g.oy = floorf(ord2f(hdr[1]) * inv) * dl;
     g.oz = floorf(ord2f(hdr[2]) * inv) * dl;
-    g.nx = (u64)floorf((ord2f(hdr[3]) - g.ox) / dl) + 1ull;
-    const u64 ny = (u64)floorf((ord2f(hdr[4]) - g.oy) / dl) + 1ull;
+    g.nx = gs_index((ord2f(hdr[3]) - g.ox) / dl) + 1ull;
+    const u64 ny = gs_index((ord2f(hdr[4]) - g.oy) / dl) + 1ull;
     g.nxy = g.nx * ny;
     return g;
 }
@@ -99,9 +104,9 @@ __global__ __launch_bounds__(256) void gs_key_kernel(int n, float dl, const floa
     if (i >= n) return;
     const GsGrid g = gs_grid(hdr, dl);
     // grid_subsampling.cpp:52-56
-    const u64 ix = (u64)floorf((pts[3 * (size_t)i] - g.ox) / dl);
-    const u64 iy = (u64)floorf((pts[3 * (size_t)i + 1] - g.oy) / dl);
-    const u64 iz = (u64)floorf((pts[3 * (size_t)i + 2] - g.oz) / dl);
+    const u64 ix = gs_index((pts[3 * (size_t)i] - g.ox) / dl);
+    const u64 iy = gs_index((pts[3 * (size_t)i + 1] - g.oy) / dl);
+    const u64 iz = gs_index((pts[3 * (size_t)i + 2] - g.oz) / dl);
     keys[i] = ix + g.nx * iy + g.nxy * iz;
     idx[i] = i;
 }
@@ -433,17 +438,19 @@ __global__ __launch_bounds__(256) void pnb_sample_kernel(int m, int num_classes,
 }
 
 __global__ __launch_bounds__(64) void pnb_weights_kernel(int num_classes, const int *__restrict__ hist_all,
-                                                         const float *__restrict__ stats, float *__restrict__ w_all,
-                                                         float *__restrict__ center, float *__restrict__ scale)
+                                                         const float *__restrict__ stats, const int *__restrict__ bad,
+                                                         float *__restrict__ w_all, float *__restrict__ center,
+                                                         float *__restrict__ scale)
 {
     const int slot = blockIdx.x;
+    const bool unusable = (bad[slot] & 2) != 0;      // zero-filled like the slot's other outputs, not 0 / 0
     const int *hist = hist_all + (size_t)slot * num_classes;
     float *w = w_all + (size_t)slot * num_classes;
     float total = 0.f;
     for (int c = 0; c < num_classes; ++c) total += (float)hist[c];
     for (int c = threadIdx.x; c < num_classes; c += blockDim.x) {
         const float v = (float)hist[c] / total;
-        w[c] = isinf(v) ? 0.f : v;
+        w[c] = (unusable || isinf(v)) ? 0.f : v;
     }
     if (threadIdx.x < 3) center[slot * 3 + threadIdx.x] = stats[slot * 4 + threadIdx.x];
     else if (threadIdx.x == 3) scale[slot] = stats[slot * 4 + 3];
@@ -533,14 +540,17 @@ GEOT_EXPORT int geot_cloud_sample(int n, int m, int num_classes, const float *po
                                   const long long *selected, const float *stats, float *out_points,
                                   long long *out_labels, float *class_weights, int *hist_ws, void *stream)
 {
-    if (n < 1 || m < 0 || !points || !stats || !out_points || !hist_ws) return hipErrorInvalidValue;
-    if (labels && (!out_labels || !class_weights || num_classes < 1 || num_classes > 4096)) return hipErrorInvalidValue;
-    if (!selected && m != n) return hipErrorInvalidValue;
+    if (n < 1 || m < 0 || !points || !stats || (m > 0 && !out_points) || !hist_ws) return hipErrorInvalidValue;
+    if (labels && ((m > 0 && !out_labels) || !class_weights || num_classes < 1 || num_classes > 4096)) return hipErrorInvalidValue;
+    if (!selected && m != n && m != 0) return hipErrorInvalidValue;      // (an empty selection has no address either)
     hipStream_t s = (hipStream_t)stream;
     const int nc = labels ? num_classes : 0;
     hipError_t e = zero_words(hist_ws, (long long)nc + 1, s);
     if (e != hipSuccess) return e;
-    if (m == 0) return hipSuccess;
+    if (m == 0) {                        // nothing gathered: the weights are still written (0 / 0 = NaN, as numpy gives)
+        if (labels) hipLaunchKernelGGL(pn_weights_kernel, dim3(1), dim3(64), 0, s, nc, hist_ws, class_weights);
+        return hipGetLastError();
+    }
     const int nb = (m + 255) / 256;
     hipLaunchKernelGGL(pn_sample_kernel, dim3(nb < 1024 ? nb : 1024), dim3(256), (size_t)(nc + 1) * sizeof(int), s, n, m, nc,
                        points, labels, selected, stats, out_points, out_labels, hist_ws, hist_ws + nc);
@@ -578,6 +588,7 @@ GEOT_EXPORT int geot_cloud_sample_batch(int s, int m, int num_classes, int n_sca
     const int nb = (m + 255) / 256;
     hipLaunchKernelGGL(pnb_sample_kernel, dim3(nb < 1024 ? nb : 1024, s), dim3(256), (size_t)num_classes * sizeof(int), st, m,
                        num_classes, n_scans, total, points, labels, offsets, scan_ids, sel, stats, raw, y, hist, bad);
-    hipLaunchKernelGGL(pnb_weights_kernel, dim3(s), dim3(64), 0, st, num_classes, hist, stats, class_weights, center, scale);
+    hipLaunchKernelGGL(pnb_weights_kernel, dim3(s), dim3(64), 0, st, num_classes, hist, stats, bad, class_weights, center,
+                       scale);
     return hipGetLastError();
 }

@@ -4,7 +4,10 @@
 Same call, same return shape conventions (points, then features and/or labels when given).  numpy inputs
 are uploaded and numpy comes back, as the reference does; CUDA tensors stay on the device.  Rows come out by
 ascending voxel key -- the reference emits the same rows in its hash map's iteration order -- and a label
-tie resolves to the smallest tied label (see include/geot_hip.h).  There is no CPU path.
+tie resolves to the smallest tied label (see include/geot_hip.h).  Cell indices follow the reference's x86-64 build, wrap
+included: where the fp32 origin lands above the minimum corner the minimum point's index of -1 wraps to 2^64 - 1, and its
+key is that of cell (NX - 1, iy - 1, iz), into which it is merged when that cell is occupied.  NaN and infinite
+coordinates are outside the contract.  There is no CPU path.
 """
 import numpy as np
 import torch

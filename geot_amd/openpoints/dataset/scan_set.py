@@ -255,8 +255,10 @@ def cloud_sample_batch(scans, scan_ids, sel, num_classes=17, check=True, ids_dev
     """geot_cloud_sample_batch: scans a DeviceScanSet; scan_ids: the set scan of every batch slot (S ints, host); sel (S, m)
     int64 vertex indices local to each slot's scan (numpy or tensor) -> dict(raw (S, m, 3), y (S, m) int64, class_weights
     (S, num_classes), center (S, 3), scale (S,), bad (S,) int32).  Slot by slot bit-identical to prepare_sample on that scan
-    alone.  check=True reads `bad` back (one host sync) and raises IndexError for an index outside its scan.  ids_dev:
-    scan_ids as an (S,) int64 tensor already on the device (the batchers upload them once for the draw and the sampling)."""
+    alone; a slot flagged 2 (an unusable table entry: only the C entry point can be handed one, the ids are checked here)
+    is zero-filled, class_weights included.  check=True reads `bad` back (one host sync) and raises IndexError for an index
+    outside its scan.  ids_dev: scan_ids as an (S,) int64 tensor already on the device (the batchers upload them once for
+    the draw and the sampling)."""
     need(isinstance(scans, DeviceScanSet), "cloud_sample_batch: scans must be a DeviceScanSet")
     ids = np.asarray(scan_ids, dtype=np.int64).reshape(-1)
     need(ids.size >= 1 and ids.min() >= 0 and ids.max() < len(scans), "cloud_sample_batch: scan ids must lie in [0, %d)" % len(scans))

@@ -39,7 +39,9 @@ def prepare_sample(points, labels, selected_idxs, num_classes=17, check=True):
     """points (N,3) float, labels (N,) int32, selected_idxs (m,) int64 (CUDA tensors or numpy).
     -> dict(pos (m,3) float32, y (m,) int64, class_weights (num_classes,), center (3,), scale ())
     = tooth_dataset.py:129-147 for one scan.  check=True reads back the out-of-range flag (numpy raises
-    IndexError for a bad index; one host sync)."""
+    IndexError for a bad index; one host sync).  A label outside [0, num_classes) is dropped from the class-weight
+    histogram and carried in y; with no label in range -- and for m == 0, where pos and y are empty -- every class weight
+    is NaN (0 / 0), as the reference's expression gives."""
     dev = points.device if isinstance(points, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
 
     def up(a, dt):

@@ -760,8 +760,12 @@ int geot_ntm_feature_loss_grad_det(int b, int n, int c, int k, int feat_dim, flo
  * number of voxels M; rows 0..M-1 are the voxel barycentres (fp32 sums in input order, bit-identical to the
  * reference), mean features and majority labels, by ascending voxel key (the reference emits the same rows in
  * its hash map's iteration order; on a label tie it takes the first maximum in that order, here the smallest
- * tied label).  ws: geot_grid_subsampling_ws_bytes(n) bytes of device scratch (sized for the current device:
- * -1 when the process has no GPU). */
+ * tied label).  Cell indices follow the reference's x86-64 build, wrap included: (size_t)floor(x) goes through a signed
+ * 64-bit integer there, and the fp32 origin floor(min / dl) * dl can land above the minimum corner, so the minimum point
+ * can get an index of -1 = 2^64 - 1; its key ix + NX iy + NX NY iz is then, modulo 2^64, that of cell (NX - 1, iy - 1, iz),
+ * and the point is merged into that cell when it is occupied.  NaN and infinite coordinates are outside the contract.
+ * ws: geot_grid_subsampling_ws_bytes(n) bytes of device scratch (sized for the current device: -1 when the process has
+ * no GPU). */
 long long geot_grid_subsampling_ws_bytes(int n);
 int geot_grid_subsampling(int n, int fdim, int ldim, float sample_dl, const float *points, const float *features,
                           const int *labels, float *out_points, float *out_features, int *out_labels,
@@ -771,9 +775,14 @@ int geot_grid_subsampling(int n, int fdim, int ldim, float sample_dl, const floa
 long long geot_pc_norm_ws_bytes(void);
 int geot_pc_norm_stats(int n, const float *points, float *stats, void *ws, long long ws_bytes, void *stream);
 /* tooth_dataset.py:132-147: out_points[i] = (points[selected[i]] - centroid) / scale (m,3); with labels (n)
- * also out_labels (m) int64 and class_weights (num_classes) = histogram of the gathered labels / m (inf -> 0).
- * selected NULL = identity (m == n).  hist_ws: num_classes + 1 ints; the last one is set non-zero when an
- * entry of selected was out of range (numpy raises IndexError there; the row is then read from point 0). */
+ * also out_labels (m) int64 and class_weights (num_classes) = histogram of the gathered labels over [0, num_classes) /
+ * its total (inf -> 0).  A label outside [0, num_classes) is DROPPED from the histogram and carried in out_labels as it is
+ * (the reference's torch.histogram closes its last bin on the right, so a label of exactly num_classes would count as
+ * num_classes - 1 there; its label map never produces one); with no label in range every weight is 0 / 0 = NaN, as the
+ * reference's expression gives.  selected NULL = identity (m == n).  m == 0: nothing is gathered, class_weights is still
+ * written (NaN, the same 0 / 0), and selected, out_points and out_labels may be NULL.  hist_ws: num_classes + 1 ints; the
+ * last one is set non-zero when an entry of selected was out of range (numpy raises IndexError there; the row is then
+ * read from point 0). */
 int geot_cloud_sample(int n, int m, int num_classes, const float *points, const int *labels,
                       const long long *selected, const float *stats, float *out_points, long long *out_labels,
                       float *class_weights, int *hist_ws, void *stream);
@@ -842,8 +851,9 @@ int geot_seg_confusion_interp(int b, int c, int n, const long long *offsets, con
  * -- each bit-identical to the single-scan calls on that scan alone (the same fp64 partial-sum tree per scan, the same
  * (x^2 + y^2) + z^2 norm, IEEE divide; the maximum and the histogram do not depend on arrival order; no float atomics).
  * bad (s) int32: set to 1 for a slot with an entry of sel outside its scan (the row is then read from vertex 0, as
- * geot_cloud_sample does) and to 2 for a slot whose scan_ids / offsets entry is unusable (nothing of that slot is read;
- * its outputs are zero-filled), 0 otherwise.  ws: geot_cloud_sample_batch_ws_bytes(s, num_classes) bytes.
+ * geot_cloud_sample does) and to 2 for a slot whose scan_ids / offsets entry is unusable -- a scan id outside [0, n_scans),
+ * an empty scan, offsets[i] < 0 or offsets[i + 1] > total -- (nothing of that slot is read; its raw, y, class_weights, center
+ * and scale are zero-filled: no 0 / 0 there), 0 otherwise.  ws: geot_cloud_sample_batch_ws_bytes(s, num_classes) bytes.
  * 1 <= s <= 65535, m >= 1, 1 <= num_classes <= 4096, n_scans >= 1, total >= 1, no NULL pointer but scan_ids; anything else
  * is hipErrorInvalidValue. */
 long long geot_cloud_sample_batch_ws_bytes(int s, int num_classes);

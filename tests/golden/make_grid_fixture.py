@@ -1,12 +1,15 @@
-"""Regenerate tests/golden/grid_subsampling_ref.npz and grid_subsampling_compiled_ref.npz (run where the
-reference checkout is present).
+"""Regenerate tests/golden/grid_subsampling_ref.npz, grid_subsampling_compiled_ref.npz and grid_subsampling_edges_ref.npz
+(run where the reference checkout is present).
 
-    python oracle/build_ref.py && python tests/golden/make_grid_fixture.py
+    python oracle/build_ref.py && python tests/golden/make_grid_fixture.py [edges]
+
+("edges" writes grid_subsampling_edges_ref.npz alone.)
 
 Inputs: seeded clouds (with duplicate points and negative coordinates).  Expected outputs: what the
 REFERENCE's own grid_subsampling() returns for them -- compiled from /root/reference by oracle/build_ref.py
 into oracle/_ref/ -- in the reference's own row order.  grid_subsampling_ref.npz holds inputs and outputs only;
-grid_subsampling_compiled_ref.npz only digests and labels (compiled_cases).
+grid_subsampling_compiled_ref.npz only digests and labels (compiled_cases); grid_subsampling_edges_ref.npz the clouds of
+tests/_dataprep_ref.py at which a cell index is -1 or a key 40 bits wide, inputs and outputs (edge_cases).
 """
 import hashlib
 import os
@@ -48,6 +51,28 @@ def main():
     np.savez_compressed(os.path.join(HERE, "grid_subsampling_ref.npz"), **out)
     print("wrote", sorted(out))
     compiled_cases()
+    edge_cases()
+
+
+def edge_cases():
+    """grid_subsampling_edges_ref.npz: the clouds of tests/_dataprep_ref.py's FIXTURE_CASES -- one per axis whose minimum
+    point gets a cell index of -1, and the cloud whose keys are 40 bits wide -- with the reference's rows for them, keyed
+    "<case>_<name>" as in grid_subsampling_ref.npz.  Inputs and outputs only."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import _dataprep_ref as R
+    out = {}
+    for case in R.FIXTURE_CASES:
+        c, name = R.gs_case(case), R.fixture_key(case)
+        origin, ijk, _ = R.grid_of(c["p"], c["dl"])
+        assert ("neg" in case) == bool((ijk == -1).any()), case
+        share = c["want"]["tied"].any(axis=1).mean()
+        assert share <= R.TIED_SHARE, (case, share)
+        r = np_data.grid_subsampling_reference(c["p"], c["f"], c["lab"], c["dl"])
+        out[name + "_points"], out[name + "_dl"] = c["p"], np.float32(c["dl"])
+        out[name + "_features"], out[name + "_labels"] = c["f"], c["lab"]
+        out[name + "_ref_points"], out[name + "_ref_features"], out[name + "_ref_labels"] = r["points"], r["features"], r["labels"]
+    np.savez_compressed(os.path.join(HERE, "grid_subsampling_edges_ref.npz"), **out)
+    print("wrote", sorted(out))
 
 
 def compiled_case_inputs(seed, n, fdim, ldim):
@@ -91,4 +116,8 @@ def compiled_cases():
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["edges"]:            # the edge fixture alone: the other two files keep their bytes
+        assert np_data.have_reference(), "run oracle/build_ref.py first"
+        edge_cases()
+    else:
+        main()
